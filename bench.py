@@ -10,6 +10,12 @@ forward (train-mode BN) + weighted categorical cross-entropy + backward + [RCCL 
 all-reduce] + Keras-Adam + weight repack, bf16 storage / fp32 accumulate.  Inputs are resident
 in HBM when the timed region starts.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times ONE region of exactly --steps steps (value, ms_per_step) and
+prints the line.  --full adds everything else the line can carry: the box probe, the region
+repeated --repeats times (median reported), one more region with the per-class HIP events on
+(roofline, extra.kernel_*), the inference timings and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (loss, updated weights) as .npy files.
+
 roofline: the dominant kernel class is the 3x3 implicit-GEMM convolution (forward + data-gradient
 launches); `achieved` = algorithmic FLOPs of those launches / their summed HIP-event durations
 inside the timed region; peak = 2.5 PFLOP/s dense bf16 MFMA (MI355X_MICROARCH.md).
@@ -291,25 +297,102 @@ def cpu_baseline(seconds_budget=20.0, CH=CH):
                        f'predict at batch 1 and 16 beside it', **res)
 
 
+def roofline(plan, prof, nprof, dt, steps, dtype, B, CHN, extra):
+    """--full: the roofline block of the line from the per-class HIP-event sums of the prof region (see the module docstring);
+    also fills extra['fused_backward']."""
+    d, d3 = prof['conv3x3_igemm_fwd_dgrad'], prof['conv3x3_fused_dgrad_wgrad']
+    peak = PEAK_BF16_TFLOPS if dtype == 'bfloat16' else 157.3
+    aw = alg_work(B, 2 if dtype == 'bfloat16' else 4, CHN)
+    a3 = aw['conv3_fwd_dgrad']
+    # achieved = ALGORITHMIC FLOPs of the 3x3 implicit-GEMM launches of the timed steps (forward + data gradient; true Cin: 4 for the
+    # first layer although 16 channels are stored) / their summed HIP-event durations on the launch stream.  The data gradients of the
+    # thin layers whose whole backward is ONE fused launch (BatchNorm apply + data gradient + weight gradient, csrc/conv_bwd_fused.hip)
+    # are not executed by this kernel class any more: their FLOPs leave the numerator as their time left the denominator, and the fused
+    # launches (HBM-bound) are reported with their own roofline under extra.fused_backward.
+    fused = [f.work for f in plan.bwd if getattr(f, 'work', {}).get('kind') == 'bwd_fused']
+    fused_dgrad_flops = sum(2.0 * w['px'] * w['cin'] * w['cout'] * 9 for w in fused if not w.get('nodx'))
+    fused_bytes = sum(w['px'] * (2 * w['cout'] + (1 if w.get('nodx') else 2) * w['cin']) * w['esize']
+                      + (w['px'] // 4 * w['cout'] * (w['esize'] + 1) if w.get('pooled') else 0) for w in fused)
+    fused_dgrad_bytes = sum(w['px'] * (w['cin'] + w['cout']) * w['esize'] + 9 * w['cin'] * w['cout'] * w['esize'] for w in fused if not w.get('nodx'))
+    n_fused_dgrad = sum(1 for w in fused if not w.get('nodx'))
+    ach = (a3['flops'] - fused_dgrad_flops) * nprof / max(d['ms'], 1e-9) / 1e9
+    # like-for-like with rounds 1-2 (every 3x3 forward + data-gradient FLOP of the step over the time of every launch that executes
+    # one of them, the fused thin-layer launches with their WHOLE duration: a lower bound)
+    ach_all = a3['flops'] * nprof / max(d['ms'] + d3['ms'], 1e-9) / 1e9
+    extra['fused_backward'] = {'launches_per_step': len(fused), 'ms_per_step': round(d3['ms'] / nprof, 3),
+                               'algorithmic_MB_per_step': round(fused_bytes / 1e6, 1), 'bound': 'hbm',
+                               'achieved_TBps': round(fused_bytes * nprof / max(d3['ms'], 1e-9) / 1e9, 3), 'peak_TBps': PEAK_HBM_TBPS,
+                               'frac': round(fused_bytes * nprof / max(d3['ms'], 1e-9) / 1e9 / PEAK_HBM_TBPS, 4),
+                               'tflops': round(d3['flops'] / max(d3['ms'], 1e-9) / 1e9, 1),
+                               'data_gradient_gflop_per_step_inside': round(fused_dgrad_flops / 1e9, 1)}
+    launches_per_step = max(d['launches'] / nprof, 1)
+    traffic, traffic_src, traffic_digest = pmc_traffic_per_launch()
+    hc = head_commit()
+    # the PMC summary is a committed file of an earlier run of this command (counters cannot be collected inside the timed run): it is
+    # STALE unless it was measured on these very kernel sources
+    built = ''
+    try:
+        built = open(os.path.join(ROOT, 'satellite_computervision_amd', '_build_commit.txt')).read().strip()
+    except Exception:
+        pass
+    traffic_stale = not (traffic_digest and traffic_digest == csrc_digest())
+    return {'bound': 'mfma', 'achieved': round(ach, 2), 'peak': peak, 'unit': 'TFLOP/s', 'frac': round(ach / peak, 4),
+            'traffic': traffic, 'traffic_unit': 'MB per launch (rocprofv3 PMC FETCH_SIZE x2 + WRITE_SIZE)', 'traffic_source': traffic_src, 'traffic_stale': traffic_stale, 'csrc_digest': csrc_digest(), 'head_commit': hc, 'build_commit': built,
+            'algorithmic_bytes_per_launch_MB': round((a3['bytes'] - fused_dgrad_bytes) / max(a3['launches'] - n_fused_dgrad, 1) / 1e6, 1),
+            'algorithmic_gflop_per_step': round(a3['flops'] / 1e9, 1),
+            'kernel': '3x3 implicit-GEMM conv (forward + data gradient launches; the thin layers\' data gradients run inside the fused backward launches: extra.fused_backward)',
+            'algorithmic_gflop_per_step_in_these_launches': round((a3['flops'] - fused_dgrad_flops) / 1e9, 1), 'launches_per_step': launches_per_step,
+            'avg_launch_us': round(1000 * d['ms'] / max(d['launches'], 1), 2),
+            # whole step against the per-layer rooflines: sum over every conv-like layer and pass (forward, data
+            # gradient, weight gradient) of max(flops / MFMA peak, unfused bytes / 8 TB/s), / measured step time
+            'step_roofline_ms': round(1000 * aw['all']['roof_s'], 3),
+            'step_frac': round(1000 * aw['all']['roof_s'] / (1000 * dt / steps), 4),
+            'stack_roofline_ms': round(1000 * a3['roof_s'], 3),
+            'stack_roofline_frac': round(1000 * a3['roof_s'] / max((d['ms'] + d3['ms']) / nprof, 1e-9), 4),
+            'frac_like_for_like_r02': round(ach_all / peak, 4)}
+
+
+WEIGHT_SAMPLE = 1 << 23            # float32 values of the weights written by --dump-outputs (32 MiB; the line's whole dump stays under 64 MB)
+
+
+def dump_outputs(model, plan, out_dir):
+    """What a caller of the timed step holds after its last step, as float32 .npy files: loss.npy (the step's loss, shape (1,)) and
+    weights.npy (every variable of get_weights_dict() -- kernels, biases, BatchNorm gamma / beta / moving statistics -- flattened and
+    concatenated in sorted-name order; when that exceeds WEIGHT_SAMPLE values, the values at a fixed seeded sample of sorted positions)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'loss.npy'), plan.loss_buf.detach().float().cpu().numpy().reshape(1))
+    wd = model.get_weights_dict()
+    flat = np.concatenate([np.asarray(wd[k], dtype=np.float32).ravel() for k in sorted(wd)])
+    if flat.size > WEIGHT_SAMPLE:
+        flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, WEIGHT_SAMPLE, replace=False))]
+    np.save(os.path.join(out_dir, 'weights.npy'), flat)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20, help='timed training steps (one region of exactly this many steps)')
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=BATCH)
     ap.add_argument('--dtype', default='bfloat16')
     ap.add_argument('--channels', type=int, default=CH, choices=(4, 13),
                     help='input bands: 4 (BASELINE configs[1], the default line) or 13 = all Sentinel-2 bands (BASELINE configs[3])')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the loss and the updated weights of the last one as DIR/*.npy (float32)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: box probe, repeated regions (median), per-class HIP-event region '
+                         '(roofline, kernel figures), inference timings, CPU baseline.  Off: set up, warm up, time --steps steps, print')
     ap.add_argument('--repeats', type=int, default=5,
-                    help='the timed region of exactly --steps steps is run this many times (same work each); value = the MEDIAN region')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+                    help='(--full) the timed region of exactly --steps steps is run this many times (same work each); value = the MEDIAN region')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
     ap.add_argument('--prof-in-timed', action='store_true',
-                    help='(rounds 1-5 behaviour) record the per-class HIP events inside the timed regions; default: the timed regions run with '
+                    help='(--full; rounds 1-5 behaviour) record the per-class HIP events inside the timed regions; default: the timed regions run with '
                          'satcv_prof_enable(0) and one EXTRA, untimed-for-the-headline region with the events on supplies the class times')
-    ap.add_argument('--infer', action='store_true', help='(default) also time bf16 / fp8 inference and the config-5 chip rate, reported under "extra"')
-    ap.add_argument('--no-infer', action='store_true', help='skip the inference timings')
-    ap.add_argument('--full-infer', action='store_true', help='(kept for old command lines: the DeepLab-v3 config-3 timings are part of the default run)')
+    ap.add_argument('--infer', action='store_true', help='(--full, default there) also time bf16 / fp8 inference and the config-5 chip rate, reported under "extra"')
+    ap.add_argument('--no-infer', action='store_true', help='(--full) skip the inference timings')
+    ap.add_argument('--full-infer', action='store_true', help='(kept for old command lines: the DeepLab-v3 config-3 timings are part of the --full run)')
     args = ap.parse_args()
+    full = args.full
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -354,16 +437,16 @@ def main():
         torch.cuda.synchronize()
 
     model._head_plan(B, TILE, TILE, True)              # buffers and launch descriptors exist before any (warm-up or timed) step
-    probe = box_probe() if rank == 0 else None
+    probe = box_probe() if rank == 0 and full else None
     for i in range(args.warmup):
         xb, yb = pool[i % len(pool)]
         model.train_step_device(xb, yb, sync)
     barrier()
-    # the timed region: EXACTLY --steps steps between barrier + synchronize pairs, max over ranks.  Boxes of the pool differ by several
-    # percent and a 0.17-s region is short, so the region is repeated (identical work) and the MEDIAN region is the reported one; the
-    # spread goes to extra.region_ms_per_step
+    # the timed region: EXACTLY --steps steps between barrier + synchronize pairs, max over ranks.  A plain run times one region.  With
+    # --full (boxes of the pool differ by several percent and a 0.17-s region is short) the region is repeated (identical work) and the
+    # MEDIAN region is the reported one; the spread goes to extra.region_ms_per_step
     # Round 6: the HIP events that time the kernel classes (two per conv-class launch, ~55 launches per step on two streams) are OFF in the
-    # timed regions; one more region of the same --steps steps with them ON supplies the class times (roofline.achieved, extra.kernel_*) and
+    # timed regions; with --full one more region of the same --steps steps with them ON supplies the class times (roofline.achieved, extra.kernel_*) and
     # its own ms_per_step goes to extra.ms_per_step_with_prof_events, so that the cost of the events is a number.
     def region():
         barrier()
@@ -378,40 +461,44 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dtr = float(tmax.item())
         return dtr, pl
-    if args.prof_in_timed:
+    prof_in_timed = full and args.prof_in_timed
+    if prof_in_timed:
         check(lib.satcv_prof_enable(0b1111))
     regions = []
-    for rep in range(max(args.repeats, 1)):
+    for rep in range(max(args.repeats, 1) if full else 1):
         dtr, plan = region()
         regions.append(dtr)
-    if args.prof_in_timed:
-        nprof = args.steps * len(regions)           # steps the HIP-event sums cover
-        dt_prof = None
-    else:
+    dt = float(np.median(regions))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, plan, args.dump_outputs)
+    if full and not prof_in_timed:
         check(lib.satcv_prof_enable(0b1111))
         dt_prof, plan = region()
         nprof = args.steps
+    else:
+        nprof = args.steps * len(regions)           # steps the HIP-event sums cover
+        dt_prof = None
     check(lib.satcv_prof_enable(0))
     loss = float(plan.loss_buf.item())
-    dt = float(np.median(regions))
 
+    extra = {'loss_last': loss}
     prof = {}
-    for kind, name in ((0, 'conv3x3_igemm_fwd_dgrad'), (1, 'conv1x1_convT_gemm'), (2, 'conv_wgrad'), (3, 'conv3x3_fused_dgrad_wgrad')):
-        ms, cnt, fl = C.c_double(), C.c_int64(), C.c_double()
-        check(lib.satcv_prof_collect(kind, C.byref(ms), C.byref(cnt), C.byref(fl)))
-        prof[name] = dict(ms=ms.value, launches=cnt.value, flops=fl.value)
-
-    extra = {'loss_last': loss, 'kernel_ms_per_step': {k: round(v['ms'] / nprof, 3) for k, v in prof.items()},
-             'region_ms_per_step': {'median': round(1000 * dt / args.steps, 3), 'min': round(1000 * min(regions) / args.steps, 3),
-                                    'max': round(1000 * max(regions) / args.steps, 3), 'repeats': len(regions)},
-             'kernel_tflops': {k: round(v['flops'] / max(v['ms'], 1e-9) / 1e9, 1) for k, v in prof.items()},
-             'prof_events_in_timed_regions': bool(args.prof_in_timed),
-             'ms_per_step_with_prof_events': round(1000 * dt_prof / args.steps, 3) if dt_prof is not None else round(1000 * dt / args.steps, 3),
-             'box_probe': probe}
+    if full:
+        for kind, name in ((0, 'conv3x3_igemm_fwd_dgrad'), (1, 'conv1x1_convT_gemm'), (2, 'conv_wgrad'), (3, 'conv3x3_fused_dgrad_wgrad')):
+            ms, cnt, fl = C.c_double(), C.c_int64(), C.c_double()
+            check(lib.satcv_prof_collect(kind, C.byref(ms), C.byref(cnt), C.byref(fl)))
+            prof[name] = dict(ms=ms.value, launches=cnt.value, flops=fl.value)
+        extra.update({'kernel_ms_per_step': {k: round(v['ms'] / nprof, 3) for k, v in prof.items()},
+                      'region_ms_per_step': {'median': round(1000 * dt / args.steps, 3), 'min': round(1000 * min(regions) / args.steps, 3),
+                                             'max': round(1000 * max(regions) / args.steps, 3), 'repeats': len(regions)},
+                      'kernel_tflops': {k: round(v['flops'] / max(v['ms'], 1e-9) / 1e9, 1) for k, v in prof.items()},
+                      'prof_events_in_timed_regions': bool(prof_in_timed),
+                      'ms_per_step_with_prof_events': round(1000 * dt_prof / args.steps, 3) if dt_prof is not None else round(1000 * dt / args.steps, 3),
+                      'box_probe': probe})
     if dist is not None:
         extra['grad_exchange'] = {'via': 'satcv_allreduce_grads (C ABI, RCCL)' if parallel.cabi_comm() is not None else f'torch.distributed {dist.get_backend()}',
                                   'payload': sync.payload, 'bucket_MiB': sync.per * 4 / 2 ** 20, 'calls': parallel._comm['calls']}
-    if not args.no_infer:
+    if full and not args.no_infer:
         xb, _ = pool[0]
         for _ in range(3):
             model.predict_on_device(xb)
@@ -462,42 +549,6 @@ def main():
     if rank == 0:
         tiles = world * B * args.steps
         value = tiles / dt
-        d, d3 = prof['conv3x3_igemm_fwd_dgrad'], prof['conv3x3_fused_dgrad_wgrad']
-        peak = PEAK_BF16_TFLOPS if args.dtype == 'bfloat16' else 157.3
-        aw = alg_work(B, 2 if args.dtype == 'bfloat16' else 4, CHN)
-        a3 = aw['conv3_fwd_dgrad']
-        # achieved = ALGORITHMIC FLOPs of the 3x3 implicit-GEMM launches of the timed steps (forward + data gradient; true Cin: 4 for the
-        # first layer although 16 channels are stored) / their summed HIP-event durations on the launch stream.  The data gradients of the
-        # thin layers whose whole backward is ONE fused launch (BatchNorm apply + data gradient + weight gradient, csrc/conv_bwd_fused.hip)
-        # are not executed by this kernel class any more: their FLOPs leave the numerator as their time left the denominator, and the fused
-        # launches (HBM-bound) are reported with their own roofline under extra.fused_backward.
-        fused = [f.work for f in plan.bwd if getattr(f, 'work', {}).get('kind') == 'bwd_fused']
-        fused_dgrad_flops = sum(2.0 * w['px'] * w['cin'] * w['cout'] * 9 for w in fused if not w.get('nodx'))
-        fused_bytes = sum(w['px'] * (2 * w['cout'] + (1 if w.get('nodx') else 2) * w['cin']) * w['esize']
-                          + (w['px'] // 4 * w['cout'] * (w['esize'] + 1) if w.get('pooled') else 0) for w in fused)
-        fused_dgrad_bytes = sum(w['px'] * (w['cin'] + w['cout']) * w['esize'] + 9 * w['cin'] * w['cout'] * w['esize'] for w in fused if not w.get('nodx'))
-        n_fused_dgrad = sum(1 for w in fused if not w.get('nodx'))
-        ach = (a3['flops'] - fused_dgrad_flops) * nprof / max(d['ms'], 1e-9) / 1e9
-        # like-for-like with rounds 1-2 (every 3x3 forward + data-gradient FLOP of the step over the time of every launch that executes
-        # one of them, the fused thin-layer launches with their WHOLE duration: a lower bound)
-        ach_all = a3['flops'] * nprof / max(d['ms'] + d3['ms'], 1e-9) / 1e9
-        extra['fused_backward'] = {'launches_per_step': len(fused), 'ms_per_step': round(d3['ms'] / nprof, 3),
-                                   'algorithmic_MB_per_step': round(fused_bytes / 1e6, 1), 'bound': 'hbm',
-                                   'achieved_TBps': round(fused_bytes * nprof / max(d3['ms'], 1e-9) / 1e9, 3), 'peak_TBps': PEAK_HBM_TBPS,
-                                   'frac': round(fused_bytes * nprof / max(d3['ms'], 1e-9) / 1e9 / PEAK_HBM_TBPS, 4),
-                                   'tflops': round(d3['flops'] / max(d3['ms'], 1e-9) / 1e9, 1),
-                                   'data_gradient_gflop_per_step_inside': round(fused_dgrad_flops / 1e9, 1)}
-        launches_per_step = max(d['launches'] / nprof, 1)
-        traffic, traffic_src, traffic_digest = pmc_traffic_per_launch()
-        hc = head_commit()
-        # the PMC summary is a committed file of an earlier run of this command (counters cannot be collected inside the timed run): it is
-        # STALE unless it was measured on these very kernel sources
-        built = ''
-        try:
-            built = open(os.path.join(ROOT, 'satellite_computervision_amd', '_build_commit.txt')).read().strip()
-        except Exception:
-            pass
-        traffic_stale = not (traffic_digest and traffic_digest == csrc_digest())
         out = {
             'metric': f'tiles/sec (train) 256x256x{CHN} U-Net', 'value': round(value, 2), 'unit': 'tiles/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -506,25 +557,13 @@ def main():
             'config': {'workload': f'U-Net 256x256x{CHN} {args.dtype} training, batch {B} per GPU (BASELINE configs[{1 if CHN == 4 else 3}])',
                        'global_batch': world * B, 'parallelism': f'dp{world}', 'loss': 'weighted_categorical_crossentropy',
                        'optimizer': 'adam(9e-4)'},
-            'roofline': {'bound': 'mfma', 'achieved': round(ach, 2), 'peak': peak, 'unit': 'TFLOP/s', 'frac': round(ach / peak, 4),
-                         'traffic': traffic, 'traffic_unit': 'MB per launch (rocprofv3 PMC FETCH_SIZE x2 + WRITE_SIZE)', 'traffic_source': traffic_src, 'traffic_stale': traffic_stale, 'csrc_digest': csrc_digest(), 'head_commit': hc, 'build_commit': built,
-                         'algorithmic_bytes_per_launch_MB': round((a3['bytes'] - fused_dgrad_bytes) / max(a3['launches'] - n_fused_dgrad, 1) / 1e6, 1),
-                         'algorithmic_gflop_per_step': round(a3['flops'] / 1e9, 1),
-                         'kernel': '3x3 implicit-GEMM conv (forward + data gradient launches; the thin layers\' data gradients run inside the fused backward launches: extra.fused_backward)',
-                         'algorithmic_gflop_per_step_in_these_launches': round((a3['flops'] - fused_dgrad_flops) / 1e9, 1), 'launches_per_step': launches_per_step,
-                         'avg_launch_us': round(1000 * d['ms'] / max(d['launches'], 1), 2),
-                         # whole step against the per-layer rooflines: sum over every conv-like layer and pass (forward, data
-                         # gradient, weight gradient) of max(flops / MFMA peak, unfused bytes / 8 TB/s), / measured step time
-                         'step_roofline_ms': round(1000 * aw['all']['roof_s'], 3),
-                         'step_frac': round(1000 * aw['all']['roof_s'] / (1000 * dt / args.steps), 4),
-                         'stack_roofline_ms': round(1000 * a3['roof_s'], 3),
-                         'stack_roofline_frac': round(1000 * a3['roof_s'] / max((d['ms'] + d3['ms']) / nprof, 1e-9), 4),
-                         'frac_like_for_like_r02': round(ach_all / peak, 4)},
             'model_tflops': round(value * (TRAIN_GFLOP_PER_TILE + (2 * 2 * 9 * 32 * (CHN - CH) * TILE * TILE / 1e9 if CHN != CH else 0.0)) / 1000, 2),
             'extra': extra,
         }
-        if not args.no_cpu_baseline and world == 1:
-            out['cpu_baseline'] = cpu_baseline(CH=CHN)
+        if full:
+            out['roofline'] = roofline(plan, prof, nprof, dt, args.steps, args.dtype, B, CHN, extra)
+            if not args.no_cpu_baseline and world == 1:
+                out['cpu_baseline'] = cpu_baseline(CH=CHN)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier(**BARRIER_KW)
