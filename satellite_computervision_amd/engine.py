@@ -165,8 +165,10 @@ class Runtime:
         self.dropout_seed = 0x5A7C0FFEE
         host = np.zeros(self.pflat.numel(), np.float32)
         hs = np.zeros(self.sflat.numel(), np.float32)
+        self.zero_gamma = set()
         for p in model.param_specs:
             v = np.asarray(p.init(), np.float32).reshape(-1)
+            self._note_gamma(p.name, v)
             if p.name in self.offsets:
                 host[self.offsets[p.name]:self.offsets[p.name] + p.size] = v
             else:
@@ -215,7 +217,21 @@ class Runtime:
         return self.gflat[self.offsets[name]:self.offsets[name] + p.size].view(p.shape)
 
     def set_param(self, name, value):
-        self.get_param(name).copy_(torch.as_tensor(np.asarray(value, np.float32)).to(self.dev).view(self.specs[name].shape))
+        v = np.asarray(value, np.float32)
+        self._note_gamma(name, v)
+        self.get_param(name).copy_(torch.as_tensor(v).to(self.dev).view(self.specs[name].shape))
+
+    def _note_gamma(self, name, v):
+        """BatchNorm layers with a zero (or subnormal) gamma, tracked on the host as the weights are set (no device read).  The sums of
+        their backward must come from the raw output: a form built from the activation a = relu(gamma xhat + beta) recovers sum g xhat as
+        (sum g a - beta sum g) / gamma, which is undefined where gamma = 0 (there a is the constant relu(beta) and carries nothing of xhat,
+        satcv_bn_bwd_finalize2 returns 0 -- while dgamma = sum g [beta > 0] xhat is not 0)."""
+        if name.endswith('/gamma'):
+            bn = name[:-len('/gamma')]
+            if np.any(np.abs(v) < np.finfo(np.float32).tiny):
+                self.zero_gamma.add(bn)
+            else:
+                self.zero_gamma.discard(bn)
 
     def _pack_table(self, lo=0, hi=None):
         """device table of the pack jobs (forward + data-gradient image) of every layer whose kernel starts in [lo, hi) of the flat parameter
@@ -267,18 +283,21 @@ class Runtime:
         # tf.keras runs a BatchNormalization whose `trainable` is False in INFERENCE mode even inside fit() (moving statistics, no
         # update): the set of frozen layers is part of a training plan's identity (retrain_model(freeze=True), utils/model_tools.py:1174)
         frozen = tuple(sorted(l.name for l in self.model.layers if not l.trainable)) if training else ()
-        key = (n, h, w, bool(training), frozen)
+        # (as is the set of BatchNorms whose backward sums must stay in the raw form: Runtime._note_gamma)
+        raw_bn = tuple(sorted(self.zero_gamma)) if training else ()
+        key = (n, h, w, bool(training), frozen, raw_bn)
         if key not in self.plans:
-            self.plans[key] = Plan(self, n, h, w, training, frozen)
+            self.plans[key] = Plan(self, n, h, w, training, frozen, raw_bn)
         return self.plans[key]
 
 
 class Plan:
     """Static launch sequence for one input shape."""
 
-    def __init__(self, rt, n, h, w, training, frozen=()):
+    def __init__(self, rt, n, h, w, training, frozen=(), raw_bn=()):
         self.rt, self.n, self.h, self.w, self.training = rt, n, h, w, training
         self.frozen = set(frozen)
+        self.raw_bn = set(raw_bn)             # BatchNorms (zero gamma) whose backward sums no activation-based producer may form
         self.tile_policy = 2 if (training and _M16_DEFAULT == 1) else 0      # satcv_conv_desc.tile_policy of this plan's convolution launches
         self.eo_lo, self.early_opt, self.eo_done = None, None, False          # split optimizer step (see _build_backward: `early`)
         self.fwd, self.bwd = [], []
@@ -848,7 +867,7 @@ class Plan:
             """the registry entry of encoder output t (a conv -> BN -> ReLU node that is pooled AND used as a skip), or None"""
             if not POOL_SUMS or t.node.op != 'cba' or not t.node.attrs.get('bn', True) or not t.node.attrs.get('relu', True):
                 return None
-            if t.node.layer.bn_name in self.frozen or t.node.layer.name in shared_layers:
+            if t.node.layer.bn_name in self.frozen or t.node.layer.bn_name in self.raw_bn or t.node.layer.name in shared_layers:
                 return None
             if t.id not in act_sums:
                 act_sums[t.id] = dict(buf=self._z(STAT_ROWS, 2, t.channels, dtype=torch.float64), parts=set())
@@ -890,6 +909,12 @@ class Plan:
                 return None
             b.update(scale=_fp(aff['scale'], aoff), shift=_fp(aff['shift'], aoff), mean=_fp(aff['mean'], aoff), rstd=_fp(aff['rstd'], aoff))
             return b, c
+
+        def act_form_unfit(t):
+            """t is the output of a BatchNorm with a zero gamma: its backward sums cannot be rebuilt from the activation (the fused
+            backward kernels' in-loader activation included) -- the separate reduce pass over the raw output forms them"""
+            P = t.node
+            return (P.op == 'cba' and P.layer.bn_name in self.raw_bn) or (P.op == 'concat_bn_relu' and P.layer.name in self.raw_bn)
 
         def dgrad_step(t, **kw):
             """data-gradient launch writing the activation gradient of tensor t (and, where the kernel can, the sums of the
@@ -1187,7 +1212,7 @@ class Plan:
                                             dw=rt.gptr(lay.name + '/kernel'), cin=pk['cin'], cout=cout, n=n, h=hh, w_=ww, dtype=dt, accumulate=accum, **sa)
                     # ... and, where the layer below is a BatchNorm + ReLU fed only by this gradient, the sums of ITS backward
                     # (what satcv_bn_bwd_reduce would compute in a pass over dx and that layer's raw output): bst_*
-                    bt = bst_target(tin) if (sa['in_relu'] and sa['in_scale'] is not None) else None
+                    bt = bst_target(tin) if (sa['in_relu'] and sa['in_scale'] is not None and not act_form_unfit(tin)) else None
                     sums_below = None
                     if bt is not None and bt[1] == cinp and bt[0].get('relu', 0) == 1:
                         sums_below = self._z(STAT_ROWS, 2, cinp, dtype=torch.float64)
@@ -1459,7 +1484,7 @@ class Plan:
                                             x=sa['x0'], ldx=sa['c0'], in_scale=sa['in_scale'], in_shift=sa['in_shift'], in_relu=sa['in_relu'],
                                             w_dgrad=pk['dgrad'].data_ptr(), w_npad=rup(cinp, 32), dx=gin.data_ptr(), lddx=cinp, dw=rt.gptr(lay.name + '/kernel'),
                                             cin=cinp, cout=cout, n=n, h=r.h, w_=r.w, dtype=dt)
-                    bt = bst_target(tin) if (sa['in_relu'] and sa['in_scale'] is not None) else None
+                    bt = bst_target(tin) if (sa['in_relu'] and sa['in_scale'] is not None and not act_form_unfit(tin)) else None
                     if bt is not None and bt[1] == cinp and bt[0].get('relu', 0) == 1:
                         sums_below = self._z(STAT_ROWS, 2, cinp, dtype=torch.float64)
                         fz.bst_sums, fz.bst_sums_ld, fz.bst_mean, fz.bst_rstd = _fp(sums_below), cinp, bt[0]['mean'], bt[0]['rstd']
