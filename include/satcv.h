@@ -138,6 +138,14 @@ typedef struct satcv_conv_desc {
    * persistent tiles, whose choice depends on the launch's tile count -- what a TRAINING plan asks for, per launch (round 6: this used to be
    * a process-global option toggled around the plan's steps).  Option igemm_m16 = 0 (SATCV_M16=0) still turns those tiles off. */
   int32_t tile_policy;
+  /* optional "pair store" (inference only): the two dates of a Siamese U-Net's shared encoder / ASPP layer run as ONE launch of
+   * n = 2 * pair_n images, and the channel concatenations concat([enc_b, enc_a]) / concat([aspp_b, aspp_a]) (utils/model_tools.py:608,
+   * 613, 624) become an address remap of the store: GEMM image i < pair_n (date a) goes to image i of y at channel offset pair_c0,
+   * image i >= pair_n (date b) to image i - pair_n at channel offset pair_c1; y is (pair_n, h, w_, ldy).  A fused max-pool (pool_y)
+   * is NOT remapped: it stays (2 * pair_n, h / pool_f, w_ / pool_f, pool_ld), the next shared encoder level's input.  pair_n = 0: off.
+   * Pipelined kernels only (satcv_conv2d_igemm_pipelined), no mode_out / accumulate / stats / bst_y, both offsets + cout within ldy
+   * and multiples of one 16-byte store vector. */
+  int32_t pair_n, pair_c0, pair_c1;
 } satcv_conv_desc;
 int satcv_conv2d_igemm(const satcv_conv_desc* d, void* stream);
 /* 1 if this descriptor runs on the pipelined kernel (required by out_scale / pool_y / the fp8 dtypes), else 0; no launch. */

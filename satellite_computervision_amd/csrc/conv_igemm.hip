@@ -334,6 +334,16 @@ static int igemm_fill_args(const satcv_conv_desc* d, IgemmArgs& a) {
   a.bst_y = d->bst_y; a.bst_y1 = d->bst_y1; a.bst_ld = d->bst_ld; a.bst_ld1 = d->bst_ld1; a.bst_split = d->bst_y1 ? d->bst_split : 0;
   a.bst_scale = d->bst_scale; a.bst_shift = d->bst_shift; a.bst_mean = d->bst_mean; a.bst_rstd = d->bst_rstd; a.bst_relu = d->bst_relu;
   a.tile_policy = d->tile_policy;
+  a.pair_n = d->pair_n; a.pair_c0 = d->pair_c0; a.pair_c1 = d->pair_c1;
+  if (d->pair_n || d->pair_c0 || d->pair_c1) {
+    // pair store: the remapped image / channel offset must stay inside y and keep the epilogue's 16-byte store vectors aligned
+    const int epv = d->dtype == SATCV_F32 ? 4 : (d->dtype == SATCV_BF16 ? 8 : 16);
+    SATCV_CHECK(d->pair_n > 0 && d->n == 2 * d->pair_n, "igemm: pair store needs n == 2 * pair_n (n=%d pair_n=%d)", d->n, d->pair_n);
+    SATCV_CHECK(!d->mode_out && !d->accumulate && !d->stats && !d->bst_y, "igemm: pair store needs a plain store (no mode_out / accumulate / stats / bst_y)");
+    SATCV_CHECK(d->pair_c0 >= 0 && d->pair_c1 >= 0 && d->pair_c0 + d->cout <= d->ldy && d->pair_c1 + d->cout <= d->ldy,
+                "igemm: pair channel offsets %d / %d + cout %d exceed ldy %d", d->pair_c0, d->pair_c1, d->cout, d->ldy);
+    SATCV_CHECK(d->pair_c0 % epv == 0 && d->pair_c1 % epv == 0, "igemm: pair channel offsets must be multiples of %d", epv);
+  }
   if (d->bst_y) {
     SATCV_CHECK(d->stats && d->bst_scale && d->bst_shift && d->bst_mean && d->bst_rstd, "igemm: bst_y needs stats and the four BatchNorm vectors");
     SATCV_CHECK(!d->accumulate && !d->mode_out && !d->out_relu && !d->pool_y && d->cstat == d->cout, "igemm: bst_y needs a plain, non-accumulating store");
@@ -390,7 +400,7 @@ extern "C" int satcv_conv2d_igemm(const satcv_conv_desc* d, void* stream) {
   }
   if (rc != SATCV_ERR_UNSUPPORTED) { /* launched (or failed hard) */ }
   else if (d->dtype == SATCV_FP8 || d->dtype == SATCV_FP8X) { satcv_set_error("igemm: this fp8 shape is outside the pipelined kernel's limits"); rc = SATCV_ERR_UNSUPPORTED; }
-  else if (d->out_scale || d->pool_y || d->bst_y) { satcv_set_error("igemm: out_scale / pool_y / bst_y need the pipelined kernel"); rc = SATCV_ERR_UNSUPPORTED; }
+  else if (d->out_scale || d->pool_y || d->bst_y || d->pair_n) { satcv_set_error("igemm: out_scale / pool_y / bst_y / pair store need the pipelined kernel"); rc = SATCV_ERR_UNSUPPORTED; }
   else if (d->dtype == SATCV_BF16) rc = launch_t<bf16>(a, st);
   else if (d->dtype == SATCV_F32) rc = launch_t<float>(a, st);
   else { satcv_set_error("igemm: bad dtype %d", d->dtype); rc = SATCV_ERR_INVALID; }

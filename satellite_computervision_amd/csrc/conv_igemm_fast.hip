@@ -621,7 +621,7 @@ __global__ __launch_bounds__(WM* WN * 64, (WPS ? WPS : (MT * NT <= 2 ? (KTraits<
         }
       return;
     } else
-    igemm_epilogue<T, TW, WM, WN, MT, NT, ABL(1), !DYN, true, M16>(a, acc, n0, y0, x0, nbase, smem_raw);      // (the dilated-halo instantiations sit at their register cap)
+    igemm_epilogue<T, TW, WM, WN, MT, NT, ABL(1), !DYN, true, M16, !DYN && !std::is_same<T, float>::value>(a, acc, n0, y0, x0, nbase, smem_raw);      // (the dilated-halo instantiations sit at their register cap)
 #ifdef SATCV_STAMP
     {
       unsigned long long k4;
@@ -790,6 +790,9 @@ static int fast_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
   const size_t lds = lds_stage + lds_tab > lds_out ? lds_stage + lds_tab : lds_out;
   if (lds > 160 * 1024) return SATCV_ERR_UNSUPPORTED;
   const bool dyn = TAPS == 9 && a.dil != 1;
+  // pair store (satcv.h): compiled into the bf16 / fp8 forms only, not into the dilated-halo instantiations (at their register cap; a dilated
+  // pair launch takes the tap loop) nor into fp32 storage (its instantiations carry scratch already) -- the epilogue's PAIR argument
+  if (a.pair_n && (dyn || std::is_same<T, float>::value)) return SATCV_ERR_UNSUPPORTED;
   long long blocks = (long long)a.ngroups * a.tiles_y * a.tiles_x * a.n_tiles;
   if (blocks <= 0 || blocks > 0x7fffffffLL) return SATCV_ERR_UNSUPPORTED;
   // ---- split-K (SK instantiations): a launch that leaves most of the chip idle (small maps: the 8 x 8 centre of the U-Net, a single
@@ -805,7 +808,7 @@ static int fast_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
     // tile puts 16 workgroups on the chip for 576 chunks of its stage-4 convolutions, 318 us per launch whatever the batch.
     const int splitk = g_opt_splitk;            // (satcv_set_option("splitk", 1): the build-defined DeepLab's inference plans set it around their launches)
     static const int splitk_tl = [] { const char* e = getenv("SATCV_SPLITK_TL"); return e ? atoi(e) : 1; }();
-    if ((TL ? splitk_tl : splitk) && !dyn && sizeof(T) == 2 && a.mode_out == 0 && !a.pool_y && !a.accumulate && !a.bst_y && a.cout % 8 == 0 && a.ldy % 8 == 0 &&
+    if ((TL ? splitk_tl : splitk) && !dyn && sizeof(T) == 2 && a.mode_out == 0 && !a.pool_y && !a.accumulate && !a.bst_y && !a.pair_n && a.cout % 8 == 0 && a.ldy % 8 == 0 &&
         a.stride == 1 && (!a.stats || (a.cout <= 1024 && 256 % (a.cout / 8) == 0))) {
       // (1 x 1 launches of a single tile: a 64-channel chunk costs a workgroup ~1.2 us of load latency whatever its MFMA count, so even
       //  16 chunks are worth cutting four ways -- 4 chunks per split + a ~7 us finish launch against 16 chunks in a row)

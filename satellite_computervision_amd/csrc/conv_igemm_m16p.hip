@@ -631,7 +631,7 @@ static int m16p_launch_bn(IgemmArgs& a, hipStream_t st, bool dry) {
 
 // SATCV_M16P_BN64=0: the 64-filter layers stay on the one-tile kernels (A/B switch of the round-6 64-channel block)
 int igemm_m16p_launch(IgemmArgs& a, int dtype, hipStream_t st, bool dry) {
-  if (dtype != SATCV_BF16) return SATCV_ERR_UNSUPPORTED;
+  if (dtype != SATCV_BF16 || a.pair_n) return SATCV_ERR_UNSUPPORTED;      // (its own store loop: no pair store, satcv.h)
   if (!g_opt_m16p) return SATCV_ERR_UNSUPPORTED;
   if (a.cout % 128 == 0) return m16p_launch_bn<128>(a, st, dry);
   static const int bn64 = [] { const char* e = getenv("SATCV_M16P_BN64"); return e ? atoi(e) : 1; }();

@@ -207,7 +207,8 @@ __global__ __launch_bounds__(256 * WN, WPS) void igemm_ws_kernel(const IgemmArgs
 #ifdef SATCV_STAMP
     STAMP(q6);
 #endif
-    igemm_epilogue<T, TW, WM, WN, MT, NT, WABL(1), true, false>(a, acc, tn0, ty0, tx0, 0, smem_raw, carry);
+    igemm_epilogue<T, TW, WM, WN, MT, NT, WABL(1), true, false, false, DIL == 1>(a, acc, tn0, ty0, tx0, 0, smem_raw, carry);      // (no pair store at
+    // dilation 3: the 16-channel instantiation sits at 168 registers, its third wave per SIMD)
 #ifdef SATCV_STAMP
     STAMP(q7);
 #endif
@@ -280,7 +281,7 @@ int igemm_ws_launch(IgemmArgs& a, int dtype, hipStream_t st, bool dry) {
   if (a.dil == 3) {
     // dilation 3 (atrous CNNs): 16 / 32 stored input channels -> 16 / 32 output channels (16: a 32-column tile whose upper half is zero weights;
     // the interior-tile epilogue skips the column groups beyond cout), bf16, no fused pool
-    if (dtype != SATCV_BF16 || a.pool_y || !(cin == 16 || cin == 32) || !(a.cout == 16 || a.cout == 32) || a.cout_pad != 32 || a.cstat != a.cout) return SATCV_ERR_UNSUPPORTED;
+    if (dtype != SATCV_BF16 || a.pool_y || a.pair_n || !(cin == 16 || cin == 32) || !(a.cout == 16 || a.cout == 32) || a.cout_pad != 32 || a.cstat != a.cout) return SATCV_ERR_UNSUPPORTED;
     if (a.x1 && (a.c0 % 8 != 0)) return SATCV_ERR_UNSUPPORTED;
     if (a.h % 8 != 0 || a.w_ % 32 != 0 || a.ldy % 8 != 0 || ((uintptr_t)a.y % 16) != 0) return SATCV_ERR_UNSUPPORTED;
     return cin == 16 ? ws_cfg<bf16, 16, 1, 2, 1, 3>(a, st, dry) : ws_cfg<bf16, 32, 1, 2, 1, 3>(a, st, dry);

@@ -458,7 +458,7 @@ static int convt_thin_dgrad_cfg(const ConvtDgradArgs& ca, hipStream_t st) {
 // the space-to-depth launch of satcv_conv2d_igemm (mode_in == 1): x0 = dy with c0 = COUT channels, cout = CIN
 int convt_thin_dgrad_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
   static const bool on = [] { const char* e = getenv("SATCV_CONVT_THIN"); return !e || atoi(e) != 0; }();
-  if (!on || dtype != SATCV_BF16) return SATCV_ERR_UNSUPPORTED;
+  if (!on || dtype != SATCV_BF16 || a.pair_n) return SATCV_ERR_UNSUPPORTED;      // (no pair store: satcv.h)
   if (a.kh != 1 || a.kw != 1 || a.mode_in != 1 || a.mode_out != 0 || a.f != 2 || a.x1 || a.stride != 1) return SATCV_ERR_UNSUPPORTED;
   if (a.out_scale || a.pool_y || a.accumulate || a.out_relu || a.in_scale || a.bias || a.bst_y1) return SATCV_ERR_UNSUPPORTED;
   if ((a.stats != nullptr) != (a.bst_y != nullptr)) return SATCV_ERR_UNSUPPORTED;      // (plain output statistics are not formed here)
@@ -484,7 +484,7 @@ int convt_thin_dgrad_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
 // SATCV_ERR_UNSUPPORTED outside the kernel's limits (the caller falls back to the tiled kernels)
 int convt_thin_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
   static const bool on = [] { const char* e = getenv("SATCV_CONVT_THIN"); return !e || atoi(e) != 0; }();
-  if (!on || dtype != SATCV_BF16) return SATCV_ERR_UNSUPPORTED;
+  if (!on || dtype != SATCV_BF16 || a.pair_n) return SATCV_ERR_UNSUPPORTED;
   if (a.kh != 1 || a.kw != 1 || a.mode_out != 1 || a.mode_in != 0 || a.f != 2 || a.x1 || a.stride != 1) return SATCV_ERR_UNSUPPORTED;
   if (a.pool_y || a.accumulate || a.bst_y || ((a.out_scale || a.out_relu) && a.stats)) return SATCV_ERR_UNSUPPORTED;      // (statistics are of the plain training output)
   const int cin = a.c0, cout_t = a.cstat;

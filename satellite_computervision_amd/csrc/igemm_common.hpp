@@ -31,6 +31,7 @@ struct IgemmArgs {
   // fp32 partial tile to kslab[split][pixel][cout]; satcv's finish kernel adds the slabs in order, applies the epilogue and the statistics
   int ksplit; float* kslab;
   int tile_policy;                 // satcv_conv_desc::tile_policy (0: option igemm_m16 decides, 2: every eligible launch on the 16x16x32 tiles)
+  int pair_n, pair_c0, pair_c1;    // satcv_conv_desc pair store: GEMM image i -> y image i % pair_n at channel offset pair_c0 / pair_c1 (0: off)
 };
 
 template <typename T>
@@ -146,7 +147,10 @@ __device__ __forceinline__ void mma16_step(f32x16 (&acc)[MT][NT], const FragT<bf
 // there instead of going to the replica rows with atomics, and the caller flushes them once per workgroup (stats_flush).
 // GENERAL = false: the caller guarantees interior tiles (whole tiles inside the image, every column valid, plain store): only the fast
 // path is compiled -- the persistent thin-layer kernel sits at its register cap and the masked path's live state spilled.
-template <typename T, int TW, int WM, int WN, int MT, int NT, bool SKIP_STORES = false, bool FAST = true, bool GENERAL = true, bool M16 = false>
+// PAIR = false: the pair store (satcv_conv_desc::pair_n) is compiled out -- instantiations whose launcher refuses it and that sit at an
+// occupancy step of their register count.
+template <typename T, int TW, int WM, int WN, int MT, int NT, bool SKIP_STORES = false, bool FAST = true, bool GENERAL = true, bool M16 = false,
+          bool PAIR = true>
 __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x16 (&acc)[MT][NT], int n0, int y0, int x0, int nbase, unsigned char* smem_raw,
                                                double* carry = nullptr) {
   constexpr int NTHREADS = WM * WN * 64, BM = WM * MT * 32, BN = WN * NT * 32;
@@ -293,7 +297,10 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x16 (&acc)
       yp = reinterpret_cast<T*>(a.y) + ((size_t)(n0 * a.h * f + y0 * f + ij / f) * wo + (size_t)x0 * f + ij % f) * a.ldy + cb;
       row_pitch = (size_t)f * wo * a.ldy; col_pitch = (size_t)f * a.ldy;
     } else {
-      yp = reinterpret_cast<T*>(a.y) + ((size_t)(n0 * a.h + y0) * a.w_ + x0) * a.ldy + nbase + vq * EPV;
+      // pair store (satcv.h): the tile is one image, so its date and with it the remap are uniform -- one offset of the base
+      T* yb = reinterpret_cast<T*>(a.y);
+      if (PAIR && a.pair_n) yb += n0 >= a.pair_n ? (ptrdiff_t)a.pair_c1 - (ptrdiff_t)a.pair_n * a.h * a.w_ * a.ldy : (ptrdiff_t)a.pair_c0;
+      yp = yb + ((size_t)(n0 * a.h + y0) * a.w_ + x0) * a.ldy + nbase + vq * EPV;
       row_pitch = (size_t)a.w_ * a.ldy; col_pitch = (size_t)a.ldy;
     }
     // (the interior-only instantiations also take tiles wider than the layer: a 32-column tile for 16 output channels -- thin dilated layers of
@@ -456,7 +463,11 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x16 (&acc)
     if (!((k < a.imgs) && (nimg < a.n) && (y < a.h) && (x < a.w_))) continue;
     size_t off;
     if (a.mode_out == 1) off = ((size_t)(nimg * ho + y * a.f + ij / a.f) * wo + x * a.f + ij % a.f) * a.ldy + cbase + cvec;
-    else off = ((size_t)(nimg * ho + y) * wo + x) * a.ldy + cbase + vq * EPV;
+    else {
+      off = ((size_t)(nimg * ho + y) * wo + x) * a.ldy + cbase + vq * EPV;
+      // pair store (satcv.h): a tile holding several small images may cross the date boundary -- the remap is per row
+      if (PAIR && a.pair_n) off += nimg >= a.pair_n ? (ptrdiff_t)a.pair_c1 - (ptrdiff_t)a.pair_n * ho * wo * a.ldy : (ptrdiff_t)a.pair_c0;
+    }
     const T* sp = ldsO + q * OPITCH + vq * EPV;
     if (SKIP_STORES) continue;
     if (a.accumulate) {

@@ -1,4 +1,4 @@
-"""FP8 (OCP e4m3fn) inference of the plain U-Net -- BASELINE config 5 ("1024x1024 large-tile sliding-window inference,
+"""FP8 (OCP e4m3fn) inference of the plain U-Net and the Siamese U-Net -- BASELINE config 5 ("1024x1024 large-tile sliding-window inference,
 fp8 MFMA conv path").  The reference has no reduced-precision path (all arithmetic fp32); this is the
 north-star's extension and is checked against the fp32 path of this build / the oracle by IoU.
 
@@ -12,6 +12,8 @@ Folded graph (inference only, `utils/model_tools.py:174-415` semantics):
   * max-pool runs on the fp8 values directly (monotone); concat([skip, up]) -> BN -> ReLU is materialised: the
     transposed conv writes its half through its epilogue, the skip half is re-quantised by `satcv_affine_requant`.
 MFMA: v_mfma_f32_32x32x16_fp8_fp8 (bf16 rate, half the operand bytes in HBM and LDS).
+Siamese graphs (utils/model_tools.py:576-663): the two dates of a shared encoder / ASPP layer run as one launch over 2n images whose
+epilogue stores straight into the channel concatenation (satcv_conv_desc pair store); see Fp8Plan._lower_dated.
 """
 import ctypes as C
 
@@ -27,6 +29,9 @@ USE_SCALED_MFMA = os.environ.get('SATCV_FP8_SCALED', '1') != '0'
 FUSE_POOL = os.environ.get('SATCV_FUSE_POOL', '1') != '0'
 HYBRID = os.environ.get('SATCV_FP8_HYBRID', '1') != '0'       # fp8 plans keep the full- and half-resolution levels in bf16 (Fp8Plan)
 THIN_FP8 = os.environ.get('SATCV_FP8_THIN', '1') != '0'       # fp8 levels: thin 3x3 convs on the persistent thin-layer kernel, two-source concatenations
+# Siamese graphs: the two dates of a shared encoder / ASPP layer as ONE launch of 2n images whose epilogue remaps the store into the channel
+# concatenation (satcv_conv_desc pair_n); SATCV_SIAMESE_PAIR=0: one launch per date (Fp8Plan(pair=False))
+SIAMESE_PAIR = os.environ.get('SATCV_SIAMESE_PAIR', '1') != '0'
 
 E4M3_MAX = 448.0
 BN_EPS = 1e-3
@@ -38,6 +43,12 @@ def _rup(a, b):
 
 def _relu_amax(t, scale, shift):
     return float((t.float() * scale + shift).clamp_min_(0).amax())
+
+
+def siamese_graph(model):
+    """True for graphs with channel concatenations (make_siamese_unet): the folded plan lowers them when asked to (enable_folded_inference /
+    enable_fp8_inference); the automatic folded default of bf16 models stays on the plain U-Net graphs."""
+    return any(nd.op == 'concat' for nd in model.nodes)
 
 
 def calibrate(model, x):
@@ -62,9 +73,10 @@ def calibrate(model, x):
             put(tid, float((held if held is not None else plan.x_by_tid[tid]).abs().amax()))
         elif node.op == 'cba':
             y, aff, c = cx['y'], cx['aff'], cx['cout']
-            if cx['yoff'] != 0 or cx['ldy'] != c:
-                raise NotImplementedError('fp8 inference: ASPP / slot-mode concatenations are not lowered')
-            put(node.outputs[0].id, _relu_amax(y, aff['scale'], aff['shift']))
+            yoff, ldy, aoff = cx['yoff'], cx['ldy'], cx.get('aoff', 0)
+            if yoff != 0 or ldy != c:           # branch of a concatenation (ASPP): its channel slice of the shared tensor
+                y = y.reshape(-1, ldy)[:, yoff:yoff + c]
+            put(node.outputs[0].id, _relu_amax(y, aff['scale'][aoff:aoff + c], aff['shift'][aoff:aoff + c]))
         elif node.op == 'concat_bn_relu':
             ra, rb, aff, ca = cx['ra'], cx['rb'], cx['aff'], cx['ca']
             a = _relu_amax(ra.srcs[0][0], aff['scale'][:ca], aff['shift'][:ca])
@@ -89,7 +101,7 @@ class _Ones:
 class Fp8Plan:
     """Static launch list of the folded fp8 forward for one (n, h, w)."""
 
-    def __init__(self, model, n, h, w, q, first_bf16=True, store=FP8, hybrid=None):
+    def __init__(self, model, n, h, w, q, first_bf16=True, store=FP8, hybrid=None, pair=None):
         # store = BF16: the same folded graph with bf16 tensors and no quantisation (every scale 1) -- BatchNorm in the conv epilogues
         # instead of the consumers' loaders, activations written once
         # hybrid (fp8 store only, default on: SATCV_FP8_HYBRID=0 turns it off): the full- and half-resolution levels keep bf16 tensors and
@@ -97,8 +109,11 @@ class Fp8Plan:
         # weights-stationary kernel, fused pooling and a two-source loader only in bf16 (their fp8 forms went through the general tiled
         # kernel plus a requantisation pass per concatenation and were SLOWER than bf16: 1.32 vs 0.83 ms per batch of 64); the deep
         # layers are where e4m3 pays, on the block-scaled K = 64 MFMA at twice the bf16 rate.
+        # pair (Siamese graphs, default SATCV_SIAMESE_PAIR): a shared layer's two dates as one launch with a pair store; False: one launch
+        # per date into the same channel slices (the bit-exact yardstick of the remap)
         self.model, self.n, self.h, self.w, self.first_bf16, self.store = model, n, h, w, first_bf16, store
         self.hybrid = (HYBRID if hybrid is None else bool(hybrid)) and store == FP8
+        self.pair = SIAMESE_PAIR if pair is None else bool(pair)
         self.q = q if store == FP8 else _Ones()
         self.tdt = torch.bfloat16 if store == BF16 else torch.float8_e4m3fn
         self.rt = model.runtime
@@ -152,6 +167,60 @@ class Fp8Plan:
         self.keep.append(fwd)
         return fwd, wscale, dt
 
+    def _dates(self):
+        """Two-date structure of a Siamese graph (make_siamese_unet): tensor id -> date (0: input a, 1: input b) of every tensor computed
+        from one input alone, tensor id -> its twin (the same layers applied to the other date), and a scale group per tensor -- twins,
+        the two halves of a concatenation and the branches of an ASPP slot tensor share one tensor (and so one fp8 scale)."""
+        m = self.model
+        date, sig, bysig = {}, {}, {}
+        if len(m.inputs) == 2:
+            for d, t in enumerate(m.inputs):
+                date[t.id], sig[t.id] = d, ('input',)
+                bysig[(sig[t.id], d)] = t.id
+        for node in m.nodes:
+            ds = {date.get(t.id, -1) for t in node.inputs}
+            if node.op == 'input' or len(ds) != 1 or -1 in ds:
+                continue
+            d = ds.pop()
+            for t in node.outputs:
+                date[t.id] = d
+                sig[t.id] = (node.op, id(node.layer) if node.layer is not None else None, node.attrs.get('f'), node.attrs.get('dil'),
+                             tuple(sig[u.id] for u in node.inputs))
+                bysig[(sig[t.id], d)] = t.id
+        twin = {tid: bysig[(sig[tid], 1 - d)] for tid, d in date.items() if (sig[tid], 1 - d) in bysig}
+        parent = {}
+
+        def find(t):
+            while parent.get(t, t) != t:
+                t = parent[t]
+            return t
+
+        def union(a, b):
+            parent[find(a)] = find(b)
+        for a_, b_ in twin.items():
+            union(a_, b_)
+        for node in m.nodes:
+            if node.op == 'concat':
+                for t in node.inputs:
+                    union(t.id, node.outputs[0].id)
+        return date, twin, find
+
+    def _qof(self, tid):
+        """fp8 scale of a tensor: the largest calibrated scale of its group (_dates)"""
+        if self.store != FP8:
+            return 1.0
+        g = self._group(tid)
+        return max(v for k, v in self.q.items() if self._group(k) == g)
+
+    def _tr_serves(self, b16, k, dil, cin_s, cout, ww):
+        """True where conv_thin_roles.hip takes the launch (igemm_tr_launch: it has no pair store, and its K order differs from the
+        weights-stationary kernel that would take the paired launch): such a shared layer keeps one launch per date on it."""
+        on, thin = C.c_int(0), C.c_int(0)
+        check(lib.satcv_get_option(b'thin_roles', C.byref(on)))
+        check(lib.satcv_get_option(b'igemm_thin', C.byref(thin)))
+        return (b16 and on.value > 0 and thin.value > 0 and k == 3 and dil == 1 and cout in (32, 64) and ww % 32 == 0 and cin_s in (16, 32, 64)
+                and (cin_s == 32 or on.value >= 2) and not (cin_s == 64 and cout == 64))
+
     def _conv(self, dtype=None, **kw):
         dtype = dtype if dtype is not None else self.store
         d = ops.make_conv_desc(dtype=dtype, out_relu=1, **kw)
@@ -175,8 +244,24 @@ class Fp8Plan:
         vals = {}                                        # tensor id -> (tensor [uint8 viewed as fp8, or bf16], channels, h, w, q [1.0 for bf16])
         prepooled = {}                                   # conv output tensor id -> its max-pooled tensor written by the conv epilogue
         cats = {}                                        # concat_bn_relu node id -> (cat tensor, ca, cb, q_cat, bn scale, bn shift)
+        # Siamese graphs: a tensor of one date lives in images [d n, d n + n) of a 2n-image tensor it shares with its twin
+        date, twin, self._group = self._dates()
+        self._dated_seen = set()
+        catbuf = {}                                      # concat node id -> the tensor its producers write (pair concat: n images, ASPP slots: 2n)
         for node in m.nodes:
             op = node.op
+            if node.outputs and node.outputs[0].id in date:
+                self._lower_dated(node, vals, date, twin, consumers, catbuf, prepooled)
+                continue
+            if op == 'concat':
+                # concat([x_b, x_a]) of the two dates: written by its producers' (pair) stores
+                tout = node.outputs[0]
+                if id(node) not in catbuf:
+                    raise NotImplementedError('folded inference: a concatenation that is not the pair store of a shared layer')
+                hh, ww = vals[node.inputs[0].id][2:4]
+                buf = catbuf[id(node)]
+                vals[tout.id] = (buf, tout.channels, hh, ww, 1.0 if buf.dtype == B16 else self._qof(tout.id))      # (bf16 tensors: scale 1)
+                continue
             if op == 'input':
                 t = node.outputs[0]
                 cp = _rup(t.channels, 16)
@@ -366,7 +451,165 @@ class Fp8Plan:
             elif op == 'classes':
                 self.outputs[node.outputs[0].id] = self._classes
             else:
-                raise NotImplementedError(f'fp8 inference: op {op} is not lowered (plain U-Net graphs only)')
+                raise NotImplementedError(f'fp8 inference: op {op} is not lowered (plain and Siamese U-Net graphs only)')
+
+    def _lower_dated(self, node, vals, date, twin, consumers, catbuf, prepooled):
+        """One op of the two-date part of a Siamese graph (inference: the shared layers' weights and moving statistics are the same for
+        both dates, so the two calls of a layer are one launch over 2n images).  Lowered once, at the LATER of the two twin nodes: the node
+        list need not interleave the dates (the second input may be staged after the first date's encoder), and the launch reads both."""
+        n, rt, B16 = self.n, self.rt, torch.bfloat16
+        op, tout = node.op, node.outputs[0]
+        if tout.id in vals:
+            return
+        tw = twin.get(tout.id)
+        if tw is None:
+            raise NotImplementedError(f'folded inference: a {op} applied to one date only')
+        if op == 'input':
+            t = tout
+            cp = _rup(t.channels, 16)
+            xin = self._z(n, self.h, self.w, t.channels, dtype=torch.float32)
+            self.x_by_tid[t.id] = xin
+            if not (self.first_bf16 or self.store == BF16 or self.hybrid):
+                raise NotImplementedError('folded inference: a Siamese graph with fp8 input bands')
+            x2 = getattr(self, '_x2', None)
+            if x2 is None:
+                x2 = self._x2 = self._z(2 * n, self.h, self.w, cp, dtype=B16)
+            npix = n * self.h * self.w
+            dst = x2.data_ptr() + date[t.id] * npix * cp * 2
+            self.fwd.append(lambda st, xin=xin, dst=dst, npix=npix, cc=t.channels, cp=cp: check(
+                lib.satcv_ingest_nhwc(xin.data_ptr(), dst, npix, cc, cp, BF16, st)))
+            vals[t.id] = (x2, cp, self.h, self.w, 1.0 if self._hi(self.h, self.w) else None)
+            if tw in self.x_by_tid:
+                del self._x2                              # (both inputs staged: the next pair of inputs would get its own tensor)
+            return                                        # (the twin input is lowered at its own node: one staging slot per input)
+        if tw not in self._dated_seen:
+            self._dated_seen.add(tout.id)
+            return
+        if op == 'dropout':
+            vals[tout.id] = vals[tw] = vals[node.inputs[0].id]
+            return
+        if op == 'pool':
+            tin = node.inputs[0]
+            if tin.id in prepooled:                      # written by the conv's epilogue (both dates)
+                vals[tout.id] = vals[tw] = prepooled[tin.id]
+                return
+            x2, c, hh, ww, qin = vals[tin.id]
+            f = node.attrs['f']
+            if x2 is None:
+                raise NotImplementedError('folded inference: a shared encoder level whose max-pool did not fuse into the pair store')
+            if hh % f or ww % f:
+                raise ValueError(f'input {self.h}x{self.w} is not divisible by the model downsampling')
+            b16 = x2.dtype == B16
+            p2 = self._z(2 * n, hh // f, ww // f, c, dtype=B16 if b16 else None)
+            self.fwd.append(lambda st, x2=x2, p2=p2, hh=hh, ww=ww, c=c, f=f, dt_=BF16 if b16 else self.store: check(
+                lib.satcv_maxpool(x2.data_ptr(), p2.data_ptr(), 2 * n, hh, ww, c, f, f, 0, dt_, st)))
+            if b16 and not self._hi(hh // f, ww // f):
+                qp = self._qof(tin.id)
+                pq = self._z(2 * n, hh // f, ww // f, c)
+                self._requant(p2, c, 2 * n * (hh // f) * (ww // f), 1.0 / qp, BF16, FP8, pq)
+                p2, qin = pq, qp
+            vals[tout.id] = vals[tw] = (p2, c, hh // f, ww // f, qin)
+            return
+        if op == 'concat':                               # ASPP slot tensor: written by its branches
+            buf = catbuf[id(node)]
+            vals[tout.id] = vals[tw] = (buf, tout.channels) + vals[node.inputs[0].id][2:4] + (1.0 if buf.dtype == B16 else self._qof(tout.id),)
+            return
+        if op != 'cba':
+            raise NotImplementedError(f'folded inference: op {op} on the two-date part of a Siamese graph')
+        tin = node.inputs[0]
+        x2, cin_s, hh, ww, qin = vals[tin.id]
+        lay = node.layer
+        if x2 is None or qin is None:
+            raise NotImplementedError(f'{lay.name}: input of a shared layer not lowered')
+        if node.attrs.get('stride', 1) != 1 or not node.attrs.get('relu', True):
+            raise NotImplementedError('fp8 inference: strided / linear conv blocks are not lowered')
+        kernel = rt.get_param(lay.name + '/kernel')
+        cout, k, dil = tout.channels, node.attrs['k'], node.attrs['dil']
+        if cout % 16 or cin_s != _rup(kernel.shape[2], 16):
+            raise NotImplementedError(f'{lay.name}: unsupported channel counts for the fp8 path')
+        if k == 3 and dil > 1 and dil >= hh and dil >= ww:
+            # every off-centre tap reads only zero padding (ASPP's dilation 6 / 12 on small maps): the 1x1 conv of the centre tap
+            kernel, k, dil = kernel[1:2, 1:2], 1, 1
+        b16 = self._hi(hh, ww)
+        if b16 != (x2.dtype == B16):
+            raise NotImplementedError(f'{lay.name}: input and output of a conv block live on different sides of the bf16 / fp8 boundary')
+        thin = (THIN_FP8 and not b16 and k == 3 and dil == 1 and cin_s in (32, 64) and cout in (32, 64) and hh % 8 == 0 and ww % 32 == 0)
+        # (dilated convs: plain e4m3 -- the tap-loop tile has no block-scaled form)
+        w8, wscale, cdt = self._pack(kernel, cin_s, False, b16, thin or dil > 1)
+        s, t_ = self._bn(lay.bn_name)
+        qo = 1.0 if b16 else self._qof(tout.id)
+        oscale = self._f32(qin * wscale * s / qo)
+        obias = self._f32((s * rt.get_param(lay.name + '/bias') + t_) / qo)
+        ydt = B16 if b16 else None
+        esz_in, esz = x2.element_size(), (2 if b16 else 1)
+        cons = consumers.get(tout.id, [])
+        catn = [cn for cn in cons if cn.op == 'concat']
+        pooln = [cn for cn in cons if cn.op == 'pool']
+        if len(catn) + len(pooln) != len(cons) or len(catn) > 1 or len(pooln) > 1:
+            raise NotImplementedError(f'{lay.name}: consumers of a shared layer not lowered')
+        cat = catn[0] if catn else None
+        pair_cat = cat is not None and len({date.get(t.id) for t in cat.inputs}) == 2
+        base = dict(c0=cin_s, w=w8.data_ptr(), bias=obias.data_ptr(), out_scale=oscale.data_ptr(), h=hh, w_=ww, cout=cout,
+                    cout_pad=_rup(cout, 32), kh=k, kw=k, dil=dil, dtype=cdt)
+        pool_f = pooln[0].attrs['f'] if pooln else 0
+        if pooln and (hh % pool_f or ww % pool_f):
+            raise ValueError(f'input {self.h}x{self.w} is not divisible by the model downsampling')
+        p2 = self._z(2 * n, hh // pool_f, ww // pool_f, cout, dtype=ydt) if pooln else None
+        pix, ppix = hh * ww, (hh // pool_f) * (ww // pool_f) if pooln else 0
+        if pair_cat:
+            # the channel concatenation of the two dates, (n, hh, ww, ctot): date d's half at the channel offset of its tensor
+            ctot = cat.outputs[0].channels
+            offs = {}
+            o = 0
+            for t in cat.inputs:
+                offs[date[t.id]] = o
+                o += t.channels
+            if id(cat) not in catbuf:
+                catbuf[id(cat)] = self._z(n, hh, ww, ctot, dtype=ydt)
+            y = catbuf[id(cat)]
+            paired = self.pair and not self._tr_serves(b16, k, dil, cin_s, cout, ww)
+            if paired:
+                launches = [dict(x0=x2.data_ptr(), n=2 * n, y=y.data_ptr(), ldy=ctot, pair=(n, offs[0], offs[1]),
+                                 pool=dict(pool_y=p2.data_ptr(), pool_ld=cout, pool_f=pool_f) if pooln else {})]
+            else:
+                launches = [dict(x0=x2.data_ptr() + d * n * pix * cin_s * esz_in, n=n, y=y.data_ptr() + offs[d] * esz, ldy=ctot,
+                                 pool=dict(pool_y=p2.data_ptr() + d * n * ppix * cout * esz, pool_ld=cout, pool_f=pool_f) if pooln else {})
+                            for d in (0, 1)]
+            for L in launches:
+                pool_kw = L.pop('pool')
+                if pool_kw and not (FUSE_POOL and lib.satcv_conv2d_igemm_pipelined(C.byref(ops.make_conv_desc(out_relu=1, **base, **L, **pool_kw)))):
+                    raise NotImplementedError(f'{lay.name}: the max-pool of a shared encoder level does not fuse into its conv')
+                self._conv(**base, **L, **pool_kw)
+            vals[tout.id] = vals[tw] = (None, cout, hh, ww, qo)            # (read only through the concatenation and the pooled map)
+        else:
+            if cat is not None:                          # a branch of a slot concatenation (ASPP): its channel slice of one 2n-image tensor
+                ctot = cat.outputs[0].channels
+                o = sum(t.channels for t in cat.inputs[:cat.inputs.index(tout)])
+                key = id(cat)
+                if key not in catbuf:                    # (one tensor for the slot concatenations of both dates)
+                    tcat = twin[cat.outputs[0].id]
+                    buf = self._z(2 * n, hh, ww, ctot, dtype=ydt)
+                    for nd in self.model.nodes:
+                        if nd is cat or (nd.op == 'concat' and nd.outputs[0].id == tcat):
+                            catbuf[id(nd)] = buf
+                y, yoff, ldy = catbuf[key], o, ctot
+            else:
+                y, yoff, ldy = self._z(2 * n, hh, ww, cout, dtype=ydt), 0, cout
+            pool_kw = dict(pool_y=p2.data_ptr(), pool_ld=cout, pool_f=pool_f) if pooln else {}
+            ckw = dict(base, x0=x2.data_ptr(), n=2 * n, y=y.data_ptr() + yoff * esz, ldy=ldy)
+            if pool_kw and not (FUSE_POOL and lib.satcv_conv2d_igemm_pipelined(C.byref(ops.make_conv_desc(out_relu=1, **ckw, **pool_kw)))):
+                pool_kw, p2 = {}, None
+            self._conv(**ckw, **pool_kw)
+            vals[tout.id] = vals[tw] = (y if ldy == cout else None, cout, hh, ww, qo)
+        if p2 is not None:
+            pooled = (p2, cout, hh // pool_f, ww // pool_f, qo)
+            if b16 and not self._hi(hh // pool_f, ww // pool_f):
+                # the pooled map belongs to the fp8 levels: quantise it (the scale of the un-pooled activation: max-pooling cannot exceed it)
+                qp = self._qof(tout.id)
+                pq = self._z(2 * n, hh // pool_f, ww // pool_f, cout)
+                self._requant(p2, cout, 2 * n * ppix, 1.0 / qp, BF16, FP8, pq)
+                pooled = (pq, cout, hh // pool_f, ww // pool_f, qp)
+            prepooled[tout.id] = prepooled[tw] = pooled
 
     def run_forward(self, st):
         for f in self.fwd:

@@ -1015,9 +1015,10 @@ class Model:
         return self.runtime.plan(n, h, w, training)
 
     def enable_fp8_inference(self, calibration_tiles):
-        """Switch predict / predict_on_device / predict_chips to the folded fp8 (e4m3) graph of fp8_infer.py.  The
-        per-tensor activation scales come from one regular inference run on `calibration_tiles` (NHWC); the weights
-        are re-quantised from the current fp32 parameters here, so call it again after training or load_weights."""
+        """Switch predict / predict_on_device / predict_chips to the folded fp8 (e4m3) graph of fp8_infer.py (plain U-Net and Siamese
+        U-Net graphs; a Siamese model takes the pair [xa_cal, xb_cal]).  The per-tensor activation scales come from one regular inference
+        run on `calibration_tiles` (NHWC); the weights are re-quantised from the current fp32 parameters when they change, the scales
+        only here: call it again after training or load_weights."""
         from . import fp8_infer
         self._fp8_q = fp8_infer.calibrate(self, calibration_tiles)
         self._fp8_store = fp8_infer.FP8
@@ -1026,7 +1027,7 @@ class Model:
 
     def enable_folded_inference(self):
         """bf16 inference on the folded graph of fp8_infer.py (BatchNorm + bias in the conv epilogues, activations written once,
-        no quantisation): plain U-Net graphs only."""
+        no quantisation): plain U-Net and Siamese U-Net graphs (the two dates of a shared layer as one launch, fp8_infer.SIAMESE_PAIR)."""
         from . import fp8_infer
         self._fp8_q, self._fp8_store, self._fp8_plans = {}, fp8_infer.BF16, {}
         return self
@@ -1039,17 +1040,20 @@ class Model:
 
     def _infer_plan(self, n, h, w):
         """inference launch list: the fp8 graph when enabled, else the folded bf16 graph (BatchNorm in the conv epilogues: 12 %
-        faster than the training-style plan) for bf16 models it can lower, else the regular plan (fp32 parity mode, ASPP /
-        Siamese / DeepLab graphs)."""
+        faster than the training-style plan) for bf16 plain U-Net models, else the regular plan (fp32 parity mode; Siamese graphs
+        unless enable_folded_inference / enable_fp8_inference asked for the folded one; DeepLab graphs)."""
         from . import fp8_infer
         key = (n, h, w)
+        ver = getattr(self, '_weights_version', 0)
         if getattr(self, '_fp8_q', None) is not None:
-            if key not in self._fp8_plans:
-                self._fp8_plans[key] = fp8_infer.Fp8Plan(self, n, h, w, self._fp8_q, store=self._fp8_store)
-            return self._fp8_plans[key]
-        if self.compute_dtype == 'bfloat16' and getattr(self, '_folded_ok', True) and os.environ.get('SATCV_FOLDED_INFER', '1') != '0':
+            plan = self._fp8_plans.get(key)
+            if plan is None or getattr(plan, 'weights_version', ver) != ver:      # folded weights follow training / set_weights_dict
+                plan = self._fp8_plans[key] = fp8_infer.Fp8Plan(self, n, h, w, self._fp8_q, store=self._fp8_store)
+                plan.weights_version = ver
+            return plan
+        if (self.compute_dtype == 'bfloat16' and getattr(self, '_folded_ok', True) and os.environ.get('SATCV_FOLDED_INFER', '1') != '0'
+                and not fp8_infer.siamese_graph(self)):
             plans = self.__dict__.setdefault('_folded_plans', {})
-            ver = getattr(self, '_weights_version', 0)
             if key not in plans or plans[key].weights_version != ver:       # BN / bias / weight images are baked in at build time
                 try:
                     plans[key] = fp8_infer.Fp8Plan(self, n, h, w, None, store=fp8_infer.BF16)
