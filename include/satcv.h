@@ -462,6 +462,47 @@ int satcv_label_onehot(const void* lc, int32_t lc_kind, const int32_t* lut, cons
                        int32_t n, int32_t hin, int32_t win, int32_t h, int32_t w_, int32_t nclasses, int32_t flip_v, int32_t flip_h,
                        int32_t rot, float* dst, int32_t ldc, int32_t coff, void* stream);
 
+/* ------------------------------------------------------------------ device-resident scene prediction
+ * The sliding-window loop of predict_pc_local / predict_chips (utils/prediction_tools.py:133-156) with the scene and the
+ * prediction map resident on the device.  `origins` is a device int32 (total, 2) table of (y, x): the upper-left corner of each
+ * chip's CENTRE in scene coordinates -- what generate_chip_indices (:87-109) returns -- uploaded once per scene; a launch
+ * takes chips [first, first + n).
+ *
+ * satcv_scene_gather replaces the window slicing of :149 and np.array([chip]) of :152.
+ *   src: scene (h, w_, c), HWC contiguous, of kind 0 u8, 1 u16, 2 f32, 3 i16 (the kinds of satcv_tile_desc)
+ *   value = (float)((double)src / rescale), rescale 0 = none (satcv_tile_ingest's convention)
+ *   chip k reads scene rows y - off .. y - off + side - 1 and columns likewise (off = buff / 2, side = kernel + buff).
+ *   Out-of-scene coordinates are mirrored without repeating the edge sample (np.pad mode='reflect': i < 0 -> -i,
+ *   i >= h -> 2 (h - 1) - i) and then clamped to [0, h - 1]: the kernel never reads outside the scene, whatever the table holds
+ *   dst: fp32 NHWC (n, side, side, ldc) written at channel offset coff */
+typedef struct {
+  const void* src; int32_t src_kind;
+  int32_t h, w_, c;
+  double rescale;
+  const int32_t* origins; int32_t total, first, n;
+  int32_t off, side;
+  float* dst; int32_t ldc, coff;
+} satcv_scene_gather_desc;
+int satcv_scene_gather(const satcv_scene_gather_desc* d, void* stream);
+/* satcv_scene_scatter replaces the crop and `template[...] +=` of :154 and the crops of :267 / :349.
+ *   src: (n, sh, sw, lds) of kind 2 f32 (probabilities) or 5 i32 (classes), channels [c0, c0 + nc)
+ *   the crop_h x crop_w window starting at (crop_y, crop_x) of chip k is placed at map position origins[first + k], clipped to
+ *   [0, h) x [0, w_)
+ *   dst: map (h, w_, ldd) of kind 2 f32 or 0 u8 (class maps: needs an i32 source and accumulate 0), written at channel offset doff;
+ *   accumulate 1: dst += src, 0: dst = src
+ * Contract: the placed windows of the chips of ONE launch are pairwise disjoint (plain read-modify-write, no atomics); launches on a
+ * stream are ordered, so overlapping chips go into separate launches and the result is deterministic. */
+typedef struct {
+  const void* src; int32_t src_kind;
+  int32_t n, sh, sw, lds, c0, nc;
+  int32_t crop_y, crop_x, crop_h, crop_w;
+  const int32_t* origins; int32_t total, first;
+  void* dst; int32_t dst_kind;
+  int32_t h, w_, ldd, doff;
+  int32_t accumulate;
+} satcv_scene_scatter_desc;
+int satcv_scene_scatter(const satcv_scene_scatter_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ losses
  * Each writes loss_out[0] += mean loss contribution (caller zeroes) and
  * dlogits = dL/dlogits (through the head activation).

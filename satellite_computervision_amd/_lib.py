@@ -46,6 +46,19 @@ class TileDesc(C.Structure):
                 ('dst', c_vp), ('ldc', c_i32), ('coff', c_i32)]
 
 
+class SceneGatherDesc(C.Structure):
+    _fields_ = [('src', c_vp), ('src_kind', c_i32), ('h', c_i32), ('w_', c_i32), ('c', c_i32), ('rescale', C.c_double),
+                ('origins', c_vp), ('total', c_i32), ('first', c_i32), ('n', c_i32), ('off', c_i32), ('side', c_i32),
+                ('dst', c_vp), ('ldc', c_i32), ('coff', c_i32)]
+
+
+class SceneScatterDesc(C.Structure):
+    _fields_ = [('src', c_vp), ('src_kind', c_i32), ('n', c_i32), ('sh', c_i32), ('sw', c_i32), ('lds', c_i32), ('c0', c_i32), ('nc', c_i32),
+                ('crop_y', c_i32), ('crop_x', c_i32), ('crop_h', c_i32), ('crop_w', c_i32),
+                ('origins', c_vp), ('total', c_i32), ('first', c_i32), ('dst', c_vp), ('dst_kind', c_i32),
+                ('h', c_i32), ('w_', c_i32), ('ldd', c_i32), ('doff', c_i32), ('accumulate', c_i32)]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [('x0', c_vp), ('x1', c_vp), ('c0', c_i32), ('c1', c_i32),
                 ('in_scale', c_vp), ('in_shift', c_vp), ('in_relu', c_i32),
@@ -177,6 +190,8 @@ _SIGS = {
     'satcv_dropout_apply': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'satcv_tile_channel_mean': (C.c_int, [C.POINTER(TileDesc), c_vp, c_vp]),
     'satcv_tile_ingest': (C.c_int, [C.POINTER(TileDesc), c_vp]),
+    'satcv_scene_gather': (C.c_int, [C.POINTER(SceneGatherDesc), c_vp]),
+    'satcv_scene_scatter': (C.c_int, [C.POINTER(SceneScatterDesc), c_vp]),
     'satcv_label_onehot': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
     'satcv_crc32c': (C.c_uint32, [c_vp, C.c_uint64, C.c_uint32]),
     'satcv_head_fwd': (C.c_int, [C.POINTER(HeadDesc), c_vp]),

@@ -86,3 +86,259 @@ def predict_chips_sharded(arr, chip_indices, template, m, kernel=256, buff=128, 
     parallel.reduce_templates(t)
     template += t.cpu().numpy().astype(template.dtype)
     return template
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Device-resident scene prediction: the scene goes to the device once, windows are cut there (satcv_scene_gather), the model reads them
+# in place (Model.predict_on_device) and the centres are stitched into a device-resident map (satcv_scene_scatter).  Layout, the
+# reflect rule and the disjointness contract: DESIGN.md, "Device-resident scene prediction".
+_SCENE_KIND = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float32): 2, np.dtype(np.int16): 3}     # kinds of satcv_tile_desc
+
+
+def _disjoint_runs(origins, height, width):
+    """Greedy split, in list order, of placed height x width rectangles with upper-left corners `origins` [(y, x)] into consecutive runs
+    [(start, stop)] whose rectangles are pairwise disjoint: a rectangle that overlaps one of the current run opens the next run.  One
+    run is one scatter launch (its contract: no two chips of a launch write the same pixel); runs are launched in order."""
+    runs, start = [], 0
+    for i, (y, x) in enumerate(origins):
+        if any(abs(y - origins[j][0]) < height and abs(x - origins[j][1]) < width for j in range(start, i)):
+            runs.append((start, i))
+            start = i
+    if len(origins) > start:
+        runs.append((start, len(origins)))
+    return runs
+
+
+def full_cover_indices(shape, kernel=256):
+    """Centre origins of the full-cover grid of an (H, W[, C]) scene: range(0, H, kernel) x range(0, W, kernel).  The centres tile the
+    scene, the last row / column clipped by the scatter, so every pixel is predicted exactly once."""
+    H, W = int(shape[0]), int(shape[1])
+    return [(y, x) for y in range(0, H, kernel) for x in range(0, W, kernel)]
+
+
+def _check_geometry(kernel, buff, batch_size):
+    if int(kernel) < 1 or int(buff) < 0 or int(batch_size) < 1:
+        raise ValueError(f'kernel and batch_size must be positive and buff non-negative, got kernel={kernel}, buff={buff}, batch_size={batch_size}')
+
+
+def _check_windows(idx, H, W, kernel, off):
+    for y, x in idx:
+        if y - off < 0 or x - off < 0 or y + kernel + off > H or x + kernel + off > W:
+            raise ValueError(f'chip index ({y}, {x}): its window rows {y - off}:{y + kernel + off}, columns {x - off}:{x + kernel + off} '
+                             f'leaves the {H} x {W} scene')
+
+
+def _patch_grid(patches, cols, patch_hw, kernel_shape, kernel_buffer):
+    """Placement rule of callback_predictions (utils/prediction_tools.py:245-291), as coded there.  Returns
+    (crop, origins, mosaic_hw): crop = (row0, col0, height, width) of the window kept of every patch, origins = [(y, x)] of the kept
+    patches in the mosaic.
+
+    The half buffers are x_buffer = kernel_buffer[0] // 2 and y_buffer = kernel_buffer[1] // 2.  The window keeps patch rows from
+    y_buffer up to (not including) kernel_shape[1] + x_buffer and columns from x_buffer up to kernel_shape[0] + y_buffer (:258-267: the
+    start of each axis uses its own buffer, the stop the other axis' one), limited to the patch like any NumPy slice.  Patch i goes to
+    mosaic row i // cols, column i % cols; only complete mosaic rows are kept (:282-288), so a trailing partial row is dropped."""
+    patches, cols = int(patches), int(cols)
+    if cols < 1 or patches // cols < 1:
+        raise ValueError(f'totalPatches={patches} does not fill one mosaic row of patchesPerRow={cols}')
+    x_buffer, y_buffer = int(kernel_buffer[0] / 2), int(kernel_buffer[1] / 2)
+    row0, row1 = y_buffer, min(int(kernel_shape[1]) + x_buffer, int(patch_hw[0]))
+    col0, col1 = x_buffer, min(int(kernel_shape[0]) + y_buffer, int(patch_hw[1]))
+    if row1 <= row0 or col1 <= col0:
+        raise ValueError(f'empty crop rows {row0}:{row1}, columns {col0}:{col1} of a {patch_hw[0]} x {patch_hw[1]} patch')
+    ch, cw = row1 - row0, col1 - col0
+    rows = patches // cols
+    origins = [((i // cols) * ch, (i % cols) * cw) for i in range(rows * cols)]
+    return (row0, col0, ch, cw), origins, (rows * ch, cols * cw)
+
+
+def _to_device(a, what):
+    import torch
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint16:
+        a = a.view(np.int16)                 # (bytes only: the kernel is told the real kind)
+    try:
+        return torch.from_numpy(a).to('cuda')
+    except torch.cuda.OutOfMemoryError as e:
+        raise MemoryError(f'{what} of {a.nbytes / 2 ** 20:.0f} MiB does not fit in device memory (scenes are not tiled into strips)') from e
+
+
+def _device_empty(shape, dtype, what, fill=None):
+    import torch
+    try:
+        return torch.empty(shape, dtype=dtype, device='cuda') if fill is None else torch.full(shape, fill, dtype=dtype, device='cuda')
+    except torch.cuda.OutOfMemoryError as e:
+        raise MemoryError(f'{what} of shape {tuple(shape)} does not fit in device memory (scenes are not tiled into strips)') from e
+
+
+def _scatter(src, src_first, n, crop, origins_dev, total, first, dst, doff, c0, nc, accumulate):
+    """centres of chips [src_first, src_first + n) of the (N, sh, sw[, lds]) tensor `src` -> map `dst` (H, W, ldd) at origins[first:first + n]"""
+    import ctypes as C
+    import torch
+    from . import ops
+    from ._lib import SceneScatterDesc, check, lib
+    sh, sw = src.shape[1], src.shape[2]
+    lds = src.shape[3] if src.dim() == 4 else 1
+    d = SceneScatterDesc(src=src.data_ptr() + src_first * sh * sw * lds * src.element_size(), src_kind=2 if src.dtype == torch.float32 else 5,
+                         n=n, sh=sh, sw=sw, lds=lds, c0=c0, nc=nc, crop_y=crop[0], crop_x=crop[1], crop_h=crop[2], crop_w=crop[3],
+                         origins=origins_dev.data_ptr(), total=total, first=first, dst=dst.data_ptr(), dst_kind=2 if dst.dtype == torch.float32 else 0,
+                         h=dst.shape[0], w_=dst.shape[1], ldd=dst.shape[2], doff=doff, accumulate=int(accumulate))
+    check(lib.satcv_scene_scatter(C.byref(d), ops.stream_ptr()))
+
+
+def _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, channel, want_classes, rescale):
+    """Shared loop of predict_chips_device / predict_scene: -> (device map (H, W, nc) float32, device class map (H, W, 1) uint8 or
+    None).  channel: int, or None for every class."""
+    import ctypes as C
+    import torch
+    from . import ops
+    from ._lib import SceneGatherDesc, check, lib
+    H, W = scenes[0].shape[:2]
+    off = buff // 2
+    side = kernel + 2 * off                  # the window of predict_chips; kernel + buff for an even buff
+    host = []
+    for sc in scenes:
+        sc = np.asarray(sc)
+        if sc.dtype not in _SCENE_KIND:
+            if rescale:
+                raise ValueError(f'rescale needs a uint8 / uint16 / int16 / float32 scene, got {sc.dtype}')
+            sc = sc.astype(np.float32)        # what Model.predict does with a host batch
+        host.append(sc)
+    dev = [_to_device(sc, 'the scene') for sc in host]
+    total = len(idx)
+    origins = _to_device(np.asarray(idx, np.int32).reshape(total, 2), 'the origin table')
+    runs = [[(s + a, s + b) for a, b in _disjoint_runs(idx[s:s + batch_size], kernel, kernel)] for s in range(0, total, batch_size)]
+    nb = min(batch_size, total)
+    bufs = [_device_empty((nb, side, side, sc.shape[2]), torch.float32, 'the chip batch') for sc in host]
+    st = ops.stream_ptr()
+    out = cls = None
+    # No host synchronisation inside this loop.  Every launch -- gather, the plan's kernels, scatter -- goes to the current stream, so
+    # stream order alone keeps the gather of batch i + 1 from overwriting `bufs` (and the plan from overwriting its output tensors) while
+    # batch i still reads them.
+    for b, s in enumerate(range(0, total, batch_size)):
+        n = min(batch_size, total - s)
+        xs = []
+        for sc, d_sc, buf in zip(host, dev, bufs):
+            d = SceneGatherDesc(src=d_sc.data_ptr(), src_kind=_SCENE_KIND[sc.dtype], h=H, w_=W, c=sc.shape[2], rescale=float(rescale or 0.0),
+                                origins=origins.data_ptr(), total=total, first=s, n=n, off=off, side=side,
+                                dst=buf.data_ptr(), ldc=sc.shape[2], coff=0)
+            check(lib.satcv_scene_gather(C.byref(d), st))
+            xs.append(buf[:n])
+        res = m.predict_on_device(xs if len(xs) > 1 else xs[0])
+        res = list(res) if isinstance(res, (list, tuple)) else [res]
+        probs = res[0]
+        if probs.dtype != torch.float32 or not probs.is_contiguous():
+            probs = probs.to(torch.float32).contiguous()
+        if out is None:
+            ncls = probs.shape[-1]
+            if channel is not None and not -ncls <= channel < ncls:
+                raise IndexError(f'channel {channel} of a {ncls}-class output')
+            c0, nc = (0, ncls) if channel is None else (channel % ncls, 1)
+            out = _device_empty((H, W, nc), torch.float32, 'the prediction map', 0.0)
+            if want_classes:
+                if len(res) < 2 or res[1].dim() != 3:
+                    raise ValueError('classes=True needs a model with an (n, h, w) class output next to its probabilities')
+                cls = _device_empty((H, W, 1), torch.uint8, 'the class map', 255)
+        for a, e in runs[b]:
+            _scatter(probs, a - s, e - a, (off, off, kernel, kernel), origins, total, a, out, 0, c0, nc, True)
+            if cls is not None:
+                _scatter(res[1], a - s, e - a, (off, off, kernel, kernel), origins, total, a, cls, 0, 0, 1, False)
+    return out, cls
+
+
+def predict_chips_device(arr, chip_indices, template, m, kernel=256, buff=128, batch_size=16, channel=0, rescale=None):
+    """`predict_chips` with the scene and the prediction map resident on the device: same signature, same result.
+
+    The scene(s) go to the device once in their own dtype (uint8 / uint16 / int16 / float32; `rescale` divides an integer scene in
+    float64 and rounds to float32, (scene.astype(float64) / rescale).astype(float32)), the index list once.  Per batch the windows are
+    gathered on the device, predicted by `m.predict_on_device` and the centres of `probs[..., channel]` accumulated into a zero float32
+    device map; nothing synchronises with the host until the one copy back, after which `template += map`.  Every pixel of the map
+    receives the value `predict_chips` would add, so for chips with disjoint centres the two functions return equal templates.
+
+    Differences from `predict_chips`:
+    * an index whose window leaves the scene raises ValueError (there a negative start wraps silently and an overrun fails on shapes);
+    * centres that overlap (legal in both) are summed in float32 on the device, in list order, before they meet the template, where
+      `predict_chips` adds each in the template's dtype.
+    `arr` may be the two-date pair (arr_a, arr_b), as for `predict_chips`.  An empty index list returns `template` untouched."""
+    scenes, _ = _scenes(arr)
+    _check_geometry(kernel, buff, batch_size)
+    idx = [(int(y), int(x)) for y, x in chip_indices]
+    if not idx:
+        return template
+    if scenes[0].ndim != 3:
+        raise ValueError(f'expected an (H, W, C) scene, got shape {scenes[0].shape}')
+    _check_windows(idx, scenes[0].shape[0], scenes[0].shape[1], kernel, buff // 2)
+    out, _ = _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, int(channel), False, rescale)
+    template += out[..., 0].cpu().numpy()
+    return template
+
+
+def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover='reference', classes=False, rescale=None):
+    """Prediction map of a whole (H, W, C) scene (or two-date pair of scenes), stitched on the device; returns new arrays.
+
+    cover='reference': the chips of `generate_chip_indices` -- the buff // 2 border and a last chip ending on the image edge stay
+    unpredicted (0 in the map, 255 in the class map), as in the reference.
+    cover='full': centres on the grid range(0, H, kernel) x range(0, W, kernel); windows that overhang the scene are filled by
+    reflection (np.pad mode='reflect') inside the gather and the centres are clipped to the scene, so every pixel is predicted exactly
+    once.  Needs H, W >= kernel + buff (one reflection then suffices), else ValueError.
+    channel: int -> (H, W) float32; None -> (H, W, n_classes).  classes=True returns (map, class map (H, W) uint8) from the model's
+    second output (ValueError for a single-output model).  The returned arrays are the only device-to-host traffic."""
+    scenes, _ = _scenes(arr)
+    _check_geometry(kernel, buff, batch_size)
+    if scenes[0].ndim != 3:
+        raise ValueError(f'expected an (H, W, C) scene, got shape {scenes[0].shape}')
+    H, W = scenes[0].shape[:2]
+    if cover == 'reference':
+        idx = generate_chip_indices(scenes[0], buff, kernel)
+    elif cover == 'full':
+        if H < kernel + buff or W < kernel + buff:
+            raise ValueError(f"cover='full' needs a scene of at least kernel + buff = {kernel + buff} pixels a side, got {H} x {W}")
+        idx = full_cover_indices((H, W), kernel)
+    else:
+        raise ValueError(f"cover must be 'reference' or 'full', got {cover!r}")
+    if classes and len(getattr(m, 'outputs', ())) < 2:
+        raise ValueError('classes=True needs a model with a class output next to its probabilities')
+    if not idx:                              # (a scene too small for one reference chip: nothing is predicted)
+        ncls = m.outputs[0].channels
+        probs = np.zeros((H, W) if channel is not None else (H, W, ncls), np.float32)
+        return (probs, np.full((H, W), 255, np.uint8)) if classes else probs
+    out, cls = _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, None if channel is None else int(channel), classes, rescale)
+    probs = (out if channel is None else out[..., 0]).cpu().numpy()
+    return (probs, cls[..., 0].cpu().numpy()) if classes else probs
+
+
+def callback_predictions(imageDataset, model, mixer, kernel_shape=[256, 256], kernel_buffer=[128, 128]):
+    """utils/prediction_tools.py:245-291 without its prints: predict mixer['totalPatches'] patches, keep the probability of class 1 and
+    assemble the cropped patches into a mosaic of mixer['patchesPerRow'] patches per row; returns the (rows, columns) float32 mosaic.
+
+    The crop and the placement are those of `_patch_grid` (as coded in the reference: each axis starts at its own half buffer and stops
+    at its kernel size plus the OTHER axis' half buffer; patch i lands at mosaic row i // patchesPerRow, column i % patchesPerRow; a
+    trailing partial row is dropped).  imageDataset: an (N, h, w, c) array or an iterable of batches.  The patches are cropped and
+    placed on the device by the scatter kernel; the mosaic is the only copy back."""
+    import torch
+    from .model_tools import _as_batches
+    patches, cols = int(mixer['totalPatches']), int(mixer['patchesPerRow'])
+    multi = len(getattr(model, 'inputs', ())) > 1
+    batches, _ = _as_batches(imageDataset, None, 16)
+    grid = origins = mosaic = None
+    filled = 0
+    for xb in batches:
+        if isinstance(xb, (tuple, list)) and not multi:
+            xb = xb[0]
+        res = model.predict_on_device(xb)
+        probs = (list(res) if isinstance(res, (list, tuple)) else [res])[0]
+        if probs.dtype != torch.float32 or not probs.is_contiguous():
+            probs = probs.to(torch.float32).contiguous()
+        if grid is None:
+            if probs.shape[-1] < 2:
+                raise ValueError('callback_predictions writes the probability of class 1: the model has a single output channel')
+            grid, place, hw = _patch_grid(patches, cols, probs.shape[1:3], kernel_shape, kernel_buffer)
+            origins = _to_device(np.asarray(place, np.int32).reshape(-1, 2), 'the origin table')
+            mosaic = _device_empty(hw + (1,), torch.float32, 'the mosaic', 0.0)
+        n = min(probs.shape[0], len(place) - filled)
+        _scatter(probs, 0, n, grid, origins, len(place), filled, mosaic, 0, 1, 1, False)
+        filled += n
+        if filled >= len(place):
+            break
+    if grid is None or filled < len(place):
+        raise ValueError(f'the dataset ended after {filled} patches, mixer announces {patches}')
+    return mosaic[..., 0].cpu().numpy()
