@@ -503,6 +503,37 @@ typedef struct {
 } satcv_scene_scatter_desc;
 int satcv_scene_scatter(const satcv_scene_scatter_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ median composite of an image time stack
+ * Everything of run_local (utils/pc_tools.py:620-668; twin predict_pc_local, utils/prediction_tools.py:731-779) between "the
+ * acquisitions are in memory" and the chip loop, in ONE launch:
+ *   per sample      v > 0 ? v : NaN (:376; NaN stays NaN, negative i16 / f32 values are nodata), then for an acquisition whose
+ *                   offset is > 0: max(v, offset) - offset (harmonize_to_old, :284-326; a valid value <= offset becomes 0 and
+ *                   stays valid)
+ *   per pixel, band median over time of the valid samples, the mean of the two middle ones for an even count, NaN for none
+ *                   (DataArray.median(dim='time'), :642-643)
+ *   per pixel       (median - mean) / (sd + 1e-6), mean and sd (ddof 0) over the bands that are not NaN; a NaN band stays NaN
+ *                   (normalize_dataArray, :90-107)
+ *   src:     (t, c, h, w_) planar, contiguous, of kind 1 u16, 2 f32 or 3 i16 (the kinds of satcv_tile_desc); c <= 16,
+ *            t <= SATCV_COMPOSITE_MAX_T, h * w_ < 2^31
+ *   offsets: t floats on the device (0 = none; 1000 for Sentinel-2 acquisitions on or after 2022-01-25), or NULL.  The 16-bit kinds
+ *            take an offset rounded to the nearest integer and limited to 65535 (their harmonisation is integer arithmetic)
+ *   median:  (h, w_, ld_med) fp32 written at channel offset coff_med, or NULL
+ *   norm:    (h, w_, ld_norm) fp32 written at channel offset coff_norm, or NULL; use_fill: NaN in norm (only there) becomes `fill`.
+ *            Both are the HWC layout satcv_scene_gather reads; with ld_norm = 2 c two launches put the before / after composites
+ *            into the halves of one scene (the xr.concat over 'band' of :650)
+ * Numerics: samples are held exactly (f32 stacks: max(v, offset) - offset is rounded to fp32); the selection is exact; the midpoint
+ * of an even count and the whole normalisation are computed in double from the double medians and rounded once to fp32. */
+#define SATCV_COMPOSITE_MAX_T 256
+typedef struct satcv_composite_desc {
+  const void* src; int32_t src_kind;
+  int32_t t, c, h, w_;
+  const float* offsets;
+  float* median; int32_t ld_med, coff_med;
+  float* norm; int32_t ld_norm, coff_norm;
+  int32_t use_fill; float fill;
+} satcv_composite_desc;
+int satcv_median_composite(const satcv_composite_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ losses
  * Each writes loss_out[0] += mean loss contribution (caller zeroes) and
  * dlogits = dL/dlogits (through the head activation).

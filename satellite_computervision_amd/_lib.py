@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('SATCV_LIB') or os.path.join(_HERE, 'libsatcv.so')    
 
 F32, BF16, FP8, FP8X, F64 = 0, 1, 2, 3, 4
 STAT_ROWS = 32
+COMPOSITE_MAX_T = 256       # SATCV_COMPOSITE_MAX_T of include/satcv.h
 
 c_i32, c_i64, c_f32, c_vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
@@ -57,6 +58,12 @@ class SceneScatterDesc(C.Structure):
                 ('crop_y', c_i32), ('crop_x', c_i32), ('crop_h', c_i32), ('crop_w', c_i32),
                 ('origins', c_vp), ('total', c_i32), ('first', c_i32), ('dst', c_vp), ('dst_kind', c_i32),
                 ('h', c_i32), ('w_', c_i32), ('ldd', c_i32), ('doff', c_i32), ('accumulate', c_i32)]
+
+
+class CompositeDesc(C.Structure):
+    _fields_ = [('src', c_vp), ('src_kind', c_i32), ('t', c_i32), ('c', c_i32), ('h', c_i32), ('w_', c_i32), ('offsets', c_vp),
+                ('median', c_vp), ('ld_med', c_i32), ('coff_med', c_i32), ('norm', c_vp), ('ld_norm', c_i32), ('coff_norm', c_i32),
+                ('use_fill', c_i32), ('fill', c_f32)]
 
 
 class WgradDesc(C.Structure):
@@ -192,6 +199,7 @@ _SIGS = {
     'satcv_tile_ingest': (C.c_int, [C.POINTER(TileDesc), c_vp]),
     'satcv_scene_gather': (C.c_int, [C.POINTER(SceneGatherDesc), c_vp]),
     'satcv_scene_scatter': (C.c_int, [C.POINTER(SceneScatterDesc), c_vp]),
+    'satcv_median_composite': (C.c_int, [C.POINTER(CompositeDesc), c_vp]),
     'satcv_label_onehot': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
     'satcv_crc32c': (C.c_uint32, [c_vp, C.c_uint64, C.c_uint32]),
     'satcv_head_fwd': (C.c_int, [C.POINTER(HeadDesc), c_vp]),

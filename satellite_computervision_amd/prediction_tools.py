@@ -187,7 +187,8 @@ def _scatter(src, src_first, n, crop, origins_dev, total, first, dst, doff, c0, 
 
 def _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, channel, want_classes, rescale):
     """Shared loop of predict_chips_device / predict_scene: -> (device map (H, W, nc) float32, device class map (H, W, 1) uint8 or
-    None).  channel: int, or None for every class."""
+    None).  channel: int, or None for every class.  A scene is a host array, or a contiguous float32 CUDA tensor (H, W, C) that is
+    read where it lies."""
     import ctypes as C
     import torch
     from . import ops
@@ -195,20 +196,26 @@ def _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, channel, want_cl
     H, W = scenes[0].shape[:2]
     off = buff // 2
     side = kernel + 2 * off                  # the window of predict_chips; kernel + buff for an even buff
-    host = []
+    dev, kinds = [], []
     for sc in scenes:
+        if isinstance(sc, torch.Tensor):     # a scene that is already resident (pc_tools.median_composite): used in place
+            if not (sc.is_cuda and sc.dtype == torch.float32 and sc.dim() == 3 and sc.is_contiguous()):
+                raise ValueError(f'a tensor scene must be a contiguous float32 CUDA tensor (H, W, C), got {sc.dtype} {tuple(sc.shape)} on {sc.device}')
+            dev.append(sc)
+            kinds.append(_SCENE_KIND[np.dtype(np.float32)])
+            continue
         sc = np.asarray(sc)
         if sc.dtype not in _SCENE_KIND:
             if rescale:
                 raise ValueError(f'rescale needs a uint8 / uint16 / int16 / float32 scene, got {sc.dtype}')
             sc = sc.astype(np.float32)        # what Model.predict does with a host batch
-        host.append(sc)
-    dev = [_to_device(sc, 'the scene') for sc in host]
+        dev.append(_to_device(sc, 'the scene'))
+        kinds.append(_SCENE_KIND[sc.dtype])
     total = len(idx)
     origins = _to_device(np.asarray(idx, np.int32).reshape(total, 2), 'the origin table')
     runs = [[(s + a, s + b) for a, b in _disjoint_runs(idx[s:s + batch_size], kernel, kernel)] for s in range(0, total, batch_size)]
     nb = min(batch_size, total)
-    bufs = [_device_empty((nb, side, side, sc.shape[2]), torch.float32, 'the chip batch') for sc in host]
+    bufs = [_device_empty((nb, side, side, sc.shape[2]), torch.float32, 'the chip batch') for sc in dev]
     st = ops.stream_ptr()
     out = cls = None
     # No host synchronisation inside this loop.  Every launch -- gather, the plan's kernels, scatter -- goes to the current stream, so
@@ -217,8 +224,8 @@ def _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, channel, want_cl
     for b, s in enumerate(range(0, total, batch_size)):
         n = min(batch_size, total - s)
         xs = []
-        for sc, d_sc, buf in zip(host, dev, bufs):
-            d = SceneGatherDesc(src=d_sc.data_ptr(), src_kind=_SCENE_KIND[sc.dtype], h=H, w_=W, c=sc.shape[2], rescale=float(rescale or 0.0),
+        for sc, kind, buf in zip(dev, kinds, bufs):
+            d = SceneGatherDesc(src=sc.data_ptr(), src_kind=kind, h=H, w_=W, c=sc.shape[2], rescale=float(rescale or 0.0),
                                 origins=origins.data_ptr(), total=total, first=s, n=n, off=off, side=side,
                                 dst=buf.data_ptr(), ldc=sc.shape[2], coff=0)
             check(lib.satcv_scene_gather(C.byref(d), st))
@@ -258,7 +265,8 @@ def predict_chips_device(arr, chip_indices, template, m, kernel=256, buff=128, b
     * an index whose window leaves the scene raises ValueError (there a negative start wraps silently and an overrun fails on shapes);
     * centres that overlap (legal in both) are summed in float32 on the device, in list order, before they meet the template, where
       `predict_chips` adds each in the template's dtype.
-    `arr` may be the two-date pair (arr_a, arr_b), as for `predict_chips`.  An empty index list returns `template` untouched."""
+    `arr` may be the two-date pair (arr_a, arr_b), as for `predict_chips`.  A scene that is already resident -- a contiguous float32 CUDA
+    tensor (H, W, C), e.g. from `pc_tools.median_composite` -- is read in place.  An empty index list returns `template` untouched."""
     scenes, _ = _scenes(arr)
     _check_geometry(kernel, buff, batch_size)
     idx = [(int(y), int(x)) for y, x in chip_indices]
@@ -281,7 +289,8 @@ def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover=
     reflection (np.pad mode='reflect') inside the gather and the centres are clipped to the scene, so every pixel is predicted exactly
     once.  Needs H, W >= kernel + buff (one reflection then suffices), else ValueError.
     channel: int -> (H, W) float32; None -> (H, W, n_classes).  classes=True returns (map, class map (H, W) uint8) from the model's
-    second output (ValueError for a single-output model).  The returned arrays are the only device-to-host traffic."""
+    second output (ValueError for a single-output model).  The returned arrays are the only device-to-host traffic.  A scene may be a
+    contiguous float32 CUDA tensor (H, W, C), read in place."""
     scenes, _ = _scenes(arr)
     _check_geometry(kernel, buff, batch_size)
     if scenes[0].ndim != 3:
