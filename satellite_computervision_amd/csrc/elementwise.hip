@@ -1226,8 +1226,9 @@ __global__ void maxpool_kernel(const T* __restrict__ x, T* __restrict__ out, int
 extern "C" int satcv_maxpool(const void* x, void* out, int32_t n, int32_t h, int32_t w_, int32_t c, int32_t k, int32_t s, int32_t pad, int32_t dtype,
                              void* stream) {
   SATCV_CHECK(x && out && n > 0 && h > 0 && w_ > 0 && c > 0 && c % 8 == 0 && k >= 1 && s >= 1 && pad >= 0, "maxpool: bad args");
+  // a window larger than the padded map: C division truncates (-1) / 2 to 0, which would pass for an output of one row
+  SATCV_CHECK(h + 2 * pad >= k && w_ + 2 * pad >= k, "maxpool: empty output");
   const int ho = (h + 2 * pad - k) / s + 1, wo = (w_ + 2 * pad - k) / s + 1;
-  SATCV_CHECK(ho > 0 && wo > 0, "maxpool: empty output");
   DISPATCH_T8(dtype, hipLaunchKernelGGL(maxpool_kernel<T>, dim3(ew_grid((long long)n * ho * wo * (c / 8))), dim3(EW_BLOCK), 0, (hipStream_t)stream,
                                        (const T*)x, (T*)out, n, h, w_, c, k, s, pad, ho, wo));
   LAUNCH_OK("maxpool");
@@ -1503,7 +1504,8 @@ __global__ void dropout_apply_kernel(const T* __restrict__ x, int ldx, const flo
 extern "C" int satcv_dropout_apply(const void* x, int32_t ldx, const float* scale, const float* shift, int32_t relu, const float* mask,
                                    int32_t ldm, int32_t mask_mode, void* out, int32_t ldo, int32_t n, int32_t hw, int32_t c, int32_t dtype,
                                    void* stream) {
-  SATCV_CHECK(x && mask && out && n > 0 && hw > 0 && c > 0 && c % 8 == 0 && ldm >= c && (mask_mode == 0 || mask_mode == 1), "dropout_apply: bad args");
+  SATCV_CHECK(x && mask && out && n > 0 && hw > 0 && c > 0 && c % 8 == 0 && ldx >= c && ldm >= c && ldo >= c && (mask_mode == 0 || mask_mode == 1),
+              "dropout_apply: bad args");
   const long long npix = (long long)n * hw;
   DISPATCH_T(dtype, hipLaunchKernelGGL(dropout_apply_kernel<T>, dim3(ew_grid(npix * (c / 8))), dim3(EW_BLOCK), 0, (hipStream_t)stream, (const T*)x, ldx,
                                        scale, shift, relu, mask, ldm, mask_mode, (T*)out, ldo, npix, hw, c));
