@@ -570,6 +570,38 @@ int satcv_adam_step(float* p, const float* g, float* m, float* v, int64_t n, flo
 int satcv_adam_step_part(float* p, const float* g, float* m, float* v, int64_t n, float beta1,
                          float beta2, float eps, float* state, const float* lr_mul, int32_t bump, void* stream);
 
+/* tf.keras.optimizers.SGD(learning_rate, momentum, nesterov) -- the `optim=` / `OPTIMIZER` a caller hands to the reference's
+ * builders (utils/model_tools.py:773-920) and notebooks.  Flat fp32 buffers as for Adam; lr = state[0] and grad_scale = state[2]
+ * are read on the device (a replayed graph picks up a new rate), the step counter is not touched (no bias correction).
+ *     momentum == 0 (v NULL):  p -= lr g
+ *     momentum  > 0:           v = momentum v - lr g;   p += v          (nesterov: p += momentum v - lr g, with the new v)
+ * `v` is passed exactly when momentum > 0.  lr_mul (optional, 0 / 1 per element): an element whose entry is 0 keeps its weight and
+ * its slot bit for bit. */
+int satcv_sgd_step(float* p, const float* g, float* v, int64_t n, float momentum, int32_t nesterov, float* state,
+                   const float* lr_mul, void* stream);
+/* tf.keras.optimizers.RMSprop(learning_rate, rho, momentum, epsilon, centered), the arithmetic TensorFlow documents for ApplyRMSProp /
+ * ApplyCenteredRMSProp (epsilon INSIDE the root):
+ *     ms = rho ms + (1 - rho) g^2;   centered (mg not NULL): mg = rho mg + (1 - rho) g
+ *     denom = sqrt(ms - mg^2 + eps)  (mg = 0 when not centered)
+ *     mom = momentum mom + lr g / denom;   p -= mom                     (momentum == 0, mom NULL: p -= lr g / denom)
+ * `mom` is passed exactly when momentum > 0, `mg` exactly when centered.  state / lr_mul as for SGD. */
+int satcv_rmsprop_step(float* p, const float* g, float* ms, float* mg, float* mom, int64_t n, float rho, float momentum, float eps,
+                       float* state, const float* lr_mul, void* stream);
+/* The `clipvalue` / `global_clipnorm` arguments of every tf.keras optimizer, applied to the flat gradient in place before the step.  Both
+ * act on what the optimizer will see, g * grad_scale (state[2]; state NULL: 1).
+ *   SATCV_CLIP_VALUE        every element clamped so that |g grad_scale| <= c (a NaN stays a NaN); no workspace.
+ *   SATCV_CLIP_GLOBAL_NORM  g *= min(1, c / ||g grad_scale||_2).  The norm is a two-stage sum in double with a fixed partition and a
+ *                           fixed order (1024 partials whatever n is, then one workgroup): no floating-point atomics, bit-identical
+ *                           from run to run and from stream to stream.  The second stage and the scaling read it from `workspace`
+ *                           (satcv_grad_clip_workspace(n) bytes, 8-byte aligned; afterwards double [1024] holds the SQUARED norm of
+ *                           g): no host synchronisation.  A gradient at or below the threshold is not written at all.  A non-finite
+ *                           norm (NaN or infinity) leaves the gradient as it is: the step is lost either way, as with
+ *                           tf.clip_by_global_norm, which marks that case by setting every entry to NaN. */
+#define SATCV_CLIP_VALUE 0
+#define SATCV_CLIP_GLOBAL_NORM 1
+int64_t satcv_grad_clip_workspace(int64_t n);
+int satcv_grad_clip(float* g, int64_t n, int32_t mode, float c, const float* state, void* workspace, void* stream);
+
 /* Clears the two buffers a training step accumulates into -- the flat gradient (bytes_a, a multiple of 16, 16-byte aligned) and a small
  * second one (the loss scalar; bytes_b a multiple of 4) -- in ONE launch of the library's own (the optimizer loop of Model.fit,
  * notebooks/UNET_G4G_2019_solar.ipynb:1267: Keras starts every step from zero gradients).  Either may be empty. */

@@ -211,6 +211,10 @@ _SIGS = {
     'satcv_confusion': (C.c_int, [c_vp, c_vp, c_i32, c_i64, c_vp, c_vp]),
     'satcv_adam_step': (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
     'satcv_adam_step_part': (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_vp, c_vp, c_i32, c_vp]),
+    'satcv_sgd_step': (C.c_int, [c_vp, c_vp, c_vp, c_i64, c_f32, c_i32, c_vp, c_vp, c_vp]),
+    'satcv_rmsprop_step': (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp]),
+    'satcv_grad_clip_workspace': (c_i64, [c_i64]),
+    'satcv_grad_clip': (C.c_int, [c_vp, c_i64, c_i32, c_f32, c_vp, c_vp, c_vp]),
     'satcv_comm_unique_id': (C.c_int, [c_vp]),
     'satcv_comm_init': (C.c_int, [C.POINTER(c_vp), c_i32, c_i32, c_vp]),
     'satcv_comm_destroy': (C.c_int, [c_vp]),

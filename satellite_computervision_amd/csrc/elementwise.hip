@@ -1827,3 +1827,170 @@ extern "C" int satcv_adam_step(float* p, const float* g, float* m, float* v, int
   LAUNCH_OK("adam");
   return SATCV_OK;
 }
+
+// ------------------------------------------------------------ SGD / RMSprop
+// Same conventions as adam_kernel: flat fp32 buffers, float4 body + scalar tail, the rate and the gradient scale read from `state` on the
+// device (a replayed graph sees a new rate), an optional 0 / 1 update mask under which a frozen element keeps its weight AND its slots.
+// Neither rule has a bias correction, so the step counter is not touched.
+__device__ __forceinline__ void sgd_elem(float& p, float g, float* v, float lr, float mom, int nesterov) {
+  if (!v) { p -= lr * g; return; }
+  const float vn = mom * (*v) - lr * g;
+  *v = vn;
+  p += nesterov ? mom * vn - lr * g : vn;
+}
+__global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v, long long n, float mom, int nesterov,
+                           const float* __restrict__ state, const float* __restrict__ lr_mul) {
+  const float lr = state[0], gs = state[2];
+  const long long n4 = n / 4;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    float4 vv = v ? reinterpret_cast<float4*>(v)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 lm = lr_mul ? reinterpret_cast<const float4*>(lr_mul)[i] : make_float4(1.f, 1.f, 1.f, 1.f);
+    float* P = &pp.x; const float* Gp = &gg.x; float* V = &vv.x; const float* L = &lm.x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (L[e] != 0.f) sgd_elem(P[e], Gp[e] * gs, v ? &V[e] : nullptr, L[e] * lr, mom, nesterov);
+    reinterpret_cast<float4*>(p)[i] = pp;
+    if (v) reinterpret_cast<float4*>(v)[i] = vv;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long long i = n4 * 4 + threadIdx.x;
+    const float l = lr_mul ? lr_mul[i] : 1.f;
+    if (l != 0.f) sgd_elem(p[i], g[i] * gs, v ? v + i : nullptr, l * lr, mom, nesterov);
+  }
+}
+extern "C" int satcv_sgd_step(float* p, const float* g, float* v, int64_t n, float momentum, int32_t nesterov, float* state,
+                              const float* lr_mul, void* stream) {
+  SATCV_CHECK(p && g && state && n > 0 && momentum >= 0.f && momentum <= 1.f, "sgd: bad args");
+  SATCV_CHECK((v != nullptr) == (momentum > 0.f), "sgd: the momentum slot is passed exactly when momentum > 0");
+  SATCV_CHECK(!nesterov || v, "sgd: nesterov needs momentum > 0");
+  SATCV_CHECK(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)lr_mul % 16 == 0), "sgd: buffers must be 16-byte aligned");
+  hipLaunchKernelGGL(sgd_kernel, dim3(ew_grid(n / 4 + 1, 4096)), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, g, v, (long long)n, momentum, (int)(nesterov != 0), state, lr_mul);
+  LAUNCH_OK("sgd");
+  return SATCV_OK;
+}
+
+__device__ __forceinline__ void rmsprop_elem(float& p, float g, float& ms, float* mg, float* mo, float lr, float rho, float mom, float eps) {
+  const float msn = rho * ms + (1.f - rho) * g * g;
+  ms = msn;
+  float var = msn;
+  if (mg) { const float mgn = rho * (*mg) + (1.f - rho) * g; *mg = mgn; var = msn - mgn * mgn; }
+  const float upd = lr * g / sqrtf(var + eps);
+  if (mo) { const float mn = mom * (*mo) + upd; *mo = mn; p -= mn; }
+  else p -= upd;
+}
+__global__ void rmsprop_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ ms, float* __restrict__ mg, float* __restrict__ mo,
+                               long long n, float rho, float mom, float eps, const float* __restrict__ state, const float* __restrict__ lr_mul) {
+  const float lr = state[0], gs = state[2];
+  const long long n4 = n / 4;
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float4 pp = reinterpret_cast<float4*>(p)[i];
+    const float4 gg = reinterpret_cast<const float4*>(g)[i];
+    float4 s = reinterpret_cast<float4*>(ms)[i];
+    float4 c = mg ? reinterpret_cast<float4*>(mg)[i] : z;
+    float4 o = mo ? reinterpret_cast<float4*>(mo)[i] : z;
+    const float4 lm = lr_mul ? reinterpret_cast<const float4*>(lr_mul)[i] : make_float4(1.f, 1.f, 1.f, 1.f);
+    float* P = &pp.x; const float* Gp = &gg.x; float* S = &s.x; float* Cc = &c.x; float* O = &o.x; const float* L = &lm.x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (L[e] != 0.f) rmsprop_elem(P[e], Gp[e] * gs, S[e], mg ? &Cc[e] : nullptr, mo ? &O[e] : nullptr, L[e] * lr, rho, mom, eps);
+    reinterpret_cast<float4*>(p)[i] = pp; reinterpret_cast<float4*>(ms)[i] = s;
+    if (mg) reinterpret_cast<float4*>(mg)[i] = c;
+    if (mo) reinterpret_cast<float4*>(mo)[i] = o;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long long i = n4 * 4 + threadIdx.x;
+    const float l = lr_mul ? lr_mul[i] : 1.f;
+    if (l != 0.f) rmsprop_elem(p[i], g[i] * gs, ms[i], mg ? mg + i : nullptr, mo ? mo + i : nullptr, l * lr, rho, mom, eps);
+  }
+}
+extern "C" int satcv_rmsprop_step(float* p, const float* g, float* ms, float* mg, float* mom, int64_t n, float rho, float momentum, float eps,
+                                  float* state, const float* lr_mul, void* stream) {
+  SATCV_CHECK(p && g && ms && state && n > 0 && rho >= 0.f && rho <= 1.f && momentum >= 0.f && eps >= 0.f, "rmsprop: bad args");
+  SATCV_CHECK((mom != nullptr) == (momentum > 0.f), "rmsprop: the momentum slot is passed exactly when momentum > 0");
+  SATCV_CHECK(((uintptr_t)p % 16 == 0) && ((uintptr_t)g % 16 == 0) && ((uintptr_t)ms % 16 == 0) && ((uintptr_t)mg % 16 == 0) && ((uintptr_t)mom % 16 == 0) &&
+              ((uintptr_t)lr_mul % 16 == 0), "rmsprop: buffers must be 16-byte aligned");
+  hipLaunchKernelGGL(rmsprop_kernel, dim3(ew_grid(n / 4 + 1, 4096)), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, g, ms, mg, mom, (long long)n, rho, momentum, eps,
+                     state, lr_mul);
+  LAUNCH_OK("rmsprop");
+  return SATCV_OK;
+}
+
+// ------------------------------------------------------------ gradient clipping
+// Global norm: GC_PARTS workgroups of GC_BLOCK lanes WHATEVER n is.  Lane t of part b squares float4 b * GC_BLOCK + t, then every
+// GC_PARTS * GC_BLOCK-th one after it, in that order, into a double; the lanes of a part are folded by a fixed LDS tree into
+// workspace[b]; one workgroup folds the GC_PARTS partials the same way into workspace[GC_PARTS] (the squared norm) and the scale pass reads
+// it from there.  Which element meets which accumulator in which order depends on n alone: no atomics, nothing on the schedule.
+#define GC_PARTS 1024
+#define GC_BLOCK 256
+__device__ __forceinline__ double gc_block_sum(double acc, double* sh) {
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = GC_BLOCK / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  return sh[0];
+}
+__global__ __launch_bounds__(GC_BLOCK) void gc_partial_kernel(const float* __restrict__ g, long long n, double* __restrict__ ws) {
+  __shared__ double sh[GC_BLOCK];
+  const long long n4 = n / 4;
+  double acc = 0.0;
+  for (long long i = blockIdx.x * (long long)GC_BLOCK + threadIdx.x; i < n4; i += (long long)GC_PARTS * GC_BLOCK) {
+    const float4 v = reinterpret_cast<const float4*>(g)[i];
+    acc += (double)v.x * v.x; acc += (double)v.y * v.y; acc += (double)v.z * v.z; acc += (double)v.w * v.w;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const double v = g[n4 * 4 + threadIdx.x]; acc += v * v; }
+  const double tot = gc_block_sum(acc, sh);
+  if (threadIdx.x == 0) ws[blockIdx.x] = tot;
+}
+__global__ __launch_bounds__(GC_BLOCK) void gc_final_kernel(double* __restrict__ ws) {
+  __shared__ double sh[GC_BLOCK];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < GC_PARTS; i += GC_BLOCK) acc += ws[i];
+  const double tot = gc_block_sum(acc, sh);
+  if (threadIdx.x == 0) ws[GC_PARTS] = tot;
+}
+__global__ void gc_scale_kernel(float* __restrict__ g, long long n, float c, const float* __restrict__ state, const double* __restrict__ ws) {
+  const double nrm = sqrt(ws[GC_PARTS]) * (double)(state ? state[2] : 1.f);       // the norm of what the optimizer will see
+  if (!(nrm > (double)c) || !(nrm <= 1.79769313486231570e308)) return;            // below the threshold, NaN or infinite: untouched
+  const float s = (float)((double)c / nrm);
+  const long long n4 = n / 4;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float4 v = reinterpret_cast<float4*>(g)[i];
+    v.x *= s; v.y *= s; v.z *= s; v.w *= s;
+    reinterpret_cast<float4*>(g)[i] = v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) g[n4 * 4 + threadIdx.x] *= s;
+}
+__global__ void gc_value_kernel(float* __restrict__ g, long long n, float c, const float* __restrict__ state) {
+  const float hi = c / (state ? state[2] : 1.f), lo = -hi;                         // |g * grad_scale| <= c
+  const long long n4 = n / 4;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    float4 v = reinterpret_cast<float4*>(g)[i];
+    float* V = &v.x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) V[e] = V[e] > hi ? hi : (V[e] < lo ? lo : V[e]);   // (a NaN stays a NaN, as tf.clip_by_value leaves it)
+    reinterpret_cast<float4*>(g)[i] = v;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { float& x = g[n4 * 4 + threadIdx.x]; x = x > hi ? hi : (x < lo ? lo : x); }
+}
+extern "C" int64_t satcv_grad_clip_workspace(int64_t n) { return n > 0 ? (int64_t)(GC_PARTS + 1) * (int64_t)sizeof(double) : 0; }
+extern "C" int satcv_grad_clip(float* g, int64_t n, int32_t mode, float c, const float* state, void* workspace, void* stream) {
+  SATCV_CHECK(g && n > 0 && c > 0.f && (mode == SATCV_CLIP_VALUE || mode == SATCV_CLIP_GLOBAL_NORM), "grad_clip: bad args");
+  SATCV_CHECK((uintptr_t)g % 16 == 0, "grad_clip: the gradient must be 16-byte aligned");
+  const hipStream_t st = (hipStream_t)stream;
+  if (mode == SATCV_CLIP_VALUE) {
+    hipLaunchKernelGGL(gc_value_kernel, dim3(ew_grid(n / 4 + 1, 4096)), dim3(EW_BLOCK), 0, st, g, (long long)n, c, state);
+    LAUNCH_OK("grad_clip");
+    return SATCV_OK;
+  }
+  SATCV_CHECK(workspace && (uintptr_t)workspace % 8 == 0, "grad_clip: global_clipnorm needs the 8-byte aligned workspace of satcv_grad_clip_workspace");
+  hipLaunchKernelGGL(gc_partial_kernel, dim3(GC_PARTS), dim3(GC_BLOCK), 0, st, g, (long long)n, (double*)workspace);
+  hipLaunchKernelGGL(gc_final_kernel, dim3(1), dim3(GC_BLOCK), 0, st, (double*)workspace);
+  hipLaunchKernelGGL(gc_scale_kernel, dim3(ew_grid(n / 4 + 1, 4096)), dim3(EW_BLOCK), 0, st, g, (long long)n, c, state, (const double*)workspace);
+  LAUNCH_OK("grad_clip");
+  return SATCV_OK;
+}

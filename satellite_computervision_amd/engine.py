@@ -160,6 +160,7 @@ class Runtime:
         self.gflat = torch.zeros_like(self.pflat)
         self.sflat = torch.zeros(max(soff, 4), dtype=torch.float32, device=self.dev)
         self.adam_m = self.adam_v = None
+        self.slot_kind, self.slots, self._clip_ws = None, {}, None      # SGD / RMSprop slots by name, allocated on their first step
         self.adam_state = torch.tensor([1e-3, 0.0, 1.0, 0.0], dtype=torch.float32, device=self.dev)
         self.lr_mul = None
         self.dropout_seed = 0x5A7C0FFEE
@@ -278,6 +279,35 @@ class Runtime:
         if self.adam_m is None:
             self.adam_m = torch.zeros_like(self.pflat)
             self.adam_v = torch.zeros_like(self.pflat)
+
+    # ---- what model_tools.apply_optimizer asks of the owner of the flat buffers
+    def opt_buffers(self):
+        return self.pflat, self.gflat, self.adam_state, self.lr_mul
+
+    def opt_slots(self, opt):
+        """the slots of `opt` by name, zero-filled on first use; slots of another kind (or of another flag set) are dropped"""
+        if opt.kind == 'adam':
+            self.ensure_adam()
+            return {'m': self.adam_m, 'v': self.adam_v}
+        if self.slot_kind != opt.kind or set(self.slots) != set(opt.slot_names):
+            self.slot_kind, self.slots = opt.kind, {k: torch.zeros_like(self.pflat) for k in opt.slot_names}
+        return self.slots
+
+    def clip_workspace(self):
+        if self._clip_ws is None:
+            self._clip_ws = ops.grad_clip_workspace(self.gflat.numel(), self.dev)
+        return self._clip_ws
+
+    def reset_opt_slots(self):
+        self.adam_m = self.adam_v = None
+        self.slot_kind, self.slots = None, {}
+        self.adam_state[1:2].zero_()
+
+    def restore_opt_slots(self, kind, arrays, state):
+        """slots read back from a file written by Model.save"""
+        self.slot_kind = kind
+        self.slots = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(self.dev) for k, v in arrays.items()}
+        self.adam_state.copy_(torch.from_numpy(np.asarray(state, np.float32)))
 
     def plan(self, n, h, w, training):
         # tf.keras runs a BatchNormalization whose `trainable` is False in INFERENCE mode even inside fit() (moving statistics, no

@@ -115,13 +115,41 @@ class _Params:
             host[off:off + int(np.prod(shape))] = np.asarray(self.init[name](), np.float32).reshape(-1)
         self.flat = torch.from_numpy(host).to(_dev())
         self.grad = torch.zeros_like(self.flat)
-        self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        self.m = self.v = None                                      # optimizer slots: allocated on the first step that needs them
+        self.slot_kind, self.slots, self._clip_ws = None, {}, None
         self.state = torch.tensor([1e-3, 0.0, 1.0, 0.0], dtype=torch.float32, device=_dev())
         mul = np.ones(max(self.n, 4), np.float32)
         for name, (off, shape, tr) in self.specs.items():
             if not tr:
                 mul[off:off + int(np.prod(shape))] = 0
         self.lr_mul = torch.from_numpy(mul).to(_dev())
+
+    # ---- what model_tools.apply_optimizer asks of the owner of the flat buffers (as engine.Runtime)
+    @property
+    def adam_state(self):
+        return self.state
+
+    def opt_buffers(self):
+        return self.flat, self.grad, self.state, self.lr_mul
+
+    def opt_slots(self, opt):
+        if opt.kind == 'adam':
+            if self.m is None:
+                self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+            return {'m': self.m, 'v': self.v}
+        if self.slot_kind != opt.kind or set(self.slots) != set(opt.slot_names):
+            self.slot_kind, self.slots = opt.kind, {k: torch.zeros_like(self.flat) for k in opt.slot_names}
+        return self.slots
+
+    def clip_workspace(self):
+        if self._clip_ws is None:
+            self._clip_ws = ops.grad_clip_workspace(self.grad.numel(), self.grad.device)
+        return self._clip_ws
+
+    def reset_opt_slots(self):
+        self.m = self.v = None
+        self.slot_kind, self.slots = None, {}
+        self.state[1:2].zero_()
 
     def p(self, name):
         off, shape, _ = self.specs[name]
@@ -533,7 +561,7 @@ def _dev_f32(a):
 
 
 class _SeqModelBase:
-    """compile / fit / predict / train_on_batch plumbing shared by the LSTM-family models (Adam through satcv_adam_step)"""
+    """compile / fit / predict / train_on_batch plumbing shared by the LSTM-family models (the optimizer step through model_tools.apply_optimizer)"""
 
     def _finish(self):
         self.P.build()
@@ -555,7 +583,7 @@ class _SeqModelBase:
             raise TypeError(f'{type(self).__name__}.compile: unsupported arguments {sorted(kw)}')
         if loss_weights is not None:
             raise NotImplementedError(f'{type(self).__name__}.compile: loss_weights (the outputs\' losses are added with weight 1, the Keras default)')
-        self.optimizer = mt.Adam() if isinstance(optimizer, str) else optimizer
+        prev, new_opt = self.optimizer, mt.resolve_optimizer(optimizer)
         spec = loss(mt._LossArg('y_true'), mt._LossArg('y_pred')) if callable(loss) else loss
         if not isinstance(spec, mt.LossSpec):
             raise ValueError('loss must be one of the model_tools loss functions (or a lambda wrapping one)')
@@ -576,6 +604,9 @@ class _SeqModelBase:
         self.stop_training = False
         self.__dict__.pop('_loss_w_dev', None)
         self._drop_graphs()
+        self.optimizer = new_opt
+        mt.reset_slots_on_recompile(self.P, prev, new_opt)
+        self.optimizer._rt = self.P              # (`optimizer.learning_rate = ...` lands in the device state buffer at once)
         self.P.state[0:1].fill_(self.optimizer._lr)
 
     @staticmethod
@@ -646,8 +677,7 @@ class _SeqModelBase:
         P, opt = self.P, self.optimizer
         if set_lr:
             P.state[0:1].fill_(opt._lr)
-        check(lib.satcv_adam_step(P.flat.data_ptr(), P.grad.data_ptr(), P.m.data_ptr(), P.v.data_ptr(), P.flat.numel(), opt.beta_1, opt.beta_2,
-                                  opt.epsilon, P.state.data_ptr(), P.lr_mul.data_ptr(), ops.stream_ptr()))
+        mt.apply_optimizer(opt, P)               # (clip if asked, then the step of whichever optimizer was compiled)
         P.bump()
 
     def get_weights_dict(self):
@@ -774,7 +804,7 @@ class _SeqModelBase:
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=0, callbacks=None, validation_data=None, steps_per_epoch=None,
             validation_steps=None, initial_epoch=0, sample_weight=None, shuffle=False, **kw):
         """x: array(s) with y, or a Sequence / iterable of (x, y[, sample_weight]) batches (LSTMDataGenerator, LSTMAutoencoderGenerator,
-        HybridDataGenerator).  callbacks (model_tools.ModelCheckpoint / TensorBoard) see `loss` and the `val_` entries of evaluate() on
+        HybridDataGenerator).  callbacks (model_tools.ModelCheckpoint / TensorBoard / LearningRateScheduler / ReduceLROnPlateau / EarlyStopping) see `loss` and the `val_` entries of evaluate() on
         validation_data (arrays (x, y) or a batch iterable).  Arrays are taken in order (shuffle=True is refused: the reference fits from generators)."""
         if kw:
             raise TypeError(f'{type(self).__name__}.fit: unsupported arguments {sorted(kw)}')
@@ -787,7 +817,9 @@ class _SeqModelBase:
         for cb in callbacks:
             cb.model = self
         self.stop_training = False
+        mt.run_callbacks(callbacks, 'on_train_begin')
         for epoch in range(initial_epoch, epochs):
+            mt.run_callbacks(callbacks, 'on_epoch_begin', epoch)
             tot, cnt = 0.0, 0
             for i, (xb, yb) in enumerate(self._batches_of(x, y, batch_size, sample_weight)):
                 if steps_per_epoch is not None and i >= steps_per_epoch:
@@ -807,13 +839,16 @@ class _SeqModelBase:
             hist.epoch.append(epoch)
             if verbose:
                 print(f'Epoch {epoch + 1}/{epochs} - ' + ' - '.join(f'{k_}: {v_:.4f}' for k_, v_ in logs.items()))
+            before = set(logs)
             for cb in callbacks:
                 if hasattr(cb, 'on_epoch_end'):
                     cb.on_epoch_end(epoch, logs)
+            mt.record_callback_logs(hist, logs, before)
             if hasattr(x, 'on_epoch_end'):
                 x.on_epoch_end()
             if self.stop_training:
                 break
+        mt.run_callbacks(callbacks, 'on_train_end')
         return hist
 
 
@@ -897,8 +932,13 @@ class HybridModel(_SeqModelBase):
         self._finish()
 
     def compile(self, optimizer='adam', loss=None, metrics=None, **kw):
+        prev = self.optimizer
+        if mt.resolve_optimizer(optimizer).global_clipnorm is not None:
+            raise NotImplementedError('HybridModel.compile: global_clipnorm (the norm would span the two parameter buffers of the U-Net branch and '
+                                      'of the ConvLSTM tape, which are clipped separately); clipvalue is element-wise and is supported')
         super().compile(optimizer, loss, metrics)
         self.unet.optimizer = self.optimizer
+        mt.reset_slots_on_recompile(self.unet.runtime, prev, self.optimizer)
         self.unet.runtime.adam_state[0:1].fill_(self.optimizer._lr)
 
     def _forward(self, xs, training):
@@ -938,7 +978,7 @@ class HybridModel(_SeqModelBase):
         if self._loss is None:
             raise RuntimeError('compile() the model before fit/train')
         rt = self.unet.runtime
-        rt.ensure_adam()
+        rt.opt_slots(self.optimizer)
         self.P.grad.zero_(); rt.gflat.zero_()
         probs, _ = self._forward(x, True)
         loss, dlog = self._loss_grad(probs, y, 'softmax')
@@ -954,8 +994,7 @@ class HybridModel(_SeqModelBase):
         plan.run_backward(ops.stream_ptr())
         opt = self.optimizer
         rt.adam_state[0:1].fill_(opt._lr)
-        check(lib.satcv_adam_step(rt.pflat.data_ptr(), rt.gflat.data_ptr(), rt.adam_m.data_ptr(), rt.adam_v.data_ptr(), rt.pflat.numel(), opt.beta_1,
-                                  opt.beta_2, opt.epsilon, rt.adam_state.data_ptr(), None, ops.stream_ptr()))
+        mt.apply_optimizer(opt, rt)
         rt.repack()
         self.unet._weights_version = getattr(self.unet, '_weights_version', 0) + 1
         self._adam()

@@ -603,12 +603,27 @@ class _LR:
         return float(self._opt._lr)
 
 
-class Adam:
-    """tf.keras.optimizers.Adam: epsilon 1e-7 outside the bias correction (SURVEY Appendix A)."""
+class _Optimizer:
+    """what the Keras optimizers share: the `learning_rate` / `lr` property whose value lands in the device state buffer, and the
+    base-class gradient clipping arguments `clipvalue` / `global_clipnorm` (at most one; the per-variable `clipnorm` is refused)."""
+    kind = None
+    slot_names = ()
 
-    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **kwargs):
-        self._lr = float(kwargs.get('lr', learning_rate))
-        self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
+    def _init_base(self, learning_rate, kwargs, strict=True):
+        kwargs = dict(kwargs)
+        if kwargs.pop('clipnorm', None) is not None:
+            raise ValueError(f'{type(self).__name__}(clipnorm=...): per-variable norm clipping is not implemented; global_clipnorm= clips by the '
+                             'norm of the whole gradient')
+        self.clipvalue, self.global_clipnorm = kwargs.pop('clipvalue', None), kwargs.pop('global_clipnorm', None)
+        if self.clipvalue is not None and self.global_clipnorm is not None:
+            raise ValueError(f'{type(self).__name__}: at most one of clipvalue and global_clipnorm may be set')
+        for name in ('clipvalue', 'global_clipnorm'):
+            c = getattr(self, name)
+            if c is not None and not float(c) > 0:
+                raise ValueError(f'{type(self).__name__}({name}={c!r}): must be positive')
+        self._lr = float(kwargs.pop('lr', learning_rate))
+        if strict and kwargs:
+            raise TypeError(f'{type(self).__name__}: unsupported arguments {sorted(kwargs)}')
         self._rt = None
 
     def _set_lr(self, v):
@@ -625,6 +640,89 @@ class Adam:
         self._set_lr(float(v))
 
     lr = learning_rate
+
+
+class Adam(_Optimizer):
+    """tf.keras.optimizers.Adam: epsilon 1e-7 outside the bias correction (SURVEY Appendix A)."""
+    kind = 'adam'
+    slot_names = ('m', 'v')
+
+    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **kwargs):
+        self._init_base(learning_rate, kwargs, strict=False)
+        self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
+
+
+class SGD(_Optimizer):
+    """tf.keras.optimizers.SGD: v = momentum v - lr g, p += v (nesterov: p += momentum v - lr g); no slot without momentum."""
+    kind = 'sgd'
+
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, **kwargs):
+        self._init_base(learning_rate, kwargs)
+        if not 0.0 <= float(momentum) <= 1.0:
+            raise ValueError('`momentum` must be between [0, 1].')
+        self.momentum, self.nesterov = float(momentum), bool(nesterov) and float(momentum) > 0     # (Keras: nesterov without momentum is plain SGD)
+        self.slot_names = ('v',) if self.momentum > 0 else ()
+
+
+class RMSprop(_Optimizer):
+    """tf.keras.optimizers.RMSprop: epsilon inside the root (ApplyRMSProp / ApplyCenteredRMSProp); `mg` only when centered, `mom`
+    only with momentum."""
+    kind = 'rmsprop'
+
+    def __init__(self, learning_rate=1e-3, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, **kwargs):
+        self._init_base(learning_rate, kwargs)
+        if not 0.0 <= float(momentum) <= 1.0:
+            raise ValueError('`momentum` must be between [0, 1].')
+        self.rho, self.momentum, self.epsilon, self.centered = float(rho), float(momentum), float(epsilon), bool(centered)
+        self.slot_names = ('ms',) + (('mg',) if self.centered else ()) + (('mom',) if self.momentum > 0 else ())
+
+
+_OPTIMIZERS = {'adam': Adam, 'sgd': SGD, 'rmsprop': RMSprop}
+
+
+def resolve_optimizer(optimizer):
+    """the `optimizer=` of compile(): 'adam' / 'sgd' / 'rmsprop' or an instance of Adam, SGD, RMSprop; anything else is refused"""
+    if isinstance(optimizer, str):
+        if optimizer.lower() not in _OPTIMIZERS:
+            raise ValueError(f'unknown optimizer {optimizer!r}: one of {sorted(_OPTIMIZERS)}')
+        return _OPTIMIZERS[optimizer.lower()]()
+    if isinstance(optimizer, (Adam, SGD, RMSprop)):
+        return optimizer
+    raise TypeError(f'compile(optimizer={type(optimizer).__name__}): supported are model_tools.Adam, model_tools.SGD, model_tools.RMSprop '
+                    "or the strings 'adam', 'sgd', 'rmsprop'")
+
+
+def reset_slots_on_recompile(owner, prev, new):
+    """Keras builds fresh slots for a newly compiled optimizer.  Here the moments of an Adam model have always survived a re-compile with
+    another Adam; any other change of optimizer starts from zero slots and step 0."""
+    if prev is not None and prev is not new and (prev.kind != new.kind or new.kind != 'adam'):
+        owner.reset_opt_slots()
+
+
+def apply_optimizer(opt, owner, st=None):
+    """The one step dispatch of every training path (U-Net engine, ConvLSTM tape, hybrid, data parallel -- whose all-reduce has run by
+    now): clip the flat gradient if the optimizer asks for it, then launch its update.  `owner` holds the flat buffers and the slots
+    (engine.Runtime or lstm_tools._Params).  A missing kernel is an error: there is no eager fallback."""
+    p, g, state, lr_mul = owner.opt_buffers()
+    st = ops.stream_ptr() if st is None else st
+    if opt.clipvalue is not None:
+        check(lib.satcv_grad_clip(g.data_ptr(), g.numel(), ops.CLIP_VALUE, float(opt.clipvalue), state.data_ptr(), None, st))
+    elif opt.global_clipnorm is not None:
+        check(lib.satcv_grad_clip(g.data_ptr(), g.numel(), ops.CLIP_GLOBAL_NORM, float(opt.global_clipnorm), state.data_ptr(),
+                                  owner.clip_workspace().data_ptr(), st))
+    lm = lr_mul.data_ptr() if lr_mul is not None else None
+    sl = owner.opt_slots(opt)
+    if opt.kind == 'adam':
+        check(lib.satcv_adam_step(p.data_ptr(), g.data_ptr(), sl['m'].data_ptr(), sl['v'].data_ptr(), p.numel(), opt.beta_1, opt.beta_2, opt.epsilon,
+                                  state.data_ptr(), lm, st))
+    elif opt.kind == 'sgd':
+        check(lib.satcv_sgd_step(p.data_ptr(), g.data_ptr(), sl['v'].data_ptr() if 'v' in sl else None, p.numel(), opt.momentum, int(opt.nesterov),
+                                 state.data_ptr(), lm, st))
+    elif opt.kind == 'rmsprop':
+        check(lib.satcv_rmsprop_step(p.data_ptr(), g.data_ptr(), sl['ms'].data_ptr(), sl['mg'].data_ptr() if 'mg' in sl else None,
+                                     sl['mom'].data_ptr() if 'mom' in sl else None, p.numel(), opt.rho, opt.momentum, opt.epsilon, state.data_ptr(), lm, st))
+    else:
+        raise TypeError(f'no update kernel for optimizer {type(opt).__name__}')
 
 
 class MeanIoU:
@@ -663,6 +761,159 @@ class ModelCheckpoint:
                 return
             self.best = cur
         (self.model.save_weights if self.save_weights_only else self.model.save)(path)
+
+
+def _auto_mode(mode, monitor):
+    if mode not in ('auto', 'min', 'max'):
+        raise ValueError(f"mode {mode!r}: one of 'auto', 'min', 'max'")
+    if mode == 'auto':
+        mode = 'max' if 'acc' in monitor else 'min'
+    return mode
+
+
+class LearningRateScheduler:
+    """tf.keras.callbacks.LearningRateScheduler: at the start of every epoch the rate becomes schedule(epoch, lr) (or schedule(epoch)
+    for a one-argument schedule), through `optimizer.learning_rate`; `lr` is added to the epoch logs."""
+
+    def __init__(self, schedule, verbose=0):
+        self.schedule, self.verbose = schedule, verbose
+        self.model = None
+
+    def on_epoch_begin(self, epoch, logs=None):
+        opt = self.model.optimizer
+        lr = float(opt.learning_rate)
+        try:
+            lr = self.schedule(epoch, lr)
+        except TypeError:               # (old one-argument form, as Keras still accepts)
+            lr = self.schedule(epoch)
+        if not isinstance(lr, (float, np.float32, np.float64)):
+            raise ValueError(f'The output of the "schedule" function should be float. Got: {lr}')
+        opt.learning_rate = float(lr)
+        if self.verbose:
+            print(f'Epoch {epoch + 1}: LearningRateScheduler setting learning rate to {float(lr)}.')
+
+    def on_epoch_end(self, epoch, logs):
+        logs['lr'] = float(self.model.optimizer.learning_rate)
+
+
+class ReduceLROnPlateau:
+    """tf.keras.callbacks.ReduceLROnPlateau: after `patience` epochs without an improvement of `monitor` by more than `min_delta` the rate
+    is multiplied by `factor` (not below `min_lr`), then `cooldown` epochs pass before the count starts again.  The rate goes through
+    `optimizer.learning_rate`; `lr` (the rate the epoch ran with) is added to the epoch logs."""
+
+    def __init__(self, monitor='val_loss', factor=0.1, patience=10, verbose=0, mode='auto', min_delta=1e-4, cooldown=0, min_lr=0, **kw):
+        if kw:
+            raise TypeError(f'ReduceLROnPlateau: unsupported arguments {sorted(kw)}')
+        if factor >= 1.0:
+            raise ValueError('ReduceLROnPlateau does not support a factor >= 1.0.')
+        self.monitor, self.factor, self.patience, self.verbose = monitor, factor, patience, verbose
+        self.min_delta, self.cooldown, self.min_lr = min_delta, cooldown, min_lr
+        self.mode = _auto_mode(mode, monitor)
+        self.model = None
+        self._reset()
+
+    def _reset(self):
+        self.best = -np.inf if self.mode == 'max' else np.inf
+        self.cooldown_counter, self.wait = 0, 0
+
+    def _better(self, cur):
+        return cur > self.best + self.min_delta if self.mode == 'max' else cur < self.best - self.min_delta
+
+    def on_train_begin(self, logs=None):
+        self._reset()
+
+    def on_epoch_end(self, epoch, logs):
+        opt = self.model.optimizer
+        logs['lr'] = float(opt.learning_rate)
+        cur = logs.get(self.monitor)
+        if cur is None:
+            import warnings
+            warnings.warn(f'ReduceLROnPlateau: metric `{self.monitor}` is not available (have {sorted(logs)})')
+            return
+        if self.cooldown_counter > 0:
+            self.cooldown_counter -= 1
+            self.wait = 0
+        if self._better(cur):
+            self.best, self.wait = cur, 0
+        elif self.cooldown_counter <= 0:
+            self.wait += 1
+            if self.wait >= self.patience:
+                old = float(opt.learning_rate)
+                if old > float(self.min_lr):
+                    opt.learning_rate = max(old * self.factor, float(self.min_lr))
+                    if self.verbose:
+                        print(f'Epoch {epoch + 1}: ReduceLROnPlateau reducing learning rate to {float(opt.learning_rate)}.')
+                    self.cooldown_counter, self.wait = self.cooldown, 0
+
+
+def _snapshot_weights(model):
+    snap = {'': model.get_weights_dict()}
+    for tag, bm in getattr(model, '_branch_models', dict)().items():
+        snap[tag] = bm.get_weights_dict()
+    return snap
+
+
+def _restore_weights(model, snap):
+    model.set_weights_dict(snap[''])
+    for tag, bm in getattr(model, '_branch_models', dict)().items():
+        bm.set_weights_dict(snap[tag])
+
+
+class EarlyStopping:
+    """tf.keras.callbacks.EarlyStopping: sets `model.stop_training` after `patience` epochs in which `monitor` has not improved on its
+    best value by more than `min_delta`; restore_best_weights puts the best epoch's variables (moving statistics included) back."""
+
+    def __init__(self, monitor='val_loss', min_delta=0, patience=0, verbose=0, mode='auto', restore_best_weights=False, **kw):
+        if kw:
+            raise TypeError(f'EarlyStopping: unsupported arguments {sorted(kw)}')
+        self.monitor, self.min_delta, self.patience, self.verbose = monitor, abs(min_delta), patience, verbose
+        self.mode = _auto_mode(mode, monitor)
+        self.restore_best_weights = restore_best_weights
+        self.model = None
+        self.on_train_begin()
+
+    def on_train_begin(self, logs=None):
+        self.wait, self.stopped_epoch, self.best_epoch = 0, 0, 0
+        self.best = -np.inf if self.mode == 'max' else np.inf
+        self.best_weights = None
+
+    def _better(self, cur):
+        return cur - self.min_delta > self.best if self.mode == 'max' else cur + self.min_delta < self.best
+
+    def on_epoch_end(self, epoch, logs):
+        cur = logs.get(self.monitor)
+        if cur is None:
+            import warnings
+            warnings.warn(f'EarlyStopping: metric `{self.monitor}` is not available (have {sorted(logs)})')
+            return
+        if self._better(cur):
+            self.best, self.best_epoch, self.wait = cur, epoch, 0
+            if self.restore_best_weights:
+                self.best_weights = _snapshot_weights(self.model)
+            return
+        self.wait += 1
+        if self.wait >= self.patience:
+            self.stopped_epoch = epoch
+            self.model.stop_training = True
+            if self.restore_best_weights and self.best_weights is not None:
+                _restore_weights(self.model, self.best_weights)
+            if self.verbose:
+                print(f'Epoch {epoch + 1}: early stopping')
+
+
+def run_callbacks(callbacks, hook, *args):
+    """call `hook` on every callback that has it (the callbacks of this module define only the hooks they use)"""
+    for cb in callbacks:
+        fn = getattr(cb, hook, None)
+        if fn is not None:
+            fn(*args)
+
+
+def record_callback_logs(hist, logs, before):
+    """entries the callbacks added to the epoch logs (`lr`) join the history, as in Keras, where History runs last"""
+    for k, v in logs.items():
+        if k not in before:
+            hist.history[k].append(v)
 
 
 class TensorBoard:
@@ -974,17 +1225,23 @@ class Model:
             if rt.adam_m is not None:
                 extra = {'optimizer_weights': [('satcv_adam/m:0', rt.adam_m.cpu().numpy()), ('satcv_adam/v:0', rt.adam_v.cpu().numpy()),
                                                ('satcv_adam/state:0', rt.adam_state.cpu().numpy())]}
+            elif rt.slots:       # SGD / RMSprop slots travel like the Adam moments: satcv_<kind>/<slot>
+                extra = {'optimizer_weights': [(f'satcv_{rt.slot_kind}/{k}:0', v.cpu().numpy()) for k, v in rt.slots.items()] +
+                                              [(f'satcv_{rt.slot_kind}/state:0', rt.adam_state.cpu().numpy())]}
             return hdf5_io.write_keras_weights(path, layers, root_attrs=attrs, model_weights_group=True, extra_groups=extra)
         d = self.get_weights_dict()
         d['__builder__'] = np.asarray(json.dumps(self._builder or {}))
         if rt.adam_m is not None:
             d['__adam_m__'], d['__adam_v__'] = rt.adam_m.cpu().numpy(), rt.adam_v.cpu().numpy()
             d['__adam_state__'] = rt.adam_state.cpu().numpy()
+        elif rt.slots:
+            d.update({f'__{rt.slot_kind}_{k}__': v.cpu().numpy() for k, v in rt.slots.items()})
+            d['__opt_kind__'], d['__opt_state__'] = np.asarray(rt.slot_kind), rt.adam_state.cpu().numpy()
         np.savez(path if path.endswith('.npz') else path + '.npz', **d)
 
     # ---- compile
     def compile(self, optimizer='adam', loss=None, metrics=None, **kw):
-        self.optimizer = Adam() if isinstance(optimizer, str) else optimizer
+        prev, new_opt = self.optimizer, resolve_optimizer(optimizer)
         if isinstance(loss, dict):           # Keras per-output form, e.g. loss={'logits': fn} (utils/model_tools.py:487, 526): one loss-bearing output
             unknown = [k for k in loss if k not in self.output_names]
             if unknown or len(loss) != 1:
@@ -1006,7 +1263,9 @@ class Model:
         for mt in self._metrics:
             names.append(mt if isinstance(mt, str) else mt.name)
         self.metrics_names = names
+        self.optimizer = new_opt
         if self._rt is not None:
+            reset_slots_on_recompile(self._rt, prev, new_opt)
             self.optimizer._rt = self._rt
             self._rt.adam_state[0:1].fill_(self.optimizer._lr)
 
@@ -1264,7 +1523,8 @@ class Model:
         if self._loss is None:
             raise RuntimeError('compile() the model before fit/train')
         rt = self.runtime
-        rt.ensure_adam()
+        opt = self.optimizer
+        rt.opt_slots(opt)
         n, h, w, _ = self._shape_of(xb)
         plan = self._head_plan(n, h, w, True)
         if getattr(self, '_frozen_applied', None) != plan.frozen:        # `layer.trainable` changed since the update masks were built
@@ -1279,10 +1539,11 @@ class Model:
         plan.step_count += 1                     # fresh dropout masks every step
         plan.run_forward(st)
         self._loss_launch(plan, st)
-        opt = self.optimizer
-        # (single replica: the bulk of the optimizer step may run inside the backward pass, engine.Plan `early`)
+        # (single replica: the bulk of the optimizer step may run inside the backward pass, engine.Plan `early` -- an opt-in experiment
+        # that exists for plain Adam only: a clipped step needs every gradient first, and the other rules have no `_part` form)
         plan.eo_done = False
-        plan.early_opt = dict(beta_1=opt.beta_1, beta_2=opt.beta_2, epsilon=opt.epsilon) if sync_grads is None else None
+        early_ok = sync_grads is None and opt.kind == 'adam' and opt.clipvalue is None and opt.global_clipnorm is None
+        plan.early_opt = dict(beta_1=opt.beta_1, beta_2=opt.beta_2, epsilon=opt.epsilon) if early_ok else None
         plan.run_backward(st)
         if sync_grads is not None:
             sync_grads(rt.gflat)
@@ -1293,9 +1554,7 @@ class Model:
                                            rt.lr_mul.data_ptr() if rt.lr_mul is not None else None, 1, st))
             rt.repack(0, lo)
         else:
-            check(lib.satcv_adam_step(rt.pflat.data_ptr(), rt.gflat.data_ptr(), rt.adam_m.data_ptr(), rt.adam_v.data_ptr(), rt.pflat.numel(),
-                                      opt.beta_1, opt.beta_2, opt.epsilon, rt.adam_state.data_ptr(),
-                                      rt.lr_mul.data_ptr() if rt.lr_mul is not None else None, st))
+            apply_optimizer(opt, rt, st)         # all-reduce (above), then clip if asked, then the optimizer's step
             rt.repack()
         self._weights_version = getattr(self, '_weights_version', 0) + 1
         return plan
@@ -1370,9 +1629,12 @@ class Model:
         callbacks = list(callbacks or [])
         for cb in callbacks:
             cb.model = self
+        self.stop_training = False
+        run_callbacks(callbacks, 'on_train_begin')
         it = None
         for epoch in range(initial_epoch, epochs):
             t0 = time.time()
+            run_callbacks(callbacks, 'on_epoch_begin', epoch)
             if it is None or steps_per_epoch is None:
                 order = None
                 if shuffle and (isinstance(x, (np.ndarray, torch.Tensor)) or (isinstance(x, (list, tuple)) and y is not None)):
@@ -1397,13 +1659,16 @@ class Model:
             hist.epoch.append(epoch)
             if verbose:
                 print(f'Epoch {epoch + 1}/{epochs} - {time.time() - t0:.1f}s - ' + ' - '.join(f'{k}: {v:.4f}' for k, v in logs.items()))
+            before = set(logs)
             for cb in callbacks:
                 if hasattr(cb, 'on_epoch_end'):
                     cb.on_epoch_end(epoch, logs)
+            record_callback_logs(hist, logs, before)
             if hasattr(x, 'on_epoch_end'):
                 x.on_epoch_end()
             if self.stop_training:
                 break
+        run_callbacks(callbacks, 'on_train_end')
         return hist
 
     def evaluate(self, x=None, y=None, batch_size=None, verbose=0, steps=None, **kw):
@@ -1444,6 +1709,11 @@ def load_model(path, custom_objects=None, compile=False):
         with hdf5_io.File(p) as f:
             cfg = json.loads(f.attrs['satcv_builder']) if 'satcv_builder' in f.attrs else {}
             opt = {k: f['optimizer_weights/satcv_adam/' + k + ':0'].read() for k in ('m', 'v', 'state')} if 'optimizer_weights/satcv_adam/m:0' in f else None
+            other = None
+            for kind, names in (('sgd', ('v',)), ('rmsprop', ('ms', 'mg', 'mom'))):
+                have = [k for k in names if f'optimizer_weights/satcv_{kind}/{k}:0' in f]
+                if have:
+                    other = (kind, {k: f[f'optimizer_weights/satcv_{kind}/{k}:0'].read() for k in have}, f[f'optimizer_weights/satcv_{kind}/state:0'].read())
         builders = {fn.__name__: fn for fn in (get_unet_model, get_deeplabv3_model, get_acnn_model, get_acnn_model2)}
         reset_uids()
         if cfg.get('fn') in builders:            # written by Model.save of this build: any of its network families
@@ -1455,6 +1725,8 @@ def load_model(path, custom_objects=None, compile=False):
             rt = m.runtime
             rt.ensure_adam()
             rt.adam_m.copy_(torch.from_numpy(opt['m'])); rt.adam_v.copy_(torch.from_numpy(opt['v'])); rt.adam_state.copy_(torch.from_numpy(opt['state']))
+        elif other is not None:
+            m.runtime.restore_opt_slots(*other)
         return m
     with np.load(p, allow_pickle=False) as z:
         cfg = json.loads(str(z['__builder__']))
@@ -1471,6 +1743,10 @@ def load_model(path, custom_objects=None, compile=False):
             rt.adam_m.copy_(torch.from_numpy(z['__adam_m__']))
             rt.adam_v.copy_(torch.from_numpy(z['__adam_v__']))
             rt.adam_state.copy_(torch.from_numpy(z['__adam_state__']))
+        elif '__opt_kind__' in z.files:
+            kind = str(z['__opt_kind__'])
+            pre = f'__{kind}_'
+            m.runtime.restore_opt_slots(kind, {k[len(pre):-2]: z[k] for k in z.files if k.startswith(pre)}, z['__opt_state__'])
     return m
 
 

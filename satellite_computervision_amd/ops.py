@@ -431,6 +431,32 @@ def adam_step(p, g, m, v, state, beta1=0.9, beta2=0.999, eps=1e-7, lr_mul=None):
     check(lib.satcv_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), beta1, beta2, eps, ptr(state), ptr(lr_mul), stream_ptr()))
 
 
+def sgd_step(p, g, v, state, momentum=0.0, nesterov=False, lr_mul=None):
+    """tf.keras.optimizers.SGD on flat buffers; `v` (the momentum slot) is None exactly when momentum == 0"""
+    check(lib.satcv_sgd_step(ptr(p), ptr(g), ptr(v), p.numel(), momentum, int(bool(nesterov)), ptr(state), ptr(lr_mul), stream_ptr()))
+
+
+def rmsprop_step(p, g, ms, mg, mom, state, rho=0.9, momentum=0.0, eps=1e-7, lr_mul=None):
+    """tf.keras.optimizers.RMSprop on flat buffers; `mg` is None unless centered, `mom` is None exactly when momentum == 0"""
+    check(lib.satcv_rmsprop_step(ptr(p), ptr(g), ptr(ms), ptr(mg), ptr(mom), p.numel(), rho, momentum, eps, ptr(state), ptr(lr_mul), stream_ptr()))
+
+
+CLIP_VALUE, CLIP_GLOBAL_NORM = 0, 1
+
+
+def grad_clip_workspace(n, device):
+    """the workspace of satcv_grad_clip(SATCV_CLIP_GLOBAL_NORM) as a float64 tensor: [0:1024] the partial sums, [1024] the squared norm"""
+    return torch.zeros(int(lib.satcv_grad_clip_workspace(n)) // 8, dtype=torch.float64, device=device)
+
+
+def grad_clip(g, mode, c, state=None, workspace=None):
+    """`clipvalue` / `global_clipnorm` of a Keras optimizer on the flat gradient, in place (no host synchronisation)"""
+    if mode == CLIP_GLOBAL_NORM and workspace is None:
+        workspace = grad_clip_workspace(g.numel(), g.device)
+    check(lib.satcv_grad_clip(ptr(g), g.numel(), mode, c, ptr(state), ptr(workspace), stream_ptr()))
+    return workspace
+
+
 def make_ctbf_desc(*, g, ldg, yup, ldy, bn_scale, bn_shift, bn_mean, bn_rstd, bn_c1, bn_c2, x, ldx, w_dgrad, w_npad, dx, lddx, dw, cin, cout, n, h, w_,
                    dtype, linear=0, in_scale=None, in_shift=None, in_relu=0, workspace=None, workspace_bytes=0, accumulate=0, defer_reduce=0,
                    bst_sums=None, bst_sums_ld=0, bst_mean=None, bst_rstd=None):
