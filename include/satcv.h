@@ -462,6 +462,58 @@ int satcv_label_onehot(const void* lc, int32_t lc_kind, const int32_t* lut, cons
                        int32_t n, int32_t hin, int32_t win, int32_t h, int32_t w_, int32_t nclasses, int32_t flip_v, int32_t flip_h,
                        int32_t rot, float* dst, int32_t ldc, int32_t coff, void* stream);
 
+/* ------------------------------------------------------------------ TFRecord training pipeline
+ * Device version of to_tuple (utils/processing.py:335-392) for one BATCH of parsed records, and of the per-record part of
+ * make_pred_dataset (utils/prediction_tools.py:159-226).
+ * src: (n, k, h, w_) fp32 planar, contiguous; plane j of sample i is feature j of that record as parsed.  kind[j]:
+ *   SATCV_PLANE_BAND             continuous band: colour augmentation, then rescale / standardise
+ *   SATCV_PLANE_ONEHOT           categorical feature: uint8(v) == e for e < depth[j] as 0/1              -- :349
+ *   SATCV_PLANE_RESPONSE         raw response                                                             -- :346
+ *   SATCV_PLANE_RESPONSE_ONEHOT  response as one-hot of depth[j]                                          -- :344
+ *   SATCV_PLANE_PASS             band copied unchanged (what custom functions append after the rescale, prediction_tools.py:463-464)
+ * Feature channels of a pixel, in order: the bands, the passthrough bands, the one-hot features (each group in plane order) -- the
+ * order to_tuple concatenates them (:355); label channels: the response planes.
+ * Per-sample parameters: params (n, ld_params) fp32 on the device, row = contra[nband] | bright[nband] | flip_lr | flip_ud | rot.
+ *   color: (x - m_c) * contra_c + m_c * bright_c per band (aug_tensor_color, :129-152); m_c = the mean over (h, w) of the statistics
+ *          table rounded to fp32, or mean_in (n, nband) fp32 when given
+ *   mode:  SATCV_RECORD_RESCALE (x - mn) / ((mx - mn) + eps) (rescale_tensor, :281-322), SATCV_RECORD_NORMALIZE
+ *          (x - mean) / sqrt(var + eps) (normalize_tensor, :225-279), applied AFTER the colour step; statistics from stat_src:
+ *          MOMENTS  mom_a / mom_b per band (min, max or mean, variance)
+ *          CHANNEL  per band over (h, w) (axes [0, 1]): the raw min / max of the table pushed through the same fp32 colour expression
+ *                   (monotone, so exact); mean and variance in closed form in double
+ *          PIXEL    per pixel over the bands of a group (axes [2])
+ *          GROUP    over everything of a group (axes [0, 1, 2])
+ *          groups: bands [gstart[g], gstart[g] + glen[g]); bands outside every group pass through (normalize_tensor's remainder)
+ *   morph: flip left-right, flip up-down, np.rot90 by rot of features and labels as one stack (aug_tensor_morph, :169-183); needs h == w_
+ * x: fp32 NHWC (n, h, w_, ld_x) written at channel offset coff_x; y: (n, h, w_, ld_y) at coff_y (may be NULL without response planes).
+ * Arithmetic: the colour and rescale expressions are separate correctly rounded fp32 operations in NumPy's order (no FMA).
+ *
+ * satcv_record_stats fills stats (n, k, 4) doubles = mean, min, max, population variance over (h, w) of every BAND plane: double sums
+ * of the fp32 samples in a fixed order, min(16, max(1, h * w_ / 4096)) workgroups per plane and a second stage (no atomics; the order
+ * does not depend on n).  stats_ws: n * k * SATCV_RECORD_STAT_SPLITS * 4 doubles are always enough.  A descriptor that names a
+ * destination x is checked as satcv_record_to_tuple checks it, so that a transform that will be refused starts no launch at all. */
+#define SATCV_RECORD_MAX_PLANES 32
+#define SATCV_RECORD_STAT_SPLITS 16
+enum { SATCV_PLANE_BAND = 0, SATCV_PLANE_ONEHOT = 1, SATCV_PLANE_RESPONSE = 2, SATCV_PLANE_RESPONSE_ONEHOT = 3, SATCV_PLANE_PASS = 4 };
+enum { SATCV_RECORD_NONE = 0, SATCV_RECORD_RESCALE = 1, SATCV_RECORD_NORMALIZE = 2 };
+enum { SATCV_STAT_MOMENTS = 0, SATCV_STAT_CHANNEL = 1, SATCV_STAT_PIXEL = 2, SATCV_STAT_GROUP = 3 };
+typedef struct satcv_record_desc {
+  const float* src;
+  int32_t n, k, h, w_;
+  int32_t kind[SATCV_RECORD_MAX_PLANES], depth[SATCV_RECORD_MAX_PLANES];
+  const float* params; int32_t ld_params;
+  int32_t color, morph, mode, stat_src;
+  int32_t ngroups, gstart[SATCV_RECORD_MAX_PLANES], glen[SATCV_RECORD_MAX_PLANES];
+  float mom_a[SATCV_RECORD_MAX_PLANES], mom_b[SATCV_RECORD_MAX_PLANES];
+  float eps;
+  double* stats; double* stats_ws; int64_t stats_ws_bytes;
+  const float* mean_in;
+  float* x; int32_t ld_x, coff_x;
+  float* y; int32_t ld_y, coff_y;
+} satcv_record_desc;
+int satcv_record_stats(const satcv_record_desc* d, void* stream);
+int satcv_record_to_tuple(const satcv_record_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ device-resident scene prediction
  * The sliding-window loop of predict_pc_local / predict_chips (utils/prediction_tools.py:133-156) with the scene and the
  * prediction map resident on the device.  `origins` is a device int32 (total, 2) table of (y, x): the upper-left corner of each

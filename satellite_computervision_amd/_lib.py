@@ -66,6 +66,19 @@ class CompositeDesc(C.Structure):
                 ('use_fill', c_i32), ('fill', c_f32)]
 
 
+RECORD_MAX_PLANES = 32     # SATCV_RECORD_MAX_PLANES of include/satcv.h
+RECORD_STAT_SPLITS = 16    # SATCV_RECORD_STAT_SPLITS
+_i32p, _f32p = c_i32 * RECORD_MAX_PLANES, c_f32 * RECORD_MAX_PLANES
+
+
+class RecordDesc(C.Structure):
+    _fields_ = [('src', c_vp), ('n', c_i32), ('k', c_i32), ('h', c_i32), ('w_', c_i32), ('kind', _i32p), ('depth', _i32p),
+                ('params', c_vp), ('ld_params', c_i32), ('color', c_i32), ('morph', c_i32), ('mode', c_i32), ('stat_src', c_i32),
+                ('ngroups', c_i32), ('gstart', _i32p), ('glen', _i32p), ('mom_a', _f32p), ('mom_b', _f32p), ('eps', c_f32),
+                ('stats', c_vp), ('stats_ws', c_vp), ('stats_ws_bytes', c_i64), ('mean_in', c_vp),
+                ('x', c_vp), ('ld_x', c_i32), ('coff_x', c_i32), ('y', c_vp), ('ld_y', c_i32), ('coff_y', c_i32)]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [('x0', c_vp), ('x1', c_vp), ('c0', c_i32), ('c1', c_i32),
                 ('in_scale', c_vp), ('in_shift', c_vp), ('in_relu', c_i32),
@@ -200,6 +213,8 @@ _SIGS = {
     'satcv_scene_gather': (C.c_int, [C.POINTER(SceneGatherDesc), c_vp]),
     'satcv_scene_scatter': (C.c_int, [C.POINTER(SceneScatterDesc), c_vp]),
     'satcv_median_composite': (C.c_int, [C.POINTER(CompositeDesc), c_vp]),
+    'satcv_record_stats': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
+    'satcv_record_to_tuple': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_label_onehot': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
     'satcv_crc32c': (C.c_uint32, [c_vp, C.c_uint64, C.c_uint32]),
     'satcv_head_fwd': (C.c_int, [C.POINTER(HeadDesc), c_vp]),

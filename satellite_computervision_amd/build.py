@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'libsatcv.so')
 OBJDIR = os.path.join(HERE, 'csrc', '_obj')
-SOURCES = ['api.hip', 'comm.hip', 'composite.hip', 'conv_igemm.hip', 'conv_igemm_fast.hip', 'conv_igemm_m16.hip', 'conv_igemm_m16p.hip', 'conv_igemm_ws.hip', 'conv_thin_roles.hip', 'conv_transpose_thin.hip', 'conv_bwd_fused.hip', 'convt_bwd_fused.hip', 'conv_wgrad.hip', 'convlstm.hip', 'elementwise.hip', 'input_pipeline.hip', 'scene.hip']
+SOURCES = ['api.hip', 'comm.hip', 'composite.hip', 'conv_igemm.hip', 'conv_igemm_fast.hip', 'conv_igemm_m16.hip', 'conv_igemm_m16p.hip', 'conv_igemm_ws.hip', 'conv_thin_roles.hip', 'conv_transpose_thin.hip', 'conv_bwd_fused.hip', 'convt_bwd_fused.hip', 'conv_wgrad.hip', 'convlstm.hip', 'elementwise.hip', 'input_pipeline.hip', 'record_pipeline.hip', 'scene.hip']
 EXTRA = []
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function',
          '-Wno-unused-variable', '-Wno-pass-failed']
@@ -97,7 +97,8 @@ def build_host_asan(verbose=False):
     if os.path.exists(out) and os.path.exists(stamp) and open(stamp).read() == h.hexdigest():
         return out
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    flags = ['--offload-arch=gfx950', '--cuda-host-only', '-O1', '-g', '-fPIC', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=undefined',
+    # -fno-gpu-sanitize: the sanitizers instrument the host objects only; said explicitly on every hipcc line that names them
+    flags = ['--offload-arch=gfx950', '--cuda-host-only', '-O1', '-g', '-fPIC', '-std=c++17', '-fsanitize=address,undefined', '-fno-gpu-sanitize', '-fno-sanitize-recover=undefined',
              '-fno-omit-frame-pointer', '-Wno-unused-function', '-Wno-unused-variable', '-Wno-pass-failed']
 
     def one(src):
@@ -116,7 +117,7 @@ def build_host_asan(verbose=False):
     open(stub, 'w').write(''.join(f'const char {sy}[16] = {{0}};\n' for sy in syms))
     subprocess.run(['gcc', '-fPIC', '-c', stub, '-o', stub[:-2] + '.o'], check=True)
     objs.append(stub[:-2] + '.o')
-    r = subprocess.run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-fsanitize=address,undefined', '-o', out] + objs + ['-ldl'], capture_output=True, text=True)
+    r = subprocess.run([hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-fsanitize=address,undefined', '-fno-gpu-sanitize', '-o', out] + objs + ['-ldl'], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f'link (host ASan) failed:\n{r.stderr[-4000:]}')
     open(stamp, 'w').write(h.hexdigest())

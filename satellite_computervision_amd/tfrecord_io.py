@@ -370,8 +370,11 @@ class Dataset:
     def __iter__(self):
         return self._source()
 
+    def _chain(self, source):                 # what shuffle / batch / repeat / take return (the device dataset keeps its last stage)
+        return Dataset(source)
+
     def map(self, fn, num_parallel_calls=None):
-        return Dataset(lambda: (fn(*e) if isinstance(e, tuple) else fn(e) for e in self._source()))
+        return Dataset(lambda: (fn(*e) if isinstance(e, tuple) else fn(e) for e in iter(self)))
 
     def shuffle(self, buffer_size):
         """tf.data shuffle semantics: a buffer of `buffer_size` elements, one drawn at random as each new element arrives."""
@@ -383,7 +386,7 @@ class Dataset:
                     yield buf.pop(int(_RNG.integers(0, len(buf))))
             while buf:
                 yield buf.pop(int(_RNG.integers(0, len(buf))))
-        return Dataset(gen)
+        return self._chain(gen)
 
     def batch(self, n, drop_remainder=False):
         def gen():
@@ -395,7 +398,7 @@ class Dataset:
                     cur = []
             if cur and not drop_remainder:
                 yield tuple(np.stack(c) for c in zip(*cur)) if isinstance(cur[0], tuple) else np.stack(cur)
-        return Dataset(gen)
+        return self._chain(gen)
 
     def repeat(self, count=None):
         def gen():
@@ -408,18 +411,221 @@ class Dataset:
                 if empty:
                     return
                 i += 1
-        return Dataset(gen)
+        return self._chain(gen)
 
     def take(self, n):
         import itertools
-        return Dataset(lambda: itertools.islice(self._source(), n))
+        return self._chain(lambda: itertools.islice(self._source(), n))
 
 
-def get_dataset(files, ftDict, features, response, axes=[2], splits=None, one_hot=None, moments=None, **kwargs):
-    """utils/processing.py:394-419: GZIP TFRecords -> parse_single_example(ftDict) -> to_tuple."""
-    files = [files] if isinstance(files, str) else list(files)
+# ---- device side of the chain: csrc/record_pipeline.hip.  Plane kinds and modes of include/satcv.h
+PLANE_BAND, PLANE_ONEHOT, PLANE_RESPONSE, PLANE_RESPONSE_ONEHOT, PLANE_PASS = 0, 1, 2, 3, 4
+_KIND_NAMES = {'band': PLANE_BAND, 'onehot': PLANE_ONEHOT, 'response': PLANE_RESPONSE, 'response_onehot': PLANE_RESPONSE_ONEHOT, 'pass': PLANE_PASS}
+_MODES = {None: 0, 'rescale': 1, 'normalize': 2}
 
-    def records():
+
+def _groups(mode, nband, splits):
+    """(start, length) of the band groups: rescale_tensor splits ALL channels (np.split: the last group runs to the end),
+    normalize_tensor standardises the first sum(splits) channels group by group and passes the rest through."""
+    if not splits:
+        return [(0, nband)] if nband else []
+    starts = [0] + [int(v) for v in np.cumsum(splits)[:-1]]
+    ends = starts[1:] + [nband if mode == 'rescale' else int(sum(splits))]
+    if any(e <= s_ or e > nband for s_, e in zip(starts, ends)):
+        raise ValueError(f'splits {list(splits)} do not fit {nband} continuous bands')
+    return [(s_, e - s_) for s_, e in zip(starts, ends)]
+
+
+def device_to_tuple(planes, kinds, params=None, *, color=True, morph=True, mode='rescale', axes=[2], splits=None, moments=None, epsilon=1e-8,
+                    x=None, coff_x=0, y=None, coff_y=0, mean=None, device=None, return_stats=False):
+    """One batch of parsed records -> (features NHWC, labels NHWC | None, tensors to keep alive) on the device: to_tuple
+    (utils/processing.py:335-392) as the two launches of csrc/record_pipeline.hip on the current stream.  Mirrors
+    processing.device_source.
+
+    planes  (n, k, h, w) float32, NumPy (uploaded here) or a device tensor
+    kinds   one entry per plane: 'band', ('onehot', depth), 'response', ('response_onehot', depth), 'pass', or the integer codes of
+            include/satcv.h (alone or as (code, depth))
+    params  (n, 2 * nband + 3) float32: contrast[nband], brightness[nband], flip left-right, flip up-down, rot90 count per record
+    mode    'rescale' (rescale_tensor), 'normalize' (normalize_tensor) or None, applied after the colour step with statistics from
+            `moments`, or over `axes` ([0, 1], [2] or [0, 1, 2]) within the groups of `splits`
+    mean    optional (n, nband) float32: the m_c of the colour step instead of the device's own means (tests inject the host's)
+    x / y   optional destination tensors, written at channel offsets coff_x / coff_y
+
+    'normalize' over axes [0, 1, 2] with colour on needs no reduction over the coloured values: the colour map is affine per channel,
+    so the kernel pools the closed-form per-channel moments of a group (all channels have h * w samples).  Refused here: `moments`
+    together with `splits` (the host expression broadcasts a full-length moment vector against each part and fails as well)."""
+    import ctypes as C
+    import torch
+    from . import ops
+    from ._lib import lib, check, RecordDesc, RECORD_MAX_PLANES, RECORD_STAT_SPLITS
+    if mode not in _MODES:
+        raise ValueError(f'mode must be "rescale", "normalize" or None, not {mode!r}')
+    if len(planes.shape) != 4:
+        raise ValueError('planes must be a (n, k, h, w) float32 batch')
+    n, k, h, w = planes.shape
+    if len(kinds) != k or k > RECORD_MAX_PLANES:
+        raise ValueError(f'{len(kinds)} plane kinds for {k} planes (at most {RECORD_MAX_PLANES})')
+    codes, depths = [], []
+    for e in kinds:
+        name, depth = (e if isinstance(e, (tuple, list)) else (e, 0))
+        codes.append(_KIND_NAMES[name] if isinstance(name, str) else int(name))
+        depths.append(int(depth))
+    nband = codes.count(PLANE_BAND)
+    nx = nband + codes.count(PLANE_PASS) + sum(d for c, d in zip(codes, depths) if c == PLANE_ONEHOT)
+    ny = codes.count(PLANE_RESPONSE) + sum(d for c, d in zip(codes, depths) if c == PLANE_RESPONSE_ONEHOT)
+    ax = sorted(int(a) % 3 for a in axes) if axes is not None else [2]
+    if moments:
+        if splits:
+            raise ValueError('moments together with splits is not supported')
+        if len(moments) != nband:
+            raise ValueError(f'{len(moments)} moments for {nband} continuous bands')
+        stat_src = 0
+    else:
+        if ax not in ([0, 1], [2], [0, 1, 2]):
+            raise ValueError(f'axes must be [0, 1], [2] or [0, 1, 2], not {list(axes)}')
+        stat_src = {2: 1, 1: 2, 3: 3}[len(ax)]
+    if isinstance(planes, torch.Tensor):
+        src, dev = planes, planes.device
+    else:
+        dev = torch.device(device if device is not None else 'cuda')
+        src = torch.from_numpy(np.ascontiguousarray(planes, dtype=np.float32)).to(dev, non_blocking=True)
+    if src.dtype != torch.float32 or not src.is_contiguous() or not src.is_cuda:
+        raise ValueError('planes must be a contiguous float32 batch on the device')
+    d = RecordDesc(src=src.data_ptr(), n=n, k=k, h=h, w_=w, color=int(bool(color)), morph=int(bool(morph)), mode=_MODES[mode], stat_src=stat_src,
+                   eps=float(epsilon), coff_x=int(coff_x), coff_y=int(coff_y))
+    for j in range(k):
+        d.kind[j], d.depth[j] = codes[j], depths[j]
+    if mode is not None:
+        groups = _groups(mode, nband, splits)
+        d.ngroups = len(groups)
+        for g, (s_, l) in enumerate(groups):
+            d.gstart[g], d.glen[g] = s_, l
+    for c, (a, b) in enumerate(moments or []):
+        d.mom_a[c], d.mom_b[c] = float(np.float32(a)), float(np.float32(b))
+    keep = [src]
+    if params is not None:
+        prm = params if isinstance(params, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev, non_blocking=True)
+        if prm.dim() != 2 or prm.shape[0] != n or prm.dtype != torch.float32 or not prm.is_contiguous():
+            raise ValueError('params must be a contiguous (n, 2 * nband + 3) float32 table')
+        d.params, d.ld_params = prm.data_ptr(), prm.shape[1]
+        keep.append(prm)
+    if mean is not None:
+        mt = mean if isinstance(mean, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mean, dtype=np.float32).reshape(n, nband)).to(dev, non_blocking=True)
+        d.mean_in = mt.data_ptr()
+        keep.append(mt)
+    if x is None:
+        x = torch.empty(n, h, w, nx, dtype=torch.float32, device=dev)
+    if y is None and ny:
+        y = torch.empty(n, h, w, ny, dtype=torch.float32, device=dev)
+    for t, what in ((x, 'x'), (y, 'y')):
+        if t is not None and (tuple(t.shape[:3]) != (n, h, w) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != src.device):
+            raise ValueError(f'{what} must be a contiguous float32 ({n}, {h}, {w}, ld) tensor on the device of the planes')
+    d.x, d.ld_x = x.data_ptr(), x.shape[3]
+    if y is not None:
+        d.y, d.ld_y = y.data_ptr(), y.shape[3]
+    st = ops.stream_ptr()
+    stats = None
+    if nband and ((color and mean is None) or (mode is not None and stat_src in (1, 3)) or return_stats):
+        stats = torch.empty(n, k, 4, dtype=torch.float64, device=dev)
+        ws = torch.empty(n * k * RECORD_STAT_SPLITS * 4, dtype=torch.float64, device=dev)
+        d.stats, d.stats_ws, d.stats_ws_bytes = stats.data_ptr(), ws.data_ptr(), ws.numel() * 8
+        check(lib.satcv_record_stats(C.byref(d), st))
+        keep += [stats, ws]
+    check(lib.satcv_record_to_tuple(C.byref(d), st))
+    if return_stats:
+        return x, y, keep, stats
+    return x, y, keep
+
+
+class _PinnedStage:
+    """Two pinned host buffers per batch shape, used in turn: a buffer is refilled only after the stream has passed the copy that read
+    it (an event recorded behind the upload)."""
+
+    def __init__(self):
+        self._slots = {}
+
+    def fill(self, arr):
+        """Copy `arr` into the next free pinned buffer of its shape (waits for the upload that last read that buffer)."""
+        import torch
+        key = (arr.shape, arr.dtype.str)
+        slots = self._slots.setdefault(key, {'i': 0, 'buf': [None, None], 'ev': [None, None]})
+        i = slots['i'] = 1 - slots['i']
+        if slots['buf'][i] is None:
+            slots['buf'][i] = torch.empty(arr.shape, dtype=torch.float32, pin_memory=True)
+        else:
+            slots['ev'][i].synchronize()
+        slots['buf'][i].numpy()[...] = arr
+        return slots, i
+
+    def send(self, filled, dev):
+        """Enqueue the upload of a filled buffer on the current stream and record the event that frees the buffer."""
+        import torch
+        slots, i = filled
+        out = slots['buf'][i].to(dev, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        slots['ev'][i] = ev
+        return out
+
+    def upload(self, arr, dev):
+        return self.send(self.fill(arr), dev)
+
+
+class DeviceDataset(Dataset):
+    """The chain of `Dataset` over (planes, params) elements with a last stage that uploads each element and runs to_tuple on the
+    device.  shuffle / batch / repeat / take work on the host elements unchanged -- and draw from the same generator at the same
+    points as the host chain -- and the stage is applied when the dataset is iterated."""
+
+    def __init__(self, source, spec):
+        super().__init__(source)
+        self._spec = spec
+
+    def _chain(self, source):
+        return DeviceDataset(source, self._spec)
+
+    def __iter__(self):
+        import torch
+        sp = self._spec
+        dev = torch.device(sp['device'])
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        stage = _PinnedStage()
+
+        def gen():
+            for planes, params in self._source():
+                single = planes.ndim == 3
+                if single:
+                    planes, params = planes[None], params[None]
+                with torch.cuda.device(dev):
+                    x, y, _ = device_to_tuple(stage.upload(planes, dev), sp['kinds'], stage.upload(params, dev), color=True, morph=True, mode='rescale',
+                                              axes=sp['axes'], splits=sp['splits'], moments=sp['moments'])
+                yield (x[0], y[0]) if single else (x, y)
+        return gen()
+
+
+def _parse_file(path, ftDict):
+    """Every record of one file as a dictionary of [H, W] float32 arrays (parse_single_example with `ftDict`), plus the error that ended
+    the file early, if any: the consumer yields what was read and then raises it, as the sequential reader does."""
+    out = []
+    try:
+        for payload in read_records(path):
+            ex = decode_example(payload)
+            dic = {}
+            for k, spec in ftDict.items():
+                if k not in ex:
+                    raise KeyError(f'{path}: feature {k} not in the record')
+                shape = tuple(getattr(spec, 'shape', spec))
+                dic[k] = np.asarray(ex[k], dtype=np.float32).reshape(shape)
+            out.append(dic)
+    except Exception as e:                    # re-raised by the consumer in file order
+        return out, e
+    return out, None
+
+
+def _parsed_records(files, ftDict, read_ahead):
+    """Parsed records of `files` in file order.  read_ahead 0: record by record, sequentially; n > 0: up to `read_ahead` following files are decompressed and parsed by worker threads
+    (at most 5, the reference's num_parallel_calls) while the current one is consumed."""
+    if not read_ahead or read_ahead <= 0:
         for path in files:
             for payload in read_records(path):
                 ex = decode_example(payload)
@@ -429,26 +635,126 @@ def get_dataset(files, ftDict, features, response, axes=[2], splits=None, one_ho
                         raise KeyError(f'{path}: feature {k} not in the record')
                     shape = tuple(getattr(spec, 'shape', spec))
                     dic[k] = np.asarray(ex[k], dtype=np.float32).reshape(shape)
+                yield dic
+        return
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
+    read_ahead = int(read_ahead)
+    with ThreadPoolExecutor(max_workers=min(int(read_ahead), 5)) as pool:
+        pending, nxt = deque(), 0
+        while nxt < len(files) or pending:
+            while nxt < len(files) and len(pending) < read_ahead + 1:
+                pending.append(pool.submit(_parse_file, files[nxt], ftDict))
+                nxt += 1
+            recs, err = pending.popleft().result()
+            yield from recs
+            if err is not None:
+                for f in pending:
+                    f.cancel()
+                raise err
+
+
+def _record_planes(features, response, one_hot):
+    """The planes of one record in the order the kernel expects, and their kinds: bands, one-hot features, response."""
+    hot = {k: v for k, v in (one_hot or {}).items() if k in features}
+    names = [k for k in features if k not in (one_hot or {})] + list(hot)
+    kinds = ['band'] * (len(names) - len(hot)) + [('onehot', int(v)) for v in hot.values()]
+    if type(response) == dict:
+        key, depth = list(response.keys())[0], list(response.values())[0]
+        names.append(key)
+        kinds.append(('response_onehot', int(depth)))
+    else:
+        names.append(response)
+        kinds.append('response')
+    return names, kinds
+
+
+def get_dataset(files, ftDict, features, response, axes=[2], splits=None, one_hot=None, moments=None, device=None, read_ahead=0, **kwargs):
+    """utils/processing.py:394-419: GZIP TFRecords -> parse_single_example(ftDict) -> to_tuple.
+
+    device: None -> NumPy batches from the host to_tuple.  A torch device -> the records are parsed (and the custom `**kwargs`
+    functions run) on the host, their random parameters are drawn from the same generator at the same points and in the same order as
+    the host to_tuple draws them (contrast, brightness, flip, flip, rotation), and the transform itself runs on the device
+    (device_to_tuple): after set_seed(s) both datasets yield the same batches in the same order, the device one as device tensors.
+    Training tiles must be square on the device.
+    read_ahead: n > 0 -> up to n following files are decompressed and parsed by at most 5 worker threads while the current one is
+    consumed; records come in file order, so the result does not depend on n."""
+    files = [files] if isinstance(files, str) else list(files)
+
+    def parsed():
+        return _parsed_records(files, ftDict, read_ahead)
+
+    if device is None:
+        def records():
+            for dic in parsed():
                 yield to_tuple(dic, features, response, axes, splits, one_hot, moments, **kwargs)
-    return Dataset(records)
+        return Dataset(records)
+
+    names, kinds = _record_planes(features, response, one_hot)
+    nband = kinds.count('band')
+
+    def records():
+        for dic in parsed():
+            for fxn in kwargs.values():
+                dic = fxn(dic)
+            missing = [k for k in names if k not in dic]
+            if missing:
+                raise KeyError(f'features {missing} not in the parsed record (ftDict names {list(dic)})')
+            planes = np.stack([np.asarray(dic[k], dtype=np.float32) for k in names], axis=0)
+            if planes.ndim != 3 or planes.shape[1] != planes.shape[2]:
+                raise ValueError(f'the device training pipeline needs square [H, W] tiles, got {planes.shape[1:]}')
+            params = np.empty(2 * nband + 3, np.float32)
+            params[:nband] = _RNG.uniform(0.95, 1.05, (1, 1, nband)).astype(np.float32).reshape(-1)          # aug_tensor_color
+            params[nband:2 * nband] = _RNG.uniform(0.95, 1.05, (1, 1, nband)).astype(np.float32).reshape(-1)
+            params[2 * nband] = _RNG.random() < 0.5                                                          # aug_tensor_morph
+            params[2 * nband + 1] = _RNG.random() < 0.5
+            params[2 * nband + 2] = int(_RNG.integers(0, 4))
+            yield planes, params
+    return DeviceDataset(records, dict(device=device, kinds=kinds, axes=axes, splits=splits, moments=moments))
 
 
-def get_training_dataset(files, ftDict, features, response, buff, batch=16, repeat=True, axes=[2], splits=None, one_hot=None, moments=None, **kwargs):
-    """utils/processing.py:421-441: shuffle(buff).batch(batch)[.repeat()]."""
-    dataset = get_dataset(files, ftDict, features, response, axes, splits, one_hot, moments, **kwargs)
+def get_training_dataset(files, ftDict, features, response, buff, batch=16, repeat=True, axes=[2], splits=None, one_hot=None, moments=None,
+                         device=None, read_ahead=0, **kwargs):
+    """utils/processing.py:421-441: shuffle(buff).batch(batch)[.repeat()].  device / read_ahead: see get_dataset."""
+    dataset = get_dataset(files, ftDict, features, response, axes, splits, one_hot, moments, device=device, read_ahead=read_ahead, **kwargs)
     return dataset.shuffle(buff).batch(batch).repeat() if repeat else dataset.shuffle(buff).batch(batch)
 
 
-def get_eval_dataset(files, ftDict, features, response, axes=[2], splits=None, one_hot=None, moments=None, **kwargs):
-    """utils/processing.py:443-454: batch(1)."""
-    return get_dataset(files, ftDict, features, response, axes, splits, one_hot, moments, **kwargs).batch(1)
+def get_eval_dataset(files, ftDict, features, response, axes=[2], splits=None, one_hot=None, moments=None, device=None, read_ahead=0, **kwargs):
+    """utils/processing.py:443-454: batch(1).  device / read_ahead: see get_dataset."""
+    return get_dataset(files, ftDict, features, response, axes, splits, one_hot, moments, device=device, read_ahead=read_ahead, **kwargs).batch(1)
 
 
 def make_pred_dataset(file_list, features, kernel_shape=[256, 256], kernel_buffer=[128, 128], axes=[2], splits=None, moments=None,
-                      one_hot=None, **kwargs):
-    """utils/prediction_tools.py:159-226: generator of (1, H+buf, W+buf, C) float32 batches, files in sorted order."""
+                      one_hot=None, device=None, **kwargs):
+    """utils/prediction_tools.py:159-226: generator of (1, H+buf, W+buf, C) float32 batches, files in sorted order.
+    device: a torch device -> the rescale and the one-hot run on the device (device_to_tuple without colour and morph; the bands
+    that the custom functions append are uploaded as passthrough planes) and the batches are device tensors."""
     file_list = sorted(file_list)
     shape = (kernel_shape[0] + kernel_buffer[0], kernel_shape[1] + kernel_buffer[1])
+
+    def gen_device():
+        import torch
+        dev = torch.device(device)
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        stage = _PinnedStage()
+        band_names = [k for k in features if not (one_hot and k in one_hot)]
+        kinds = ['band'] * len(band_names) + ['pass'] * len(kwargs) + [('onehot', int(d_)) for d_ in (one_hot or {}).values()]
+        for path in file_list:
+            for payload in read_records(path):
+                dic = {k: v.reshape(shape).astype(np.float32) for k, v in decode_example(payload).items() if k in features}
+                missing = [k for k in features if k not in dic]
+                if missing:
+                    raise KeyError(f'{path}: features {missing} not in the record')
+                planes = [dic[k] for k in band_names] + [np.asarray(fxn(dic), dtype=np.float32) for fxn in kwargs.values()]
+                planes += [dic[k] for k in (one_hot or {})]
+                with torch.cuda.device(dev):
+                    x, _, _ = device_to_tuple(stage.upload(np.stack(planes, axis=0)[None], dev), kinds, None, color=False, morph=False, mode='rescale',
+                                              axes=axes, splits=splits, moments=moments)
+                yield x
+    if device is not None:
+        return gen_device()
 
     def gen():
         for path in file_list:
