@@ -716,6 +716,8 @@ typedef struct satcv_lstm_gates_desc {
   int32_t act;                         /* 0 linear (activation=None, as every reference call site), 1 tanh (the Keras default)    */
   int32_t dtype;
 } satcv_lstm_gates_desc;
+/* Both refuse filters outside 8, 16, 32, 64, 128, 256 and any leading dimension narrower than its tensor (ldx, ldh_g, lddz >= 4 F; ldh,
+ * stats_ld, lddh_a, lddh_b >= F).  The backward takes the hard-sigmoid slope from the STORED gate: 0.2 strictly inside (0, 1), else 0. */
 int satcv_convlstm_gates_fwd(const satcv_lstm_gates_desc* d, void* stream);
 int satcv_convlstm_gates_bwd(const satcv_lstm_gates_desc* d, void* stream);
 
@@ -741,6 +743,9 @@ typedef struct satcv_dense_desc {
   int64_t npix; int32_t h, w_;                     /* output grid (npix = images * h * w_)                                         */
   const float* dout; float* dz_out; float* dw; float* db;
 } satcv_dense_desc;
+/* Both validate every source (x, cin > 0, ld >= cin, dtype, hs / ws both zero or both set, in_scale and in_shift together) and the grid
+ * (h, w_ > 0, npix a whole number of images); the forward refuses an activation outside 0 .. 3, the backward a dx with lddx < cin or a
+ * dx_dtype other than float32 / bf16.  The nearest index is evaluated in float32, floorf((i + 0.5f) * ((float) in / (float) out)). */
 int satcv_dense_small_fwd(const satcv_dense_desc* d, void* stream);
 int satcv_dense_small_bwd(const satcv_dense_desc* d, void* stream);
 

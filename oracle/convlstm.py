@@ -135,10 +135,18 @@ def bn5_train_bwd(x, gamma, mean, var, dy, eps=1e-3):
 
 def resize_nearest(x, oh, ow):
     """tf.image.resize(x, [oh, ow], method='nearest') (utils/model_tools.py:908, 1055).  TF 2.x's resize_images_v2 calls
-    ResizeNearestNeighbor with half_pixel_centers=True: source index = min(floor((dst + 0.5) * in / out), in - 1)."""
+    ResizeNearestNeighbor with half_pixel_centers=True: source index = min(floor((dst + 0.5) * in / out), in - 1).
+
+    The index is evaluated in FLOAT32, (dst + 0.5f) * (in / (float) out) then floorf, as the TF kernel does -- the adopted reading, from
+    recollection of TF's source (TensorFlow is not available to the tests; tests/test_lstm_kernels_cpu.py::test_nearest_is_tf_image_resize
+    checks it wherever it is).  Float64 or exact integer arithmetic gives another index on a few size pairs (14 -> 23, 26 -> 11, ...: 22 of
+    the pairs up to 48 x 48); on the 8 -> 48 of the reference models all forms agree."""
     n, h, w, c = x.shape
-    iy = np.minimum(np.floor((np.arange(oh) + 0.5) * (h / oh)).astype(np.int64), h - 1)
-    ix = np.minimum(np.floor((np.arange(ow) + 0.5) * (w / ow)).astype(np.int64), w - 1)
+
+    def index(n_in, n_out):
+        s = np.floor((np.arange(n_out, dtype=np.float32) + np.float32(0.5)) * (np.float32(n_in) / np.float32(n_out)))
+        return np.minimum(s.astype(np.int64), n_in - 1)
+    iy, ix = index(h, oh), index(w, ow)
     return x[:, iy][:, :, ix], (iy, ix)
 
 

@@ -182,8 +182,9 @@ __global__ __launch_bounds__(EW_BLOCK) void convlstm_gates_bwd_kernel(const satc
 
 extern "C" int satcv_convlstm_gates_bwd(const satcv_lstm_gates_desc* d, void* stream) {
   SATCV_CHECK(d && d->gates_out && d->c_out && d->dz_out && d->dc_prev_out && (d->dh_a || d->dh_b) && d->npix > 0, "lstm_gates_bwd: null pointer");
-  SATCV_CHECK(d->filters >= 8 && d->filters % 8 == 0 && d->lddz >= 4 * d->filters && d->lddz % 8 == 0, "lstm_gates_bwd: bad filters / lddz");
-  SATCV_CHECK((!d->dh_a || d->lddh_a % 8 == 0) && (!d->dh_b || d->lddh_b % 8 == 0), "lstm_gates_bwd: bad dh leading dimensions");
+  SATCV_CHECK(d->filters >= 8 && d->filters <= 256 && d->filters % 8 == 0 && EW_BLOCK % (d->filters / 8) == 0, "lstm_gates_bwd: filters must be 8, 16, 32, 64, 128 or 256");
+  SATCV_CHECK(d->lddz >= 4 * d->filters && d->lddz % 8 == 0, "lstm_gates_bwd: bad lddz");
+  SATCV_CHECK((!d->dh_a || (d->lddh_a >= d->filters && d->lddh_a % 8 == 0)) && (!d->dh_b || (d->lddh_b >= d->filters && d->lddh_b % 8 == 0)), "lstm_gates_bwd: bad dh leading dimensions");
   const int grid = lstm_grid(d->npix * (d->filters / 8));
   if (d->dtype == SATCV_BF16) hipLaunchKernelGGL(convlstm_gates_bwd_kernel<bf16>, dim3(grid), dim3(EW_BLOCK), 0, (hipStream_t)stream, *d);
   else if (d->dtype == SATCV_F32) hipLaunchKernelGGL(convlstm_gates_bwd_kernel<float>, dim3(grid), dim3(EW_BLOCK), 0, (hipStream_t)stream, *d);
@@ -247,12 +248,22 @@ __global__ __launch_bounds__(EW_BLOCK) void dense_small_fwd_kernel(const satcv_d
     }
   }
 }
+// what both directions ask of the sources and of the output grid (the kernels index with ld / cin, divide by h and w_, and read in_shift
+// wherever in_scale is set)
+static int dense_check_sources(const satcv_dense_desc* d, const char* name) {
+  for (int i = 0; i < d->nsrc; ++i) {
+    const satcv_dense_src& s = d->src[i];
+    SATCV_CHECK(s.x && s.cin > 0 && s.ld >= s.cin && (s.dtype == SATCV_F32 || s.dtype == SATCV_BF16) && s.hs >= 0 && s.ws >= 0 &&
+                ((s.hs == 0) == (s.ws == 0)), "%s: bad source %d", name, i);
+    SATCV_CHECK((s.in_scale != nullptr) == (s.in_shift != nullptr), "%s: source %d has one of in_scale / in_shift without the other", name, i);
+  }
+  SATCV_CHECK(d->h > 0 && d->w_ > 0 && d->npix % ((long long)d->h * d->w_) == 0, "%s: npix is not a whole number of h x w images", name);
+  return SATCV_OK;
+}
 extern "C" int satcv_dense_small_fwd(const satcv_dense_desc* d, void* stream) {
   SATCV_CHECK(d && d->w && d->b && d->out && d->npix > 0 && d->nsrc >= 1 && d->nsrc <= 2 && d->cout >= 1 && d->cout <= DENSE_KMAX, "dense_small_fwd: bad args");
-  for (int i = 0; i < d->nsrc; ++i)
-    SATCV_CHECK(d->src[i].x && d->src[i].cin > 0 && d->src[i].ld >= d->src[i].cin && (d->src[i].dtype == SATCV_F32 || d->src[i].dtype == SATCV_BF16) &&
-                ((d->src[i].hs == 0) == (d->src[i].ws == 0)), "dense_small_fwd: bad source %d", i);
-  SATCV_CHECK(d->h > 0 && d->w_ > 0 && d->npix % ((long long)d->h * d->w_) == 0, "dense_small_fwd: npix is not a whole number of h x w images");
+  SATCV_CHECK(d->activation >= 0 && d->activation <= 3, "dense_small_fwd: activation must be 0 softmax, 1 sigmoid, 2 linear or 3 ReLU");
+  if (const int rc = dense_check_sources(d, "dense_small_fwd")) return rc;
   hipLaunchKernelGGL(dense_small_fwd_kernel, dim3(lstm_grid(d->npix)), dim3(EW_BLOCK), 0, (hipStream_t)stream, *d);
   LSTM_OK("dense_small_fwd");
   return SATCV_OK;
@@ -391,9 +402,12 @@ __global__ __launch_bounds__(EW_BLOCK) void dense_small_bwd_gather_kernel(const 
 extern "C" int satcv_dense_small_bwd(const satcv_dense_desc* d, void* stream) {
   SATCV_CHECK(d && d->w && d->dout && d->dw && d->db && d->npix > 0 && d->nsrc >= 1 && d->nsrc <= 2 && d->cout >= 1 && d->cout <= DENSE_KMAX, "dense_small_bwd: bad args");
   SATCV_CHECK(d->activation == 2 || (d->activation == 3 && d->out), "dense_small_bwd: activation must be linear (dlogits given) or ReLU (with the forward output)");
+  if (const int rc = dense_check_sources(d, "dense_small_bwd")) return rc;
   int rows = 0;
   bool resized = false;
   for (int i = 0; i < d->nsrc; ++i) {
+    SATCV_CHECK(!d->src[i].dx || (d->src[i].lddx >= d->src[i].cin && (d->src[i].dx_dtype == SATCV_F32 || d->src[i].dx_dtype == SATCV_BF16)),
+                "dense_small_bwd: bad dx of source %d", i);
     rows += d->src[i].cin;
     if (d->src[i].hs && d->src[i].dx) resized = true;
   }
