@@ -758,17 +758,105 @@ int satcv_graph_destroy(void* graph_exec);
  * forward / data gradient, 1 = 1x1 / transposed-conv GEMMs, 2 = weight gradients, 3 = fused thin-layer backward (data + weight gradient) */
 int satcv_prof_enable(int32_t kind_mask);
 int satcv_prof_collect(int32_t kind, double* total_ms, int64_t* launches, double* flops);
-/* kernel-selection knobs (tests force a tile configuration on small shapes; probes A/B variants in one process).  Keys:
- * "igemm_db"  0 = 128x128 single-buffered tile only, 1 = automatic (default), 2 = the double-buffered 256x128 tile wherever
- *             its shape limits allow;
- * "igemm_thin" 0 = general kernel, 1 (default) = the persistent weights-stationary kernel for thin 3x3 layers (Cin 16/32/64 -> Cout 32/64,
- *             maps of whole 8 x 32 tiles), whatever the batch size (2 = the same; kept for older callers);
- *             "igemm_thin_launches" (read-only) counts the launches it has served in this process (tests check the path taken).
- * "wgrad_db"  1 (default) = double-buffered weight-gradient kernel where its limits allow, 0 = the single-buffered one, 2 = the
- *             64 x 128 block for 1 x 1 / transposed-conv gradients instead of the 128 x 256 one.
- * Returns SATCV_ERR_INVALID for an unknown key.  Not thread-safe against concurrent launches. */
+/* Runtime switches of the library (tests force a tile configuration on small shapes; probes A/B variants in one process).  One table,
+ * csrc/options.hpp, declares every one of them; each value comes from its environment variable once, when the library is loaded.
+ *   settable      satcv_set_option changes it (not thread-safe against concurrent launches)
+ *   startup-only  the environment decides; satcv_set_option returns SATCV_ERR_INVALID (several size workspaces that plans cache)
+ *   counter       launches a path has served in this process (tests check the path taken); satcv_set_option returns SATCV_ERR_INVALID
+ * satcv_get_option reads any of them.  satcv_option_key(i) enumerates the keys in table order and returns NULL past the end.
+ * An unknown key is SATCV_ERR_INVALID.  Keys:
+ * "igemm_db"  SATCV_DB, default 1, settable:
+ *     0 the single-buffered 128x128 tile (and 32-channel chunks for deep 1x1) only, 1 automatic, 2 the double-buffered
+ *     256x128 tile wherever its shape limits allow (profiles/r03_db_vs_single.txt)
+ * "igemm_sched"  SATCV_IGEMM_SCHED, default 0, settable:
+ *     experiment bits handed to the deep tile (half-chunk stagger, no gain); none wired at present
+ * "igemm_thin"  SATCV_THIN, default 1, settable:
+ *     persistent weights-stationary kernel of the thin 3x3 layers (conv_igemm_ws.hip, conv_thin_roles.hip): 0 off, 1 / 2 on
+ *     wherever the shape limits allow, whatever the batch size
+ * "igemm_m16"  SATCV_M16, default 1, settable:
+ *     the 16x16x32 deep 3x3 tiles (conv_igemm_m16.hip, conv_igemm_m16p.hip): 0 off, 1 launches that write statistics
+ *     (training), 2 every eligible launch; a training plan's tile_policy raises 1 to 2 (profiles/r05_ab_m16_step.txt)
+ * "splitk"  SATCV_SPLITK, default 0, settable:
+ *     split-K of under-filled plain (halo-tile / 1x1) launches, opt-in because the K order then depends on the workgroup
+ *     count: 1 every eligible launch, 2 launches of fewer than 64 workgroups (the DeepLab inference plans;
+ *     profiles/r04_ab_splitk.txt)
+ * "splitk_tl"  SATCV_SPLITK_TL, default 1, startup-only:
+ *     split-K of under-filled tap-loop launches (dilated / strided convolutions); 0 off
+ * "convt_wide"  SATCV_CONVT_WIDE, default 1, startup-only:
+ *     transposed-conv tiles span several sub-pixel positions (input read once, whole-line stores); 0 one position per tile
+ * "wdma"  SATCV_WDMA, default 1, startup-only:
+ *     deep 3x3 tile: weights by LDS-DMA into a three-slot ring (profiles/r04_ab_weight_ring_dma.txt); 0 register-staged
+ *     weights
+ * "db64"  SATCV_DB64, default 1, startup-only:
+ *     512-pixel x 64-channel double-buffered tile for 64 output channels with deep K (profiles/r03_ab_late_switches.txt): 0
+ *     off, 2 also other multiples of 64, 3 also below 128 input channels
+ * "db_tl"  SATCV_DB_TL, default 1, startup-only:
+ *     double-buffered 256x128 tap-loop tile with 64-channel chunks (profiles/r04_deeplab_ab_double_buffered_taploop.txt): 0
+ *     off, 1 from 96 tiles on, n > 1 from n tiles on
+ * "db1x1"  SATCV_DB1X1, default 1, startup-only:
+ *     deep 1x1 / transposed convolutions on the double-buffered 256x128 tile (profiles/r03_ab_late_switches.txt); 0 the
+ *     single-buffered tile
+ * "db1x1_small"  SATCV_DB1X1_SMALL, default 1, startup-only:
+ *     ... also where even 128-pixel tiles leave CUs idle (profiles/r04_deeplab_ab_db1x1_small.txt); 0 off
+ * "igemm_generic"  SATCV_IGEMM, default 0, startup-only:
+ *     SATCV_IGEMM=generic: every convolution on the generic kernel of conv_igemm.hip (ablation; the value is 1 when the word
+ *     starts with g)
+ * "m16_ws"  SATCV_M16_WS, default 1, startup-only:
+ *     wave roles in the one-tile 16x16x32 kernel: 0 never (symmetric kernel), 1 from 256 input channels on, 2 always
+ *     (profiles/r05_ablation_m16.txt)
+ * "m16p"  SATCV_M16P, default 1, settable:
+ *     persistent 16x16x32 kernel: 0 off, 1 where a workgroup gets at least two tiles, 2 every eligible launch
+ *     (profiles/r06_ab_m16p_step.txt)
+ * "m16p_prio"  SATCV_M16P_PRIO, default 30, settable:
+ *     s_setprio of its staging waves, decimal digits (plain launches)(launches with the fused input BatchNorm)(launches with
+ *     the fused BatchNorm-backward sums), each 0 ... 3 (30: profiles/r06_ab_m16p_prio_step.txt)
+ * "m16p_prio64"  SATCV_M16P_PRIO64, default -1, startup-only:
+ *     the same digits for its 64-channel output block; negative: as m16p_prio
+ * "m16p_bn64"  SATCV_M16P_BN64, default 1, startup-only:
+ *     its 64-channel output block (profiles/r06_ab_m16p_bn64_step.txt); 0 the 64-filter layers stay on the one-tile kernels
+ * "thin_roles"  SATCV_THIN_ROLES, default 1, settable:
+ *     wave-role kernel of the thin 3x3 layers: 0 off, 1 the shapes it measured faster on, 2 every shape it serves
+ *     (profiles/r05_ab_thin_roles_step.txt)
+ * "convt_thin"  SATCV_CONVT_THIN, default 1, startup-only:
+ *     streaming kernels of the thin transposed convolutions and their data gradient (profiles/r03_ab_convt_thin.txt): 0 off
+ *     (tiled kernels), non-zero on, >= 2 also the 64 <- 4 x 32 data gradient, where the tiled kernel measured faster
+ * "convt_wps"  SATCV_CONVT_WPS, default 3, startup-only:
+ *     waves per SIMD of the 64 -> 4 x 32 forward: 2, anything else 3
+ * "convt_mid"  SATCV_CONVT_MID, default 1, startup-only:
+ *     256 -> 4 x 128 on the streaming kernel, one position per workgroup; 0 the tiled kernel
+ * "wgrad_db"  SATCV_WGRAD_DB, default 1, settable:
+ *     double-buffered weight-gradient kernel where its limits allow: 0 the single-buffered one, 2 the 64x128 block for 1x1 /
+ *     transposed-conv gradients instead of 128x256
+ * "wgrad_m16"  SATCV_WGRAD_M16, default 0, settable:
+ *     wgrad_dma_kernel on v_mfma_f32_16x16x32_bf16: measured slower, off (profiles/r06_ab_wgrad_m16.txt)
+ * "wgrad_pix256"  SATCV_WGRAD_PIX256, default 1, startup-only:
+ *     thin layers stage 256 pixels per step; 0 always 128
+ * "wgrad_dma"  SATCV_WGRAD_DMA, default 1, startup-only:
+ *     deep 3x3 layers: the 64x128 block with dY by LDS-DMA (profiles/r04_ab_wgrad_dma.txt); 0 the 32x128 block
+ * "wgrad_wgs"  SATCV_WGRAD_WGS, default 128, startup-only:
+ *     workgroups of a double-buffered weight-gradient launch that shares the chip (profiles/r04_ab_wgrad_workgroups.txt);
+ *     below 8 reads as 128
+ * "ew_per_cu"  SATCV_EW_PER_CU, default 6, startup-only:
+ *     workgroups per CU of the grid-stride elementwise kernels (3 ... 16 within 0.3 % of the step, elementwise.hip); below 1
+ *     reads as 6
+ * "bn_apply"  SATCV_BN_APPLY, default 1, startup-only:
+ *     BatchNorm-backward apply on its own kernel; 0 the round-3 loop for every apply launch (a null in the step:
+ *     profiles/r06_ab_env_switches.txt)
+ * "bn_rev"  SATCV_BN_REV, default 1, startup-only:
+ *     BatchNorm-backward apply walks the pixels in reversed order; 0 forward (ablation of a single kernel choice, DESIGN.md
+ *     section 6)
+ * "loss_fast"  SATCV_LOSS_FAST, default 1, startup-only:
+ *     vectorised softmax cross-entropy kernel for 2 / 4 classes; 0 the general loss kernel
+ * "igemm_thin_launches"  no variable, starts at 0, read-only counter:
+ *     launches served by the persistent thin-layer kernels (conv_igemm_ws.hip and conv_thin_roles.hip)
+ * "thin_roles_launches"  no variable, starts at 0, read-only counter:
+ *     ... of them by conv_thin_roles.hip
+ * "m16p_launches"  no variable, starts at 0, read-only counter:
+ *     launches served by conv_igemm_m16p.hip
+ */
 int satcv_set_option(const char* key, int32_t value);
 int satcv_get_option(const char* key, int32_t* value);
+const char* satcv_option_key(int32_t index);
 
 #ifdef __cplusplus
 }

@@ -128,51 +128,40 @@ extern "C" int satcv_prof_collect(int32_t kind, double* total_ms, int64_t* launc
   return SATCV_OK;
 }
 
-// ------------------------------------------------------------------ kernel-selection knobs
-// (environment defaults SATCV_DB / SATCV_THIN; satcv_set_option overrides them at run time)
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-int g_opt_igemm_db = env_int("SATCV_DB", 1);
-int g_opt_wgrad_db = env_int("SATCV_WGRAD_DB", 1);
-int g_opt_igemm_sched = env_int("SATCV_IGEMM_SCHED", 0);
-int g_opt_igemm_thin = env_int("SATCV_THIN", 1);      // 0 off, 1 / 2 on wherever the shape limits allow (independent of the batch size)
-int g_opt_igemm_m16 = env_int("SATCV_M16", 1);       // the 16x16x32 deep 3x3 tile: 0 off, 1 launches that produce statistics (training), 2 every eligible launch
-int g_opt_m16p = env_int("SATCV_M16P", 1);               // conv_igemm_m16p.hip (persistent 16x16x32 tile): 0 off, 1 where a workgroup gets >= 2 tiles, 2 every eligible launch
-extern int g_m16p_launches;
-int g_tr_launches = 0;                                   // launches conv_thin_roles.hip took (tests: "path taken")
-int g_opt_thin_roles = env_int("SATCV_THIN_ROLES", 1);   // conv_thin_roles.hip: 0 off, 1 the shapes it measured faster on, 2 every shape it serves
-// conv_igemm_m16p.hip: s_setprio of the staging waves, decimal digits (plain launches)(launches with the fused input BatchNorm)(launches with the
-// fused BatchNorm-backward sums), each 0 ... 3 -- e.g. 30 = priority 3 for the forward launches that transform their input, 0 elsewhere
-int g_opt_m16p_prio = env_int("SATCV_M16P_PRIO", 30);      // (30: profiles/r06_ab_m16p_prio_step.txt)
-int g_opt_wgrad_m16 = env_int("SATCV_WGRAD_M16", 0);   // wgrad_dma_kernel on v_mfma_f32_16x16x32_bf16 (round 6: built as the review asked, measured slower: off)
-int g_opt_splitk = env_int("SATCV_SPLITK", 0);         // split-K of under-filled PLAIN (halo-tile / 1x1) launches: opt-in, see conv_igemm_fast.hip
-static int* opt_slot(const char* key) {
-  if (!key) return nullptr;
-  if (!strcmp(key, "igemm_db")) return &g_opt_igemm_db;
-  if (!strcmp(key, "igemm_thin")) return &g_opt_igemm_thin;
-  if (!strcmp(key, "wgrad_db")) return &g_opt_wgrad_db;
-  if (!strcmp(key, "igemm_sched")) return &g_opt_igemm_sched;
-  if (!strcmp(key, "splitk")) return &g_opt_splitk;
-  if (!strcmp(key, "igemm_m16")) return &g_opt_igemm_m16;
-  if (!strcmp(key, "thin_roles")) return &g_opt_thin_roles;
-  if (!strcmp(key, "thin_roles_launches")) return &g_tr_launches;
-  if (!strcmp(key, "m16p")) return &g_opt_m16p;
-  if (!strcmp(key, "m16p_prio")) return &g_opt_m16p_prio;
-  if (!strcmp(key, "wgrad_m16")) return &g_opt_wgrad_m16;
-  if (!strcmp(key, "m16p_launches")) return &g_m16p_launches;
-  return nullptr;
+// ------------------------------------------------------------------ kernel-selection switches (options.hpp is the table)
+static const char* opt_env(const char* name) { return name ? getenv(name) : nullptr; }      // (a counter has no variable)
+satcv_options g_opt = [] {
+  satcv_options o;
+#define X(key, env, dflt, reader, kind, meaning) o.key = reader(opt_env(env), dflt);
+  SATCV_OPTIONS(X)
+#undef X
+  return o;
+}();
+enum { SETTABLE, STARTUP, COUNTER };
+static const struct { const char* key; int satcv_options::*slot; int kind; } g_opt_rows[] = {
+#define X(key, env, dflt, reader, kind, meaning) {#key, &satcv_options::key, kind},
+  SATCV_OPTIONS(X)
+#undef X
+};
+static constexpr int g_opt_count = (int)(sizeof(g_opt_rows) / sizeof(g_opt_rows[0]));
+static int opt_find(const char* key) {
+  for (int i = 0; key && i < g_opt_count; ++i)
+    if (!strcmp(key, g_opt_rows[i].key)) return i;
+  return -1;
 }
+extern "C" const char* satcv_option_key(int32_t index) { return index >= 0 && index < g_opt_count ? g_opt_rows[index].key : nullptr; }
 extern "C" int satcv_set_option(const char* key, int32_t value) {
-  int* p = opt_slot(key);
-  SATCV_CHECK(p, "set_option: unknown key '%s'", key ? key : "(null)");
-  *p = value;
+  const int i = opt_find(key);
+  SATCV_CHECK(i >= 0, "set_option: unknown key '%s'", key ? key : "(null)");
+  SATCV_CHECK(g_opt_rows[i].kind == SETTABLE, "set_option: '%s' is %s", key,
+              g_opt_rows[i].kind == COUNTER ? "a read-only counter" : "startup-only (set its environment variable before the library loads)");
+  g_opt.*g_opt_rows[i].slot = value;
   return SATCV_OK;
 }
-extern int g_ws_launches;          // conv_igemm_ws.hip
 extern "C" int satcv_get_option(const char* key, int32_t* value) {
-  if (key && value && !strcmp(key, "igemm_thin_launches")) { *value = g_ws_launches; return SATCV_OK; }
-  int* p = opt_slot(key);
-  SATCV_CHECK(p && value, "get_option: unknown key '%s'", key ? key : "(null)");
-  *value = *p;
+  const int i = opt_find(key);
+  SATCV_CHECK(i >= 0 && value, "get_option: unknown key '%s'", key ? key : "(null)");
+  *value = g_opt.*g_opt_rows[i].slot;
   return SATCV_OK;
 }
 

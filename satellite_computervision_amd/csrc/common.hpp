@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/satcv.h"
+#include "options.hpp"      // g_opt: every runtime switch of the library
 
 typedef __bf16 bf16;
 typedef __hip_fp8_e4m3 fp8;          // OCP e4m3fn on gfx950 (hardware v_cvt_pk_fp8_f32 / v_cvt_f32_fp8, saturating)

@@ -358,14 +358,9 @@ static int igemm_fill_args(const satcv_conv_desc* d, IgemmArgs& a) {
   return SATCV_OK;
 }
 
-static bool igemm_force_generic() {
-  static const bool v = [] { const char* e = getenv("SATCV_IGEMM"); return e && e[0] == 'g'; }();
-  return v;
-}
-
 extern "C" int satcv_conv2d_igemm_pipelined(const satcv_conv_desc* d) {
   IgemmArgs a;
-  if (!d || igemm_fill_args(d, a) != SATCV_OK || igemm_force_generic()) return 0;
+  if (!d || igemm_fill_args(d, a) != SATCV_OK || g_opt.igemm_generic) return 0;
   if (a.kh == 3 && a.kw == 3 && a.stride == 1 && a.dil >= a.h && a.dil >= a.w_) { a.kh = a.kw = 1; a.dil = 1; }
   if (d->bst_y && a.dil == 3) {
     // thin dilated layers (atrous CNNs): without the fused sums the launch runs on the persistent weights-stationary kernel at 3-4 x the rate of the
@@ -391,7 +386,7 @@ extern "C" int satcv_conv2d_igemm(const satcv_conv_desc* d, void* stream) {
   }
   satcv_prof_begin(d->kh * d->kw > 1 ? 0 : 1, flops, st);
   rc = SATCV_ERR_UNSUPPORTED;
-  if (!igemm_force_generic()) {
+  if (!g_opt.igemm_generic) {
     rc = convt_thin_launch(a, d->dtype, st);                 // thin transposed convolutions: streaming kernel
     if (rc == SATCV_ERR_UNSUPPORTED) rc = convt_thin_dgrad_launch(a, d->dtype, st);      // ... and their data gradients
     if (rc == SATCV_ERR_UNSUPPORTED) rc = igemm_tr_launch(a, d->dtype, st, false);            // thin 3x3 layers: staging / matrix wave roles (round 5)

@@ -18,7 +18,6 @@
 //     halos run on the same XCD (private L2).
 #include "igemm_common.hpp"
 #include <cstdlib>
-extern int g_opt_igemm_db, g_opt_igemm_thin, g_opt_igemm_sched, g_opt_splitk, g_opt_igemm_m16;      // api.hip: satcv_set_option
 
 // compile-time ablation switches for profiling builds (-DSATCV_ABLATE=bits): 1 skip global stores, 2 skip MFMA,
 // 4 skip activation loads, 8 skip weight loads, 16 skip the LDS fragment reads, 32 skip the whole epilogue, 64 skip the LDS stores,
@@ -806,9 +805,8 @@ static int fast_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
     // launch's workgroup count would break the bit-identity of inference across batch splits.  Tap-loop launches (dilated / strided
     // convolutions: ASPP, the ResNet backbone of the build-defined DeepLab): ON (SATCV_SPLITK_TL=0 turns it off) -- a single 512 x 512
     // tile puts 16 workgroups on the chip for 576 chunks of its stage-4 convolutions, 318 us per launch whatever the batch.
-    const int splitk = g_opt_splitk;            // (satcv_set_option("splitk", 1): the build-defined DeepLab's inference plans set it around their launches)
-    static const int splitk_tl = [] { const char* e = getenv("SATCV_SPLITK_TL"); return e ? atoi(e) : 1; }();
-    if ((TL ? splitk_tl : splitk) && !dyn && sizeof(T) == 2 && a.mode_out == 0 && !a.pool_y && !a.accumulate && !a.bst_y && !a.pair_n && a.cout % 8 == 0 && a.ldy % 8 == 0 &&
+    const int splitk = g_opt.splitk;            // (satcv_set_option("splitk", 1): the build-defined DeepLab's inference plans set it around their launches)
+    if ((TL ? g_opt.splitk_tl : splitk) && !dyn && sizeof(T) == 2 && a.mode_out == 0 && !a.pool_y && !a.accumulate && !a.bst_y && !a.pair_n && a.cout % 8 == 0 && a.ldy % 8 == 0 &&
         a.stride == 1 && (!a.stats || (a.cout <= 1024 && 256 % (a.cout / 8) == 0))) {
       // (1 x 1 launches of a single tile: a 64-channel chunk costs a workgroup ~1.2 us of load latency whatever its MFMA count, so even
       //  16 chunks are worth cutting four ways -- 4 chunks per split + a ~7 us finish launch against 16 chunks in a row)
@@ -847,17 +845,16 @@ static int fast_tw(IgemmArgs& a, hipStream_t st, bool dry) {
   const int cin = a.c0 + a.c1;
   // transposed conv: N = f*f sub-pixel positions x cstat channels.  Tiles spanning several positions read the input tile once
   // instead of once per position and write whole lines (SATCV_CONVT_WIDE=0: one position per tile, the earlier behaviour)
-  static const bool convt_wide = !(getenv("SATCV_CONVT_WIDE") && atoi(getenv("SATCV_CONVT_WIDE")) == 0);
-  const int nspace = (a.mode_out && !convt_wide) ? a.cstat : a.cout;
+  const int nspace = (a.mode_out && !g_opt.convt_wide) ? a.cstat : a.cout;
   if constexpr (TAPS == 9 && std::is_same<T, bf16>::value) {
     // deep 3x3 layers: 256-pixel x 128-channel tile, 8 waves, double-buffered stages (SATCV_DB=0 keeps the 128 x 128 tile)
-    const int db_mode = g_opt_igemm_db;
-    a.dbg = g_opt_igemm_sched;            // (experiment bits; none wired at present)
+    const int db_mode = g_opt.igemm_db;
+    a.dbg = g_opt.igemm_sched;            // (experiment bits; none wired at present)
     // round 5: the persistent 16x16x32 kernel (conv_igemm_m16p.hip) takes the mid layers -- 64 ... 256 input channels, Cout % 128 == 0, several
     // tiles per workgroup -- under the same option as the one-tile 16x16x32 kernels below (launches that write statistics, or every launch of a
     // training plan)
     // (the per-launch tile_policy of a training plan raises the option's default 1 to 2; SATCV_M16=0 still wins)
-    const int m16 = (g_opt_igemm_m16 > 0 && a.tile_policy > g_opt_igemm_m16) ? a.tile_policy : g_opt_igemm_m16;
+    const int m16 = (g_opt.igemm_m16 > 0 && a.tile_policy > g_opt.igemm_m16) ? a.tile_policy : g_opt.igemm_m16;
     if (TW == 32 && a.dil == 1 && (m16 >= 2 || (m16 == 1 && (a.stats || a.bst_y)))) {
       const int rc = igemm_m16p_launch(a, SATCV_BF16, st, dry);
       if (rc != SATCV_ERR_UNSUPPORTED) return rc;
@@ -871,7 +868,6 @@ static int fast_tw(IgemmArgs& a, hipStream_t st, bool dry) {
       if (db_mode >= 2 || tiles256 >= 192) {
         // weights by LDS-DMA into a three-slot ring (SATCV_WDMA=0: register-staged weights; the ring does not fit beside the halo tiles
         // of the 8-pixel-wide maps, which stay on the register path)
-        static const int wdma = [] { const char* e = getenv("SATCV_WDMA"); return e ? atoi(e) : 1; }();
         // round 5: the 16x16x32 tile of conv_igemm_m16.hip -- 32-channel chunks, weights in tap-row units.  Maps at least 16 pixels wide,
         // Cin % 64 == 0 (the 8-pixel-wide maps keep the 32x32x16 register path).  It sums K in another grouping than the 32x32x16 tiles, and
         // which tile serves a shape depends on the launch's tile count: option igemm_m16 = 1 (default) therefore limits it to launches that
@@ -882,7 +878,7 @@ static int fast_tw(IgemmArgs& a, hipStream_t st, bool dry) {
           const int rc = igemm_m16_launch(a, SATCV_BF16, st, dry);
           if (rc != SATCV_ERR_UNSUPPORTED) return rc;
         }
-        if (wdma) {
+        if (g_opt.wdma) {
           const int rc = fast_cfg<T, TW, 4, 2, 2, 2, 1, TAPS, false, true, 0, true>(a, st, dry);
           if (rc != SATCV_ERR_UNSUPPORTED) return rc;
         }
@@ -892,7 +888,7 @@ static int fast_tw(IgemmArgs& a, hipStream_t st, bool dry) {
     }
     // 64 output channels with deep K (64 + 64 -> 64 at 128 x 128): a 512-pixel x 64-channel tile, 8 waves of 64 x 64 -- the 9-tap weight slab
     // (18 KB per 16-channel chunk) is fetched once per 512 pixels instead of once per 128 (SATCV_DB64=0: the 128 x 64 tile)
-    static const int db64 = [] { const char* e = getenv("SATCV_DB64"); return e ? atoi(e) : 1; }();
+    const int db64 = g_opt.db64;
     if (db_mode && db64 && a.dil == 1 && a.mode_in == 0 && a.mode_out == 0 && !a.pool_y && nspace % 64 == 0 && (nspace == 64 || db64 >= 2) && (cin >= 128 || db64 >= 3) &&
         (long long)cdiv(a.n * a.h * a.w_, 512) * (nspace / 64) >= 192) {
       const int rc = fast_cfg<T, TW, 8, 1, 2, 2, 1, TAPS, false, true>(a, st, dry);
@@ -925,8 +921,8 @@ static int fast_tw(IgemmArgs& a, hipStream_t st, bool dry) {
           // convolutions of a DeepLab batch / the ASPP ran at 230-460 TFLOP/s on the single-buffered 128 x 128 tile with 32-channel
           // chunks (8 MFMAs per wave between two barrier pairs).  SATCV_DB_TL=0: the single-buffered tile.  (Different chunk size: the
           // two forms sum K in a different grouping -- the choice depends on the shape AND the tile count, like split-K above)
-          static const int db_tl = [] { const char* e = getenv("SATCV_DB_TL"); return e ? atoi(e) : 1; }();
-          if (db_tl && g_opt_igemm_db != 0 && cin % 64 == 0 && (!a.x1 || a.c0 % 64 == 0) &&
+          const int db_tl = g_opt.db_tl;
+          if (db_tl && g_opt.igemm_db != 0 && cin % 64 == 0 && (!a.x1 || a.c0 % 64 == 0) &&
               ((long long)cdiv(a.n * a.h * a.w_, 256) * (nspace / 128) >= (db_tl > 1 ? db_tl : 96))) {
             const int rc2 = fast_cfg<T, TW, 4, 2, 2, 2, 4, TAPS, true, true>(a, st, dry);
             if (rc2 != SATCV_ERR_UNSUPPORTED) return rc2;
@@ -942,21 +938,19 @@ static int fast_tw(IgemmArgs& a, hipStream_t st, bool dry) {
       if constexpr (std::is_same<T, bf16>::value) {
         // deep 1x1 / transposed convolutions (K = Cin >= 512; at 256 it measured slower): 64-channel chunks -- with 32 a chunk is 8 MFMAs per wave between two
         // barrier pairs; SATCV_DB=0 keeps the 32-channel form
-        const bool ks4 = g_opt_igemm_db != 0 && (cin % 64 == 0) && cin >= 512 && (!a.x1 || a.c0 % 64 == 0) && (a.mode_in != 1 || a.c0 % 64 == 0);
+        const bool ks4 = g_opt.igemm_db != 0 && (cin % 64 == 0) && cin >= 512 && (!a.x1 || a.c0 % 64 == 0) && (a.mode_in != 1 || a.c0 % 64 == 0);
         // ... and on the double-buffered 256-pixel x 128-channel tile, one barrier per chunk (SATCV_DB1X1=0: the single-buffered tile)
-        static const bool db1 = !(getenv("SATCV_DB1X1") && atoi(getenv("SATCV_DB1X1")) == 0);
         // (forward transposed convs: 48.5 -> 40.2 and 50.3 -> 42.8 us at 8 x 8 and 16 x 16; their space-to-depth data gradients measured slower on it)
         // ... or when even the 128-pixel tiles leave CUs idle (a single DeepLab tile: 16-128 workgroups): the launch then lasts one
         // workgroup's K loop, whose chunk costs the single-buffered tile a full load latency between two barriers (~1.5 us for 0.3 us of
         // MFMAs) -- SATCV_DB1X1_SMALL=0 turns this case off.  Same 64-channel chunks and k order: the two tiles give identical bits.
-        static const bool db1s = !(getenv("SATCV_DB1X1_SMALL") && atoi(getenv("SATCV_DB1X1_SMALL")) == 0);
         const long long mt256 = cdiv(a.n * a.h * a.w_, 256), mt128 = cdiv(a.n * a.h * a.w_, 128);
-        if (ks4 && g_opt_splitk && nspace >= 128 && nspace % 128 == 0) {       // opt-in split-K of under-filled deep 1x1 launches
+        if (ks4 && g_opt.splitk && nspace >= 128 && nspace % 128 == 0) {       // opt-in split-K of under-filled deep 1x1 launches
           const int rc = fast_cfg<T, TW, 2, 2, 2, 2, 4, TAPS, false, false, 2, false, true>(a, st, dry);
           if (rc != SATCV_ERR_UNSUPPORTED) return rc;
         }
-        if (ks4 && db1 && a.mode_in == 0 && nspace >= 128 && nspace % 128 == 0 &&
-            (mt256 * (nspace / 128) >= 192 || (db1s && mt128 * (nspace / 128) <= 256))) {
+        if (ks4 && g_opt.db1x1 && a.mode_in == 0 && nspace >= 128 && nspace % 128 == 0 &&
+            (mt256 * (nspace / 128) >= 192 || (g_opt.db1x1_small && mt128 * (nspace / 128) <= 256))) {
           const int rc = fast_cfg<T, TW, 4, 2, 2, 2, 4, TAPS, false, true>(a, st, dry);
           if (rc != SATCV_ERR_UNSUPPORTED) return rc;
         }

@@ -485,8 +485,7 @@ static int m16_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
   if (dry) return SATCV_OK;
   // wave roles from 256 input channels on (SATCV_M16_WS=2: always, =0: never): with four chunks the longer prologue of the role kernel (three
   // chunks loaded before the first MFMA) is not amortised -- 128 -> 128 at 64 x 64: 97-99 us symmetric, 101-105 with roles, 108 on the 32x32x16 tile
-  static const int roles_opt = [] { const char* e = getenv("SATCV_M16_WS"); return e ? atoi(e) : 1; }();
-  const bool roles = roles_opt >= 2 || (roles_opt == 1 && cin >= 256);
+  const bool roles = g_opt.m16_ws >= 2 || (g_opt.m16_ws == 1 && cin >= 256);
   auto kern = roles ? igemm_m16_kernel<TW> : igemm_m16sym_kernel<TW>;
   { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(roles ? 768 : 512), lds, st, a);

@@ -48,9 +48,6 @@ __device__ __forceinline__ bf16x4 m16p_tr_read(const bf16* p) {
   return __builtin_bit_cast(bf16x4, v);
 }
 
-extern int g_opt_m16p_prio;            // api.hip
-extern int g_opt_m16p;                 // api.hip: 0 off, 1 on where a workgroup gets at least two tiles
-int g_m16p_launches = 0;               // launches taken here (satcv_get_option("m16p_launches"): tests assert the path)
 
 // BN_: output channels per workgroup -- 128 (two 64-channel wave columns), or 64 for the layers with 64 filters (round 6: 64 -> 64 and
 // 64 + 64 -> 64 at 128 x 128 and their data gradients; wave tile 64 pixels x 32 channels, half the accumulators, the same pixel tile and stream)
@@ -607,9 +604,9 @@ static int m16p_launch_bn(IgemmArgs& a, hipStream_t st, bool dry) {
   a.n_tiles = a.cout / BN;
   a.cpt = cin / 32; a.nchunks = a.cpt; a.taploop = 0; a.halh_tl = a.halw_tl = 1;
   a.ksplit = 1; a.kslab = nullptr;
-  a.dbg = a.bst_y ? g_opt_m16p_prio % 10 : a.in_scale ? (g_opt_m16p_prio / 10) % 10 : (g_opt_m16p_prio / 100) % 10;
+  a.dbg = a.bst_y ? g_opt.m16p_prio % 10 : a.in_scale ? (g_opt.m16p_prio / 10) % 10 : (g_opt.m16p_prio / 100) % 10;
   if (BN == 64) {      // (half the MFMAs per staged byte: the staging waves set the pace of every launch kind -- SATCV_M16P_PRIO64, same digits)
-    static const int p64 = [] { const char* e = getenv("SATCV_M16P_PRIO64"); return e ? atoi(e) : -1; }();
+    const int p64 = g_opt.m16p_prio64;
     if (p64 >= 0) a.dbg = a.bst_y ? p64 % 10 : a.in_scale ? (p64 / 10) % 10 : (p64 / 100) % 10;
   }
   const long long m_total = (long long)a.n * a.tiles_y * a.tiles_x;
@@ -618,12 +615,12 @@ static int m16p_launch_bn(IgemmArgs& a, hipStream_t st, bool dry) {
   if (ranges > m_total) ranges = m_total;
   // (one tile per workgroup has nothing to pipeline across: the one-tile kernels, with their higher occupancy of waves per tile, keep those;
   //  option m16p = 2 sends every eligible launch here)
-  if (g_opt_m16p < 2 && m_total < 2 * ranges) return SATCV_ERR_UNSUPPORTED;
+  if (g_opt.m16p < 2 && m_total < 2 * ranges) return SATCV_ERR_UNSUPPORTED;
   if (dry) return SATCV_OK;
   auto kern = a.bst_y ? igemm_m16p_kernel<true, BN> : igemm_m16p_kernel<false, BN>;
   { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3((unsigned)(ranges * a.n_tiles)), dim3(768), lds, st, a, (int)m_total);
-  ++g_m16p_launches;
+  ++g_opt.m16p_launches;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { satcv_set_error("igemm_m16p launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
   return SATCV_OK;
@@ -632,9 +629,8 @@ static int m16p_launch_bn(IgemmArgs& a, hipStream_t st, bool dry) {
 // SATCV_M16P_BN64=0: the 64-filter layers stay on the one-tile kernels (A/B switch of the round-6 64-channel block)
 int igemm_m16p_launch(IgemmArgs& a, int dtype, hipStream_t st, bool dry) {
   if (dtype != SATCV_BF16 || a.pair_n) return SATCV_ERR_UNSUPPORTED;      // (its own store loop: no pair store, satcv.h)
-  if (!g_opt_m16p) return SATCV_ERR_UNSUPPORTED;
+  if (!g_opt.m16p) return SATCV_ERR_UNSUPPORTED;
   if (a.cout % 128 == 0) return m16p_launch_bn<128>(a, st, dry);
-  static const int bn64 = [] { const char* e = getenv("SATCV_M16P_BN64"); return e ? atoi(e) : 1; }();
-  if (bn64 && a.cout % 64 == 0) return m16p_launch_bn<64>(a, st, dry);
+  if (g_opt.m16p_bn64 && a.cout % 64 == 0) return m16p_launch_bn<64>(a, st, dry);
   return SATCV_ERR_UNSUPPORTED;
 }

@@ -15,8 +15,6 @@
 // weights, v_mfma_f32_32x32x16_bf16), the epilogue is the shared igemm_epilogue (bias, BN statistics, LDS-staged 16-byte stores).
 #include "igemm_common.hpp"
 #include <cstdlib>
-extern int g_opt_igemm_thin;      // api.hip: satcv_set_option("igemm_thin", ...)
-int g_ws_launches = 0;            // launches served by this kernel (satcv_get_option("igemm_thin_launches"): tests check the path taken)
 
 #ifndef SATCV_ABLATE
 #define SATCV_ABLATE 0
@@ -264,7 +262,7 @@ static int ws_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
   long long grid = (long long)ncu * per_cu;
   if (grid > total) grid = total;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256 * WN), LDS, st, a, (int)total);
-  ++g_ws_launches;
+  ++g_opt.igemm_thin_launches;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { satcv_set_error("igemm_ws launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
   return SATCV_OK;
@@ -272,7 +270,7 @@ static int ws_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
 
 // returns SATCV_ERR_UNSUPPORTED when the shape is outside this kernel's limits (the caller falls back to conv_igemm_fast.hip)
 int igemm_ws_launch(IgemmArgs& a, int dtype, hipStream_t st, bool dry) {
-  if (!g_opt_igemm_thin || (dtype != SATCV_BF16 && dtype != SATCV_FP8)) return SATCV_ERR_UNSUPPORTED;
+  if (!g_opt.igemm_thin || (dtype != SATCV_BF16 && dtype != SATCV_FP8)) return SATCV_ERR_UNSUPPORTED;
   const int cin = a.c0 + a.c1;
   // (accumulate == 1, y += result, on the bf16 forms without statistics / fused pool: residual data gradients)
   if (a.kh != 3 || a.kw != 3 || (a.dil != 1 && a.dil != 3) || a.stride != 1 || a.mode_in || a.mode_out || a.bst_y) return SATCV_ERR_UNSUPPORTED;

@@ -16,8 +16,6 @@
 // Whole tiles only; the kernel is chosen by shape alone (bit-identical inference across batch splits).
 #include "igemm_common.hpp"
 #include <cstdlib>
-extern int g_opt_igemm_thin, g_opt_thin_roles;      // api.hip: satcv_set_option
-extern int g_ws_launches, g_tr_launches;                  // conv_igemm_ws.hip: launches of the persistent thin-layer kernels (tests assert the path taken)
 
 template <int CINS, int COUT, int TH>      // CINS: stored input channels (16 / 32 / 64)
 struct TrGeom {
@@ -319,7 +317,7 @@ static int tr_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
   long long grid = ncu;
   if (grid > total) grid = total;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(768), G::LDS, st, a, (int)total);
-  ++g_ws_launches; ++g_tr_launches;
+  ++g_opt.igemm_thin_launches; ++g_opt.thin_roles_launches;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { satcv_set_error("igemm_tr launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
   return SATCV_OK;
@@ -328,8 +326,8 @@ static int tr_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
 // bf16 3x3, dilation 1, whole TH x 32 tiles, 16 / 32 / 64 stored input channels -> 32 / 64 output channels (64 -> 64 stays on the
 // weights-stationary kernel: its 74 KB of weights leave no room for two halo images and two staging tiles).  SATCV_ERR_UNSUPPORTED otherwise.
 int igemm_tr_launch(IgemmArgs& a, int dtype, hipStream_t st, bool dry) {
-  const int on = g_opt_thin_roles;
-  if (!on || !g_opt_igemm_thin || dtype != SATCV_BF16) return SATCV_ERR_UNSUPPORTED;
+  const int on = g_opt.thin_roles;
+  if (!on || !g_opt.igemm_thin || dtype != SATCV_BF16) return SATCV_ERR_UNSUPPORTED;
   const int cin = a.c0 + a.c1;
   if (a.kh != 3 || a.kw != 3 || a.dil != 1 || a.stride != 1 || a.mode_in || a.mode_out || a.accumulate || a.bst_y || a.pair_n) return SATCV_ERR_UNSUPPORTED;
   if (!(cin == 16 || cin == 32 || cin == 64) || !(a.cout == 32 || a.cout == 64) || a.cout_pad != a.cout || a.cstat != a.cout) return SATCV_ERR_UNSUPPORTED;

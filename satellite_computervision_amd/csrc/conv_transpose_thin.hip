@@ -457,8 +457,7 @@ static int convt_thin_dgrad_cfg(const ConvtDgradArgs& ca, hipStream_t st) {
 
 // the space-to-depth launch of satcv_conv2d_igemm (mode_in == 1): x0 = dy with c0 = COUT channels, cout = CIN
 int convt_thin_dgrad_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
-  static const bool on = [] { const char* e = getenv("SATCV_CONVT_THIN"); return !e || atoi(e) != 0; }();
-  if (!on || dtype != SATCV_BF16 || a.pair_n) return SATCV_ERR_UNSUPPORTED;      // (no pair store: satcv.h)
+  if (!g_opt.convt_thin || dtype != SATCV_BF16 || a.pair_n) return SATCV_ERR_UNSUPPORTED;      // (no pair store: satcv.h)
   if (a.kh != 1 || a.kw != 1 || a.mode_in != 1 || a.mode_out != 0 || a.f != 2 || a.x1 || a.stride != 1) return SATCV_ERR_UNSUPPORTED;
   if (a.out_scale || a.pool_y || a.accumulate || a.out_relu || a.in_scale || a.bias || a.bst_y1) return SATCV_ERR_UNSUPPORTED;
   if ((a.stats != nullptr) != (a.bst_y != nullptr)) return SATCV_ERR_UNSUPPORTED;      // (plain output statistics are not formed here)
@@ -475,16 +474,14 @@ int convt_thin_dgrad_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
   ca.h = a.h; ca.w_ = a.w_; ca.total_strips = (int)strips;
   // (64 <- 4 x 32 channels at 128 x 128 moves 536 MB -- dy, the raw outputs for the fused sums, dx -- and the tiled kernel already does it at
   //  5.0 TB/s, 107 us; this kernel measured 113-120 us there.  SATCV_CONVT_THIN=2 runs it anyway.)
-  static const bool all = [] { const char* e = getenv("SATCV_CONVT_THIN"); return e && atoi(e) >= 2; }();
-  if (cin == 64 && cout_t == 32 && all) return convt_thin_dgrad_cfg<64, 32, 4, 3>(ca, st);
+  if (cin == 64 && cout_t == 32 && g_opt.convt_thin >= 2) return convt_thin_dgrad_cfg<64, 32, 4, 3>(ca, st);
   if (cin == 128 && cout_t == 64) return convt_thin_dgrad_cfg<128, 64, 8, 2>(ca, st);
   return SATCV_ERR_UNSUPPORTED;
 }
 
 // SATCV_ERR_UNSUPPORTED outside the kernel's limits (the caller falls back to the tiled kernels)
 int convt_thin_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
-  static const bool on = [] { const char* e = getenv("SATCV_CONVT_THIN"); return !e || atoi(e) != 0; }();
-  if (!on || dtype != SATCV_BF16 || a.pair_n) return SATCV_ERR_UNSUPPORTED;
+  if (!g_opt.convt_thin || dtype != SATCV_BF16 || a.pair_n) return SATCV_ERR_UNSUPPORTED;
   if (a.kh != 1 || a.kw != 1 || a.mode_out != 1 || a.mode_in != 0 || a.f != 2 || a.x1 || a.stride != 1) return SATCV_ERR_UNSUPPORTED;
   if (a.pool_y || a.accumulate || a.bst_y || ((a.out_scale || a.out_relu) && a.stats)) return SATCV_ERR_UNSUPPORTED;      // (statistics are of the plain training output)
   const int cin = a.c0, cout_t = a.cstat;
@@ -497,13 +494,11 @@ int convt_thin_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
   ca.x = a.x0; ca.in_scale = a.in_scale; ca.in_shift = a.in_shift; ca.in_relu = a.in_relu;
   ca.w = a.w; ca.bias = a.bias; ca.out_scale = a.out_scale; ca.out_relu = a.out_relu; ca.y = a.y; ca.ldy = a.ldy; ca.stats = a.stats; ca.stats_ld = a.stats_ld;
   ca.h = a.h; ca.w_ = a.w_; ca.total_strips = (int)strips;
-  static const int wps = [] { const char* e = getenv("SATCV_CONVT_WPS"); return e ? atoi(e) : 3; }();
   if (cin == 64 && cout_t == 32) {
-    if (wps == 2) return convt_thin_cfg<64, 32, 4, 2>(ca, st);
+    if (g_opt.convt_wps == 2) return convt_thin_cfg<64, 32, 4, 2>(ca, st);
     return convt_thin_cfg<64, 32, 4, 3>(ca, st);
   }
   if (cin == 128 && cout_t == 64) return convt_thin_cfg<128, 64, 8, 2>(ca, st);
-  static const bool mid = [] { const char* e = getenv("SATCV_CONVT_MID"); return !e || atoi(e) != 0; }();
-  if (cin == 256 && cout_t == 128 && mid) return convt_thin_cfg<256, 128, 8, 2, 4>(ca, st);      // one position (64 KB of weights) per workgroup
+  if (cin == 256 && cout_t == 128 && g_opt.convt_mid) return convt_thin_cfg<256, 128, 8, 2, 4>(ca, st);      // one position (64 KB of weights) per workgroup
   return SATCV_ERR_UNSUPPORTED;
 }

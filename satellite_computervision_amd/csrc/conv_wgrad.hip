@@ -1159,13 +1159,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce16_kernel(const float* __rest
 
 // ------------------------------------------------------------------ host side
 struct WgradPlan { int tw, nci, nco, nw, nks, ntaps, nsplit, kpad, npad, n_ci_blk, n_co_blk, pix, db, dma; size_t ws_bytes; };
-extern int g_opt_wgrad_db;        // api.hip: satcv_set_option("wgrad_db", ...)
-extern int g_opt_wgrad_m16;       // api.hip: satcv_set_option("wgrad_m16", ...)
-
-static bool wgrad_pix256() {
-  static const bool on = [] { const char* e = getenv("SATCV_WGRAD_PIX256"); return !e || atoi(e) != 0; }();
-  return on;
-}
 
 static int pick_tw_w(int w) {
   int best = 8, bestpad = cdiv(w, 8) * 8;
@@ -1185,7 +1178,7 @@ static int wgrad_plan(const satcv_wgrad_desc* d, WgradPlan& p) {
   p.ntaps = d->kh * d->kw;
   if (!(p.ntaps == 1 || (d->kh == 3 && d->kw == 3))) { satcv_set_error("wgrad: only 1x1 and 3x3 taps"); return SATCV_ERR_UNSUPPORTED; }
   p.tw = pick_tw_w(d->w_);
-  const bool db_ok = g_opt_wgrad_db != 0 && d->dil == 1 && d->dtype == SATCV_BF16;
+  const bool db_ok = g_opt.wgrad_db != 0 && d->dil == 1 && d->dtype == SATCV_BF16;
   // 1x1 / transposed convolutions: 16 accumulator registers per (ci, co) tile, so the double-buffered kernel's 8 waves cover a
   // 64 x 128 block (each dY tile is re-read by half as many ci blocks: these launches are staging-bound, ~110 us whatever their size)
   // ... and, where the layer has them, a 128 x 256 block with four co tiles per wave (see wgrad_db_kernel)
@@ -1193,15 +1186,14 @@ static int wgrad_plan(const satcv_wgrad_desc* d, WgradPlan& p) {
   p.dma = 0;
   {
     // deep 3x3 layers: the (64 ci) x (128 co) block with dY by LDS-DMA (wgrad_dma_kernel; SATCV_WGRAD_DMA=0 keeps the (32 x 128) block)
-    static const int dma_on = [] { const char* e = getenv("SATCV_WGRAD_DMA"); return e ? atoi(e) : 1; }();
     const int th_ = 128 / p.tw;
     const bool whole = d->w_ % p.tw == 0 && (d->h >= th_ ? d->h % th_ == 0 : (th_ % d->h == 0 && d->n % (th_ / d->h) == 0));
-    if (dma_on && db_ok && p.ntaps == 9 && !d->mode_dy && cinx % 64 == 0 && nspace % 128 == 0 && whole && d->lddy % 8 == 0 &&
+    if (g_opt.wgrad_dma && db_ok && p.ntaps == 9 && !d->mode_dy && cinx % 64 == 0 && nspace % 128 == 0 && whole && d->lddy % 8 == 0 &&
         ((uintptr_t)d->dy % 16) == 0 && (!d->x1 || d->c0 % 8 == 0) && d->cin == cinx)
       p.dma = 1;
   }
   if (p.dma) { p.nci = 2; p.nco = 4; }
-  else if (p.ntaps == 1 && db_ok && cinx % 128 == 0 && nspace % 256 == 0 && g_opt_wgrad_db != 2) { p.nci = 4; p.nco = 2; p.nw = 4; }
+  else if (p.ntaps == 1 && db_ok && cinx % 128 == 0 && nspace % 256 == 0 && g_opt.wgrad_db != 2) { p.nci = 4; p.nco = 2; p.nw = 4; }
   else if (p.ntaps == 1) { p.nci = (db_ok && cinx % 64 == 0) ? 2 : 1; p.nco = 4; }
   else if (nspace % 128 == 0) { p.nci = 1; p.nco = 4; }
   else if (nspace % 64 == 0) { p.nci = (cinx % 64 == 0) ? 2 : 1; p.nco = 2; }
@@ -1216,7 +1208,7 @@ static int wgrad_plan(const satcv_wgrad_desc* d, WgradPlan& p) {
   //  measured 842 us on dec0.conv1 (64->32), the slowest kernel of the step)
   // (and only the 1 x 1 block form in bf16: every other 256-pixel instantiation spills into scratch, which is ruinous)
   p.pix = (p.ntaps == 9 && p.tw == 32 && p.nci == 1 && p.nco == 1 && d->dtype == SATCV_BF16 && p.n_ci_blk * p.n_co_blk <= 3 && d->h >= 8 && d->w_ >= 256 &&
-           d->dil == 1 && wgrad_pix256()) ? 256 : 128;
+           d->dil == 1 && g_opt.wgrad_pix256) ? 256 : 128;
   if (p.nw > 1) p.pix = 64;
   if (p.dma) p.pix = 128;
   const int th = p.pix / p.tw;
@@ -1239,8 +1231,7 @@ static int wgrad_plan(const satcv_wgrad_desc* d, WgradPlan& p) {
   // same step, weight gradients 25 % slower; 224: -1.0 %; 96: the weight gradients become the critical path, +3 %).
   // With the round-4 LDS-DMA kernel (11 % faster by itself) the balance moved: 128 workgroups 8.53 ms, 160 8.64 ms (A/B on one box,
   // medians of five 20-step regions, gpurun_out -> profiles/r04_ab_wgs.txt).  SATCV_WGRAD_WGS overrides.
-  static const int db_wgs = [] { const char* e = getenv("SATCV_WGRAD_WGS"); const int v = e ? atoi(e) : 128; return v >= 8 ? v : 128; }();
-  const int wgs = d->whole_chip ? 256 : db_wgs;
+  const int wgs = d->whole_chip ? 256 : g_opt.wgrad_wgs;
   if (p.db) ns = nblk >= wgs ? 1 : wgs / nblk;
   if (ns > ptiles) ns = ptiles;
   if (ns > 768) ns = 768;
@@ -1376,7 +1367,7 @@ static int wgrad_db_cfg(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream
   if constexpr (std::is_same<T, bf16>::value) {
     if (p.dma) {
       // option wgrad_m16 (SATCV_WGRAD_M16, default 0): the 16x16x32 form -- correct, and measured 33 % SLOWER per launch (profiles/r06_ab_wgrad_m16.txt)
-      return g_opt_wgrad_m16 ? wgrad_dma_launch<TW, true>(d, p, st) : wgrad_dma_launch<TW, false>(d, p, st);
+      return g_opt.wgrad_m16 ? wgrad_dma_launch<TW, true>(d, p, st) : wgrad_dma_launch<TW, false>(d, p, st);
     }      // (the plan's slab geometry is this kernel's: no other kernel can serve it)
   }
   if (p.ntaps == 1 && p.nw == 4) return wgrad_db_launch<T, TW, 4, 2, 1, 1, 64, 4>(d, p, st, sy, sx);

@@ -10,8 +10,7 @@
 // stream (5070 -> 5350 tiles/s).  With the weight gradients on 160 workgroups (round 2) the count hardly matters: 2 per CU +2.7 %
 // step time, 3 / 6 / 8 / 12 / 16 within 0.3 %, 6 the best by a hair (9.50 vs 9.52 ms).  SATCV_EW_PER_CU overrides.
 static inline int ew_grid(long long items, int cap = 0) {
-  static const int dflt = [] { const char* e = getenv("SATCV_EW_PER_CU"); const int v = e ? atoi(e) : 6; return 256 * (v >= 1 ? v : 6); }();
-  if (cap <= 0) cap = dflt;
+  if (cap <= 0) cap = ew_grid_cap();
   long long b = (items + EW_BLOCK - 1) / EW_BLOCK;
   if (b < 1) b = 1;
   if (b > cap) b = cap;
@@ -749,9 +748,8 @@ __global__ __launch_bounds__(EW_BLOCK) void bn_bwd_apply_dense_kernel(const satc
 // (SATCV_BN_APPLY=0: the round-3 loop for every apply launch -- A/B switch)
 template <typename T>
 static void bn_bwd_apply_dense_launch(const satcv_bnbwd_desc& e, long long items, size_t lds_bytes, int rev, int cld, hipStream_t st) {
-  static const int mode = getenv("SATCV_BN_APPLY") ? atoi(getenv("SATCV_BN_APPLY")) : 1;
   const dim3 grid(ew_grid(items)), block(EW_BLOCK);
-  if (mode == 0) { hipLaunchKernelGGL((bn_bwd_dense_kernel<T, true>), grid, block, lds_bytes, st, e, rev, cld); return; }
+  if (g_opt.bn_apply == 0) { hipLaunchKernelGGL((bn_bwd_dense_kernel<T, true>), grid, block, lds_bytes, st, e, rev, cld); return; }
   if (e.sk_sums) hipLaunchKernelGGL((bn_bwd_apply_dense_kernel<T, true, false, 4>), grid, block, lds_bytes, st, e, rev, cld);
   else if (e.dbias) hipLaunchKernelGGL((bn_bwd_apply_dense_kernel<T, false, true, 4>), grid, block, lds_bytes, st, e, rev, cld);
   else hipLaunchKernelGGL((bn_bwd_apply_dense_kernel<T, false, false, 4>), grid, block, lds_bytes, st, e, rev, cld);
@@ -787,7 +785,7 @@ extern "C" int satcv_bn_bwd_reduce(const satcv_bnbwd_desc* d, void* stream) {
   return SATCV_OK;
 }
 extern "C" int satcv_bn_bwd_apply(const satcv_bnbwd_desc* d, void* stream) {
-  static const int rev = getenv("SATCV_BN_REV") ? atoi(getenv("SATCV_BN_REV")) : 1;
+  const int rev = g_opt.bn_rev;
   int rc = bnbwd_check(d, true); if (rc) return rc;
   const int f = d->dpool ? d->f : 1;
   if (d->c_split > 0 && !d->dy1) {
@@ -1624,9 +1622,8 @@ extern "C" int satcv_loss_fwd_bwd(int32_t kind, const float* probs, const float*
                                   int64_t npix, float grad_scale, float* loss_out, float* dlogits, void* stream) {
   SATCV_CHECK(probs && y_true && weights && loss_out && dlogits, "loss: null pointer");
   SATCV_CHECK((kind == 0 || kind == 1) && ncls >= 1 && ncls <= HEAD_NCMAX && npix > 0, "loss: bad args (kind=%d ncls=%d)", kind, ncls);
-  static const bool fast = !(getenv("SATCV_LOSS_FAST") && atoi(getenv("SATCV_LOSS_FAST")) == 0);
   const bool al = ((uintptr_t)probs % (4 * ncls) == 0) && ((uintptr_t)y_true % (4 * ncls) == 0) && ((uintptr_t)dlogits % (4 * ncls) == 0);
-  if (fast && kind == 0 && activation == 0 && (ncls == 2 || ncls == 4) && al) {
+  if (g_opt.loss_fast && kind == 0 && activation == 0 && (ncls == 2 || ncls == 4) && al) {
     if (ncls == 2) hipLaunchKernelGGL(loss_cce_softmax_kernel<2>, dim3(ew_grid(npix)), dim3(EW_BLOCK), 0, (hipStream_t)stream, probs, y_true, weights, (long long)npix, grad_scale, loss_out, dlogits);
     else hipLaunchKernelGGL(loss_cce_softmax_kernel<4>, dim3(ew_grid(npix)), dim3(EW_BLOCK), 0, (hipStream_t)stream, probs, y_true, weights, (long long)npix, grad_scale, loss_out, dlogits);
     LAUNCH_OK("loss");

@@ -11,7 +11,7 @@
 #define EW_BLOCK 256
 // grid-stride kernels on a bounded number of workgroups per CU (elementwise.hip: 6 per CU; SATCV_EW_PER_CU overrides)
 static inline int ew_grid(long long items) {
-  static const int cap = [] { const char* e = getenv("SATCV_EW_PER_CU"); const int v = e ? atoi(e) : 6; return 256 * (v >= 1 ? v : 6); }();
+  const int cap = ew_grid_cap();
   long long b = (items + EW_BLOCK - 1) / EW_BLOCK;
   if (b < 1) b = 1;
   if (b > cap) b = cap;

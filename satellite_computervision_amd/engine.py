@@ -24,7 +24,7 @@ import torch
 from . import ops, parallel
 from ._lib import lib, check, F32, BF16, STAT_ROWS
 
-_M16_DEFAULT = int(os.environ.get('SATCV_M16', '1'))      # library default of option igemm_m16 (csrc/api.hip)
+_M16_DEFAULT = ops.options()['igemm_m16']      # the library's value of option igemm_m16 at import (csrc/options.hpp)
 
 BN_EPS = 1e-3
 BN_MOMENTUM = 0.99

@@ -1369,13 +1369,15 @@ class Model:
         self._stage_x(plan, xb)
         sk = getattr(self, '_infer_splitk', False) and n * h * w <= 2 * 512 * 512      # (measured: +4 % on one 512 x 512 tile, -3 % on four)
         if sk:       # (build-defined DeepLab: single tiles leave the deep 1x1 launches on 16-128 workgroups; kernel choice is baked into a captured graph)
+            splitk_was = C.c_int32()
+            check(lib.satcv_get_option(b'splitk', C.byref(splitk_was)))
             lib.satcv_set_option(b'splitk', 2)
         try:
             if not self._replay_graph(plan):
                 plan.run_forward(ops.stream_ptr())
         finally:
             if sk:
-                lib.satcv_set_option(b'splitk', int(os.environ.get('SATCV_SPLITK', '0')))
+                lib.satcv_set_option(b'splitk', splitk_was.value)
         return [plan.outputs[t.id] for t in self.outputs]
 
     # ---- hipGraph replay of launch-bound inference plans (satcv_graph_begin / _end / _launch, include/satcv.h)

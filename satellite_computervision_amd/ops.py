@@ -5,6 +5,8 @@ Each wrapper names the Keras layer call site of /root/reference/utils/model_tool
 the underlying kernel replaces.  There is no CPU path: tensors must live on a ROCm device.
 """
 import ctypes as C
+import itertools
+
 import torch
 
 from . import _lib
@@ -27,6 +29,17 @@ def ptr(t):
         return None
     assert t.is_cuda, 'satcv ops need device tensors (no CPU fallback)'
     return C.c_void_p(t.data_ptr())
+
+
+def options():
+    """{key: value} of every runtime switch and launch counter of the library, by enumeration (csrc/options.hpp)."""
+    out, v = {}, C.c_int32()
+    for i in itertools.count():
+        key = lib.satcv_option_key(i)
+        if key is None:
+            return out
+        check(lib.satcv_get_option(key, C.byref(v)))
+        out[key.decode()] = v.value
 
 
 def new_stats(c, device):

@@ -60,6 +60,25 @@ int main(void) {
   EXPECT(satcv_get_option("igemm_m16", &v) == 0 && v >= 0, "igemm_m16 option");
   EXPECT(satcv_set_option("igemm_m16", 2) == 0 && satcv_get_option("igemm_m16", &v) == 0 && v == 2, "set/get round trip");
   EXPECT(satcv_set_option(NULL, 1) != 0, "NULL key");
+  /* the whole table by enumeration: every key reads; a set either round-trips (and is put back) or is refused with a message and changes nothing */
+  int nkeys = 0, nsettable = 0;
+  EXPECT(satcv_option_key(-1) == NULL, "option_key(-1)");
+  for (const char* key; (key = satcv_option_key(nkeys)) != NULL; ++nkeys) {
+    int32_t was = -12345, now = -12345;
+    EXPECT(satcv_get_option(key, &was) == 0, "get_option(%s)", key);
+    EXPECT(satcv_get_option(key, NULL) != 0, "get_option(%s, NULL)", key);
+    if (satcv_set_option(key, was + 1) == 0) {
+      ++nsettable;
+      EXPECT(satcv_get_option(key, &now) == 0 && now == was + 1, "%s: set/get round trip", key);
+      EXPECT(satcv_set_option(key, was) == 0, "%s: restore", key);
+    } else {
+      EXPECT(strstr(satcv_last_error(), key) != NULL, "%s: the refusal names the key: %s", key, satcv_last_error());
+      EXPECT(satcv_get_option(key, &now) == 0 && now == was, "%s: a refused set must change nothing", key);
+    }
+  }
+  EXPECT(satcv_option_key(nkeys + 1) == NULL && satcv_option_key(INT32_MAX) == NULL, "option_key past the end");
+  EXPECT(nkeys == 34 && nsettable == 10, "%d keys, %d settable (include/satcv.h lists 34 and 10)", nkeys, nsettable);
+  EXPECT(satcv_set_option("m16p_launches", 0) != 0 && satcv_set_option("wgrad_wgs", 256) != 0, "counters and startup-only keys are read-only");
 
   /* ---- null and zeroed descriptors: refused with a message, no dereference */
   satcv_conv_desc cd; memset(&cd, 0, sizeof(cd));

@@ -250,3 +250,145 @@ def test_host_side_of_the_c_abi_under_asan_ubsan(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert 'runtime error' not in r.stderr and 'AddressSanitizer' not in r.stderr, r.stderr[-4000:]
     assert ' 0 failures' in r.stdout, r.stdout
+
+
+# ------------------------------------------------------------------ the option table (csrc/options.hpp)
+# the keys satcv_set_option accepted before the table existed: they keep their names, and stay the settable ones
+SETTABLE_KEYS = ('igemm_db', 'igemm_thin', 'wgrad_db', 'igemm_sched', 'splitk', 'igemm_m16', 'thin_roles', 'm16p', 'm16p_prio', 'wgrad_m16')
+COUNTER_KEYS = ('igemm_thin_launches', 'thin_roles_launches', 'm16p_launches')
+# every default, written from the sources of the commit before the table (the env_int(...) initialisers of csrc/api.hip and the getenv
+# lambdas at the call sites), not from the library under test
+OPTION_DEFAULTS = {
+    'igemm_db': 1, 'igemm_sched': 0, 'igemm_thin': 1, 'igemm_m16': 1, 'splitk': 0, 'splitk_tl': 1, 'convt_wide': 1, 'wdma': 1, 'db64': 1, 'db_tl': 1,
+    'db1x1': 1, 'db1x1_small': 1, 'igemm_generic': 0, 'm16_ws': 1, 'm16p': 1, 'm16p_prio': 30, 'm16p_prio64': -1, 'm16p_bn64': 1, 'thin_roles': 1,
+    'convt_thin': 1, 'convt_wps': 3, 'convt_mid': 1, 'wgrad_db': 1, 'wgrad_m16': 0, 'wgrad_pix256': 1, 'wgrad_dma': 1, 'wgrad_wgs': 128,
+    'ew_per_cu': 6, 'bn_apply': 1, 'bn_rev': 1, 'loss_fast': 1, 'igemm_thin_launches': 0, 'thin_roles_launches': 0, 'm16p_launches': 0}
+# key -> its environment variable (the launch counters have none)
+OPTION_ENV = {
+    'igemm_db': 'SATCV_DB', 'igemm_sched': 'SATCV_IGEMM_SCHED', 'igemm_thin': 'SATCV_THIN', 'igemm_m16': 'SATCV_M16', 'splitk': 'SATCV_SPLITK',
+    'splitk_tl': 'SATCV_SPLITK_TL', 'convt_wide': 'SATCV_CONVT_WIDE', 'wdma': 'SATCV_WDMA', 'db64': 'SATCV_DB64', 'db_tl': 'SATCV_DB_TL',
+    'db1x1': 'SATCV_DB1X1', 'db1x1_small': 'SATCV_DB1X1_SMALL', 'igemm_generic': 'SATCV_IGEMM', 'm16_ws': 'SATCV_M16_WS', 'm16p': 'SATCV_M16P',
+    'm16p_prio': 'SATCV_M16P_PRIO', 'm16p_prio64': 'SATCV_M16P_PRIO64', 'm16p_bn64': 'SATCV_M16P_BN64', 'thin_roles': 'SATCV_THIN_ROLES',
+    'convt_thin': 'SATCV_CONVT_THIN', 'convt_wps': 'SATCV_CONVT_WPS', 'convt_mid': 'SATCV_CONVT_MID', 'wgrad_db': 'SATCV_WGRAD_DB',
+    'wgrad_m16': 'SATCV_WGRAD_M16', 'wgrad_pix256': 'SATCV_WGRAD_PIX256', 'wgrad_dma': 'SATCV_WGRAD_DMA', 'wgrad_wgs': 'SATCV_WGRAD_WGS',
+    'ew_per_cu': 'SATCV_EW_PER_CU', 'bn_apply': 'SATCV_BN_APPLY', 'bn_rev': 'SATCV_BN_REV', 'loss_fast': 'SATCV_LOSS_FAST'}
+
+
+def _option_keys():
+    from satellite_computervision_amd import _lib
+    keys = []
+    while _lib.lib.satcv_option_key(len(keys)) is not None:
+        keys.append(_lib.lib.satcv_option_key(len(keys)).decode())
+    return keys
+
+
+def _options_in_child(env):
+    """ops.options() and the bias-gradient workspace of 10^6 x 8 in a fresh process whose only SATCV_* variables are `env`"""
+    import json
+    code = ('import sys, json; sys.path.insert(0, %r); from satellite_computervision_amd import ops; '
+            'print(json.dumps([ops.options(), ops.lib.satcv_bias_grad_workspace(10 ** 6, 8)]))' % ROOT)
+    clean = {k: v for k, v in os.environ.items() if not k.startswith('SATCV_')}
+    r = subprocess.run([sys.executable, '-c', code], env=dict(clean, **env), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def test_option_table_is_enumerated_and_documented():
+    from satellite_computervision_amd import _lib, ops
+    keys = _option_keys()
+    assert len(keys) == len(set(keys)) and _lib.lib.satcv_option_key(len(keys) + 5) is None and _lib.lib.satcv_option_key(-1) is None
+    assert set(keys) == set(OPTION_DEFAULTS) == set(OPTION_ENV) | set(COUNTER_KEYS)
+    assert set(SETTABLE_KEYS) | {'thin_roles_launches', 'm16p_launches', 'igemm_thin_launches'} <= set(keys)
+    assert list(ops.options()) == keys
+    v = ctypes.c_int32()
+    for k in keys:
+        assert _lib.lib.satcv_get_option(k.encode(), ctypes.byref(v)) == 0, k
+    hdr = open(os.path.join(ROOT, 'include', 'satcv.h')).read()
+    hdr = hdr[hdr.index('Runtime switches of the library'):hdr.index('int satcv_set_option')]
+    doc = open(os.path.join(ROOT, 'DESIGN.md')).read()
+    doc = doc[doc.index('## Appendix: Switches'):]
+    table = open(os.path.join(ROOT, 'satellite_computervision_amd', 'csrc', 'options.hpp')).read()
+    for k in keys:
+        env, kind = OPTION_ENV.get(k), 'settable' if k in SETTABLE_KEYS else 'counter' if k in COUNTER_KEYS else 'startup-only'
+        h = re.search(r'^ \* "%s"  (.*):$' % k, hdr, re.M)
+        assert h, f'{k}: not listed above satcv_set_option in satcv.h'
+        assert kind in h.group(1) and (env is None or f'{env}, default {OPTION_DEFAULTS[k]},' in h.group(1)), (k, h.group(1))
+        d = re.search(r'^\| (\S+) \| `%s` \| (-?\d+) \| (.*?) \|' % k, doc, re.M)
+        assert d, f'{k}: no row in the DESIGN.md appendix'
+        assert d.group(1) == (f'`{env}`' if env else '—') and int(d.group(2)) == OPTION_DEFAULTS[k], (k, d.group(0))
+        assert d.group(3).startswith('yes') == (k in SETTABLE_KEYS), (k, d.group(0))
+        row = re.search(r'X\(%s, (\S+), (-?\d+), ' % k, table)
+        assert row and row.group(1) == (f'"{env}"' if env else 'nullptr') and int(row.group(2)) == OPTION_DEFAULTS[k], k
+
+
+def test_option_defaults_are_pinned():
+    """no SATCV_* variable in the environment: every switch at the default the sources before the table gave it"""
+    got, ws = _options_in_child({})
+    assert got == OPTION_DEFAULTS, {k: (got.get(k), OPTION_DEFAULTS.get(k)) for k in set(got) | set(OPTION_DEFAULTS) if got.get(k) != OPTION_DEFAULTS.get(k)}
+    assert ws == 256 * 6 * 8 * 4
+
+
+def test_option_environment_parsing_is_pinned():
+    """every variable at a value other than its default, with the odd readings: a word for SATCV_IGEMM, the two clamps, CONVT_THIN >= 2"""
+    env = {'SATCV_DB': '2', 'SATCV_IGEMM_SCHED': '1', 'SATCV_THIN': '0', 'SATCV_M16': '2', 'SATCV_SPLITK': '1', 'SATCV_SPLITK_TL': '0',
+           'SATCV_CONVT_WIDE': '0', 'SATCV_WDMA': '0', 'SATCV_DB64': '3', 'SATCV_DB_TL': '200', 'SATCV_DB1X1': '0', 'SATCV_DB1X1_SMALL': '0',
+           'SATCV_IGEMM': 'generic', 'SATCV_M16_WS': '2', 'SATCV_M16P': '2', 'SATCV_M16P_PRIO': '123', 'SATCV_M16P_PRIO64': '21', 'SATCV_M16P_BN64': '0',
+           'SATCV_THIN_ROLES': '0', 'SATCV_CONVT_THIN': '2', 'SATCV_CONVT_WPS': '2', 'SATCV_CONVT_MID': '0', 'SATCV_WGRAD_DB': '2', 'SATCV_WGRAD_M16': '1',
+           'SATCV_WGRAD_PIX256': '0', 'SATCV_WGRAD_DMA': '0', 'SATCV_WGRAD_WGS': '4', 'SATCV_EW_PER_CU': '0', 'SATCV_BN_APPLY': '0', 'SATCV_BN_REV': '0',
+           'SATCV_LOSS_FAST': '0'}
+    assert set(env) == set(OPTION_ENV.values())
+    want = {k: int(env[e]) for k, e in OPTION_ENV.items() if k not in ('igemm_generic', 'wgrad_wgs', 'ew_per_cu')}
+    want.update(igemm_generic=1, wgrad_wgs=128, ew_per_cu=6, igemm_thin_launches=0, thin_roles_launches=0, m16p_launches=0)
+    assert all(want[k] != OPTION_DEFAULTS[k] for k in OPTION_ENV if k not in ('wgrad_wgs', 'ew_per_cu'))
+    got, ws = _options_in_child(env)
+    assert got == want, {k: (got.get(k), want.get(k)) for k in set(got) | set(want) if got.get(k) != want.get(k)}
+    assert ws == 256 * 6 * 8 * 4
+    # the same variables inside their ranges, a word that does not start with g, a non-numeric value (atoi: 0), a negative one
+    got, ws = _options_in_child({'SATCV_WGRAD_WGS': '8', 'SATCV_EW_PER_CU': '1', 'SATCV_IGEMM': 'fast', 'SATCV_CONVT_THIN': 'off', 'SATCV_CONVT_MID': '-1'})
+    assert got == dict(OPTION_DEFAULTS, wgrad_wgs=8, ew_per_cu=1, igemm_generic=0, convt_thin=0, convt_mid=-1)
+    assert ws == 256 * 8 * 4                                     # (tests/test_elementwise_gpu.py asserts the same on the device)
+
+
+def test_options_settable_and_startup_only():
+    from satellite_computervision_amd import _lib
+    lib, v = _lib.lib, ctypes.c_int32()
+
+    def get(k):
+        assert lib.satcv_get_option(k.encode(), ctypes.byref(v)) == 0
+        return v.value
+    for k in _option_keys():
+        was = get(k)
+        if k in SETTABLE_KEYS:
+            try:
+                assert lib.satcv_set_option(k.encode(), was + 7) == 0 and get(k) == was + 7, k
+            finally:
+                assert lib.satcv_set_option(k.encode(), was) == 0
+            assert get(k) == was
+        else:
+            assert lib.satcv_set_option(k.encode(), was + 7) == -1, k
+            msg = lib.satcv_last_error().decode()
+            assert k in msg and ('read-only counter' if k in COUNTER_KEYS else 'startup-only') in msg, msg
+            assert get(k) == was, k
+    assert lib.satcv_set_option(b'no_such_option', 1) != 0 and lib.satcv_get_option(b'no_such_option', ctypes.byref(v)) != 0
+
+
+def test_one_reader_of_the_environment_in_the_library():
+    csrc = os.path.join(ROOT, 'satellite_computervision_amd', 'csrc')
+    readers = sorted(f for f in os.listdir(csrc) if f.endswith(('.hip', '.hpp')) and 'getenv' in open(os.path.join(csrc, f)).read())
+    assert readers == ['api.hip', 'comm.hip'], readers
+    assert open(os.path.join(csrc, 'api.hip')).read().count('getenv(') == 1 and open(os.path.join(csrc, 'comm.hip')).read().count('getenv(') == 1
+    for top in ('satellite_computervision_amd', 'include', 'tests', 'tools'):
+        for d, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                if f.endswith(('.hip', '.hpp', '.h', '.c', '.cpp')):
+                    assert not re.search(r'extern\s+int\s+g_opt_', open(os.path.join(d, f)).read()), os.path.join(d, f)
+
+
+def test_python_reads_library_state_instead_of_the_environment():
+    """engine's igemm_m16 default and predict_on_device's splitk restore come from satcv_get_option, not from a second parse of the variables"""
+    import inspect
+    from satellite_computervision_amd import engine, model_tools as mt, ops
+    assert engine._M16_DEFAULT == ops.options()['igemm_m16']
+    assert "'SATCV_M16'" not in inspect.getsource(engine)
+    src = inspect.getsource(mt.Model.predict_on_device)
+    assert 'SATCV_SPLITK' not in src and "satcv_get_option(b'splitk'" in src

@@ -1673,3 +1673,28 @@ def test_fit_uploads_host_batches_one_ahead_and_stays_bit_identical(mt):
     sm.compile(optimizer=mt.Adam(1e-3), loss=lambda yt, yp: mt.weighted_bce(yt, yp, 2.0))
     h = sm.fit([xa, xb_], ys, batch_size=4, epochs=2, verbose=0, shuffle=False)
     assert np.isfinite(h.history['loss']).all()
+
+
+def test_launch_counters_are_live_through_the_option_table(mt):
+    """One bf16 training step of the tiny U-Net at batch 2, 32 x 64 (the maps of both levels, 32 x 64 and 16 x 32, are whole 8 x 32 tiles
+    of the thin-layer kernel): ops.options() -- the table read by enumeration -- shows the three "path taken" counters as ints that did
+    not fall, and the thin-layer one strictly grown."""
+    from satellite_computervision_amd import ops
+    counters = ('igemm_thin_launches', 'thin_roles_launches', 'm16p_launches')
+    mt.reset_uids()
+    m = mt.get_unet_model(2, 4, [32, 64], [2, 2])
+    m.compute_dtype = 'bfloat16'
+    m.compile(optimizer=mt.Adam(9e-4), loss=lambda yt, yp: mt.weighted_categorical_crossentropy(yt, yp, [1.0, 20.0]))
+    rng = np.random.default_rng(0)
+    x = rng.random((2, 32, 64, 4)).astype(np.float32)
+    t = np.eye(2, dtype=np.float32)[(rng.random((2, 32, 64)) < 0.3).astype(np.int64)]
+    before = ops.options()
+    loss = m.train_on_batch(x, t)
+    torch.cuda.synchronize()
+    after = ops.options()
+    assert np.isfinite(loss)
+    print('[fig] counters before', {k: before[k] for k in counters}, 'after', {k: after[k] for k in counters})
+    for k in counters:
+        assert type(before[k]) is int and type(after[k]) is int and 0 <= before[k] <= after[k], (k, before[k], after[k])
+    assert after['igemm_thin_launches'] > before['igemm_thin_launches']
+    assert {k: v for k, v in after.items() if k not in counters} == {k: v for k, v in before.items() if k not in counters}      # a step leaves every switch as it found it
