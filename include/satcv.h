@@ -177,6 +177,25 @@ typedef struct satcv_wgrad_desc {
 int64_t satcv_conv2d_wgrad_workspace(const satcv_wgrad_desc* d);
 int satcv_conv2d_wgrad(const satcv_wgrad_desc* d, void* stream);
 
+/* Which kernel form satcv_conv2d_wgrad(d) would run under the current options: host only, nothing is launched and no device is
+ * touched (the pointers of `d` may be null; their 16-byte alignment is all the plan reads of them).  The query walks the launch path's
+ * own decision chain, LDS-fit tests included, so it cannot drift from what runs.  Fields are the template arguments of the chosen
+ * instantiation (nks, pix, nw: of the kernel, not of the slab plan) and the slab geometry; on the per-tap path of strongly dilated 3x3
+ * layers (per_tap = 1) they describe each of the nine shifted 1x1 launches and their slab sums.  ws_bytes = nsplit * ntaps * kpad *
+ * npad * 4 of the described launch (satcv_conv2d_wgrad_workspace is the larger of that and the per-tap plan's). */
+enum { SATCV_WGRAD_KERNEL_SINGLE = 0, SATCV_WGRAD_KERNEL_DB = 1, SATCV_WGRAD_KERNEL_DMA = 2 };       /* wgrad_kernel, wgrad_db_kernel, wgrad_dma_kernel */
+enum { SATCV_WGRAD_REDUCE_GENERIC = 0, SATCV_WGRAD_REDUCE_4 = 1, SATCV_WGRAD_REDUCE_16 = 2 };          /* wgrad_reduce_kernel, ..4_kernel, ..16_kernel */
+typedef struct satcv_wgrad_plan_info {
+  int32_t kernel;                    /* SATCV_WGRAD_KERNEL_* */
+  int32_t tw, nci, nco, nw, nks, ntaps, pix;
+  int32_t db, dma, m16;              /* double-buffered template (db or dma kernel); LDS-DMA kernel; its 16x16x32 variant */
+  int32_t nsplit, kpad, npad, n_ci_blk, n_co_blk;
+  int32_t reduce;                    /* SATCV_WGRAD_REDUCE_*: the slab sum a launch without defer_reduce ends in */
+  int32_t per_tap;                   /* 1: nine shifted 1x1 launches (the 3x3 halo tile does not fit the LDS) */
+  int64_t ws_bytes, lds_bytes;
+} satcv_wgrad_plan_info;
+int satcv_conv2d_wgrad_plan_info(const satcv_wgrad_desc* d, satcv_wgrad_plan_info* info);
+
 /* Deferred, batched slab sum (round 5).  Every weight-gradient launch ends in an ordered sum of its workgroups' fp32 partial slabs into the
  * Keras-layout gradient -- a launch of 5-30 us per layer, 21 per training step.  With defer_reduce the producers skip it; the caller
  * collects one job per layer (the slab geometry the library chose), keeps the layers' workspaces apart, and runs ONE launch over a DEVICE

@@ -90,6 +90,17 @@ class WgradDesc(C.Structure):
                 ('workspace', c_vp), ('workspace_bytes', c_i64), ('dtype', c_i32), ('accumulate', c_i32), ('whole_chip', c_i32), ('defer_reduce', c_i32)]
 
 
+class WgradPlanInfo(C.Structure):
+    """satcv_wgrad_plan_info: the kernel form satcv_conv2d_wgrad would run (host-only query, nothing is launched)."""
+    _fields_ = [(k, c_i32) for k in ('kernel', 'tw', 'nci', 'nco', 'nw', 'nks', 'ntaps', 'pix', 'db', 'dma', 'm16',
+                                     'nsplit', 'kpad', 'npad', 'n_ci_blk', 'n_co_blk', 'reduce', 'per_tap')] + \
+               [('ws_bytes', c_i64), ('lds_bytes', c_i64)]
+
+
+WGRAD_KERNELS = ('single', 'db', 'dma')              # SATCV_WGRAD_KERNEL_*
+WGRAD_REDUCES = ('generic', 'reduce4', 'reduce16')   # SATCV_WGRAD_REDUCE_*
+
+
 class BwdfDesc(C.Structure):
     _fields_ = [('g', c_vp), ('yraw', c_vp), ('ldg', c_i32),
                 ('bn_scale', c_vp), ('bn_shift', c_vp), ('bn_mean', c_vp), ('bn_rstd', c_vp), ('bn_coef', c_vp), ('linear', c_i32),
@@ -180,6 +191,7 @@ _SIGS = {
     'satcv_conv2d_igemm_pipelined': (C.c_int, [C.POINTER(ConvDesc)]),
     'satcv_conv2d_wgrad_workspace': (c_i64, [C.POINTER(WgradDesc)]),
     'satcv_conv2d_wgrad': (C.c_int, [C.POINTER(WgradDesc), c_vp]),
+    'satcv_conv2d_wgrad_plan_info': (C.c_int, [C.POINTER(WgradDesc), C.POINTER(WgradPlanInfo)]),
     'satcv_conv2d_wgrad_reduce_job': (C.c_int, [C.POINTER(WgradDesc), C.POINTER(ReduceJob)]),
     'satcv_reduce_job_items': (c_i64, [C.POINTER(ReduceJob)]),
     'satcv_reduce_slabs_batched': (C.c_int, [c_vp, c_vp, c_i32, c_i64, c_vp]),

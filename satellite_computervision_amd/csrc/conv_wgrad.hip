@@ -54,6 +54,11 @@ struct WgradGeom {
   static constexpr int DP = CO_T + (CO_T == 32 && sizeof(T) == 2 ? 0 : PADE);
 };
 
+// Rows of the largest halo tile of a 3x3 / dilation-1 layer that the kernels stage in registers: `th` tile rows plus two halo rows per
+// image of the tile, for up to max(th / 4, 1) images.  ONE definition: the kernels size their register arrays (XMAXPIX) with it, the
+// launch functions' fit tests and the planner (wgrad_dma_fits) compare against it.
+__host__ __device__ constexpr int wgrad_halo_rows(int th) { return th + 2 * (th / 4 > 1 ? th / 4 : 1); }
+
 __device__ __forceinline__ bf16x4 tr_read(const bf16* p) {
   short4v v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)(p));
   return __builtin_bit_cast(bf16x4, v);
@@ -117,7 +122,7 @@ __global__ __launch_bounds__(NCI* NCO* NKS * 64, (TW == 8 ? 1 : 2)) void wgrad_k
   constexpr int d_items = BMPIX * (CO_T / 8);
   constexpr int TH = BMPIX / TW;
   // register-staged items per thread: halo tile of a 3x3 / dilation-1 conv incl. the several-images-per-tile case
-  constexpr int XMAXPIX = (TH + 2 * (TH / 4 > 1 ? TH / 4 : 1)) * (TW + 2);
+  constexpr int XMAXPIX = wgrad_halo_rows(TH) * (TW + 2);
   constexpr int XI = (XMAXPIX * (CI_T / 8) + NTHREADS - 1) / NTHREADS;
   constexpr int DI = (d_items + NTHREADS - 1) / NTHREADS;
 
@@ -445,7 +450,7 @@ __global__ __launch_bounds__(NCI* NCO* NKS * 64, 1) void wgrad_db_kernel(const W
   const int x_items = a.rl * a.cl * GX;
   constexpr int d_items = BMPIX * GD;
   // (no halo without taps; the 256-pixel tile is only planned for maps of at least its height: one image, one halo)
-  constexpr int XMAXPIX = NTAPS == 1 ? BMPIX : (PIX == 256 ? (TH + 2) * (TW + 2) : (TH + 2 * (TH / 4 > 1 ? TH / 4 : 1)) * (TW + 2));
+  constexpr int XMAXPIX = NTAPS == 1 ? BMPIX : (PIX == 256 ? (TH + 2) * (TW + 2) : wgrad_halo_rows(TH) * (TW + 2));
   constexpr int XI = (XMAXPIX * GX + NTHREADS - 1) / NTHREADS;
   constexpr int DI = (d_items + NTHREADS - 1) / NTHREADS;
   constexpr int NU = XI + DI;
@@ -779,7 +784,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_dma_kernel(const WgradArgs a) {
 
   // ---- X: per-thread, tile-invariant description of the staged items (as in wgrad_db_kernel)
   const int x_items = a.rl * a.cl * GX;
-  constexpr int XMAXPIX = (TH + 2 * (TH / 4 > 1 ? TH / 4 : 1)) * (TW + 2);
+  constexpr int XMAXPIX = wgrad_halo_rows(TH) * (TW + 2);
   constexpr int XI = (XMAXPIX * GX + NTHREADS - 1) / NTHREADS;
   constexpr int NPIECE = 4;                              // 1-KB dY pieces per wave and tile: 8 waves x 4 x 4 pixel rows = 128 pixels
   constexpr int NU = XI + NPIECE;
@@ -1159,12 +1164,28 @@ __global__ __launch_bounds__(256) void wgrad_reduce16_kernel(const float* __rest
 
 // ------------------------------------------------------------------ host side
 struct WgradPlan { int tw, nci, nco, nw, nks, ntaps, nsplit, kpad, npad, n_ci_blk, n_co_blk, pix, db, dma; size_t ws_bytes; };
+// the template instantiation a launch function serves.  The plan query (satcv_conv2d_wgrad_plan_info) walks the SAME wgrad_any ->
+// wgrad_cfg -> wgrad_db_cfg -> *_launch chain as a launch, with a non-null `pick`: the launch function runs its fit tests, records
+// itself here and returns before it touches the device.  There is no second copy of the decision.
+struct WgradPick { int kernel, tw, nci, nco, nks, ntaps, pix, nw, m16; size_t lds; };
 
 static int pick_tw_w(int w) {
   int best = 8, bestpad = cdiv(w, 8) * 8;
   const int cands[2] = {16, 32};
   for (int i = 0; i < 2; ++i) { int p = cdiv(w, cands[i]) * cands[i]; if (p <= bestpad) { best = cands[i]; bestpad = p; } }
   return best;
+}
+
+// Limits of wgrad_dma_kernel that depend on the map alone: its register staging holds a halo tile of at most TH + 2 max(TH / 4, 1) rows
+// (several short images per tile add two halo rows each), and a lane's dY offset inside a tile is a 32-bit byte offset.  Asked by
+// wgrad_plan -- a plan with the DMA kernel's 64 x 128 slab geometry that the kernel then refuses has no other kernel to run on -- and by
+// wgrad_dma_launch.
+static bool wgrad_dma_fits(const satcv_wgrad_desc* d, int tw) {
+  const int th = 128 / tw;
+  const int imgs = d->h >= th ? 1 : th / d->h, rpi = d->h >= th ? th : d->h;
+  if (imgs * (rpi + 2) > wgrad_halo_rows(th)) return false;                               // (the kernel's XMAXPIX = wgrad_halo_rows(TH) * (TW + 2) pixels)
+  if ((long long)imgs * d->h * d->w_ * d->lddy * 2 >= (1ll << 31)) return false;
+  return true;
 }
 
 static int wgrad_plan(const satcv_wgrad_desc* d, WgradPlan& p) {
@@ -1189,7 +1210,7 @@ static int wgrad_plan(const satcv_wgrad_desc* d, WgradPlan& p) {
     const int th_ = 128 / p.tw;
     const bool whole = d->w_ % p.tw == 0 && (d->h >= th_ ? d->h % th_ == 0 : (th_ % d->h == 0 && d->n % (th_ / d->h) == 0));
     if (g_opt.wgrad_dma && db_ok && p.ntaps == 9 && !d->mode_dy && cinx % 64 == 0 && nspace % 128 == 0 && whole && d->lddy % 8 == 0 &&
-        ((uintptr_t)d->dy % 16) == 0 && (!d->x1 || d->c0 % 8 == 0) && d->cin == cinx)
+        ((uintptr_t)d->dy % 16) == 0 && (!d->x1 || d->c0 % 8 == 0) && d->cin == cinx && wgrad_dma_fits(d, p.tw))
       p.dma = 1;
   }
   if (p.dma) { p.nci = 2; p.nco = 4; }
@@ -1256,7 +1277,7 @@ extern "C" int64_t satcv_conv2d_wgrad_workspace(const satcv_wgrad_desc* d) {
 }
 
 template <typename T, int TW, int NCI, int NCO, int NKS, int NTAPS, int PIX = 128>
-static int wgrad_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0) {
+static int wgrad_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0, WgradPick* pick = nullptr) {
   using G = WgradGeom<TW, NCI, NCO, NTAPS, T>;
   constexpr int TH = PIX / TW;
   WgradArgs a;
@@ -1278,6 +1299,7 @@ static int wgrad_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream
   size_t lds = ((size_t)a.rl * a.cl * G::XP + PIX * G::DP) * sizeof(T) + (PIX + (size_t)a.rl * a.cl) * sizeof(int);
   if (lds < 3 * 4096) lds = 3 * 4096;          // k-slice reduction scratch
   if (lds > 160 * 1024) return SATCV_ERR_UNSUPPORTED;
+  if (pick) { *pick = WgradPick{SATCV_WGRAD_KERNEL_SINGLE, TW, NCI, NCO, NKS, NTAPS, PIX, 1, 0, lds}; return SATCV_OK; }
   auto kern = wgrad_kernel<T, TW, NCI, NCO, NKS, NTAPS, PIX>;
   { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3(p.n_ci_blk * p.n_co_blk * p.nsplit), dim3(NCI * NCO * NKS * 64), lds, st, a);
@@ -1287,7 +1309,7 @@ static int wgrad_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream
 }
 
 template <typename T, int TW, int NCI, int NCO, int NKS, int NTAPS, int PIX = 128, int NW = 1>
-static int wgrad_db_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0) {
+static int wgrad_db_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0, WgradPick* pick = nullptr) {
   using G = WgradGeom<TW, NCI, NCO * NW, NTAPS, T>;
   constexpr int TH = PIX / TW, NTHREADS = NCI * NCO * NKS * 64, GX = G::CI_T / 8;
   WgradArgs a;
@@ -1307,7 +1329,7 @@ static int wgrad_db_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStr
   a.n_ci_blk = p.n_ci_blk; a.n_co_blk = p.n_co_blk; a.nsplit = p.nsplit;
   a.total_ptiles = a.ngroups * a.tiles_y * a.tiles_x;
   // register-staged items per thread (same bound as in the kernel)
-  constexpr int XMAXPIX = NTAPS == 1 ? PIX : (PIX == 256 ? (TH + 2) * (TW + 2) : (TH + 2 * (TH / 4 > 1 ? TH / 4 : 1)) * (TW + 2));
+  constexpr int XMAXPIX = NTAPS == 1 ? PIX : (PIX == 256 ? (TH + 2) * (TW + 2) : wgrad_halo_rows(TH) * (TW + 2));
   constexpr int XI = (XMAXPIX * GX + NTHREADS - 1) / NTHREADS;
   if ((long long)a.rl * a.cl * GX > (long long)XI * NTHREADS) return SATCV_ERR_UNSUPPORTED;
   if (a.rl >= 1024 || a.cl >= 1024 || a.imgs >= 1024) return SATCV_ERR_UNSUPPORTED;
@@ -1317,6 +1339,7 @@ static int wgrad_db_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStr
   const size_t red = (size_t)NCI * NCO * (NKS > 1 ? NKS - 1 : 0) * 16 * 64 * sizeof(float);
   if (lds < red) lds = red;
   if (lds > 160 * 1024) return SATCV_ERR_UNSUPPORTED;
+  if (pick) { *pick = WgradPick{SATCV_WGRAD_KERNEL_DB, TW, NCI, NCO, NKS, NTAPS, PIX, NW, 0, lds}; return SATCV_OK; }
   auto kern = wgrad_db_kernel<T, TW, NCI, NCO, NKS, NTAPS, PIX, NW>;
   { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3(p.n_ci_blk * p.n_co_blk * p.nsplit), dim3(NTHREADS), lds, st, a);
@@ -1326,7 +1349,7 @@ static int wgrad_db_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStr
 }
 
 template <int TW, bool M16 = false>
-static int wgrad_dma_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st) {
+static int wgrad_dma_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, WgradPick* pick = nullptr) {
   constexpr int PIX = 128, TH = PIX / TW, NTHREADS = 512, XP = M16 ? 80 : 96, GX = 8;
   WgradArgs a;
   memset(&a, 0, sizeof(a));
@@ -1344,15 +1367,13 @@ static int wgrad_dma_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipSt
   a.seg = a.rpi + 2; a.rl = a.imgs * a.seg; a.cl = TW + 2;
   a.n_ci_blk = p.n_ci_blk; a.n_co_blk = p.n_co_blk; a.nsplit = p.nsplit;
   a.total_ptiles = a.ngroups * a.tiles_y * a.tiles_x;
-  constexpr int XMAXPIX = (TH + 2 * (TH / 4 > 1 ? TH / 4 : 1)) * (TW + 2);
-  constexpr int XI = (XMAXPIX * GX + NTHREADS - 1) / NTHREADS;
-  if ((long long)a.rl * a.cl * GX > (long long)XI * NTHREADS) return SATCV_ERR_UNSUPPORTED;
+  // the halo tile fits the kernel's register staging (rl <= wgrad_halo_rows(TH), cl == TW + 2): the planner's test, and the only one
+  if (!wgrad_dma_fits(d, TW)) return SATCV_ERR_UNSUPPORTED;
   if (a.rl >= 1024 || a.cl >= 1024 || a.imgs >= 1024) return SATCV_ERR_UNSUPPORTED;
-  // a lane's dY offset inside a tile is a 32-bit byte offset
-  if ((long long)a.imgs * d->h * d->w_ * d->lddy * 2 >= (1ll << 31)) return SATCV_ERR_UNSUPPORTED;
   const size_t stage = (size_t)a.rl * a.cl * XP + (size_t)PIX * 128;
   const size_t lds = 2 * stage * sizeof(bf16) + (size_t)PIX * sizeof(int) + (size_t)GX * 16 * sizeof(float);
   if (lds > 160 * 1024) return SATCV_ERR_UNSUPPORTED;
+  if (pick) { *pick = WgradPick{SATCV_WGRAD_KERNEL_DMA, TW, 2, 4, 1, 9, PIX, 1, M16 ? 1 : 0, lds}; return SATCV_OK; }
   auto kern = wgrad_dma_kernel<TW, M16>;
   { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3(p.n_ci_blk * p.n_co_blk * p.nsplit), dim3(NTHREADS), lds, st, a);
@@ -1363,65 +1384,72 @@ static int wgrad_dma_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipSt
 
 // the double-buffered kernel (bf16): 8 waves = (ci, co) tiles x k-slices
 template <typename T, int TW>
-static int wgrad_db_cfg(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy, int sx) {
+static int wgrad_db_cfg(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy, int sx, WgradPick* pick) {
   if constexpr (std::is_same<T, bf16>::value) {
     if (p.dma) {
       // option wgrad_m16 (SATCV_WGRAD_M16, default 0): the 16x16x32 form -- correct, and measured 33 % SLOWER per launch (profiles/r06_ab_wgrad_m16.txt)
-      return g_opt.wgrad_m16 ? wgrad_dma_launch<TW, true>(d, p, st) : wgrad_dma_launch<TW, false>(d, p, st);
+      return g_opt.wgrad_m16 ? wgrad_dma_launch<TW, true>(d, p, st, pick) : wgrad_dma_launch<TW, false>(d, p, st, pick);
     }      // (the plan's slab geometry is this kernel's: no other kernel can serve it)
   }
-  if (p.ntaps == 1 && p.nw == 4) return wgrad_db_launch<T, TW, 4, 2, 1, 1, 64, 4>(d, p, st, sy, sx);
-  if (p.ntaps == 1 && p.nci == 2) return wgrad_db_launch<T, TW, 2, 4, 1, 1>(d, p, st, sy, sx);
-  if (p.ntaps == 1) return wgrad_db_launch<T, TW, 1, 4, 2, 1>(d, p, st, sy, sx);
-  if (p.nci == 1 && p.nco == 4) return wgrad_db_launch<T, TW, 1, 4, 2, 9>(d, p, st);
-  if (p.nci == 2 && p.nco == 2) return wgrad_db_launch<T, TW, 2, 2, 2, 9>(d, p, st);
+  if (p.ntaps == 1 && p.nw == 4) return wgrad_db_launch<T, TW, 4, 2, 1, 1, 64, 4>(d, p, st, sy, sx, pick);
+  if (p.ntaps == 1 && p.nci == 2) return wgrad_db_launch<T, TW, 2, 4, 1, 1>(d, p, st, sy, sx, pick);
+  if (p.ntaps == 1) return wgrad_db_launch<T, TW, 1, 4, 2, 1>(d, p, st, sy, sx, pick);
+  if (p.nci == 1 && p.nco == 4) return wgrad_db_launch<T, TW, 1, 4, 2, 9>(d, p, st, 0, 0, pick);
+  if (p.nci == 2 && p.nco == 2) return wgrad_db_launch<T, TW, 2, 2, 2, 9>(d, p, st, 0, 0, pick);
   if constexpr (TW == 32) {
-    if (p.pix == 256 && p.nci == 1 && p.nco == 1) return wgrad_db_launch<T, TW, 1, 1, 8, 9, 256>(d, p, st);
+    if (p.pix == 256 && p.nci == 1 && p.nco == 1) return wgrad_db_launch<T, TW, 1, 1, 8, 9, 256>(d, p, st, 0, 0, pick);
   }
-  if (p.nci == 1 && p.nco == 2) return wgrad_db_launch<T, TW, 1, 2, 4, 9>(d, p, st);
-  if (p.nci == 2 && p.nco == 1) return wgrad_db_launch<T, TW, 2, 1, 4, 9>(d, p, st);
-  return wgrad_db_launch<T, TW, 1, 1, 8, 9>(d, p, st);
+  if (p.nci == 1 && p.nco == 2) return wgrad_db_launch<T, TW, 1, 2, 4, 9>(d, p, st, 0, 0, pick);
+  if (p.nci == 2 && p.nco == 1) return wgrad_db_launch<T, TW, 2, 1, 4, 9>(d, p, st, 0, 0, pick);
+  return wgrad_db_launch<T, TW, 1, 1, 8, 9>(d, p, st, 0, 0, pick);
 }
 
 template <typename T, int TW>
-static int wgrad_cfg(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0) {
+static int wgrad_cfg(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0, WgradPick* pick = nullptr) {
   if constexpr (std::is_same<T, bf16>::value) {
     if (p.db) {
-      const int rc = wgrad_db_cfg<T, TW>(d, p, st, sy, sx);
+      const int rc = wgrad_db_cfg<T, TW>(d, p, st, sy, sx, pick);
       if (rc != SATCV_ERR_UNSUPPORTED) return rc;
-      if (p.ntaps == 1 && (p.nci != 1 || p.nw != 1)) { satcv_set_error("wgrad: block plan without a kernel"); return rc; }   // (the plan's slab geometry is the db kernel's)
+      if (p.dma || (p.ntaps == 1 && (p.nci != 1 || p.nw != 1))) { satcv_set_error("wgrad: block plan without a kernel"); return rc; }   // (the plan's slab geometry is the db / dma kernel's)
     }
   }
-  if (p.ntaps == 1) return wgrad_launch<T, TW, 1, 4, 1, 1>(d, p, st, sy, sx);
-  if (p.nci == 1 && p.nco == 4) return wgrad_launch<T, TW, 1, 4, 1, 9>(d, p, st);
-  if (p.nci == 2 && p.nco == 2) return wgrad_launch<T, TW, 2, 2, 1, 9>(d, p, st);
+  if (p.ntaps == 1) return wgrad_launch<T, TW, 1, 4, 1, 1>(d, p, st, sy, sx, pick);
+  if (p.nci == 1 && p.nco == 4) return wgrad_launch<T, TW, 1, 4, 1, 9>(d, p, st, 0, 0, pick);
+  if (p.nci == 2 && p.nco == 2) return wgrad_launch<T, TW, 2, 2, 1, 9>(d, p, st, 0, 0, pick);
   if constexpr (TW == 32) {
     if constexpr (std::is_same<T, bf16>::value) {
-      if (p.pix == 256 && p.nci == 1 && p.nco == 1) return wgrad_launch<T, TW, 1, 1, 4, 9, 256>(d, p, st);
+      if (p.pix == 256 && p.nci == 1 && p.nco == 1) return wgrad_launch<T, TW, 1, 1, 4, 9, 256>(d, p, st, 0, 0, pick);
     }
   }
-  if (p.nci == 1 && p.nco == 2) return wgrad_launch<T, TW, 1, 2, 2, 9>(d, p, st);
-  if (p.nci == 2 && p.nco == 1) return wgrad_launch<T, TW, 2, 1, 2, 9>(d, p, st);
-  return wgrad_launch<T, TW, 1, 1, 4, 9>(d, p, st);
+  if (p.nci == 1 && p.nco == 2) return wgrad_launch<T, TW, 1, 2, 2, 9>(d, p, st, 0, 0, pick);
+  if (p.nci == 2 && p.nco == 1) return wgrad_launch<T, TW, 2, 1, 2, 9>(d, p, st, 0, 0, pick);
+  return wgrad_launch<T, TW, 1, 1, 4, 9>(d, p, st, 0, 0, pick);
 }
 template <typename T>
-static int wgrad_t(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0) {
+static int wgrad_t(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0, WgradPick* pick = nullptr) {
   switch (p.tw) {
-    case 32: return wgrad_cfg<T, 32>(d, p, st, sy, sx);
-    case 16: return wgrad_cfg<T, 16>(d, p, st, sy, sx);
-    default: return wgrad_cfg<T, 8>(d, p, st, sy, sx);
+    case 32: return wgrad_cfg<T, 32>(d, p, st, sy, sx, pick);
+    case 16: return wgrad_cfg<T, 16>(d, p, st, sy, sx, pick);
+    default: return wgrad_cfg<T, 8>(d, p, st, sy, sx, pick);
   }
 }
-static int wgrad_any(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0) {
-  if (d->dtype == SATCV_BF16) return wgrad_t<bf16>(d, p, st, sy, sx);
-  if (d->dtype == SATCV_F32) return wgrad_t<float>(d, p, st, sy, sx);
+static int wgrad_any(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0, WgradPick* pick = nullptr) {
+  if (d->dtype == SATCV_BF16) return wgrad_t<bf16>(d, p, st, sy, sx, pick);
+  if (d->dtype == SATCV_F32) return wgrad_t<float>(d, p, st, sy, sx, pick);
   satcv_set_error("wgrad: bad dtype");
   return SATCV_ERR_INVALID;
 }
+// which slab-sum kernel serves a launch (SATCV_WGRAD_REDUCE_*): asked by wgrad_reduce_launch and by the plan query
+static int wgrad_reduce_kind(const satcv_wgrad_desc* d, const WgradPlan& p, const float* dw, int nvalid) {
+  if (!d->transposed && nvalid % 4 == 0 && p.npad % 4 == 0 && ((uintptr_t)dw % 16) == 0 && ((uintptr_t)d->workspace % 16) == 0)
+    return p.nsplit >= 32 ? SATCV_WGRAD_REDUCE_16 : SATCV_WGRAD_REDUCE_4;
+  return SATCV_WGRAD_REDUCE_GENERIC;
+}
 static int wgrad_reduce_launch(const satcv_wgrad_desc* d, const WgradPlan& p, float* dw, int nvalid, hipStream_t st) {
   const long long total = (long long)p.ntaps * d->cin * nvalid;
-  if (!d->transposed && nvalid % 4 == 0 && p.npad % 4 == 0 && ((uintptr_t)dw % 16) == 0 && ((uintptr_t)d->workspace % 16) == 0) {
-    if (p.nsplit >= 32) {
+  const int kind = wgrad_reduce_kind(d, p, dw, nvalid);
+  if (kind != SATCV_WGRAD_REDUCE_GENERIC) {
+    if (kind == SATCV_WGRAD_REDUCE_16) {
       int grid16 = (int)((total / 4 + 15) / 16); if (grid16 > 16384) grid16 = 16384;
       hipLaunchKernelGGL(wgrad_reduce16_kernel, dim3(grid16), dim3(256), 0, st, (const float*)d->workspace, dw, p.nsplit, p.ntaps, p.kpad, p.npad, d->cin, nvalid,
                          d->accumulate);
@@ -1469,28 +1497,53 @@ int wgrad_reduce_slabs_t(const float* ws, float* dw, int nslab, int kpad, int np
   return wgrad_reduce_launch(&d, p, dw, nvalid, st);
 }
 
-extern "C" int satcv_conv2d_wgrad(const satcv_wgrad_desc* d, void* stream) {
-  SATCV_CHECK(d && d->x0 && d->dy && d->dw && d->workspace, "wgrad: null pointer");
-  SATCV_CHECK(d->c0 > 0 && d->c0 % 8 == 0 && d->c1 % 8 == 0 && (d->c1 == 0) == (d->x1 == nullptr), "wgrad: bad source channels");
+// the descriptor checks that need no pointer: shared by the launch and the plan query
+static int wgrad_check_desc(const satcv_wgrad_desc* d) {
+  SATCV_CHECK(d->c0 > 0 && d->c0 % 8 == 0 && d->c1 >= 0 && d->c1 % 8 == 0, "wgrad: bad source channels");
   SATCV_CHECK(d->cin > 0 && d->cin <= d->c0 + d->c1 && d->cout > 0, "wgrad: bad cin/cout");
   SATCV_CHECK(d->n > 0 && d->h > 0 && d->w_ > 0 && d->dil >= 1, "wgrad: bad dims");
   SATCV_CHECK(!d->mode_dy || (d->f >= 2 && d->kh == 1 && d->kw == 1 && d->cout % 8 == 0), "wgrad: transposed conv needs 1x1 taps, f>=2");
-  SATCV_CHECK(!d->x1 || d->c0 % 8 == 0, "wgrad: dual source needs c0 %% 8 == 0");      // (a thread's 8-channel item never straddles the two sources)
+  return SATCV_OK;
+}
+
+static void wgrad_fill_info(satcv_wgrad_plan_info* o, const satcv_wgrad_desc* d, const WgradPlan& p, const WgradPick& k, int per_tap, int nvalid) {
+  o->kernel = k.kernel; o->tw = k.tw; o->nci = k.nci; o->nco = k.nco; o->nw = k.nw; o->nks = k.nks; o->ntaps = k.ntaps; o->pix = k.pix;
+  o->db = k.kernel != SATCV_WGRAD_KERNEL_SINGLE; o->dma = k.kernel == SATCV_WGRAD_KERNEL_DMA; o->m16 = k.m16;
+  o->nsplit = p.nsplit; o->kpad = p.kpad; o->npad = p.npad; o->n_ci_blk = p.n_ci_blk; o->n_co_blk = p.n_co_blk;
+  o->reduce = wgrad_reduce_kind(d, p, d->dw, nvalid); o->per_tap = per_tap;
+  o->ws_bytes = (int64_t)p.ws_bytes; o->lds_bytes = (int64_t)k.lds;
+}
+
+// One walk serves the launch (info == nullptr) and the plan query (info != nullptr: every launch function records itself instead of
+// launching, nothing touches the device).
+static int wgrad_drive(const satcv_wgrad_desc* d, hipStream_t st, satcv_wgrad_plan_info* info) {
+  { const int rc = wgrad_check_desc(d); if (rc) return rc; }
   WgradPlan p;
   int rc = wgrad_plan(d, p); if (rc) return rc;
-  SATCV_CHECK((size_t)d->workspace_bytes >= p.ws_bytes, "wgrad: workspace %lld < %zu", (long long)d->workspace_bytes, p.ws_bytes);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!info) SATCV_CHECK((size_t)d->workspace_bytes >= p.ws_bytes, "wgrad: workspace %lld < %zu", (long long)d->workspace_bytes, p.ws_bytes);
   const int nvalid = d->mode_dy ? d->f * d->f * d->cout : d->cout;
   const double flops = 2.0 * d->n * d->h * d->w_ * (double)nvalid * (double)(d->c0 + d->c1) * d->kh * d->kw;
-  satcv_prof_begin(2, flops, st);
-  rc = wgrad_any(d, p, st);
+  WgradPick pick;
+  memset(&pick, 0, sizeof(pick));
+  WgradPick* const pk = info ? &pick : nullptr;
+  if (!info) satcv_prof_begin(2, flops, st);
+  rc = wgrad_any(d, p, st, 0, 0, pk);
   if (rc == SATCV_ERR_UNSUPPORTED && p.ntaps == 9) {
-    if (d->defer_reduce) { satcv_prof_end(2, st); satcv_set_error("wgrad: defer_reduce is not available on the per-tap path of strongly dilated convolutions"); return SATCV_ERR_UNSUPPORTED; }
+    if (d->defer_reduce) {
+      if (!info) satcv_prof_end(2, st);
+      satcv_set_error("wgrad: defer_reduce is not available on the per-tap path of strongly dilated convolutions");
+      return SATCV_ERR_UNSUPPORTED;
+    }
     // halo tile of a strongly dilated conv does not fit the LDS: treat every tap as a shifted 1x1 product
     satcv_wgrad_desc d1 = *d;
     d1.kh = d1.kw = 1;
     WgradPlan p1;
     rc = wgrad_plan(&d1, p1);
+    if (info) {        // (the nine launches share one kernel form: the fit tests do not depend on the shift)
+      if (rc == SATCV_OK) rc = wgrad_any(&d1, p1, st, -d->dil, -d->dil, pk);
+      if (rc == SATCV_OK) wgrad_fill_info(info, &d1, p1, pick, 1, nvalid);
+      return rc;
+    }
     if (rc == SATCV_OK && (size_t)d->workspace_bytes < p1.ws_bytes) { satcv_set_error("wgrad: workspace too small for the per-tap path"); rc = SATCV_ERR_INVALID; }
     for (int tap = 0; tap < 9 && rc == SATCV_OK; ++tap) {
       rc = wgrad_any(&d1, p1, st, (tap / 3 - 1) * d->dil, (tap % 3 - 1) * d->dil);
@@ -1499,10 +1552,26 @@ extern "C" int satcv_conv2d_wgrad(const satcv_wgrad_desc* d, void* stream) {
     satcv_prof_end(2, st);
     return rc;
   }
+  if (info) {
+    if (rc == SATCV_OK) wgrad_fill_info(info, d, p, pick, 0, nvalid);
+    return rc;
+  }
   satcv_prof_end(2, st);
   if (rc) return rc;
   if (d->defer_reduce) return SATCV_OK;            // the caller sums the slabs later (satcv_reduce_slabs_batched)
   return wgrad_reduce_launch(d, p, d->dw, nvalid, st);
+}
+
+extern "C" int satcv_conv2d_wgrad(const satcv_wgrad_desc* d, void* stream) {
+  SATCV_CHECK(d && d->x0 && d->dy && d->dw && d->workspace, "wgrad: null pointer");
+  SATCV_CHECK((d->c1 == 0) == (d->x1 == nullptr), "wgrad: bad source channels");
+  return wgrad_drive(d, reinterpret_cast<hipStream_t>(stream), nullptr);
+}
+
+extern "C" int satcv_conv2d_wgrad_plan_info(const satcv_wgrad_desc* d, satcv_wgrad_plan_info* info) {
+  SATCV_CHECK(d && info, "wgrad_plan_info: null pointer");
+  memset(info, 0, sizeof(*info));
+  return wgrad_drive(d, nullptr, info);
 }
 
 // ------------------------------------------------------------------ deferred, batched slab sum (include/satcv.h)

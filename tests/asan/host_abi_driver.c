@@ -88,6 +88,9 @@ int main(void) {
   satcv_wgrad_desc wd; memset(&wd, 0, sizeof(wd));
   EXPECT(satcv_conv2d_wgrad(NULL, NULL) != 0 && satcv_conv2d_wgrad(&wd, NULL) != 0, "invalid wgrad desc");
   EXPECT(satcv_conv2d_wgrad_workspace(NULL) < 0, "wgrad workspace of NULL");
+  satcv_wgrad_plan_info wi;
+  EXPECT(satcv_conv2d_wgrad_plan_info(NULL, &wi) != 0 && satcv_conv2d_wgrad_plan_info(&wd, NULL) != 0 && satcv_conv2d_wgrad_plan_info(&wd, &wi) != 0,
+         "invalid wgrad plan query");
   satcv_bwdf_desc fd; memset(&fd, 0, sizeof(fd));
   EXPECT(satcv_conv2d_bwd_fused(NULL, NULL) != 0 && satcv_conv2d_bwd_fused(&fd, NULL) != 0, "invalid fused desc");
   EXPECT(satcv_conv2d_bwd_fused_workspace(NULL) < 0 && satcv_conv2d_bwd_fused_workspace(&fd) < 0, "fused workspace of an invalid desc");
@@ -131,6 +134,12 @@ int main(void) {
                 w.n = n; w.h = HW[hi][0]; w.w_ = HW[hi][1]; w.kh = w.kw = KD[ki][0]; w.dil = KD[ki][1]; w.f = 1; w.dtype = dt;
                 const int64_t nb = satcv_conv2d_wgrad_workspace(&w);
                 EXPECT(nb != 0, "wgrad workspace 0 bytes");
+                if (nb > 0 && w.c0 % 8 == 0) {        /* the plan query: null-free, host only, consistent with the workspace */
+                  satcv_wgrad_plan_info pi;
+                  EXPECT(satcv_conv2d_wgrad_plan_info(&w, &pi) == 0, "wgrad plan query: %s", satcv_last_error());
+                  EXPECT(pi.ws_bytes == (int64_t)pi.nsplit * pi.ntaps * pi.kpad * pi.npad * 4 && pi.ws_bytes <= nb && pi.lds_bytes <= 160 * 1024,
+                         "wgrad plan query geometry");
+                }
                 if (nb > 0) {
                   w.workspace = (float*)fake; w.workspace_bytes = nb;
                   satcv_reduce_job j;

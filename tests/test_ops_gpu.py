@@ -55,6 +55,7 @@ def close(got, ref, td, what='', k=1.0):
     tol = (2e-5 if td == torch.float32 else 1.2e-2) * k
     err = np.abs(got - ref).max() / scale
     assert err < tol, f'{what}: rel-to-max err {err:.3e} >= {tol:.1e} (scale {scale:.3e})'
+    return err, tol                      # for records (tests/test_wgrad_plan_gpu.py prints them)
 
 
 def rup(a, b):
@@ -147,27 +148,29 @@ def test_conv2d_dual_source_affine(ops, td):
 
 
 # ---------------------------------------------------------------------- conv backward
+# weight-gradient form of each shape as satcv_conv2d_wgrad_plan_info reports it: fp32 runs wgrad_kernel, bf16 the double-buffered kernel
+# (`db`) or the LDS-DMA kernel (`dma`) with the same (nci, nco) block unless noted; tests/wgrad_cases.py holds the per-instantiation table
 BWD_CASES = [
-    (2, 32, 32, 16, 32),     # wgrad cfg (1,1)
-    (2, 32, 32, 64, 32),     # wgrad cfg (2,1)
-    (2, 16, 16, 32, 64),     # (1,2), TW=16
-    (2, 16, 32, 64, 64),     # (2,2)
-    (3, 8, 8, 64, 128),      # (1,4), TW=8 multi-image
-    (1, 20, 24, 32, 32),     # ragged
-    (1, 64, 64, 32, 32),     # many pixel tiles -> split-K
-    (2, 32, 32, 64, 64),     # (2,2) at TW=32
-    (2, 24, 24, 64, 64),     # ragged rows, TW=8
-    (2, 48, 48, 32, 32),     # 3 column tiles of 16
-    # deep shapes of the benchmarked model (data gradient: Cout -> Cin; weight gradient tiles of 128 channels and more)
-    (2, 16, 16, 512, 512),   # dec4.conv2
-    (2, 16, 16, 1024, 512),  # dec4.conv1
-    (2, 8, 8, 512, 1024),    # centre block
-    (2, 32, 32, 512, 256),   # dec3.conv1
-    (2, 16, 16, 256, 512),   # enc4
-    (1, 64, 64, 256, 128),   # dec2.conv1
-    (1, 64, 64, 128, 128),   # dec2.conv2
-    (1, 128, 128, 128, 64),  # dec1.conv1
-    (1, 256, 256, 64, 32),   # dec0.conv1
+    (2, 32, 32, 16, 32),     # (1,1), tw 32, 16 slabs
+    (2, 32, 32, 64, 32),     # (2,1), tw 32
+    (2, 16, 16, 32, 64),     # (1,2), tw 16
+    (2, 16, 32, 64, 64),     # (2,2), tw 32
+    (3, 8, 8, 64, 128),      # (1,4), tw 8, two images per tile and a partial last group (no DMA kernel: not whole tiles)
+    (1, 20, 24, 32, 32),     # (1,1), tw 8, ragged rows
+    (1, 64, 64, 32, 32),     # (1,1), tw 32, 32 slabs -> the 16-lane slab sum
+    (2, 32, 32, 64, 64),     # (2,2), tw 32
+    (2, 24, 24, 64, 64),     # (2,2), tw 8, ragged rows
+    (2, 48, 48, 32, 32),     # (1,1), tw 16, 3 column tiles, 32 slabs
+    # deep shapes of the benchmarked model (data gradient: Cout -> Cin): fp32 (1,4); bf16 the DMA kernel's (2,4) block
+    (2, 16, 16, 512, 512),   # dec4.conv2   tw 16
+    (2, 16, 16, 1024, 512),  # dec4.conv1   tw 16
+    (2, 8, 8, 512, 1024),    # centre block tw 8, one slab
+    (2, 32, 32, 512, 256),   # dec3.conv1   tw 32
+    (2, 16, 16, 256, 512),   # enc4         tw 16
+    (1, 64, 64, 256, 128),   # dec2.conv1   tw 32, 32 slabs
+    (1, 64, 64, 128, 128),   # dec2.conv2   tw 32, 32 slabs
+    (1, 128, 128, 128, 64),  # dec1.conv1   (2,2), tw 32; fp32 128 slabs, bf16 db 64
+    (1, 256, 256, 64, 32),   # dec0.conv1   (2,1), tw 32; fp32 512 slabs, bf16 db 128 (128 pixels per step: the 256-pixel form needs 32-channel X blocks)
 ]
 
 
