@@ -10,8 +10,10 @@ import os
 # import torch first (it loads its bundled libamdhip64) so that libsatcv.so binds to that copy.
 import torch  # noqa: F401
 
+from . import switches
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('SATCV_LIB') or os.path.join(_HERE, 'libsatcv.so')     # SATCV_LIB: profiling variants only
+LIB_PATH = switches.read('lib') or os.path.join(_HERE, 'libsatcv.so')
 
 F32, BF16, FP8, FP8X, F64 = 0, 1, 2, 3, 4
 STAT_ROWS = 32

@@ -13,7 +13,6 @@ Fusion contract (what the HIP kernels expect):
 There is no CPU path: everything here requires the HIP library and a ROCm device.
 """
 import ctypes as C
-import os
 import itertools
 from collections import defaultdict
 from fractions import Fraction
@@ -21,7 +20,7 @@ from fractions import Fraction
 import numpy as np
 import torch
 
-from . import ops, parallel
+from . import ops, parallel, switches
 from ._lib import lib, check, F32, BF16, STAT_ROWS
 
 _M16_DEFAULT = ops.options()['igemm_m16']      # the library's value of option igemm_m16 at import (csrc/options.hpp)
@@ -64,33 +63,24 @@ class ParamSpec:
         return int(np.prod(self.shape))
 
 
-# The bias of a convolution that feeds a training-mode BatchNormalization has an identically zero gradient: with
+# Import-time switches (switches.py holds variable, default and meaning of each; DESIGN.md section 6 the measurements).
+# BIAS_NOISE: the bias of a convolution that feeds a training-mode BatchNormalization has an identically zero gradient: with
 # dy = scale*rstd*(g - mean(g) - xhat*mean(g*xhat)) the sum over the batch vanishes because sum(xhat) = 0.  TensorFlow computes
 # reduce_sum(dy) anyway and gets rounding noise (~1e-9), which Adam's normalisation turns into +-lr steps of a parameter that has
-# no effect on any output.  Here the gradient is the exact 0 (the bias stays at its value) unless SATCV_BN_BIAS_NOISE=1 asks for
-# the summed-noise form; the atomics it needs are also the one remaining source of run-to-run differences in a training step.
-BIAS_NOISE = os.environ.get('SATCV_BN_BIAS_NOISE', '0') == '1'
-# weight-gradient launches (second stream) enqueued AFTER the data gradient of their layer instead of before it: they then start beside the
-# HBM-bound BatchNorm-backward kernels of the next layer rather than beside their own layer's MFMA-bound data gradient
-# a layer's weight gradient is enqueued BEHIND its data gradient (both only need dy): with the weight gradients on 160 workgroups the
-# step time is the same either way (9.54 ms, three A/B pairs) and the 3x3 data gradients run without their own layer's weight
-# gradient beside them (roofline.frac 0.251 -> 0.262); SATCV_WGRAD_LATE=0 restores the earlier order
-# round 6, weight gradients on 128 workgroups, profiling events off: enqueued BEFORE the data gradient the step is 7.89-7.90 ms against 7.99-8.00 behind it
-# (profiles/r06_ab_env_switches.txt, A/B/A/B on one box) -- the weight gradient then starts beside its own layer's data gradient and the side stream
-# finishes earlier; SATCV_WGRAD_LATE=1 restores the round-3 order
-WGRAD_LATE = os.environ.get('SATCV_WGRAD_LATE', '0') == '1'
-# round 5: decoder_block's up-sampling path backward as one launch (csrc/convt_bwd_fused.hip) for these Conv2DTranspose filter counts (SATCV_CTBF=0: off;
-# SATCV_CTBF_COUTS restricts the set)
-CTBF = os.environ.get('SATCV_CTBF', '1') != '0'
-CTBF_COUTS = tuple(int(v) for v in os.environ.get('SATCV_CTBF_COUTS', '32,64').split(',') if v)
-FUSE_RESIDUAL = os.environ.get('SATCV_FUSE_RESIDUAL', '1') == '1'      # inference: residual joins written by the block's last convolution
-# round 6 experiment, OFF by default: Adam + operand repack of the parameters whose gradients are final early in the backward pass (99.5 % of them
-# once the fourth encoder block is done) on the weight-gradient stream beside the rest of it.  Measured 7.87-7.89 ms against 7.82-7.87 without
-# (profiles/r06_ab_early_opt_and_reduce_stream.txt): the trace of a step shows why -- the weight-gradient stream is busy to the last
-# microsecond of the backward pass, so work moved onto it only lengthens it.  SATCV_EARLY_OPT=1 turns it on (tests run both).
-EARLY_OPT = os.environ.get('SATCV_EARLY_OPT', '0') == '1'
+# no effect on any output.  Here the gradient is the exact 0 (the bias stays at its value) unless the summed-noise form is asked for;
+# the atomics it needs are also the one remaining source of run-to-run differences in a training step.
+BIAS_NOISE = switches.read('bn_bias_noise')
+# default: a layer's weight gradient (second stream) is enqueued BEFORE its data gradient -- it starts beside its own layer's data gradient and
+# the side stream finishes earlier; WGRAD_LATE enqueues it behind the data gradient
+WGRAD_LATE = switches.read('wgrad_late')
+CTBF = switches.read('ctbf')
+CTBF_COUTS = switches.read('ctbf_couts')
+FUSE_RESIDUAL = switches.read('fuse_residual')
+# EARLY_OPT (tests run both): the parameters whose gradients are final early in the backward pass are 99.5 % of them once the fourth encoder
+# block is done; the weight-gradient stream is busy to the last microsecond of the backward pass, so work moved onto it only lengthens it
+EARLY_OPT = switches.read('early_opt')
 EARLY_OPT_FRAC = 0.05
-FUSE_DGRAD_ALL = os.environ.get('SATCV_FUSE_DGRAD_BN_BWD', '1') == '2'      # 2: every eligible data gradient carries the BN-backward sums
+FUSE_DGRAD_ALL = switches.read('fuse_dgrad_bn_bwd') == 2      # (Model.fuse_dgrad_bn_bwd is the same row != 0)
 
 
 def rup(a, b):
@@ -336,9 +326,8 @@ class Plan:
         self.x_inputs = []                    # fp32 staging tensor of every model input
         self.x_by_tid = {}
         self.x_src = {}                       # tensor id -> device pointer of a caller's batch read in place (Model._stage_x), else the staging tensor
-        # (SATCV_SIDE_PRIORITY: HIP stream priority of the weight-gradient stream -- positive = lower than the main stream; measured)
-        _sp = os.environ.get('SATCV_SIDE_PRIORITY')
-        self.side = (torch.cuda.Stream(priority=int(_sp)) if _sp is not None else torch.cuda.Stream()) if (training and rt.model.wgrad_side_stream) else None
+        _sp = switches.read('side_priority')
+        self.side = (torch.cuda.Stream(priority=_sp) if _sp is not None else torch.cuda.Stream()) if (training and rt.model.wgrad_side_stream) else None
         self.step_count = 0
         self.outputs = {}
         self.sync_bn = bool(training and getattr(rt.model, 'sync_bn', False) and parallel.active())
@@ -803,20 +792,13 @@ class Plan:
         shared_layers = {k for k, v in _cnt.items() if v > 1}      # layers applied to several inputs (Siamese encoders)
         ws_need = 0
         wdescs = []
-        # deferred, batched slab sums (satcv_reduce_slabs_batched; SATCV_DEFER_REDUCE=0: one sum launch behind every weight-gradient launch):
+        # DEFER: deferred, batched slab sums (satcv_reduce_slabs_batched; otherwise one sum launch behind every weight-gradient launch):
         # a deferring launch keeps a workspace of its own; the sums run in groups, one launch per ~16 MiB of finished gradients (the bucket size
         # of the gradient exchange, whose checkpoints move to the group boundaries)
-        # MEASURED (profiles/r05_ab_defer_reduce.txt, A/B/A/B on one box): 8.59 ms per step with one sum launch per layer, 8.625 with 4 batched
-        # launches -- the per-layer sum reads slabs that were written microseconds earlier (37 MB: L2 / Infinity-Cache resident), the deferred one
-        # finds 150-220 MB of slabs of several layers pushed out to HBM.  Opt-in (SATCV_DEFER_REDUCE=1).
-        DEFER = int(os.environ.get('SATCV_DEFER_REDUCE', '0')) != 0
-        # round 6: the slab sum of a side-stream weight gradient on a THIRD stream, behind an event of its launch.  The trace of a step
-        # (profiles/r06_step_timeline_before.txt) shows the weight-gradient stream running to the very end of the step, and a quarter of its
-        # time in the 21 slab sums (0.8 ms in the step for 0.17 ms of work: small HBM-bound launches between 128-workgroup MFMA launches).
-        # With a workspace of its own per layer the next weight gradient does not have to wait for the sum of the previous one.
-        # MEASURED, same box: 7.80-7.85 ms against 7.78-7.81 with the sums on the weight-gradient stream -- the step is bound by the chip's total work,
-        # not by the order of these launches (profiles/r06_ab_early_opt_and_reduce_stream.txt).  Off by default (SATCV_REDUCE_STREAM=1).
-        RED3 = (not DEFER) and self.side is not None and os.environ.get('SATCV_REDUCE_STREAM', '0') == '1'
+        DEFER = switches.read('defer_reduce') != 0
+        # RED3: the slab sum of a side-stream weight gradient on a THIRD stream, behind an event of its launch; with a workspace of its own per
+        # layer the next weight gradient does not have to wait for the sum of the previous one
+        RED3 = (not DEFER) and self.side is not None and switches.read('reduce_stream')
         self.rstream = torch.cuda.Stream() if RED3 else None
         self._last_red_ev = None
         rpending = []                       # (descriptor, 'w' | 'f', gradient bytes) of launches whose sum has not been scheduled yet
@@ -1381,7 +1363,7 @@ class Plan:
                 pk = rt.packed[lay.name]
                 # (the weight gradient of a layer fed by a model input is the last launch of the backward pass: nothing runs beside it)
                 wstep = wgrad_step(r, dy.data_ptr(), cout, lay, pk['cin'], cout, hh, ww, cx['k'], cx['dil'], accum=accum,
-                                   last=tin.node.op == 'input' and len(m.inputs) == 1 and os.environ.get('SATCV_WGRAD_LAST_FULL', '1') != '0')
+                                   last=tin.node.op == 'input' and len(m.inputs) == 1 and switches.read('wgrad_last_full'))
                 if not WGRAD_LATE:
                     self.bwd.append(wstep)
                 if tin.node.op != 'input':

@@ -19,19 +19,14 @@ import ctypes as C
 
 import torch
 
-from . import ops
-import os
-
+from . import ops, switches
 from ._lib import lib, check, FP8, FP8X, BF16
 
-# layers whose input channels are a multiple of 64 run on the block-scaled K=64 MFMA (2x the bf16 rate)
-USE_SCALED_MFMA = os.environ.get('SATCV_FP8_SCALED', '1') != '0'
-FUSE_POOL = os.environ.get('SATCV_FUSE_POOL', '1') != '0'
-HYBRID = os.environ.get('SATCV_FP8_HYBRID', '1') != '0'       # fp8 plans keep the full- and half-resolution levels in bf16 (Fp8Plan)
-THIN_FP8 = os.environ.get('SATCV_FP8_THIN', '1') != '0'       # fp8 levels: thin 3x3 convs on the persistent thin-layer kernel, two-source concatenations
-# Siamese graphs: the two dates of a shared encoder / ASPP layer as ONE launch of 2n images whose epilogue remaps the store into the channel
-# concatenation (satcv_conv_desc pair_n); SATCV_SIAMESE_PAIR=0: one launch per date (Fp8Plan(pair=False))
-SIAMESE_PAIR = os.environ.get('SATCV_SIAMESE_PAIR', '1') != '0'
+USE_SCALED_MFMA = switches.read('fp8_scaled')      # (2x the bf16 rate)
+FUSE_POOL = switches.read('fuse_pool')
+HYBRID = switches.read('fp8_hybrid')               # (Fp8Plan)
+THIN_FP8 = switches.read('fp8_thin')
+SIAMESE_PAIR = switches.read('siamese_pair')       # the epilogue remaps the store into the channel concatenation (satcv_conv_desc pair_n); off: Fp8Plan(pair=False)
 
 E4M3_MAX = 448.0
 BN_EPS = 1e-3

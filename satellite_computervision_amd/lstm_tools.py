@@ -21,11 +21,11 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, switches
 from . import model_tools as mt
 from ._lib import lib, check, F32, BF16, LstmGatesDesc, DenseDesc
 
-RECURRENT_ACTIVATION = os.environ.get('SATCV_LSTM_RECURRENT_ACTIVATION', 'hard_sigmoid')
+RECURRENT_ACTIVATION = switches.read('lstm_recurrent_activation')
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
 
 
@@ -642,7 +642,7 @@ class _SeqModelBase:
 
     def _graphed_step(self, step_fn, tensors):
         """step_fn(*device tensors) -> loss tensor (no host synchronisation inside); returns the loss tensor of this step"""
-        if os.environ.get('SATCV_LSTM_GRAPH', '1') == '0' or getattr(self, '_no_graph', False):
+        if not switches.read('lstm_graph') or getattr(self, '_no_graph', False):
             self.P.state[0:1].fill_(self.optimizer._lr)
             return step_fn(*tensors)
         graphs = self.__dict__.setdefault('_graphs', {})

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import engine as E
-from . import ops
+from . import ops, switches
 from ._lib import lib, check, F32, BF16
 
 # ------------------------------------------------------------------------- globals
@@ -439,7 +439,7 @@ def get_deeplabv3_model(nclasses, nchannels=4, aspp_filters=256, blocks=(3, 4, 6
     probs = n_up.out(nclasses, Fraction(1), 'probs')
     classes = _classes(probs, f'{head_name}classes')
     model = Model(inputs=inputs, outputs=[probs, classes])
-    model._infer_splitk = os.environ.get('SATCV_DEEPLAB_SPLITK', '1') == '1'
+    model._infer_splitk = switches.read('deeplab_splitk')
     model._builder = dict(fn='get_deeplabv3_model', nclasses=nclasses, nchannels=nchannels, aspp_filters=aspp_filters, blocks=list(blocks),
                           widths=list(widths), head_name=head_name)
     return model
@@ -993,7 +993,7 @@ def _prefetch_to_device(batches, dev):
         xs = b[0] if isinstance(b[0], (list, tuple)) else [b[0]]
         return all(isinstance(a, np.ndarray) for a in xs) and isinstance(b[1], np.ndarray)
 
-    if os.environ.get('SATCV_PREFETCH', '1') == '0' or not torch.cuda.is_available() or not is_host_pair(first):
+    if not switches.read('prefetch') or not torch.cuda.is_available() or not is_host_pair(first):
         yield first
         yield from it
         return
@@ -1060,14 +1060,14 @@ class Model:
                     self.param_specs += l.specs
         self.compute_dtype = dtype or _DEFAULT_DTYPE
         self.bn_bessel = True       # tf.keras (TF 2.x) BatchNormalization on NHWC input runs the fused kernel, whose running variance is the Bessel-corrected batch variance; False = Keras 3 / unfused behaviour
-        self.fuse_head_bn_bwd = os.environ.get('SATCV_FUSE_HEAD_BN_BWD', '1') != '0'   # head backward also does the reduce pass of the last BN
-        self.fuse_dgrad_bn_bwd = os.environ.get('SATCV_FUSE_DGRAD_BN_BWD', '1') != '0'  # data-gradient epilogues do the reduce pass of the BN below them
-        self.wgrad_side_stream = os.environ.get('SATCV_WGRAD_STREAM', '1') != '0'      # weight gradients on a second HIP stream
-        self.fuse_pool_bn_sums = os.environ.get('SATCV_FUSE_POOL_BN_SUMS', '1') != '0'  # encoder BN-backward sums formed by the producers of its gradients
-        self.fuse_head_grad = os.environ.get('SATCV_FUSE_HEAD_GRAD', '1') != '0'      # the block under the head forms the head's data gradient in its loader
-        self.fuse_pool_bwd = os.environ.get('SATCV_FUSE_POOL_BWD', '1') != '0'         # encoder blocks: pooled BN apply + weight (+ data) gradient in one launch
-        self.fuse_thin_bwd = os.environ.get('SATCV_FUSE_THIN_BWD', '1') != '0'         # thin layers: BN-backward apply + data + weight gradient in one launch
-        self.sync_bn = os.environ.get('SATCV_SYNC_BN', '0') == '1'      # data parallel: BatchNorm statistics over ALL replicas (parallel.py)
+        self.fuse_head_bn_bwd = switches.read('fuse_head_bn_bwd')      # (the switches of the backward pass: switches.py)
+        self.fuse_dgrad_bn_bwd = switches.read('fuse_dgrad_bn_bwd') != 0      # (engine.FUSE_DGRAD_ALL is the same row == 2)
+        self.wgrad_side_stream = switches.read('wgrad_stream')
+        self.fuse_pool_bn_sums = switches.read('fuse_pool_bn_sums')
+        self.fuse_head_grad = switches.read('fuse_head_grad')
+        self.fuse_pool_bwd = switches.read('fuse_pool_bwd')
+        self.fuse_thin_bwd = switches.read('fuse_thin_bwd')
+        self.sync_bn = switches.read('sync_bn')
         self._rt = None
         self.optimizer, self._loss, self._metrics = None, None, []
         self.metrics_names = []
@@ -1310,7 +1310,7 @@ class Model:
                 plan = self._fp8_plans[key] = fp8_infer.Fp8Plan(self, n, h, w, self._fp8_q, store=self._fp8_store)
                 plan.weights_version = ver
             return plan
-        if (self.compute_dtype == 'bfloat16' and getattr(self, '_folded_ok', True) and os.environ.get('SATCV_FOLDED_INFER', '1') != '0'
+        if (self.compute_dtype == 'bfloat16' and getattr(self, '_folded_ok', True) and switches.read('folded_infer')
                 and not fp8_infer.siamese_graph(self)):
             plans = self.__dict__.setdefault('_folded_plans', {})
             if key not in plans or plans[key].weights_version != ver:       # BN / bias / weight images are baked in at build time
@@ -1386,11 +1386,11 @@ class Model:
     # captured once per (plan, input address) after a warm-up run and replayed with ONE call; the U-Net plans (~50 launches, GPU-bound
     # even at batch 1) stay eager.  SATCV_INFER_GRAPH=0 turns it off, =2 forces it for every inference plan.
     def _replay_graph(self, plan):
-        mode = int(os.environ.get('SATCV_INFER_GRAPH', '1'))
+        mode = switches.read('infer_graph')
         fwd = getattr(plan, 'fwd', None)
         if mode == 0 or fwd is None or getattr(plan, 'training', False) or getattr(plan, 'dropouts', None):
             return False
-        if mode < 2 and len(fwd) < int(os.environ.get('SATCV_INFER_GRAPH_MIN', '64')):
+        if mode < 2 and len(fwd) < switches.read('infer_graph_min'):
             return False
         cache = plan.__dict__.setdefault('_graphs', {})
         key = tuple(sorted((getattr(plan, 'x_src', None) or {}).items()))      # (a resident batch is read in place: its address is part of the graph)

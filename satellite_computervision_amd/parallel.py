@@ -18,6 +18,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import switches
+
 
 def init_from_env(backend=None):
     """Initialise the default process group from RANK/WORLD_SIZE/MASTER_* (torchrun)."""
@@ -36,7 +38,7 @@ def init_from_env(backend=None):
 # test switch: run every collective at world size 1 as well (RCCL accepts a one-rank communicator), so that the nccl code
 # path -- communicator init, ReduceOp.AVG, the async bucketed all-reduce on the side stream, the stream waits -- can execute on
 # a single-GPU box (tests/test_dp_gpu.py::test_rccl_single_rank_path)
-FORCE = os.environ.get('SATCV_FORCE_COLLECTIVES', '0') == '1'
+FORCE = switches.read('force_collectives')
 
 
 # ---- the C-ABI communicator (include/satcv.h: satcv_comm_*): with the RCCL backend the gradient exchange and the SyncBN means CAN go
@@ -44,7 +46,7 @@ FORCE = os.environ.get('SATCV_FORCE_COLLECTIVES', '0') == '1'
 # communicator bootstrapped over the default process group.  torch.distributed stays the rendezvous (and the whole path for gloo,
 # i.e. the CPU tests).  OPT-IN (SATCV_CABI_COMM=1) until a world >= 2 run on real hardware has been recorded: the path has only ever
 # executed on a one-rank communicator (tests/test_dp_gpu.py), the default exchange is torch.distributed's ProcessGroupNCCL.
-CABI_COMM = os.environ.get('SATCV_CABI_COMM', '0') == '1'
+CABI_COMM = switches.read('cabi_comm')
 _comm = {'handle': None, 'tried': False, 'calls': 0}
 
 
@@ -145,7 +147,7 @@ class GradSync:
         self.per = per
         # wire format of the gradient: fp32 (74.1 MB for get_unet_model(2, 4)) or bf16 (37 MB: rounded, summed in bf16, widened
         # back; C-ABI communicator only).  SATCV_GRAD_PAYLOAD=bf16 selects it for every GradSync of the process.
-        self.payload = payload or os.environ.get('SATCV_GRAD_PAYLOAD', 'fp32')
+        self.payload = payload or switches.read('grad_payload')
         self._warned_payload = False
         self._scratch = None
         self._side_ev = None
@@ -267,7 +269,7 @@ def make_grad_sync(model, bucket_bytes=16 << 20, overlap=None):
     model._weights_version = getattr(model, '_weights_version', 0) + 1
     rt.adam_state[2:3].fill_(1.0 / world)
     if overlap is None:
-        overlap = os.environ.get('SATCV_OVERLAP_ALLREDUCE', '1') != '0'
+        overlap = switches.read('overlap_allreduce')
     sync = GradSync(rt.gflat.numel(), bucket_bytes, overlap=overlap)
     model._sync_grads = sync
     return sync
