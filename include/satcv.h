@@ -573,6 +573,28 @@ typedef struct {
   int32_t accumulate;
 } satcv_scene_scatter_desc;
 int satcv_scene_scatter(const satcv_scene_scatter_desc* d, void* stream);
+/* satcv_series_gather: the gather of the ConvLSTM2D time-series models.  One launch cuts chips [first, first + n) out of a resident
+ * time stack and writes them as the time-major input tensor those models read (satcv_ingest_seq's output layout).  It replaces, for
+ * a chip batch, the host steps of LSTMDataGenerator.__getitem__ (utils/processing.py:937-972): the window slicing of the
+ * (T, C, H, W) arrays, np.moveaxis(batch, 2, 4), normalize_timeseries (utils/processing.py:185-193: arr / maxval, NaN -> 0), the
+ * cast to float32, and the ingest into the storage type.
+ *   src:     (t, c, h, w_) planar, contiguous, of kind 1 u16, 2 f32 or 3 i16 (the kinds of satcv_tile_desc); the launch reads the
+ *            first `steps` acquisitions, 1 <= steps <= t
+ *   value = (float)((double)src / maxval), NaN becoming 0; maxval != 0 (satcv_scene_gather's double-then-round convention)
+ *   origins, total, first, n, off, side: as for satcv_scene_gather, including the reflect-then-clamp rule for coordinates outside
+ *            the (h, w_) plane: the kernel never reads outside the stack, whatever the table holds
+ *   dst:     (steps, n, side, side, cpad) in the storage type `dtype` (SATCV_BF16 or SATCV_F32), 16-byte aligned; cpad % 8 == 0,
+ *            cpad >= c; channels c .. cpad - 1 are written as zero.  The conversion to bf16 is that of satcv_ingest_seq: equal
+ *            float32 values give equal bits */
+typedef struct {
+  const void* src; int32_t src_kind;
+  int32_t t, c, h, w_, steps;
+  double maxval;
+  const int32_t* origins; int32_t total, first, n;
+  int32_t off, side;
+  void* dst; int32_t dtype, cpad;
+} satcv_series_gather_desc;
+int satcv_series_gather(const satcv_series_gather_desc* d, void* stream);
 
 /* ------------------------------------------------------------------ median composite of an image time stack
  * Everything of run_local (utils/pc_tools.py:620-668; twin predict_pc_local, utils/prediction_tools.py:731-779) between "the

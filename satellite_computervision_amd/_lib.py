@@ -62,6 +62,12 @@ class SceneScatterDesc(C.Structure):
                 ('h', c_i32), ('w_', c_i32), ('ldd', c_i32), ('doff', c_i32), ('accumulate', c_i32)]
 
 
+class SeriesGatherDesc(C.Structure):
+    _fields_ = [('src', c_vp), ('src_kind', c_i32), ('t', c_i32), ('c', c_i32), ('h', c_i32), ('w_', c_i32), ('steps', c_i32),
+                ('maxval', C.c_double), ('origins', c_vp), ('total', c_i32), ('first', c_i32), ('n', c_i32), ('off', c_i32), ('side', c_i32),
+                ('dst', c_vp), ('dtype', c_i32), ('cpad', c_i32)]
+
+
 class CompositeDesc(C.Structure):
     _fields_ = [('src', c_vp), ('src_kind', c_i32), ('t', c_i32), ('c', c_i32), ('h', c_i32), ('w_', c_i32), ('offsets', c_vp),
                 ('median', c_vp), ('ld_med', c_i32), ('coff_med', c_i32), ('norm', c_vp), ('ld_norm', c_i32), ('coff_norm', c_i32),
@@ -226,6 +232,7 @@ _SIGS = {
     'satcv_tile_ingest': (C.c_int, [C.POINTER(TileDesc), c_vp]),
     'satcv_scene_gather': (C.c_int, [C.POINTER(SceneGatherDesc), c_vp]),
     'satcv_scene_scatter': (C.c_int, [C.POINTER(SceneScatterDesc), c_vp]),
+    'satcv_series_gather': (C.c_int, [C.POINTER(SeriesGatherDesc), c_vp]),
     'satcv_median_composite': (C.c_int, [C.POINTER(CompositeDesc), c_vp]),
     'satcv_record_stats': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_record_to_tuple': (C.c_int, [C.POINTER(RecordDesc), c_vp]),

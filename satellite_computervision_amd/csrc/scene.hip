@@ -4,7 +4,11 @@
 //                  then clamped, so no origin can make the kernel read outside the scene
 //   scene_scatter: the centre of every predicted chip -> its place in a resident (H, W, ldd) map, clipped to the map (replaces the
 //                  crop and `template[...] +=` of :154 and the crops of :267 / :349)
-// Lanes run along a row in both: a chip row is side * c contiguous source elements, a centre row is crop_w contiguous map pixels.
+//   series_gather: windows of a resident (t, c, h, w) time stack -> the time-major (steps, n, side, side, cpad) storage tensor the
+//                  ConvLSTM2D models read in place: the window slicing, np.moveaxis(cut, 2, 4), normalize_timeseries
+//                  (utils/processing.py:185-193, :937-972) and satcv_ingest_seq in one pass; same reflect-then-clamp rule
+// Lanes run along a row in all three: a chip row is side * c contiguous source elements (side contiguous samples of a band plane for
+// the planar stack), a centre row is crop_w contiguous map pixels.
 #include "common.hpp"
 #include <cstdlib>
 
@@ -86,6 +90,42 @@ __global__ __launch_bounds__(EW_BLOCK) void scene_gather_kernel(const satcv_scen
   }
 }
 
+// ---------------------------------------------------------------- series gather (planar time stack -> time-major storage tensor)
+// one lane per destination pixel and 8-channel group, the pixel's x fastest: the (up to) 8 loads of a lane are one sample of 8 band
+// planes each, consecutive lanes on consecutive samples of a plane row; the 8 values leave as ONE 16-byte store (bf16; two for f32).
+// The groups of a chip row follow each other in item order, so the two halves of a pixel's 32 bytes are written by neighbouring waves.
+// value = (float)((double)v / maxval), NaN -> 0: normalize_timeseries followed by the generator's astype(float32)
+template <typename S, typename T>
+__global__ __launch_bounds__(EW_BLOCK) void series_gather_kernel(const satcv_series_gather_desc d) {
+  const S* __restrict__ src = reinterpret_cast<const S*>(d.src);
+  T* __restrict__ dst = reinterpret_cast<T*>(d.dst);
+  const int side = d.side, groups = d.cpad / 8;
+  const long long plane = (long long)d.h * d.w_;
+  const long long total = (long long)d.steps * d.n * side * groups * side;
+  for (long long it = blockIdx.x * (long long)blockDim.x + threadIdx.x; it < total; it += (long long)gridDim.x * blockDim.x) {
+    const int px = (int)(it % side);
+    long long q = it / side;
+    const int g = (int)(q % groups); q /= groups;
+    const int r = (int)(q % side); q /= side;            // q = s * n + k: the destination image
+    const int k = (int)(q % d.n), s = (int)(q / d.n);
+    const int* o = d.origins + 2 * (size_t)(d.first + k);
+    const int sy = mirror((long long)o[0] - d.off + r, d.h);
+    const int sx = mirror((long long)o[1] - d.off + px, d.w_);
+    const S* p = src + ((long long)s * d.c + g * 8) * plane + (long long)sy * d.w_ + sx;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float f = 0.f;
+      if (g * 8 + e < d.c) {
+        f = (float)((double)p[e * plane] / d.maxval);
+        f = f != f ? 0.f : f;
+      }
+      v[e] = f;
+    }
+    store8<T>(dst + ((q * side + r) * side + px) * d.cpad + g * 8, v);
+  }
+}
+
 // ---------------------------------------------------------------- scatter
 // one lane per centre pixel, consecutive lanes along the row.  LDS > 0: the whole source pixel (LDS channels, one vector load -- the
 // unwanted channels share its cache line anyway) and a select; LDS == 0: the channel range with scalar loads.
@@ -137,6 +177,13 @@ void launch_gather(const satcv_scene_gather_desc& d, hipStream_t st) {
   else hipLaunchKernelGGL(scene_gather_kernel<S>, dim3(ew_grid((long long)d.n * d.side * d.side * d.c)), dim3(EW_BLOCK), 0, st, d);
 }
 
+template <typename S>
+void launch_series_gather(const satcv_series_gather_desc& d, hipStream_t st) {
+  const dim3 grid(ew_grid((long long)d.steps * d.n * d.side * d.side * (d.cpad / 8))), block(EW_BLOCK);
+  if (d.dtype == SATCV_BF16) hipLaunchKernelGGL((series_gather_kernel<S, bf16>), grid, block, 0, st, d);
+  else hipLaunchKernelGGL((series_gather_kernel<S, float>), grid, block, 0, st, d);
+}
+
 }  // namespace
 
 extern "C" int satcv_scene_gather(const satcv_scene_gather_desc* d, void* stream) {
@@ -155,6 +202,29 @@ extern "C" int satcv_scene_gather(const satcv_scene_gather_desc* d, void* stream
     default: launch_gather<int16_t>(*d, st); break;
   }
   LAUNCH_OK("scene_gather");
+  return SATCV_OK;
+}
+
+extern "C" int satcv_series_gather(const satcv_series_gather_desc* d, void* stream) {
+  SATCV_CHECK(d && d->src && d->origins && d->dst, "series_gather: null pointer");
+  SATCV_CHECK(d->t > 0 && d->c > 0 && d->h > 0 && d->w_ > 0 && d->side > 0 && d->off >= 0 && d->n > 0, "series_gather: sizes must be positive (off >= 0)");
+  SATCV_CHECK(d->src_kind >= 1 && d->src_kind <= 3, "series_gather: src_kind %d (1 u16, 2 f32, 3 i16)", d->src_kind);
+  SATCV_CHECK(d->steps > 0 && d->steps <= d->t, "series_gather: steps %d outside 1 .. t = %d", d->steps, d->t);
+  SATCV_CHECK(d->maxval == d->maxval && d->maxval != 0.0, "series_gather: maxval must be a non-zero number");
+  SATCV_CHECK(d->dtype == SATCV_BF16 || d->dtype == SATCV_F32, "series_gather: dtype %d (bf16 or f32 storage)", d->dtype);
+  SATCV_CHECK(d->cpad > 0 && d->cpad % 8 == 0 && d->cpad >= d->c, "series_gather: destination channels (cpad %% 8 == 0, cpad >= c)");
+  SATCV_CHECK((uintptr_t)d->dst % 16 == 0, "series_gather: dst must be 16-byte aligned");
+  SATCV_CHECK(d->first >= 0 && d->total > 0 && (long long)d->first + d->n <= d->total, "series_gather: chips [first, first + n) outside the origin table");
+  SATCV_CHECK(satcv_pixels_ok(1, d->h, d->w_, 1), "series_gather: acquisition beyond 2^31 pixels");
+  SATCV_CHECK(satcv_pixels_ok((long long)d->steps * d->n, d->side, d->side, 1) &&
+              (long long)d->steps * d->n * d->side * d->side * d->cpad < (1LL << 31), "series_gather: chips beyond 2^31 elements");
+  const hipStream_t st = (hipStream_t)stream;
+  switch (d->src_kind) {
+    case 1: launch_series_gather<uint16_t>(*d, st); break;
+    case 2: launch_series_gather<float>(*d, st); break;
+    default: launch_series_gather<int16_t>(*d, st); break;
+  }
+  LAUNCH_OK("series_gather");
   return SATCV_OK;
 }
 

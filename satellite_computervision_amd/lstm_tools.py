@@ -555,6 +555,12 @@ def _ingest_seq(x, cpad, dtype):
     return out, (B, T, H, W)
 
 
+def _check_ingested(xt, shape, cpad, dtype):
+    B, T, H, W = shape
+    if tuple(xt.shape) != (T * B, H, W, cpad) or xt.dtype != ops.TORCH_DTYPE[dtype] or not xt.is_contiguous():
+        raise ValueError(f'expected a contiguous time-major {ops.TORCH_DTYPE[dtype]} tensor {(T * B, H, W, cpad)}, got {xt.dtype} {tuple(xt.shape)}')
+
+
 def _dev_f32(a):
     t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
     return t.to(_dev(), torch.float32).contiguous()
@@ -573,6 +579,18 @@ class _SeqModelBase:
     @property
     def dtype_code(self):
         return BF16 if self.compute_dtype == 'bfloat16' else F32
+
+    def _ingested_input(self, xt, shape):
+        """the sequence input of predict_on_device -> (time-major storage tensor (T * B, H, W, cpad), (B, T, H, W)): with `shape` xt is
+        that tensor already (checked, read in place), without it a (B, T, H, W, C) float32 CUDA tensor that is ingested here"""
+        cpad = ops.rup(self.n_channels, 16)
+        if shape is None:
+            if not (isinstance(xt, torch.Tensor) and xt.is_cuda and xt.dtype == torch.float32 and xt.dim() == 5):
+                raise ValueError('predict_on_device without shape takes a (B, T, H, W, C) float32 CUDA tensor')
+            xt, shape = _ingest_seq(xt, cpad, self.dtype_code)
+        shape = tuple(int(v) for v in shape)
+        _check_ingested(xt, shape, cpad, self.dtype_code)
+        return xt, shape
 
     # ---- Keras surface of the reference's call sites (compile / fit / evaluate as in notebooks/UNET_G4G_2019_solar.ipynb:1206-1275 and
     # utils/model_tools.py:1162-1176).  Arguments this implementation does not act on are REFUSED, never swallowed.
@@ -867,17 +885,36 @@ class LSTMModel(_SeqModelBase):
         self._finish()
 
     def _forward(self, x, training):
-        xt, (B, T, H, W) = _ingest_seq(x, ops.rup(self.n_channels, 16), self.dtype_code)
+        return self._forward_ingested(*_ingest_seq(x, ops.rup(self.n_channels, 16), self.dtype_code), training)
+
+    def _forward_ingested(self, xt, shape, training, want_classes=False):
+        """xt: the time-major storage tensor (T * B, H, W, cpad) of satcv_ingest_seq / satcv_series_gather, shape = (B, T, H, W)"""
+        B, T, H, W = shape
         if T != self.n_time:
             raise ValueError(f'model was built for {self.n_time} time steps, got {T}')
         feats = self.layers_.forward(Act(xt, self.n_channels), T, B, training, self.dtype_code)
-        return self.dense.forward([(feats, False)])
+        return self.dense.forward([(feats, False)], want_classes=want_classes)
 
     def predict(self, x, batch_size=None, verbose=0, **kw):
         n = x.shape[0]
         bs = batch_size or 32
         outs = [self._forward(x[i:i + bs], False).cpu().numpy() for i in range(0, n, bs)]
         return np.concatenate(outs, 0)
+
+    @property
+    def class_output(self):
+        """the head writes a class tensor next to its output (softmax heads: the argmax of satcv_dense_small_fwd)"""
+        return self.dense.activation == Dense1x1.ACT['softmax']
+
+    def predict_on_device(self, xt, shape=None, want_classes=False):
+        """Inference that stays on the device: -> (B, H, W, n_classes) float32 CUDA tensor, with want_classes also the (B, H, W) int32
+        class tensor of a softmax head (ValueError for another head).  shape=(B, T, H, W): xt is an already ingested time-major storage
+        tensor (T * B, H, W, cpad) -- cpad the channels padded to 16, in the model's storage type -- read in place; without shape, xt is
+        a (B, T, H, W, C) float32 CUDA tensor.  The whole batch is one forward; no host synchronisation, no copy."""
+        if want_classes and not self.class_output:
+            raise ValueError("want_classes needs a model with activation='softmax'")
+        xt, shape = self._ingested_input(xt, shape)
+        return self._forward_ingested(xt, shape, False, want_classes=want_classes)
 
     def _eval_outputs(self, xb):
         return [(self._forward(xb, False), 'linear', lambda t: t)]
@@ -1029,17 +1066,36 @@ class LSTMAutoencoder(_SeqModelBase):
 
     def _forward(self, xs, training):
         x, sincos = xs
-        xt, (B, T, H, W) = _ingest_seq(x, ops.rup(self.n_channels, 16), self.dtype_code)
+        xt, self._shape = _ingest_seq(x, ops.rup(self.n_channels, 16), self.dtype_code)
+        return self._forward_ingested(xt, self._shape, sincos, training)
+
+    def _forward_ingested(self, xt, shape, sincos, training, temporal=True):
+        """xt: the time-major storage tensor (T * B, H, W, cpad), shape = (B, T, H, W).  temporal=False leaves the decoder branch out
+        (its output is then None): `single` does not read it."""
+        B, T, H, W = shape
         if T != self.n_time:
             raise ValueError(f'model was built for {self.n_time} time steps, got {T}')
         enc = self.enc.forward(Act(xt, self.n_channels), T, B, training, self.dtype_code)
-        dseq, _, _ = self.dec.forward(enc, T, B, training, self.dtype_code, want_stats=False, repeat=True)
-        tout = self.temporal.forward([(dseq, False)])                         # (T * B, H, W, k), time-major
+        tout = None
+        if temporal:
+            dseq, _, _ = self.dec.forward(enc, T, B, training, self.dtype_code, want_stats=False, repeat=True)
+            tout = self.temporal.forward([(dseq, False)])                     # (T * B, H, W, k), time-major
         sc = sincos if isinstance(sincos, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sincos, dtype=np.float32))
         sc = sc.to(_dev(), torch.float32).contiguous()
         sout = self.single.forward([(enc, False), (Act(sc, 2), False)])
-        self._shape = (B, T, H, W)
         return tout, sout
+
+    def predict_on_device(self, xs, shape=None):
+        """The `single` output (the next image) on the device: -> (B, H, W, n_classes) float32 CUDA tensor.  xs = [xt, sincos]; xt as for
+        LSTMModel.predict_on_device (with shape=(B, T, H, W) an ingested time-major storage tensor, else (B, T, H, W, C) float32 on the
+        device), sincos (B, H, W, 2) float32.  The `temporal` output is not computed.  No host synchronisation, no copy."""
+        xt, sincos = xs
+        if not (isinstance(sincos, torch.Tensor) and sincos.is_cuda and sincos.dtype == torch.float32):
+            raise ValueError('predict_on_device takes sincos as a (B, H, W, 2) float32 CUDA tensor')
+        xt, shape = self._ingested_input(xt, shape)
+        if tuple(sincos.shape) != (shape[0], shape[2], shape[3], 2) or not sincos.is_contiguous():
+            raise ValueError(f'sincos must be a contiguous {(shape[0], shape[2], shape[3], 2)} tensor, got {tuple(sincos.shape)}')
+        return self._forward_ingested(xt, shape, sincos, False, temporal=False)[1]
 
     def predict(self, x, batch_size=None, verbose=0, **kw):
         tout, sout = self._forward(x, False)

@@ -315,6 +315,134 @@ def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover=
     return (probs, cls[..., 0].cpu().numpy()) if classes else probs
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Scene prediction for the ConvLSTM2D time-series models (lstm_tools.LSTMModel / LSTMAutoencoder): the (T, C, H, W) stack goes to the
+# device once, satcv_series_gather cuts, normalises and ingests a chip batch in one launch, the model reads the result in place
+# (predict_on_device(..., shape=...)) and satcv_scene_scatter stitches the centres.  DESIGN.md, "Scene prediction for the time-series
+# models".
+_SERIES_KIND = {np.dtype(np.uint16): 1, np.dtype(np.float32): 2, np.dtype(np.int16): 3}     # kinds of satcv_tile_desc the gather reads
+
+
+def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=0, cover='reference', classes=False, maxval=10000,
+                         harmonics=None):
+    """Prediction map of a (T, C, H, W) time stack -- the layout of the LSTMDataGenerator files and of `pc_tools.median_composite`'s
+    input -- by a ConvLSTM2D time-series model (get_lstm_model, get_lstm_autoencoder), stitched on the device; returns new arrays.
+
+    stack: a host array (uint16 / int16 / float32; anything else is cast to float32) or a contiguous int16 / float32 CUDA tensor, read in
+    place.  The first m.n_time acquisitions are used (of a host stack only those are uploaded); every sample becomes float32(float64(v) / maxval) with NaN -> 0
+    (normalize_timeseries, what LSTMDataGenerator feeds the model).  ValueError unless the stack is 4-D with T >= m.n_time and
+    C == m.n_channels.
+    kernel, buff, batch_size, channel, cover, classes: as for `predict_scene` -- cover='reference' predicts the chips of
+    `generate_chip_indices` on the (H, W) plane (the border stays 0, 255 in the class map), cover='full' the full-cover grid with
+    reflected windows (needs H, W >= kernel + buff); channel int -> (H, W) float32, None -> (H, W, n_classes); classes=True returns
+    (map, class map (H, W) uint8) and needs a model with a softmax head (ValueError for another head or an autoencoder).
+    harmonics=(sin, cos): the scene-wide harmonic pair of an LSTMAutoencoder (processing.sin_cos of the series' start), whose `single`
+    output -- the next image -- is the map; required for the autoencoder, refused for any other model.
+    The returned arrays are the only device-to-host traffic; hybrid and hierarchical models (two inputs at two resolutions) are not
+    covered."""
+    from .lstm_tools import LSTMAutoencoder
+    _check_geometry(kernel, buff, batch_size)
+    if getattr(stack, 'ndim', None) != 4:
+        raise ValueError(f'expected a (T, C, H, W) time stack, got shape {tuple(getattr(stack, "shape", ()))}')
+    T, C_, H, W = (int(v) for v in stack.shape)
+    if T < m.n_time:
+        raise ValueError(f'the model reads {m.n_time} acquisitions, the stack holds {T}')
+    if C_ != m.n_channels:
+        raise ValueError(f'the model reads {m.n_channels} bands, the stack holds {C_}')
+    if not float(maxval) or float(maxval) != float(maxval):
+        raise ValueError(f'maxval must be a non-zero number, got {maxval}')
+    if cover == 'reference':
+        idx = generate_chip_indices(np.empty((H, W, 0)), buff, kernel)
+    elif cover == 'full':
+        if H < kernel + buff or W < kernel + buff:
+            raise ValueError(f"cover='full' needs a scene of at least kernel + buff = {kernel + buff} pixels a side, got {H} x {W}")
+        idx = full_cover_indices((H, W), kernel)
+    else:
+        raise ValueError(f"cover must be 'reference' or 'full', got {cover!r}")
+    is_ae = isinstance(m, LSTMAutoencoder)
+    if is_ae and harmonics is None:
+        raise ValueError('an LSTMAutoencoder needs harmonics=(sin, cos), its second input')
+    if harmonics is not None:
+        if not is_ae:
+            raise ValueError('harmonics is the second input of an LSTMAutoencoder; this model has none')
+        if len(harmonics) != 2:
+            raise ValueError(f'harmonics must be the pair (sin, cos), got {len(harmonics)} values')
+        harmonics = (float(harmonics[0]), float(harmonics[1]))
+    if classes and (is_ae or not getattr(m, 'class_output', True)):
+        raise ValueError("classes=True needs a model with a class output: an LSTMModel with activation='softmax'")
+    ncls = m.n_classes if idx else None
+    if idx and channel is not None and not -ncls <= int(channel) < ncls:
+        raise IndexError(f'channel {channel} of a {ncls}-class output')
+    if not idx:                              # (a scene too small for one reference chip: nothing is predicted)
+        probs = np.zeros((H, W) if channel is not None else (H, W, m.n_classes), np.float32)
+        return (probs, np.full((H, W), 255, np.uint8)) if classes else probs
+    out, cls = _stitch_series(stack, idx, m, kernel, buff, batch_size, None if channel is None else int(channel), classes, float(maxval), harmonics)
+    probs = (out if channel is None else out[..., 0]).cpu().numpy()
+    return (probs, cls[..., 0].cpu().numpy()) if classes else probs
+
+
+def _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, want_classes, maxval, harmonics):
+    """the batch loop of predict_series_scene: -> (device map (H, W, nc) float32, device class map (H, W, 1) uint8 or None)"""
+    import ctypes as C
+    import torch
+    from . import ops
+    from ._lib import SeriesGatherDesc, check, lib
+    T, C_, H, W = stack.shape
+    steps = m.n_time
+    off = buff // 2
+    side = kernel + 2 * off
+    if isinstance(stack, torch.Tensor):      # a stack that is already resident: read where it lies
+        if not (stack.is_cuda and stack.dtype in (torch.int16, torch.float32) and stack.is_contiguous()):
+            raise ValueError(f'a tensor stack must be a contiguous int16 / float32 CUDA tensor (T, C, H, W), got {stack.dtype} on {stack.device}')
+        dev, kind = stack, _SERIES_KIND[np.dtype(np.int16 if stack.dtype == torch.int16 else np.float32)]
+    else:
+        st_ = np.asarray(stack)[:steps]      # (only the acquisitions the model reads are cast and uploaded: a contiguous prefix)
+        T = steps
+        if st_.dtype not in _SERIES_KIND:
+            st_ = st_.astype(np.float32)
+        kind = _SERIES_KIND[st_.dtype]
+        dev = _to_device(st_, 'the time stack')
+    total = len(idx)
+    origins = _to_device(np.asarray(idx, np.int32).reshape(total, 2), 'the origin table')
+    runs = [[(s + a, s + b) for a, b in _disjoint_runs(idx[s:s + batch_size], kernel, kernel)] for s in range(0, total, batch_size)]
+    nb = min(batch_size, total)
+    cpad, dtype = ops.rup(C_, 16), m.dtype_code
+    buf = _device_empty((steps * nb * side * side * cpad,), ops.TORCH_DTYPE[dtype], 'the chip batch')
+    sincos = None
+    if harmonics is not None:
+        sincos = _device_empty((nb, side, side, 2), torch.float32, 'the harmonics')
+        sincos[..., 0] = harmonics[0]
+        sincos[..., 1] = harmonics[1]
+    ncls = m.n_classes
+    c0, nc = (0, ncls) if channel is None else (channel % ncls, 1)
+    out = _device_empty((H, W, nc), torch.float32, 'the prediction map', 0.0)
+    cls = _device_empty((H, W, 1), torch.uint8, 'the class map', 255) if want_classes else None
+    st = ops.stream_ptr()
+    # No host synchronisation inside this loop.  Every launch -- gather, the model's kernels, scatter -- goes to the current stream, so
+    # stream order alone keeps the gather of batch i + 1 from overwriting `buf` (and the model from overwriting its output tensors) while
+    # batch i still reads them.
+    for b, s in enumerate(range(0, total, batch_size)):
+        n = min(batch_size, total - s)
+        xt = buf[:steps * n * side * side * cpad].view(steps * n, side, side, cpad)      # (steps, n, ...) is contiguous for every n
+        d = SeriesGatherDesc(src=dev.data_ptr(), src_kind=kind, t=T, c=C_, h=H, w_=W, steps=steps, maxval=maxval, origins=origins.data_ptr(),
+                             total=total, first=s, n=n, off=off, side=side, dst=xt.data_ptr(), dtype=dtype, cpad=cpad)
+        check(lib.satcv_series_gather(C.byref(d), st))
+        try:
+            if sincos is not None:
+                res = (m.predict_on_device([xt, sincos[:n]], shape=(n, steps, side, side)),)
+            elif want_classes:
+                res = m.predict_on_device(xt, shape=(n, steps, side, side), want_classes=True)
+            else:
+                res = (m.predict_on_device(xt, shape=(n, steps, side, side)),)
+        except torch.cuda.OutOfMemoryError as e:
+            raise MemoryError(f'a batch of {n} chips of {steps} x {side} x {side} does not fit in device memory; lower batch_size') from e
+        for a, e in runs[b]:
+            _scatter(res[0], a - s, e - a, (off, off, kernel, kernel), origins, total, a, out, 0, c0, nc, True)
+            if cls is not None:
+                _scatter(res[1], a - s, e - a, (off, off, kernel, kernel), origins, total, a, cls, 0, 0, 1, False)
+    return out, cls
+
+
 def callback_predictions(imageDataset, model, mixer, kernel_shape=[256, 256], kernel_buffer=[128, 128]):
     """utils/prediction_tools.py:245-291 without its prints: predict mixer['totalPatches'] patches, keep the probability of class 1 and
     assemble the cropped patches into a mosaic of mixer['patchesPerRow'] patches per row; returns the (rows, columns) float32 mosaic.
