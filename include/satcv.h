@@ -762,6 +762,35 @@ typedef struct satcv_lstm_gates_desc {
 int satcv_convlstm_gates_fwd(const satcv_lstm_gates_desc* d, void* stream);
 int satcv_convlstm_gates_bwd(const satcv_lstm_gates_desc* d, void* stream);
 
+/* satcv_convlstm_step_fwd: one ConvLSTM2D INFERENCE step in one launch (utils/model_tools.py:685-720) -- the recurrent 3x3 'same'
+ * convolution of h_{t-1} (never dilated: Keras dilates the input kernel only) with the gate arithmetic above as its epilogue:
+ *     z = conv3x3(h_prev, w) + xg      (fp32 accumulators, never stored; xg = the input convolution's output, bias inside)
+ *     i, f, g, o = ra(z_i), ra(z_f), act(z_c), ra(z_o);   c_t = f c_prev + i g (float32);   h_t = o act(c_t) (storage type)
+ * with rec_act / act exactly as in satcv_lstm_gates_desc.  No BatchNorm statistics and no gate stash are produced.
+ *
+ * Gate-interleaved channel order.  xg (its 4 F channels) and the OUTPUT channels of w are in the order
+ *     position  blk * 4 G + gate * G + j   holds natural channel  gate * F + blk * G + j,     G = min(F, 32), blk < F / G, j < G, gate = i, f, c, o
+ * (lstm_infer.gate_order(F)): permute the recurrent kernel, the input kernel and the bias with it on the host, then pack as usual --
+ * w is the forward image of satcv_pack_weights for the permuted (3, 3, F, 4 F) kernel with cin_pad = F.  h_prev, c_prev, c_out and
+ * h_out are in NATURAL channel order.
+ *
+ * h_prev (n, h, w_, ldh_prev) storage type, NULL at t = 0 (no K loop: z = xg; w is then not read); c_prev (npix, F) float32 or NULL.
+ * Refused (error code, satcv_last_error naming convlstm_step_fwd, nothing written): filters other than 16, 32, 64; h_out overlapping
+ * h_prev or c_out overlapping c_prev (ping-pong the buffers); ldx < 4 F, ldh < F, ldh_prev < F or any of them not a multiple of 8. */
+typedef struct satcv_lstm_step_desc {
+  const void* h_prev; int32_t ldh_prev;
+  const void* w;
+  const void* xg; int32_t ldx;
+  const float* c_prev;
+  float* c_out;
+  void* h_out; int32_t ldh;
+  int32_t n, h, w_, filters;
+  int32_t rec_act, act, dtype;
+} satcv_lstm_step_desc;
+int satcv_convlstm_step_fwd(const satcv_lstm_step_desc* d, void* stream);
+/* 1 when satcv_convlstm_step_fwd was built for this filter count and storage type, else 0 (host query: a plan decides per layer, once) */
+int satcv_convlstm_step_supported(int32_t filters, int32_t dtype);
+
 /* Conv2D(cout <= 16, 1x1) over the channel concatenation of one or two sources -- the `dense` layers and fusion heads of the LSTM
  * family (utils/model_tools.py:797, 847-857, 902-910, 1050-1056).  A source is an NHWC tensor (float32 or bf16) with an optional
  * pending BatchNorm + ReLU and, if hs / ws are set, on a coarser grid that is read through tf.image.resize(..., 'nearest')

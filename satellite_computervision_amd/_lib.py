@@ -168,6 +168,12 @@ class LstmGatesDesc(C.Structure):
                 ('npix', c_i64), ('filters', c_i32), ('rec_act', c_i32), ('act', c_i32), ('dtype', c_i32)]
 
 
+class LstmStepDesc(C.Structure):
+    _fields_ = [('h_prev', c_vp), ('ldh_prev', c_i32), ('w', c_vp), ('xg', c_vp), ('ldx', c_i32), ('c_prev', c_vp),
+                ('c_out', c_vp), ('h_out', c_vp), ('ldh', c_i32),
+                ('n', c_i32), ('h', c_i32), ('w_', c_i32), ('filters', c_i32), ('rec_act', c_i32), ('act', c_i32), ('dtype', c_i32)]
+
+
 class DenseSrc(C.Structure):
     _fields_ = [('x', c_vp), ('ld', c_i32), ('cin', c_i32), ('dtype', c_i32),
                 ('in_scale', c_vp), ('in_shift', c_vp), ('in_relu', c_i32),
@@ -260,6 +266,8 @@ _SIGS = {
     'satcv_ingest_seq': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'satcv_convlstm_gates_fwd': (C.c_int, [C.POINTER(LstmGatesDesc), c_vp]),
     'satcv_convlstm_gates_bwd': (C.c_int, [C.POINTER(LstmGatesDesc), c_vp]),
+    'satcv_convlstm_step_fwd': (C.c_int, [C.POINTER(LstmStepDesc), c_vp]),
+    'satcv_convlstm_step_supported': (C.c_int, [c_i32, c_i32]),
     'satcv_dense_small_fwd': (C.c_int, [C.POINTER(DenseDesc), c_vp]),
     'satcv_dense_small_bwd': (C.c_int, [C.POINTER(DenseDesc), c_vp]),
     'satcv_zero2': (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),

@@ -33,6 +33,11 @@ def _dev():
     return torch.device('cuda', torch.cuda.current_device())
 
 
+def graph_enabled():
+    """the `lstm_graph` switch (SATCV_LSTM_GRAPH, read per call): training steps and inference plans of this family replay captured graphs"""
+    return bool(switches.read('lstm_graph'))
+
+
 class _Params:
     """flat float32 parameters / gradients / Adam slots of one model (what engine.Runtime is to the U-Net graphs)"""
 
@@ -592,6 +597,12 @@ class _SeqModelBase:
         _check_ingested(xt, shape, cpad, self.dtype_code)
         return xt, shape
 
+    def inference_plan(self, shape, fused=False):
+        """lstm_infer.SeriesInferPlan(self, shape=(B, T, H, W), fused): the preallocated, graph-replayed forward of predict_on_device for
+        one input shape (LSTMModel and LSTMAutoencoder; the hybrid and hierarchical models are refused)"""
+        from .lstm_infer import SeriesInferPlan
+        return SeriesInferPlan(self, shape, fused=fused)
+
     # ---- Keras surface of the reference's call sites (compile / fit / evaluate as in notebooks/UNET_G4G_2019_solar.ipynb:1206-1275 and
     # utils/model_tools.py:1162-1176).  Arguments this implementation does not act on are REFUSED, never swallowed.
     output_names = ('output',)
@@ -660,7 +671,7 @@ class _SeqModelBase:
 
     def _graphed_step(self, step_fn, tensors):
         """step_fn(*device tensors) -> loss tensor (no host synchronisation inside); returns the loss tensor of this step"""
-        if not switches.read('lstm_graph') or getattr(self, '_no_graph', False):
+        if not graph_enabled() or getattr(self, '_no_graph', False):
             self.P.state[0:1].fill_(self.optimizer._lr)
             return step_fn(*tensors)
         graphs = self.__dict__.setdefault('_graphs', {})

@@ -324,7 +324,7 @@ _SERIES_KIND = {np.dtype(np.uint16): 1, np.dtype(np.float32): 2, np.dtype(np.int
 
 
 def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=0, cover='reference', classes=False, maxval=10000,
-                         harmonics=None):
+                         harmonics=None, plan=None):
     """Prediction map of a (T, C, H, W) time stack -- the layout of the LSTMDataGenerator files and of `pc_tools.median_composite`'s
     input -- by a ConvLSTM2D time-series model (get_lstm_model, get_lstm_autoencoder), stitched on the device; returns new arrays.
 
@@ -338,6 +338,10 @@ def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=
     (map, class map (H, W) uint8) and needs a model with a softmax head (ValueError for another head or an autoencoder).
     harmonics=(sin, cos): the scene-wide harmonic pair of an LSTMAutoencoder (processing.sin_cos of the series' start), whose `single`
     output -- the next image -- is the map; required for the autoencoder, refused for any other model.
+    plan: None runs every batch through m.predict_on_device (the eager tape).  True builds one lstm_infer.SeriesInferPlan for batch_size
+    chips (m.inference_plan), a SeriesInferPlan built for (batch_size, m.n_time, kernel + buff, kernel + buff) is used as given: the
+    batches run through its preallocated, graph-replayed forward; a short last batch fills a prefix of the plan's input, the stale rest
+    is computed and ignored.
     The returned arrays are the only device-to-host traffic; hybrid and hierarchical models (two inputs at two resolutions) are not
     covered."""
     from .lstm_tools import LSTMAutoencoder
@@ -376,12 +380,22 @@ def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=
     if not idx:                              # (a scene too small for one reference chip: nothing is predicted)
         probs = np.zeros((H, W) if channel is not None else (H, W, m.n_classes), np.float32)
         return (probs, np.full((H, W), 255, np.uint8)) if classes else probs
-    out, cls = _stitch_series(stack, idx, m, kernel, buff, batch_size, None if channel is None else int(channel), classes, float(maxval), harmonics)
+    if plan is not None and plan is not False:
+        side = kernel + 2 * (buff // 2)
+        want = (min(batch_size, len(idx)), m.n_time, side, side)
+        if plan is True:
+            plan = m.inference_plan(want)
+        elif getattr(plan, 'model', None) is not m or tuple(plan.shape) != want:
+            raise ValueError(f'plan must be a SeriesInferPlan of this model for shape {want}, got {getattr(plan, "shape", plan)!r}')
+    else:
+        plan = None
+    out, cls = _stitch_series(stack, idx, m, kernel, buff, batch_size, None if channel is None else int(channel), classes, float(maxval), harmonics,
+                              plan)
     probs = (out if channel is None else out[..., 0]).cpu().numpy()
     return (probs, cls[..., 0].cpu().numpy()) if classes else probs
 
 
-def _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, want_classes, maxval, harmonics):
+def _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, want_classes, maxval, harmonics, plan=None):
     """the batch loop of predict_series_scene: -> (device map (H, W, nc) float32, device class map (H, W, 1) uint8 or None)"""
     import ctypes as C
     import torch
@@ -407,7 +421,10 @@ def _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, want_classe
     runs = [[(s + a, s + b) for a, b in _disjoint_runs(idx[s:s + batch_size], kernel, kernel)] for s in range(0, total, batch_size)]
     nb = min(batch_size, total)
     cpad, dtype = ops.rup(C_, 16), m.dtype_code
-    buf = _device_empty((steps * nb * side * side * cpad,), ops.TORCH_DTYPE[dtype], 'the chip batch')
+    # with a plan, full batches are gathered straight into its static input; a short last batch goes through a buffer of its own and
+    # is spread over a prefix of every time step by plan.run
+    buf = plan.x_in.view(-1) if plan is not None else _device_empty((steps * nb * side * side * cpad,), ops.TORCH_DTYPE[dtype], 'the chip batch')
+    short = _device_empty((steps * (total % nb) * side * side * cpad,), ops.TORCH_DTYPE[dtype], 'the chip batch') if plan is not None and total % nb else None
     sincos = None
     if harmonics is not None:
         sincos = _device_empty((nb, side, side, 2), torch.float32, 'the harmonics')
@@ -423,12 +440,15 @@ def _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, want_classe
     # batch i still reads them.
     for b, s in enumerate(range(0, total, batch_size)):
         n = min(batch_size, total - s)
-        xt = buf[:steps * n * side * side * cpad].view(steps * n, side, side, cpad)      # (steps, n, ...) is contiguous for every n
+        xt = (buf if n == nb or short is None else short)[:steps * n * side * side * cpad].view(steps * n, side, side, cpad)      # (steps, n, ...) is contiguous for every n
         d = SeriesGatherDesc(src=dev.data_ptr(), src_kind=kind, t=T, c=C_, h=H, w_=W, steps=steps, maxval=maxval, origins=origins.data_ptr(),
                              total=total, first=s, n=n, off=off, side=side, dst=xt.data_ptr(), dtype=dtype, cpad=cpad)
         check(lib.satcv_series_gather(C.byref(d), st))
         try:
-            if sincos is not None:
+            if plan is not None:
+                res = plan.run(xt if sincos is None else [xt, sincos[:n]], want_classes=want_classes)
+                res = res if want_classes else (res,)
+            elif sincos is not None:
                 res = (m.predict_on_device([xt, sincos[:n]], shape=(n, steps, side, side)),)
             elif want_classes:
                 res = m.predict_on_device(xt, shape=(n, steps, side, side), want_classes=True)
