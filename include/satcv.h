@@ -151,6 +151,34 @@ int satcv_conv2d_igemm(const satcv_conv_desc* d, void* stream);
 /* 1 if this descriptor runs on the pipelined kernel (required by out_scale / pool_y / the fp8 dtypes), else 0; no launch. */
 int satcv_conv2d_igemm_pipelined(const satcv_conv_desc* d);
 
+/* Which kernel form satcv_conv2d_igemm(d) would run under the current options: host only, nothing is launched and no device is touched
+ * when ncu > 0 (x0 / x1 / w / y may be null: a null one counts as present and 16-byte aligned; of the others only presence and 16-byte
+ * alignment are read).  The query and the launch run the SAME function (igemm_dispatch, conv_igemm.hip), centre-tap rewrite, LDS- and
+ * register-fit tests included, so the answer cannot drift from what runs.  ncu: the CU count the persistent kernels size their grids by
+ * and the persistent 16x16x32 kernel decides on; 0 asks the device, as a launch does.
+ * family says which fields are meaningful:
+ *   FAST     igemm_fast_kernel<T, tw, wm, wn, mt, nt, ks, taps, dyn, tl, db, wps, wdma, sk, m16>   (conv_igemm_fast.hip)
+ *   GENERIC  igemm_kernel<T, tw, wm, wn, mt, nt, ks>                                               (conv_igemm.hip)
+ *   M16      igemm_m16_kernel<tw> (roles = 1) / igemm_m16sym_kernel<tw> (roles = 0); bst: the launch carries the fused sums
+ *   M16P     igemm_m16p_kernel<bst, bn>
+ *   WS       igemm_ws_kernel<T, cin, nt, wps, wn, dil>
+ *   TR       igemm_tr_kernel<cin, cout, th>
+ *   CONVT_THIN / CONVT_THIN_DGRAD   convt_thin_kernel<cin, cout, nw, wps, nsplit> / convt_thin_dgrad_kernel<cin, cout, nw, wps>
+ * Geometry: imgs images of rpi rows per tile, tiles_x x tiles_y pixel tiles per image group, n_tiles column tiles, nchunks K chunks,
+ * ksplit K ranges (split-K, else 1), workgroups of the launch (split-K: of its main kernel), lds_bytes dynamic LDS per workgroup. */
+enum { SATCV_CONV_FAMILY_GENERIC = 0, SATCV_CONV_FAMILY_FAST = 1, SATCV_CONV_FAMILY_M16 = 2, SATCV_CONV_FAMILY_M16P = 3, SATCV_CONV_FAMILY_WS = 4,
+       SATCV_CONV_FAMILY_TR = 5, SATCV_CONV_FAMILY_CONVT_THIN = 6, SATCV_CONV_FAMILY_CONVT_THIN_DGRAD = 7 };
+typedef struct satcv_conv_plan_info {
+  int32_t family, dtype;
+  int32_t tw, wm, wn, mt, nt, ks, taps, tl, db, wps, wdma, sk, m16, dyn;
+  int32_t cin, cout, th, nw, nsplit, dil;      /* WS / TR / CONVT_THIN*: the per-family template arguments */
+  int32_t bn, roles, bst;                      /* M16 / M16P */
+  int32_t imgs, rpi, tiles_x, tiles_y, n_tiles, nchunks, ksplit;
+  int32_t centre_tap;                          /* 1: a strongly dilated 3x3 (dil >= h and w_) runs as the 1x1 conv of its centre tap */
+  int64_t workgroups, lds_bytes;
+} satcv_conv_plan_info;
+int satcv_conv2d_igemm_plan_info(const satcv_conv_desc* d, int32_t ncu, satcv_conv_plan_info* info);
+
 /* Weight gradient of the same convolutions: dW[tap][ci][co] = sum_p X[p+tap][ci]*dY[p][co],
  * written as Keras HWIO fp32.  X is staged with the same optional affine+ReLU as the
  * forward.  Needs a caller-provided fp32 workspace (satcv_conv2d_wgrad_workspace). */

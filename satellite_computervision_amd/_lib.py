@@ -109,6 +109,23 @@ WGRAD_KERNELS = ('single', 'db', 'dma')              # SATCV_WGRAD_KERNEL_*
 WGRAD_REDUCES = ('generic', 'reduce4', 'reduce16')   # SATCV_WGRAD_REDUCE_*
 
 
+class ConvPlanInfo(C.Structure):
+    """satcv_conv_plan_info: the kernel form satcv_conv2d_igemm would run (host-only query, nothing is launched)."""
+    _fields_ = [(k, c_i32) for k in ('family', 'dtype', 'tw', 'wm', 'wn', 'mt', 'nt', 'ks', 'taps', 'tl', 'db', 'wps', 'wdma', 'sk', 'm16', 'dyn',
+                                     'cin', 'cout', 'th', 'nw', 'nsplit', 'dil', 'bn', 'roles', 'bst',
+                                     'imgs', 'rpi', 'tiles_x', 'tiles_y', 'n_tiles', 'nchunks', 'ksplit', 'centre_tap')] + \
+               [('workgroups', c_i64), ('lds_bytes', c_i64)]
+
+
+CONV_FAMILIES = ('generic', 'fast', 'm16', 'm16p', 'ws', 'tr', 'convt_thin', 'convt_thin_dgrad')      # SATCV_CONV_FAMILY_*
+# the fields of ConvPlanInfo that name the instantiation of each family (its template arguments)
+CONV_KEY_FIELDS = {'generic': ('tw', 'wm', 'wn', 'mt', 'nt', 'ks'),
+                   'fast': ('tw', 'wm', 'wn', 'mt', 'nt', 'ks', 'taps', 'tl', 'db', 'wps', 'wdma', 'sk', 'm16', 'dyn'),
+                   'm16': ('tw', 'roles', 'bst'), 'm16p': ('bn', 'bst'),
+                   'ws': ('cin', 'nt', 'wps', 'wn', 'dil'), 'tr': ('cin', 'cout', 'th'),
+                   'convt_thin': ('cin', 'cout', 'nw', 'wps', 'nsplit'), 'convt_thin_dgrad': ('cin', 'cout', 'nw', 'wps')}
+
+
 class BwdfDesc(C.Structure):
     _fields_ = [('g', c_vp), ('yraw', c_vp), ('ldg', c_i32),
                 ('bn_scale', c_vp), ('bn_shift', c_vp), ('bn_mean', c_vp), ('bn_rstd', c_vp), ('bn_coef', c_vp), ('linear', c_i32),
@@ -203,6 +220,7 @@ _SIGS = {
     'satcv_pack_weights_batched': (C.c_int, [c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
     'satcv_conv2d_igemm': (C.c_int, [C.POINTER(ConvDesc), c_vp]),
     'satcv_conv2d_igemm_pipelined': (C.c_int, [C.POINTER(ConvDesc)]),
+    'satcv_conv2d_igemm_plan_info': (C.c_int, [C.POINTER(ConvDesc), c_i32, C.POINTER(ConvPlanInfo)]),
     'satcv_conv2d_wgrad_workspace': (c_i64, [C.POINTER(WgradDesc)]),
     'satcv_conv2d_wgrad': (C.c_int, [C.POINTER(WgradDesc), c_vp]),
     'satcv_conv2d_wgrad_plan_info': (C.c_int, [C.POINTER(WgradDesc), C.POINTER(WgradPlanInfo)]),

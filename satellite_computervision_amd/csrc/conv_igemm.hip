@@ -226,7 +226,7 @@ __global__ __launch_bounds__(WM* WN * 64) void igemm_kernel(const IgemmArgs a) {
 
 // ------------------------------------------------------------------ host side
 template <typename T, int TW, int WM, int WN, int MT, int NT, int KS>
-static int launch_cfg(IgemmArgs& a, hipStream_t st) {
+static int launch_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
   constexpr int BM = WM * MT * 32, BN = WN * NT * 32, TH = BM / TW, KC = KS * 16;
   a.halh = a.dil * (a.kh - 1) / 2;
   a.halw = a.dil * (a.kw - 1) / 2;
@@ -250,10 +250,14 @@ static int launch_cfg(IgemmArgs& a, hipStream_t st) {
   if (a.cout_pad < a.n_tiles * BN) { satcv_set_error("igemm: cout_pad %d < %d", a.cout_pad, a.n_tiles * BN); return SATCV_ERR_INVALID; }
   const size_t lds = ((size_t)(KC / 8) * a.rl * a.pitch * 8 + (size_t)a.kh * a.kw * (KC / 8) * BN * 8) * sizeof(T);
   if (lds > 160 * 1024) { satcv_set_error("igemm: LDS %zu too large", lds); return SATCV_ERR_UNSUPPORTED; }
-  auto kern = igemm_kernel<T, TW, WM, WN, MT, NT, KS>;
-  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   const long long blocks = (long long)a.ngroups * a.tiles_y * a.tiles_x * a.n_tiles;
   if (blocks <= 0 || blocks > 0x7fffffffLL) { satcv_set_error("igemm: bad grid %lld", blocks); return SATCV_ERR_INVALID; }
+  if (satcv_conv_plan_info* o = igemm_note_begin(&a, SATCV_CONV_FAMILY_GENERIC, blocks, lds)) {
+    o->tw = TW; o->wm = WM; o->wn = WN; o->mt = MT; o->nt = NT; o->ks = KS; o->taps = a.kh * a.kw;
+  }
+  if (dry) return SATCV_OK;
+  auto kern = igemm_kernel<T, TW, WM, WN, MT, NT, KS>;
+  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(WM * WN * 64), lds, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { satcv_set_error("igemm launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
@@ -261,7 +265,7 @@ static int launch_cfg(IgemmArgs& a, hipStream_t st) {
 }
 
 template <typename T, int TW>
-static int launch_tw(IgemmArgs& a, hipStream_t st) {
+static int launch_tw(IgemmArgs& a, hipStream_t st, bool dry) {
   const int cin = a.c0 + a.c1;
   const int nspace = a.mode_out ? a.cstat : a.cout;      // BN must divide cstat in d2s mode
   const bool ks2 = (cin % 32 == 0) && (!a.x1 || a.c0 % 32 == 0) && (a.mode_in != 1 || a.c0 % 32 == 0) &&
@@ -270,23 +274,23 @@ static int launch_tw(IgemmArgs& a, hipStream_t st) {
   // narrower N tile, whose weight slab is smaller
   int rc = SATCV_ERR_UNSUPPORTED;
   if (nspace >= 128 && nspace % 128 == 0)
-    rc = ks2 ? launch_cfg<T, TW, 2, 2, 2, 2, 2>(a, st) : launch_cfg<T, TW, 2, 2, 2, 2, 1>(a, st);
+    rc = ks2 ? launch_cfg<T, TW, 2, 2, 2, 2, 2>(a, st, dry) : launch_cfg<T, TW, 2, 2, 2, 2, 1>(a, st, dry);
   if (rc == SATCV_ERR_UNSUPPORTED && nspace >= 64 && nspace % 64 == 0)
-    rc = ks2 ? launch_cfg<T, TW, 2, 2, 2, 1, 2>(a, st) : launch_cfg<T, TW, 2, 2, 2, 1, 1>(a, st);
+    rc = ks2 ? launch_cfg<T, TW, 2, 2, 2, 1, 2>(a, st, dry) : launch_cfg<T, TW, 2, 2, 2, 1, 1>(a, st, dry);
   if (rc == SATCV_ERR_UNSUPPORTED)
-    rc = ks2 ? launch_cfg<T, TW, 4, 1, 2, 1, 2>(a, st) : launch_cfg<T, TW, 4, 1, 2, 1, 1>(a, st);
+    rc = ks2 ? launch_cfg<T, TW, 4, 1, 2, 1, 2>(a, st, dry) : launch_cfg<T, TW, 4, 1, 2, 1, 1>(a, st, dry);
   if (rc == SATCV_ERR_UNSUPPORTED)          // many taps (7x7 stem) in fp32: halve the pixel tile as well
-    rc = launch_cfg<T, TW, 2, 1, 2, 1, 1>(a, st);
+    rc = launch_cfg<T, TW, 2, 1, 2, 1, 1>(a, st, dry);
   if (rc == SATCV_ERR_UNSUPPORTED) satcv_set_error("igemm: no tile configuration fits the LDS for this shape");
   return rc;
 }
 
 template <typename T>
-static int launch_t(IgemmArgs& a, hipStream_t st) {
+static int launch_t(IgemmArgs& a, hipStream_t st, bool dry) {
   switch (igemm_pick_tw(a.w_)) {
-    case 32: return launch_tw<T, 32>(a, st);
-    case 16: return launch_tw<T, 16>(a, st);
-    default: return launch_tw<T, 8>(a, st);
+    case 32: return launch_tw<T, 32>(a, st, dry);
+    case 16: return launch_tw<T, 16>(a, st, dry);
+    default: return launch_tw<T, 8>(a, st, dry);
   }
 }
 
@@ -372,33 +376,72 @@ extern "C" int satcv_conv2d_igemm_pipelined(const satcv_conv_desc* d) {
   return igemm_fast_launch(a, d->dtype, nullptr, true) == SATCV_OK ? 1 : 0;
 }
 
+thread_local IgemmNote* t_igemm_note = nullptr;
+
+int igemm_device_ncu() {
+  static int ncu = 0;
+  if (!ncu) {
+    int dev = 0; hipDeviceProp_t p;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return 0;
+    ncu = p.multiProcessorCount;
+  }
+  return ncu;
+}
+
+// The decision chain of satcv_conv2d_igemm, for the launch (dry = false) and for satcv_conv2d_igemm_plan_info (dry = true) alike: the
+// centre-tap rewrite of a strongly dilated 3x3, then the kernel families in their order, then the generic kernel.  note (may be null):
+// the CU count to plan with and the record of the chosen form (igemm_common.hpp).
+static int igemm_dispatch(IgemmArgs& a, int dtype, hipStream_t st, bool dry, IgemmNote* note) {
+  struct Scope { IgemmNote* old; Scope(IgemmNote* n) : old(t_igemm_note) { t_igemm_note = n; } ~Scope() { t_igemm_note = old; } } scope(note);
+  if (note && note->info) { *note->info = satcv_conv_plan_info{}; note->info->dtype = dtype; }
+  if (a.kh == 3 && a.kw == 3 && a.stride == 1 && a.dil >= a.h && a.dil >= a.w_) {
+    // every off-centre tap of this dilated conv reads only zero padding: it IS the 1x1 conv of its centre tap
+    const size_t esz = dtype == SATCV_BF16 ? 2 : 4;
+    a.w = reinterpret_cast<const unsigned char*>(a.w) + (size_t)4 * ((a.c0 + a.c1) / 8) * a.cout_pad * 8 * esz;
+    a.kh = a.kw = 1; a.dil = 1;
+    if (note && note->info) note->info->centre_tap = 1;
+  }
+  int rc = SATCV_ERR_UNSUPPORTED;
+  if (!g_opt.igemm_generic) {
+    rc = convt_thin_launch(a, dtype, st, dry);                 // thin transposed convolutions: streaming kernel
+    if (rc == SATCV_ERR_UNSUPPORTED) rc = convt_thin_dgrad_launch(a, dtype, st, dry);      // ... and their data gradients
+    if (rc == SATCV_ERR_UNSUPPORTED) rc = igemm_tr_launch(a, dtype, st, dry);            // thin 3x3 layers: staging / matrix wave roles (round 5)
+    if (rc == SATCV_ERR_UNSUPPORTED) rc = igemm_ws_launch(a, dtype, st, dry);            // ... or the persistent weights-stationary kernel (64 -> 64, fp8)
+    if (rc == SATCV_ERR_UNSUPPORTED) rc = igemm_fast_launch(a, dtype, st, dry);
+  }
+  if (rc != SATCV_ERR_UNSUPPORTED) { /* launched (or failed hard) */ }
+  else if (dtype == SATCV_FP8 || dtype == SATCV_FP8X) { satcv_set_error("igemm: this fp8 shape is outside the pipelined kernel's limits"); rc = SATCV_ERR_UNSUPPORTED; }
+  else if (a.out_scale || a.pool_y || a.bst_y || a.pair_n) { satcv_set_error("igemm: out_scale / pool_y / bst_y / pair store need the pipelined kernel"); rc = SATCV_ERR_UNSUPPORTED; }
+  else if (dtype == SATCV_BF16) rc = launch_t<bf16>(a, st, dry);
+  else if (dtype == SATCV_F32) rc = launch_t<float>(a, st, dry);
+  else { satcv_set_error("igemm: bad dtype %d", dtype); rc = SATCV_ERR_INVALID; }
+  return rc;
+}
+
 extern "C" int satcv_conv2d_igemm(const satcv_conv_desc* d, void* stream) {
   IgemmArgs a;
   int rc = igemm_fill_args(d, a);
   if (rc) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const double flops = 2.0 * d->n * d->h * d->w_ * (double)d->cout * (double)(a.c0 + a.c1) * d->kh * d->kw;
-  if (a.kh == 3 && a.kw == 3 && a.stride == 1 && a.dil >= a.h && a.dil >= a.w_) {
-    // every off-centre tap of this dilated conv reads only zero padding: it IS the 1x1 conv of its centre tap
-    const size_t esz = d->dtype == SATCV_BF16 ? 2 : 4;
-    a.w = reinterpret_cast<const unsigned char*>(a.w) + (size_t)4 * ((a.c0 + a.c1) / 8) * a.cout_pad * 8 * esz;
-    a.kh = a.kw = 1; a.dil = 1;
-  }
   satcv_prof_begin(d->kh * d->kw > 1 ? 0 : 1, flops, st);
-  rc = SATCV_ERR_UNSUPPORTED;
-  if (!g_opt.igemm_generic) {
-    rc = convt_thin_launch(a, d->dtype, st);                 // thin transposed convolutions: streaming kernel
-    if (rc == SATCV_ERR_UNSUPPORTED) rc = convt_thin_dgrad_launch(a, d->dtype, st);      // ... and their data gradients
-    if (rc == SATCV_ERR_UNSUPPORTED) rc = igemm_tr_launch(a, d->dtype, st, false);            // thin 3x3 layers: staging / matrix wave roles (round 5)
-    if (rc == SATCV_ERR_UNSUPPORTED) rc = igemm_ws_launch(a, d->dtype, st, false);            // ... or the persistent weights-stationary kernel (64 -> 64, fp8)
-    if (rc == SATCV_ERR_UNSUPPORTED) rc = igemm_fast_launch(a, d->dtype, st);
-  }
-  if (rc != SATCV_ERR_UNSUPPORTED) { /* launched (or failed hard) */ }
-  else if (d->dtype == SATCV_FP8 || d->dtype == SATCV_FP8X) { satcv_set_error("igemm: this fp8 shape is outside the pipelined kernel's limits"); rc = SATCV_ERR_UNSUPPORTED; }
-  else if (d->out_scale || d->pool_y || d->bst_y || d->pair_n) { satcv_set_error("igemm: out_scale / pool_y / bst_y / pair store need the pipelined kernel"); rc = SATCV_ERR_UNSUPPORTED; }
-  else if (d->dtype == SATCV_BF16) rc = launch_t<bf16>(a, st);
-  else if (d->dtype == SATCV_F32) rc = launch_t<float>(a, st);
-  else { satcv_set_error("igemm: bad dtype %d", d->dtype); rc = SATCV_ERR_INVALID; }
+  rc = igemm_dispatch(a, d->dtype, st, false, nullptr);
   satcv_prof_end(d->kh * d->kw > 1 ? 0 : 1, st);
   return rc;
+}
+
+extern "C" int satcv_conv2d_igemm_plan_info(const satcv_conv_desc* d, int32_t ncu, satcv_conv_plan_info* info) {
+  SATCV_CHECK(d && info && ncu >= 0, "igemm_plan_info: null pointer or negative CU count");
+  // x0 / x1 / w / y may be null in a query: a null one stands for a present, 16-byte aligned tensor (nothing is dereferenced)
+  satcv_conv_desc q = *d;
+  void* const fake = reinterpret_cast<void*>((uintptr_t)4096);
+  if (!q.x0) q.x0 = fake;
+  if (!q.w) q.w = fake;
+  if (!q.y) q.y = fake;
+  if (!q.x1 && q.c1 > 0) q.x1 = fake;
+  IgemmArgs a;
+  int rc = igemm_fill_args(&q, a);
+  if (rc) return rc;
+  IgemmNote note{ncu, info};
+  return igemm_dispatch(a, q.dtype, nullptr, true, &note);
 }

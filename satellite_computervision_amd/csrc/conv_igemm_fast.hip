@@ -818,6 +818,10 @@ static int fast_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
     }
     if (ks == 1) return SATCV_ERR_UNSUPPORTED;          // (the caller continues with the single-pass instantiation)
   }
+  if (satcv_conv_plan_info* o = igemm_note_begin(&a, SATCV_CONV_FAMILY_FAST, blocks * ks, lds)) {
+    o->tw = TW; o->wm = WM; o->wn = WN; o->mt = MT; o->nt = NT; o->ks = KS; o->taps = TAPS; o->tl = TL; o->db = DB; o->wps = WPS; o->wdma = WDMA; o->sk = SK; o->m16 = M16;
+    o->dyn = dyn; o->ksplit = ks;
+  }
   if (dry) return SATCV_OK;
   if (!dyn) {            // the kernel hard-codes these for the undilated case: keep the two derivations in lock step
     constexpr int CLc = TW + (TAPS == 9 ? 2 : 0);

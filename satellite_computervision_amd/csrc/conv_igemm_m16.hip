@@ -482,10 +482,13 @@ static int m16_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
   if (lds > 160 * 1024) return SATCV_ERR_UNSUPPORTED;
   const long long blocks = (long long)a.n * a.tiles_y * a.tiles_x * a.n_tiles;
   if (blocks <= 0 || blocks > 0x7fffffffLL) return SATCV_ERR_UNSUPPORTED;
-  if (dry) return SATCV_OK;
   // wave roles from 256 input channels on (SATCV_M16_WS=2: always, =0: never): with four chunks the longer prologue of the role kernel (three
   // chunks loaded before the first MFMA) is not amortised -- 128 -> 128 at 64 x 64: 97-99 us symmetric, 101-105 with roles, 108 on the 32x32x16 tile
   const bool roles = g_opt.m16_ws >= 2 || (g_opt.m16_ws == 1 && cin >= 256);
+  if (satcv_conv_plan_info* o = igemm_note_begin(&a, SATCV_CONV_FAMILY_M16, blocks, lds)) {
+    o->tw = TW; o->taps = 9; o->m16 = 1; o->bn = G::BN; o->roles = roles; o->bst = a.bst_y != nullptr;
+  }
+  if (dry) return SATCV_OK;
   auto kern = roles ? igemm_m16_kernel<TW> : igemm_m16sym_kernel<TW>;
   { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(roles ? 768 : 512), lds, st, a);

@@ -591,12 +591,8 @@ static int m16p_launch_bn(IgemmArgs& a, hipStream_t st, bool dry) {
   if (a.bst_y && a.in_scale) return SATCV_ERR_UNSUPPORTED;
   const size_t lds = G::FIXED_BYTES + (a.bst_y ? (size_t)2 * G::BN * sizeof(float) : a.in_scale ? (size_t)2 * cin * sizeof(float) : 0);
   if (lds > 160 * 1024) return SATCV_ERR_UNSUPPORTED;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0; hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) { satcv_set_error("igemm_m16p: device query failed"); return SATCV_ERR_HIP; }
-    ncu = p.multiProcessorCount;
-  }
+  const int ncu = igemm_ncu();      // (the plan query hands its own count down; a launch asks the device)
+  if (ncu <= 0) { satcv_set_error("igemm_m16p: device query failed"); return SATCV_ERR_HIP; }
   a.halh = a.halw = 1;
   a.tiles_x = a.w_ / G::TW; a.tiles_y = a.h / G::TH;
   a.rpi = G::TH; a.imgs = 1; a.ngroups = a.n;
@@ -616,6 +612,9 @@ static int m16p_launch_bn(IgemmArgs& a, hipStream_t st, bool dry) {
   // (one tile per workgroup has nothing to pipeline across: the one-tile kernels, with their higher occupancy of waves per tile, keep those;
   //  option m16p = 2 sends every eligible launch here)
   if (g_opt.m16p < 2 && m_total < 2 * ranges) return SATCV_ERR_UNSUPPORTED;
+  if (satcv_conv_plan_info* o = igemm_note_begin(&a, SATCV_CONV_FAMILY_M16P, ranges * a.n_tiles, lds)) {
+    o->tw = G::TW; o->taps = 9; o->m16 = 1; o->bn = BN; o->roles = 1; o->bst = a.bst_y != nullptr;
+  }
   if (dry) return SATCV_OK;
   auto kern = a.bst_y ? igemm_m16p_kernel<true, BN> : igemm_m16p_kernel<false, BN>;
   { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }

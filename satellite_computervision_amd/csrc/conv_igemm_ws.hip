@@ -246,21 +246,23 @@ static int ws_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
   a.rpi = TH; a.imgs = 1; a.ngroups = a.n; a.seg = RL; a.rl = RL; a.cl = PITCH; a.pitch = PITCH; a.n_tiles = 1;
   const long long total = (long long)a.n * a.tiles_y * a.tiles_x;
   if (total <= 0 || total > 0x7fffffffLL) return SATCV_ERR_UNSUPPORTED;
-  if (dry) return SATCV_OK;
-  auto kern = igemm_ws_kernel<T, CIN, NT, WPS, WN, DIL>;
-  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS); if (rc) return rc; }
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0; hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) { satcv_set_error("ws: device query failed"); return SATCV_ERR_HIP; }
-    ncu = p.multiProcessorCount;
-  }
   // resident workgroups per CU: LDS- or wave-limited (4 waves each, WPS per SIMD requested)
   int per_cu = (int)((160 * 1024) / LDS);
   if (per_cu > WPS) per_cu = WPS;
   if (per_cu < 1) per_cu = 1;
+  // (the grid needs the CU count: a dry run that nobody takes notes of -- satcv_conv2d_igemm_pipelined -- returns before it is asked for)
+  const bool noted = t_igemm_note && t_igemm_note->info;
+  if (dry && !noted) return SATCV_OK;
+  const int ncu = igemm_ncu();
+  if (ncu <= 0) { satcv_set_error("ws: device query failed"); return SATCV_ERR_HIP; }
   long long grid = (long long)ncu * per_cu;
   if (grid > total) grid = total;
+  if (satcv_conv_plan_info* o = igemm_note_begin(&a, SATCV_CONV_FAMILY_WS, grid, LDS)) {
+    o->nchunks = 1; o->tw = TW; o->th = TH; o->taps = 9; o->cin = CIN; o->cout = BN; o->nt = NT; o->wps = WPS; o->wn = WN; o->dil = DIL;
+  }
+  if (dry) return SATCV_OK;
+  auto kern = igemm_ws_kernel<T, CIN, NT, WPS, WN, DIL>;
+  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), LDS); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256 * WN), LDS, st, a, (int)total);
   ++g_opt.igemm_thin_launches;
   hipError_t e = hipGetLastError();

@@ -305,17 +305,19 @@ static int tr_cfg(IgemmArgs& a, hipStream_t st, bool dry) {
   const long long total = (long long)a.n * a.tiles_y * a.tiles_x;
   if (total <= 0 || total > 0x7fffffffLL) return SATCV_ERR_UNSUPPORTED;
   if ((long long)(TH + 2) * a.w_ * (a.c0 > a.c1 ? a.c0 : a.c1) >= (1LL << 23)) return SATCV_ERR_UNSUPPORTED;      // 24-bit multiplies of the halo offsets
+  // (the grid needs the CU count: a dry run that nobody takes notes of returns before it is asked for)
+  const bool noted = t_igemm_note && t_igemm_note->info;
+  if (dry && !noted) return SATCV_OK;
+  const int ncu = igemm_ncu();
+  if (ncu <= 0) { satcv_set_error("igemm_tr: device query failed"); return SATCV_ERR_HIP; }
+  long long grid = ncu;
+  if (grid > total) grid = total;
+  if (satcv_conv_plan_info* o = igemm_note_begin(&a, SATCV_CONV_FAMILY_TR, grid, G::LDS)) {
+    o->nchunks = 1; o->tw = 32; o->th = TH; o->taps = 9; o->cin = CINS; o->cout = COUT;
+  }
   if (dry) return SATCV_OK;
   auto kern = igemm_tr_kernel<CINS, COUT, TH>;
   { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), G::LDS); if (rc) return rc; }
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0; hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) { satcv_set_error("igemm_tr: device query failed"); return SATCV_ERR_HIP; }
-    ncu = p.multiProcessorCount;
-  }
-  long long grid = ncu;
-  if (grid > total) grid = total;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(768), G::LDS, st, a, (int)total);
   ++g_opt.igemm_thin_launches; ++g_opt.thin_roles_launches;
   hipError_t e = hipGetLastError();

@@ -228,16 +228,9 @@ __global__ __launch_bounds__(NW * 64, WPS) void convt_thin_kernel(const ConvtArg
 }
 
 template <int CIN, int COUT, int NW, int WPS, int NSPLIT = 1>
-static int convt_thin_cfg(const ConvtArgs& ca, hipStream_t st) {
+static int convt_thin_cfg(const ConvtArgs& ca, hipStream_t st, bool dry) {
   constexpr size_t lds = (size_t)CIN * 4 * COUT / NSPLIT * sizeof(bf16) + (size_t)(2 * CIN + 2 * COUT > 2 * NW * COUT ? 2 * CIN + 2 * COUT : 2 * NW * COUT) * sizeof(float) + (size_t)NW * 32 * 144;
-  auto kern = convt_thin_kernel<CIN, COUT, NW, WPS, NSPLIT>;
-  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-  static const int cus = [] {
-    int dev = 0, v = 256;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) v = p.multiProcessorCount;
-    return v;
-  }();
+  const int cus = igemm_ncu() > 0 ? igemm_ncu() : 256;
   int per_cu = WPS * 4 / NW;                                                  // resident workgroups: WPS waves per SIMD
   while (per_cu > 1 && (size_t)per_cu * lds > 150 * 1024) --per_cu;
   if (per_cu < 1) per_cu = 1;
@@ -246,6 +239,12 @@ static int convt_thin_cfg(const ConvtArgs& ca, hipStream_t st) {
   if (grid > need) grid = need;
   if (NSPLIT > 1) { grid -= grid % (8 * NSPLIT); if (grid < 8 * NSPLIT) grid = 8 * NSPLIT; }      // whole groups on every XCD
   if (grid < 1) grid = 1;
+  if (satcv_conv_plan_info* o = igemm_note_begin(nullptr, SATCV_CONV_FAMILY_CONVT_THIN, grid, lds)) {
+    o->taps = 1; o->cin = CIN; o->cout = COUT; o->nw = NW; o->wps = WPS; o->nsplit = NSPLIT;
+  }
+  if (dry) return SATCV_OK;
+  auto kern = convt_thin_kernel<CIN, COUT, NW, WPS, NSPLIT>;
+  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, ca);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { satcv_set_error("convt_thin launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
@@ -432,16 +431,9 @@ __global__ __launch_bounds__(NW * 64, WPS) void convt_thin_dgrad_kernel(const Co
 }
 
 template <int CIN, int COUT, int NW, int WPS>
-static int convt_thin_dgrad_cfg(const ConvtDgradArgs& ca, hipStream_t st) {
+static int convt_thin_dgrad_cfg(const ConvtDgradArgs& ca, hipStream_t st, bool dry) {
   constexpr size_t lds = (size_t)4 * COUT * CIN * sizeof(bf16) + (size_t)(4 * CIN > 2 * NW * CIN ? 4 * CIN : 2 * NW * CIN) * sizeof(float) + (size_t)NW * 32 * 144;
-  auto kern = convt_thin_dgrad_kernel<CIN, COUT, NW, WPS>;
-  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-  static const int cus = [] {
-    int dev = 0, v = 256;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) v = p.multiProcessorCount;
-    return v;
-  }();
+  const int cus = igemm_ncu() > 0 ? igemm_ncu() : 256;
   int per_cu = WPS * 4 / NW;
   while (per_cu > 1 && (size_t)per_cu * lds > 150 * 1024) --per_cu;
   if (per_cu < 1) per_cu = 1;
@@ -449,6 +441,12 @@ static int convt_thin_dgrad_cfg(const ConvtDgradArgs& ca, hipStream_t st) {
   const long long need = (ca.total_strips + NW - 1) / NW;
   if (grid > need) grid = need;
   if (grid < 1) grid = 1;
+  if (satcv_conv_plan_info* o = igemm_note_begin(nullptr, SATCV_CONV_FAMILY_CONVT_THIN_DGRAD, grid, lds)) {
+    o->taps = 1; o->cin = CIN; o->cout = COUT; o->nw = NW; o->wps = WPS; o->nsplit = 1; o->bst = ca.bst_y != nullptr;
+  }
+  if (dry) return SATCV_OK;
+  auto kern = convt_thin_dgrad_kernel<CIN, COUT, NW, WPS>;
+  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NW * 64), lds, st, ca);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { satcv_set_error("convt_thin_dgrad launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
@@ -456,7 +454,7 @@ static int convt_thin_dgrad_cfg(const ConvtDgradArgs& ca, hipStream_t st) {
 }
 
 // the space-to-depth launch of satcv_conv2d_igemm (mode_in == 1): x0 = dy with c0 = COUT channels, cout = CIN
-int convt_thin_dgrad_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
+int convt_thin_dgrad_launch(const IgemmArgs& a, int dtype, hipStream_t st, bool dry) {
   if (!g_opt.convt_thin || dtype != SATCV_BF16 || a.pair_n) return SATCV_ERR_UNSUPPORTED;      // (no pair store: satcv.h)
   if (a.kh != 1 || a.kw != 1 || a.mode_in != 1 || a.mode_out != 0 || a.f != 2 || a.x1 || a.stride != 1) return SATCV_ERR_UNSUPPORTED;
   if (a.out_scale || a.pool_y || a.accumulate || a.out_relu || a.in_scale || a.bias || a.bst_y1) return SATCV_ERR_UNSUPPORTED;
@@ -474,13 +472,13 @@ int convt_thin_dgrad_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
   ca.h = a.h; ca.w_ = a.w_; ca.total_strips = (int)strips;
   // (64 <- 4 x 32 channels at 128 x 128 moves 536 MB -- dy, the raw outputs for the fused sums, dx -- and the tiled kernel already does it at
   //  5.0 TB/s, 107 us; this kernel measured 113-120 us there.  SATCV_CONVT_THIN=2 runs it anyway.)
-  if (cin == 64 && cout_t == 32 && g_opt.convt_thin >= 2) return convt_thin_dgrad_cfg<64, 32, 4, 3>(ca, st);
-  if (cin == 128 && cout_t == 64) return convt_thin_dgrad_cfg<128, 64, 8, 2>(ca, st);
+  if (cin == 64 && cout_t == 32 && g_opt.convt_thin >= 2) return convt_thin_dgrad_cfg<64, 32, 4, 3>(ca, st, dry);
+  if (cin == 128 && cout_t == 64) return convt_thin_dgrad_cfg<128, 64, 8, 2>(ca, st, dry);
   return SATCV_ERR_UNSUPPORTED;
 }
 
 // SATCV_ERR_UNSUPPORTED outside the kernel's limits (the caller falls back to the tiled kernels)
-int convt_thin_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
+int convt_thin_launch(const IgemmArgs& a, int dtype, hipStream_t st, bool dry) {
   if (!g_opt.convt_thin || dtype != SATCV_BF16 || a.pair_n) return SATCV_ERR_UNSUPPORTED;
   if (a.kh != 1 || a.kw != 1 || a.mode_out != 1 || a.mode_in != 0 || a.f != 2 || a.x1 || a.stride != 1) return SATCV_ERR_UNSUPPORTED;
   if (a.pool_y || a.accumulate || a.bst_y || ((a.out_scale || a.out_relu) && a.stats)) return SATCV_ERR_UNSUPPORTED;      // (statistics are of the plain training output)
@@ -495,10 +493,10 @@ int convt_thin_launch(const IgemmArgs& a, int dtype, hipStream_t st) {
   ca.w = a.w; ca.bias = a.bias; ca.out_scale = a.out_scale; ca.out_relu = a.out_relu; ca.y = a.y; ca.ldy = a.ldy; ca.stats = a.stats; ca.stats_ld = a.stats_ld;
   ca.h = a.h; ca.w_ = a.w_; ca.total_strips = (int)strips;
   if (cin == 64 && cout_t == 32) {
-    if (g_opt.convt_wps == 2) return convt_thin_cfg<64, 32, 4, 2>(ca, st);
-    return convt_thin_cfg<64, 32, 4, 3>(ca, st);
+    if (g_opt.convt_wps == 2) return convt_thin_cfg<64, 32, 4, 2>(ca, st, dry);
+    return convt_thin_cfg<64, 32, 4, 3>(ca, st, dry);
   }
-  if (cin == 128 && cout_t == 64) return convt_thin_cfg<128, 64, 8, 2>(ca, st);
-  if (cin == 256 && cout_t == 128 && g_opt.convt_mid) return convt_thin_cfg<256, 128, 8, 2, 4>(ca, st);      // one position (64 KB of weights) per workgroup
+  if (cin == 128 && cout_t == 64) return convt_thin_cfg<128, 64, 8, 2>(ca, st, dry);
+  if (cin == 256 && cout_t == 128 && g_opt.convt_mid) return convt_thin_cfg<256, 128, 8, 2, 4>(ca, st, dry);      // one position (64 KB of weights) per workgroup
   return SATCV_ERR_UNSUPPORTED;
 }

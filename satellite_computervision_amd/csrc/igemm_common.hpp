@@ -545,6 +545,28 @@ static inline int igemm_pick_tw(int w) {
   return best;
 }
 
+// ---- what a dispatch notes on the host (never part of IgemmArgs, which is the kernel argument): the CU count the persistent kernels
+// plan with (0: ask the device) and, for satcv_conv2d_igemm_plan_info, the record of the chosen instantiation.  igemm_dispatch
+// (conv_igemm.hip) installs it for the calling thread while it walks the chain; every *_cfg that answers OK writes its template arguments
+// and derived geometry through igemm_note_begin() -- the last writer is the form that runs (a refused attempt writes nothing).
+struct IgemmNote { int ncu; satcv_conv_plan_info* info; };
+extern thread_local IgemmNote* t_igemm_note;      // conv_igemm.hip; null outside a dispatch
+int igemm_device_ncu();                           // CU count of the current device, asked once; <= 0: the query failed
+// the CU count this dispatch plans with
+static inline int igemm_ncu() { return (t_igemm_note && t_igemm_note->ncu > 0) ? t_igemm_note->ncu : igemm_device_ncu(); }
+// the record to fill, zeroed apart from what the dispatch itself set (dtype, centre_tap), with the geometry of `a`; null: nobody asked
+// (a: the tiled kernels' argument block with its derived tiling; null for the streaming kernels, which have none)
+static inline satcv_conv_plan_info* igemm_note_begin(const IgemmArgs* a, int family, long long workgroups, size_t lds) {
+  satcv_conv_plan_info* o = t_igemm_note ? t_igemm_note->info : nullptr;
+  if (!o) return nullptr;
+  const int dtype = o->dtype, centre = o->centre_tap;
+  *o = satcv_conv_plan_info{};
+  o->family = family; o->dtype = dtype; o->centre_tap = centre; o->ksplit = 1;
+  if (a) { o->imgs = a->imgs; o->rpi = a->rpi; o->tiles_x = a->tiles_x; o->tiles_y = a->tiles_y; o->n_tiles = a->n_tiles; o->nchunks = a->nchunks; }
+  o->workgroups = workgroups; o->lds_bytes = (int64_t)lds;
+  return o;
+}
+
 // software-pipelined variant (conv_igemm_fast.hip); returns SATCV_ERR_UNSUPPORTED when the
 // shape is outside its static limits so that the caller falls back to the generic kernel.
 int igemm_fast_launch(IgemmArgs& a, int dtype, hipStream_t st, bool dry_run = false);
@@ -557,5 +579,5 @@ int igemm_ws_launch(IgemmArgs& a, int dtype, hipStream_t st, bool dry_run);
 // the thin 3x3 layers with wave roles (conv_thin_roles.hip); SATCV_ERR_UNSUPPORTED outside its limits
 int igemm_tr_launch(IgemmArgs& a, int dtype, hipStream_t st, bool dry);
 // streaming kernel of the thin transposed convolutions (conv_transpose_thin.hip); SATCV_ERR_UNSUPPORTED outside its limits
-int convt_thin_launch(const IgemmArgs& a, int dtype, hipStream_t st);
-int convt_thin_dgrad_launch(const IgemmArgs& a, int dtype, hipStream_t st);
+int convt_thin_launch(const IgemmArgs& a, int dtype, hipStream_t st, bool dry);
+int convt_thin_dgrad_launch(const IgemmArgs& a, int dtype, hipStream_t st, bool dry);

@@ -85,6 +85,31 @@ int main(void) {
   EXPECT(satcv_conv2d_igemm(NULL, NULL) != 0, "NULL conv desc");
   EXPECT(satcv_conv2d_igemm(&cd, NULL) != 0 && strstr(satcv_last_error(), "null"), "zeroed conv desc: %s", satcv_last_error());
   EXPECT(satcv_conv2d_igemm_pipelined(NULL) == 0 && satcv_conv2d_igemm_pipelined(&cd) == 0, "dry run of an invalid descriptor answers 0");
+  satcv_conv_plan_info ci;
+  EXPECT(satcv_conv2d_igemm_plan_info(NULL, 256, &ci) != 0 && satcv_conv2d_igemm_plan_info(&cd, 256, NULL) != 0 && satcv_conv2d_igemm_plan_info(&cd, 256, &ci) != 0 &&
+         satcv_conv2d_igemm_plan_info(&cd, -1, &ci) != 0, "invalid conv plan query");
+  {
+    /* channel counts, taps, extents and option-like fields out of range: refused with a message, nothing indexed by them */
+    satcv_conv_desc bd2; memset(&bd2, 0, sizeof(bd2));
+    bd2.c0 = 64; bd2.ldy = 64; bd2.n = 2; bd2.h = 8; bd2.w_ = 32; bd2.cout = 64; bd2.cout_pad = 64; bd2.kh = bd2.kw = 3; bd2.dil = 1; bd2.cstat = 64; bd2.dtype = SATCV_BF16;
+    EXPECT(satcv_conv2d_igemm_plan_info(&bd2, 256, &ci) == 0 && ci.lds_bytes > 0 && ci.workgroups > 0, "null tensors are fine in a plan query: %s", satcv_last_error());
+    satcv_conv_desc t = bd2; t.c0 = 24;
+    EXPECT(satcv_conv2d_igemm_plan_info(&t, 256, &ci) != 0, "c0 not a multiple of 16");
+    t = bd2; t.kh = 4;
+    EXPECT(satcv_conv2d_igemm_plan_info(&t, 256, &ci) != 0, "even taps");
+    t = bd2; t.mode_out = 1; t.f = 0;
+    EXPECT(satcv_conv2d_igemm_plan_info(&t, 256, &ci) != 0, "depth-to-space without a factor");
+    t = bd2; t.stride = 2;
+    EXPECT(satcv_conv2d_igemm_plan_info(&t, 256, &ci) != 0, "stride without the input extents");
+    t = bd2; t.pair_n = 3;
+    EXPECT(satcv_conv2d_igemm_plan_info(&t, 256, &ci) != 0, "pair store of an odd batch");
+    t = bd2; t.dtype = 77;
+    EXPECT(satcv_conv2d_igemm_plan_info(&t, 256, &ci) != 0, "unknown dtype");
+    t = bd2; t.n = 0x7fffffff; t.h = 0x7fffffff; t.w_ = 0x7fffffff;
+    EXPECT(satcv_conv2d_igemm_plan_info(&t, 256, &ci) != 0, "extents beyond 2^31 pixels");
+    t = bd2; t.tile_policy = 0x7fffffff; t.pool_f = -5; t.bst_ld = -1;
+    (void)satcv_conv2d_igemm_plan_info(&t, 0x7fffffff, &ci);
+  }
   satcv_wgrad_desc wd; memset(&wd, 0, sizeof(wd));
   EXPECT(satcv_conv2d_wgrad(NULL, NULL) != 0 && satcv_conv2d_wgrad(&wd, NULL) != 0, "invalid wgrad desc");
   EXPECT(satcv_conv2d_wgrad_workspace(NULL) < 0, "wgrad workspace of NULL");
@@ -111,7 +136,7 @@ int main(void) {
   static const int HW[][2] = {{1, 1}, {4, 4}, {8, 8}, {12, 20}, {16, 16}, {20, 24}, {32, 32}, {40, 72}, {64, 64}, {100, 36}, {128, 128}, {256, 256}, {8, 264}, {512, 512}, {1024, 1024}};
   static const int CH[] = {16, 32, 48, 64, 96, 128, 192, 256, 512, 1024, 2048};
   static const int KD[][2] = {{1, 1}, {3, 1}, {3, 2}, {3, 3}, {3, 6}, {3, 12}, {3, 64}, {5, 1}, {7, 1}};
-  long long planned = 0, accepted = 0;
+  long long planned = 0, accepted = 0, conv_plans = 0;
   for (unsigned hi = 0; hi < sizeof(HW) / sizeof(HW[0]); ++hi)
     for (unsigned ci = 0; ci < sizeof(CH) / sizeof(CH[0]); ++ci)
       for (unsigned co = 0; co < sizeof(CH) / sizeof(CH[0]); ++co)
@@ -125,9 +150,24 @@ int main(void) {
               if (dt == 3 && (d.c0 % 64)) continue;
               accepted += satcv_conv2d_igemm_pipelined(&d);
               ++planned;
+              /* the plan query walks the launch's own chain: an fp32 / bf16 descriptor always has a form (the generic kernel at the least) or an error
+               * message, never a crash; what it reports stays inside the LDS */
+              for (int ncu = 8; ncu <= 256; ncu *= 32) {
+                satcv_conv_plan_info pi;
+                (void)satcv_set_option("no_such_option", 1);        /* a known message in the error channel: a refusal must replace it */
+                const int rc = satcv_conv2d_igemm_plan_info(&d, ncu, &pi);
+                if (rc == 0) { EXPECT(pi.lds_bytes > 0 && pi.lds_bytes <= 160 * 1024 && pi.workgroups > 0 && pi.ksplit >= 1, "conv plan query geometry"); ++conv_plans; }
+                else EXPECT(strlen(satcv_last_error()) > 0 && !strstr(satcv_last_error(), "no_such_option"), "a refused plan query says why: %s", satcv_last_error());
+              }
               /* two-source input (decoder_block's concat) and a statistics target: other planning branches */
               d.x1 = fake; d.c1 = CH[ci]; d.stats = (satcv_stat_t*)fake; d.stats_ld = CH[co];
-              if (!(dt == 3 && (d.c1 % 64))) { accepted += satcv_conv2d_igemm_pipelined(&d); ++planned; }
+              if (!(dt == 3 && (d.c1 % 64))) {
+                accepted += satcv_conv2d_igemm_pipelined(&d); ++planned;
+                satcv_conv_plan_info pi;
+                d.tile_policy = 2;
+                if (satcv_conv2d_igemm_plan_info(&d, 256, &pi) == 0) { EXPECT(pi.lds_bytes <= 160 * 1024 && pi.workgroups > 0, "conv plan query geometry (two sources)"); ++conv_plans; }
+                d.tile_policy = 0;
+              }
               if (dt <= 1 && (KD[ki][0] == 1 || KD[ki][0] == 3)) {
                 satcv_wgrad_desc w; memset(&w, 0, sizeof(w));
                 w.x0 = fake; w.c0 = CH[ci]; w.dy = fake; w.lddy = CH[co]; w.dw = (float*)fake; w.cin = CH[ci]; w.cout = CH[co];
@@ -151,6 +191,7 @@ int main(void) {
                 ++planned;
               }
             }
+  EXPECT(conv_plans > 10000, "conv plan queries answered (%lld)", conv_plans);
   EXPECT(planned > 10000 && accepted > 1000, "planning sweep ran (%lld planned, %lld on the pipelined kernel)", planned, accepted);
   /* extreme extents: must be refused or planned without overflow */
   {

@@ -11,6 +11,11 @@ import torch
 from oracle import keras_ops as K
 from oracle import losses as OL
 
+import sys
+if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import conv_cases as CC  # noqa: E402  planned(): the kernel form satcv_conv2d_igemm runs for a shape (satcv_conv2d_igemm_plan_info)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -93,7 +98,11 @@ CONV_CASES = [
     (2, 16, 16, 64, 32, 1, 1),     # 1x1
     (1, 32, 32, 48, 96, 3, 1),     # channel counts that are not powers of two
     (1, 256, 256, 16, 32, 3, 1),   # full-resolution tile
-    # the deep shapes of get_unet_model(2, 4) at 256x256 -- the instantiations bench.py times (K up to 9 * 1024)
+    # the deep shapes of get_unet_model(2, 4) at 256x256 (K up to 9 * 1024).  NOT the instantiations bench.py times: at n = 1 .. 2 these have
+    # 1 - 32 tiles of 256 pixels, far below the 192 behind the double-buffered tile, and no tile_policy = 2 -- the plan query says the 128 / 64-column
+    # ones run the single-buffered 128-pixel tiles here (bf16 with statistics at tile width 16 / 32: the one-tile 16x16x32 kernel only from 192 tiles
+    # on), where the benchmark's batch 64 runs the 16x16x32 and persistent kernels.  tests/conv_cases.py pins the benchmark's own launches
+    # (BENCH_LAUNCHES) and reaches each of their forms at small shapes.
     (2, 16, 16, 1024, 512, 3, 1),  # dec4.conv1 (consumes concat([skip, up]))
     (2, 16, 16, 512, 512, 3, 1),   # dec4.conv2
     (2, 8, 8, 512, 1024, 3, 1),    # centre block
@@ -239,6 +248,14 @@ DB_CASES = [
 def test_conv2d_double_buffered_tile(ops, td, case, force_db):
     """forward (with BN statistics) and data gradient of the 3x3 conv through the 8-wave double-buffered configuration."""
     n, h, w, cin, cout = case
+    # the forms named: with statistics the one-tile 16x16x32 kernel where it serves the shape (maps at least 16 wide and a tile high, Cin % 64 == 0),
+    # else the double-buffered 32x32x16 tile; without statistics (the data gradient below) always the latter
+    g = CC.planned(n, h, w, cin, cout, CC.BF16, bias=True, stats=True)
+    tw = min((8, 16, 32), key=lambda t: (-(-w // t) * t, -t))           # igemm_pick_tw: least padding, the wider tile on a tie
+    m16 = cin % 64 == 0 and tw >= 16 and h >= 256 // tw
+    assert (g['family'] == 'm16') if m16 else (g['family'] == 'fast' and g['db'] == 1 and (g['wm'], g['wn']) == (4, 2)), (case, g)
+    g = CC.planned(n, h, w, cin, cout, CC.BF16)
+    assert g['family'] == 'fast' and g['db'] == 1 and (g['wm'], g['wn'], g['taps']) == (4, 2, 9), (case, g)
     rng = np.random.default_rng(hash(case) % 2**31)
     x = rnd(rng, (n, h, w, cin), td)
     kern = rnd(rng, (3, 3, cin, cout), td, 0.2)
@@ -267,6 +284,8 @@ def test_16x16x32_tile_fused_bn_backward_sums(ops, case, force_db):
     one (a lane owns two columns): against float64 sums of the stored gradient; the stored gradient itself against the oracle."""
     n, h, w, cin, cout, split = case
     td = torch.bfloat16
+    g = CC.planned(n, h, w, cin, cout, CC.BF16, bst=2 if split else 1)
+    assert (g['family'], g['bst']) == ('m16', 1), f'{case}: the fused sums would run on {g} -- not the 16x16x32 tile this test is about'
     rng = np.random.default_rng(hash(case) % 2**31)
     x = rnd(rng, (n, h, w, cin), td)
     kern = rnd(rng, (3, 3, cin, cout), td, 0.1)
@@ -712,6 +731,9 @@ def test_conv2d_transpose_streaming_kernel_with_input_batchnorm(ops, case):
     same result as the tiled kernel (SATCV_CONVT_THIN=0 is read once per process, so the tiled result comes from a narrower twin map)."""
     td = torch.bfloat16
     n, h, w, cin, cout = case
+    for kw in (dict(bias=True, stats=True, affine=True), dict(), dict(bias=True, out_scale=True, out_relu=True)):
+        g = CC.planned(n, h, w, cin, cout, CC.BF16, k=1, mode='convt', f=2, **kw)
+        assert g['family'] == 'convt_thin' and (g['cin'], g['cout']) == (cin, cout), (case, kw, g)
     rng = np.random.default_rng(sum(case))
     x = rnd(rng, (n, h, w, cin), td)
     kt = rnd(rng, (2, 2, cout, cin), td, 0.2)
@@ -745,10 +767,16 @@ def test_conv2d_transpose_streaming_kernel_with_input_batchnorm(ops, case):
 
 @pytest.mark.parametrize('case', [(2, 32, 32, 64, 32), (1, 16, 64, 128, 64), (3, 8, 96, 64, 32), (1, 64, 64, 64, 32), (2, 32, 64, 128, 64)])
 def test_conv2d_transpose_streaming_data_gradient_with_fused_bn_sums(ops, case):
-    """Data gradient of the thin transposed convolutions on the streaming kernel (maps a multiple of 32 wide), with and without the fused
-    BatchNorm-backward sums of the layer below: the stored gradient is the same either way, the sums are those of the STORED gradient."""
+    """Data gradient of the thin transposed convolutions (maps a multiple of 32 wide), with and without the fused BatchNorm-backward sums of
+    the layer below: the stored gradient is the same either way, the sums are those of the STORED gradient.  The plan query shows that only
+    the 128 <- 4 x 64 cases run the streaming kernel: 64 <- 4 x 32 needs SATCV_CONVT_THIN=2 (the tiled kernel measured faster there) and runs the
+    tiled 1x1 kernel here, fused sums included -- those cases stay as tests of that path; tests/conv_cases.py reaches the streaming 64 <- 32 form
+    in its startup-option set."""
     td = torch.bfloat16
     n, h, w, cin, cout = case
+    for bst in (0, 1):
+        g = CC.planned(n, h, w, cout, cin, CC.BF16, k=1, mode='convt_dgrad', f=2, bst=bst)
+        assert g['family'] == ('convt_thin_dgrad' if cin == 128 else 'fast') and g['bst'] == (bst if cin == 128 else 0), (case, g)
     rng = np.random.default_rng(sum(case) + 1)
     x = rnd(rng, (n, h, w, cin), td)
     kt = rnd(rng, (2, 2, cout, cin), td, 0.2)
@@ -1353,6 +1381,8 @@ def test_conv2d_split_k(case):
     code = r"""
 import sys, json, numpy as np, torch
 sys.path.insert(0, %r)
+sys.path.insert(0, %r)
+import conv_cases as CC
 from satellite_computervision_amd import ops
 from oracle import keras_ops as K
 n, h, w, cin, cout, k = %r
@@ -1363,16 +1393,19 @@ wf, _ = ops.pack_weights(kern.float().cuda(), cin, 1)
 st = ops.new_stats(cout, torch.device('cuda'))
 y = ops.conv2d(x.cuda(), wf, cout, kh=k, kw=k, bias=b, stats=st)
 ref = K.conv2d_same(x.double().numpy(), kern.double().numpy(), b.double().cpu().numpy(), 1)
+g = CC.planned(n, h, w, cin, cout, CC.BF16, k=k, bias=True, stats=True)
 got = y.double().cpu().numpy()
 s = st.sum(0).double().cpu().numpy()
 print(json.dumps(dict(err=float(np.abs(got - ref).max() / np.abs(ref).max()), s1=float(np.abs(s[0] - got.reshape(-1, cout).sum(0)).max() / max(np.abs(s[0]).max(), 1.0)),
-                      s2=float(np.abs(s[1] - (got.reshape(-1, cout) ** 2).sum(0)).max() / np.abs(s[1]).max()), y=got.ravel()[:4096:7].tolist())))
-""" % (ROOT, case)
+                      s2=float(np.abs(s[1] - (got.reshape(-1, cout) ** 2).sum(0)).max() / np.abs(s[1]).max()), y=got.ravel()[:4096:7].tolist(),
+                      sk=g['sk'], ksplit=g['ksplit'])))
+""" % (ROOT, os.path.join(ROOT, 'tests'), case)
     outs = {}
     for sk in ('1', '0'):
         r = subprocess.run([sys.executable, '-c', code], env=dict(os.environ, SATCV_SPLITK=sk), capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, r.stderr[-2000:]
         outs[sk] = json.loads(r.stdout.strip().splitlines()[-1])
+    assert outs['1']['sk'] == 1 and outs['1']['ksplit'] >= 2 and (outs['0']['sk'], outs['0']['ksplit']) == (0, 1), 'the split-K instantiation did not run'
     assert outs['1']['err'] < 1.2e-2 and outs['1']['s1'] < 1e-3 and outs['1']['s2'] < 1e-3, outs['1']
     # the split sum differs from the single-pass one by fp32 association only: at most one bf16 ulp on a few elements
     a, b_ = np.array(outs['1']['y']), np.array(outs['0']['y'])
@@ -1424,6 +1457,8 @@ def test_dilated_conv_double_buffered_taploop(ops, case):
     with the fused input BatchNorm + ReLU and a dual-source input, against the float64 oracle."""
     n, h, w, cin, cout, dil, dual = case
     td = torch.bfloat16
+    g = CC.planned(n, h, w, 128 if dual else cin, cout, CC.BF16, c1=cin - 128 if dual else 0, dil=dil, affine=True)
+    assert g['family'] == 'fast' and (g['tl'], g['db'], g['ks']) == (1, 1, 4), f'{case}: not the double-buffered tap loop: {g}'
     rng = np.random.default_rng(hash(case) % 2**31)
     x = rnd(rng, (n, h, w, cin), td)
     kern = rnd(rng, (3, 3, cin, cout), td, 0.05)
