@@ -266,7 +266,10 @@ typedef struct satcv_bwdf_desc {
   int32_t accumulate;                  /* dw += result (shared weights) */
   /* optional: the sums of the BatchNorm backward of the layer BELOW -- the BatchNormalization + ReLU whose scale / shift are this
    * launch's in_scale / in_shift (needs in_relu = 1) -- formed from the stored dx and the staged input: what satcv_bn_bwd_reduce would
-   * compute in a pass of its own over dx and that layer's raw output.  [ROWS][2][bst_sums_ld] rows as for satcv_bn_bwd_finalize. */
+   * compute in a pass of its own over dx and that layer's raw output.  [ROWS][2][bst_sums_ld] rows as for satcv_bn_bwd_finalize.
+   * The sums are ADDED to the rows (one atomic add per channel and workgroup): the caller zeroes them, or keeps what other launches
+   * put there.  xhat is rebuilt from the staged activation a = relu(in_scale * x + in_shift) as (a - in_shift) / in_scale: a channel
+   * whose in_scale is exactly 0 gets sum g xhat = 0, because xhat cannot be rebuilt from a constant activation. */
   satcv_stat_t* bst_sums; int32_t bst_sums_ld;
   const float* bst_mean; const float* bst_rstd;
   int32_t bst_act_form;                /* 1: the input x is itself an activation (in_scale NULL: a max-pooled encoder output); the rows get
@@ -286,6 +289,21 @@ typedef struct satcv_bwdf_desc {
 int64_t satcv_conv2d_bwd_fused_workspace(const satcv_bwdf_desc* d);
 int satcv_conv2d_bwd_fused(const satcv_bwdf_desc* d, void* stream);
 int satcv_conv2d_bwd_fused_reduce_job(const satcv_bwdf_desc* d, satcv_reduce_job* job);
+
+/* Which instantiation satcv_conv2d_bwd_fused(d) would run, and how its persistent workgroups share the tiles: host only, nothing is
+ * launched.  ncu > 0 plans for that CU count and does not touch the HIP runtime; ncu == 0 asks the device, as the launch does.  The
+ * query walks the launch path's own chain (bwdf_shape_ok -> bwdf_dispatch -> bwdf_launch of csrc/conv_bwd_fused.hip), so it cannot drift
+ * from what runs; pointers are read for null-ness and alignment only.  Fields: the template arguments of
+ * bwd_fused_kernel<cin, cout, nw, wps, pool, nodg, cins, hg>; bst = 1 where that instantiation carries the fused sums; tiles of 8 x 32
+ * pixels; workgroups of the launch, each with a contiguous range of tiles_min or tiles_max (= tiles_min + 1 where the division leaves
+ * a remainder) tiles; dynamic LDS per workgroup; ws_bytes = workgroups * 9 * cin * cout * 4, what satcv_conv2d_bwd_fused_workspace
+ * answers.  SATCV_ERR_UNSUPPORTED where the workspace query answers -1. */
+typedef struct satcv_bwdf_plan_info {
+  int32_t cin, cout, nw, wps, pool, nodg, cins, hg;
+  int32_t bst, pad_;
+  int64_t tiles, workgroups, tiles_min, tiles_max, lds_bytes, ws_bytes;
+} satcv_bwdf_plan_info;
+int satcv_conv2d_bwd_fused_plan_info(const satcv_bwdf_desc* d, int32_t ncu, satcv_bwdf_plan_info* info);
 
 /* Fused backward of decoder_block's up-sampling path (utils/model_tools.py:306-309: Conv2DTranspose(filters, up_size, strides = up_size) ->
  * concatenate([skip, up]) -> BatchNormalization -> Activation('relu'), differentiated by Keras inside Model.fit), round 5.  For the `up`
@@ -316,6 +334,17 @@ typedef struct satcv_ctbf_desc {
 int64_t satcv_convt_bwd_fused_workspace(const satcv_ctbf_desc* d);
 int satcv_convt_bwd_fused(const satcv_ctbf_desc* d, void* stream);
 int satcv_convt_bwd_fused_reduce_job(const satcv_ctbf_desc* d, satcv_reduce_job* job);
+
+/* The same question for satcv_convt_bwd_fused (ctbf_dispatch -> ctbf_launch of csrc/convt_bwd_fused.hip): the template arguments of
+ * convt_bwd_fused_kernel<cout4, px, cblk> (4 cout gradient channels, px input pixels per tile, cblk input channels per workgroup), nblk =
+ * cin / cblk channel blocks, `slabs` workgroups per channel block (slabs * nblk workgroups in all), tiles of px pixels, tiles_min /
+ * tiles_max per slab, dynamic LDS, ws_bytes = slabs * cin * 4 cout * 4.  bst_sums, accumulate and defer_reduce are bound to the descriptor
+ * as for satcv_conv2d_bwd_fused: the sums are added to the rows, and a zero in_scale gives sum g xhat = 0. */
+typedef struct satcv_ctbf_plan_info {
+  int32_t cout4, px, cblk, nblk;
+  int64_t slabs, tiles, tiles_min, tiles_max, lds_bytes, ws_bytes;
+} satcv_ctbf_plan_info;
+int satcv_convt_bwd_fused_plan_info(const satcv_ctbf_desc* d, int32_t ncu, satcv_ctbf_plan_info* info);
 
 /* --------------------------------------------------------------- batch norm
  * layers.BatchNormalization (utils/model_tools.py:179,308,313,316): eps, momentum as given.

@@ -150,6 +150,18 @@ class CtbfDesc(C.Structure):
                 ('bst_sums', c_vp), ('bst_sums_ld', c_i32), ('bst_mean', c_vp), ('bst_rstd', c_vp)]
 
 
+class BwdfPlanInfo(C.Structure):
+    """satcv_bwdf_plan_info: the instantiation satcv_conv2d_bwd_fused would run and its tile ranges (host-only query, nothing is launched)."""
+    _fields_ = [(k, c_i32) for k in ('cin', 'cout', 'nw', 'wps', 'pool', 'nodg', 'cins', 'hg', 'bst', 'pad_')] + \
+               [(k, c_i64) for k in ('tiles', 'workgroups', 'tiles_min', 'tiles_max', 'lds_bytes', 'ws_bytes')]
+
+
+class CtbfPlanInfo(C.Structure):
+    """satcv_ctbf_plan_info: the same for satcv_convt_bwd_fused."""
+    _fields_ = [(k, c_i32) for k in ('cout4', 'px', 'cblk', 'nblk')] + \
+               [(k, c_i64) for k in ('slabs', 'tiles', 'tiles_min', 'tiles_max', 'lds_bytes', 'ws_bytes')]
+
+
 class ReduceJob(C.Structure):
     _fields_ = [('ws', c_vp), ('dw', c_vp), ('nslab', c_i32), ('taps', c_i32), ('kpad', c_i32), ('npad', c_i32), ('cin', c_i32), ('nvalid', c_i32),
                 ('transposed', c_i32), ('accumulate', c_i32), ('lanes', c_i32), ('pad_', c_i32)]
@@ -230,6 +242,8 @@ _SIGS = {
     'satcv_conv2d_bwd_fused_workspace': (c_i64, [C.POINTER(BwdfDesc)]),
     'satcv_conv2d_bwd_fused': (C.c_int, [C.POINTER(BwdfDesc), c_vp]),
     'satcv_conv2d_bwd_fused_reduce_job': (C.c_int, [C.POINTER(BwdfDesc), C.POINTER(ReduceJob)]),
+    'satcv_conv2d_bwd_fused_plan_info': (C.c_int, [C.POINTER(BwdfDesc), c_i32, C.POINTER(BwdfPlanInfo)]),
+    'satcv_convt_bwd_fused_plan_info': (C.c_int, [C.POINTER(CtbfDesc), c_i32, C.POINTER(CtbfPlanInfo)]),
     'satcv_convt_bwd_fused_workspace': (c_i64, [C.POINTER(CtbfDesc)]),
     'satcv_convt_bwd_fused': (C.c_int, [C.POINTER(CtbfDesc), c_vp]),
     'satcv_convt_bwd_fused_reduce_job': (C.c_int, [C.POINTER(CtbfDesc), C.POINTER(ReduceJob)]),

@@ -56,6 +56,9 @@ __device__ __forceinline__ bf16x4 tr_read4(const bf16* p) {
   return __builtin_bit_cast(bf16x4, v);
 }
 
+// which instantiations carry the fused sums of the layer below: one rule for the kernel and for the host's plan query
+constexpr bool bwdf_carries_sums(bool nodg, int wps, bool pool) { return !nodg && (wps != 1 || pool); }
+
 // WPS = waves per SIMD the registers are budgeted for: 2 (256 registers; 4 waves x 2 workgroups per CU, or 8 waves x 1), or 1 for
 // 64 -> 64 channels, whose 36 weight-gradient accumulator tiles + in-flight tile do not fit 256 registers at any wave count
 // POOL: encoder blocks -- the gradient of the activated output is da (skip) + the 2 x 2 max-pool's gradient routed by the arg-max bytes
@@ -268,7 +271,7 @@ __global__ __launch_bounds__(NW * 64, WPS) void bwd_fused_kernel(const BwdfArgs 
   }
 
   // (not in the one-wave-per-SIMD instantiation: its 120 registers of prefetched tile leave no room for 16 more accumulators)
-  constexpr bool BST = !NODG && (WPS != 1 || POOL);      // (not in the dense one-wave-per-SIMD form; the pooled one has the room)
+  constexpr bool BST = bwdf_carries_sums(NODG, WPS, POOL);      // (not in the dense one-wave-per-SIMD form; the pooled one has the room)
   float bs1[8], bs2[8];                                                       // fused sums of the layer below: this thread's 8 channels, all its tiles
 #pragma unroll
   for (int e = 0; e < 8; ++e) { bs1[e] = 0.f; bs2[e] = 0.f; }
@@ -563,17 +566,21 @@ struct BwdfGeom {
 };
 
 static int g_ncu = 0;
-static int bwdf_grid(size_t lds, int waves, int wps, long long total) {
-  if (!g_ncu) {
-    int dev = 0; hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return -1;
-    g_ncu = p.multiProcessorCount;
+// ncu > 0: plan for that CU count (the plan query: the HIP runtime is not touched); 0: the device's
+static int bwdf_grid(size_t lds, int waves, int wps, long long total, int ncu) {
+  if (ncu <= 0) {
+    if (!g_ncu) {
+      int dev = 0; hipDeviceProp_t p;
+      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) { (void)hipGetLastError(); return -1; }
+      g_ncu = p.multiProcessorCount;
+    }
+    ncu = g_ncu;
   }
   int per_cu = (int)((160 * 1024) / lds);
   const int by_waves = 4 * wps / waves;                             // wps waves per SIMD
   if (per_cu > by_waves) per_cu = by_waves;
   if (per_cu < 1) per_cu = 1;
-  long long grid = (long long)g_ncu * per_cu;
+  long long grid = (long long)ncu * per_cu;
   if (grid > total) grid = total;
   return (int)grid;
 }
@@ -581,6 +588,7 @@ static int bwdf_grid(size_t lds, int waves, int wps, long long total) {
 static bool bwdf_shape_ok(const satcv_bwdf_desc* d, int& cin_s) {
   cin_s = d->c0 + d->c1;
   if (d->dtype != SATCV_BF16 || d->kh != 3 || d->kw != 3 || d->dil != 1) return false;
+  if (d->n <= 0 || d->h <= 0 || d->w_ <= 0 || !satcv_pixels_ok(d->n, d->h, d->w_, 1)) return false;      // (pixel indices are 32-bit in the kernel)
   if (d->x1 && d->c0 % 8 != 0) return false;
   if (d->h % 8 != 0 || d->w_ % 32 != 0) return false;               // whole 8 x 32 tiles
   if (d->ldg % 8 != 0 || ((uintptr_t)d->g % 16) != 0 || ((uintptr_t)d->yraw % 16) != 0) return false;
@@ -601,13 +609,23 @@ static bool bwdf_shape_ok(const satcv_bwdf_desc* d, int& cin_s) {
 }
 
 template <int CIN, int COUT, int NW, int WPS, bool POOL = false, bool NODG = false, int CINS = CIN, bool HG = false>
-static int bwdf_launch(const satcv_bwdf_desc* d, hipStream_t st, bool query, int64_t* ws_bytes, satcv_reduce_job* job = nullptr) {
+static int bwdf_launch(const satcv_bwdf_desc* d, hipStream_t st, bool query, int64_t* ws_bytes, satcv_reduce_job* job, int ncu, satcv_bwdf_plan_info* plan) {
   using G = BwdfGeom<CIN, COUT, NW, NODG>;
   static_assert(G::LDS <= 160 * 1024, "tile + weights exceed the LDS");
   const long long total = (long long)d->n * (d->h / 8) * (d->w_ / 32);
-  const int grid = bwdf_grid(G::LDS, NW, WPS, total);
+  const int grid = bwdf_grid(G::LDS, NW, WPS, total, ncu);
   if (grid <= 0) { satcv_set_error("bwd_fused: device query failed"); return SATCV_ERR_HIP; }
   const size_t need = (size_t)grid * 9 * CIN * COUT * sizeof(float);
+  if (plan) {
+    // the instantiation and the tile ranges the kernel derives from (total, gridDim.x): total / grid tiles per workgroup, the first total % grid one more
+    *plan = satcv_bwdf_plan_info{};
+    plan->cin = CIN; plan->cout = COUT; plan->nw = NW; plan->wps = WPS; plan->pool = POOL; plan->nodg = NODG; plan->cins = CINS; plan->hg = HG;
+    plan->bst = bwdf_carries_sums(NODG, WPS, POOL);
+    plan->tiles = total; plan->workgroups = grid;
+    plan->tiles_min = total / grid; plan->tiles_max = total / grid + (total % grid ? 1 : 0);
+    plan->lds_bytes = (int64_t)G::LDS; plan->ws_bytes = (int64_t)need;
+    return SATCV_OK;
+  }
   if (job) { reduce_job_fill(job, d->workspace, d->dw, grid, 9, CIN, COUT, d->cin, COUT, 0, d->accumulate); return SATCV_OK; }
   if (query) { *ws_bytes = (int64_t)need; return SATCV_OK; }
   SATCV_CHECK((size_t)d->workspace_bytes >= need, "bwd_fused: workspace %lld < %zu", (long long)d->workspace_bytes, need);
@@ -634,26 +652,34 @@ static int bwdf_launch(const satcv_bwdf_desc* d, hipStream_t st, bool query, int
   return wgrad_reduce_slabs(d->workspace, d->dw, grid, 9, CIN, COUT, d->cin, COUT, d->accumulate, st);
 }
 
-static int bwdf_dispatch(const satcv_bwdf_desc* d, hipStream_t st, bool query, int64_t* ws_bytes, satcv_reduce_job* job = nullptr) {
+static int bwdf_dispatch(const satcv_bwdf_desc* d, hipStream_t st, bool query, int64_t* ws_bytes, satcv_reduce_job* job = nullptr, int ncu = 0,
+                         satcv_bwdf_plan_info* plan = nullptr) {
   int cin_s;
   if (!bwdf_shape_ok(d, cin_s)) return SATCV_ERR_UNSUPPORTED;
   if (d->dpool) {
     // (32 -> 64 with the pooled gradient: 92 registers of prefetched items -- the 8-wave form needs 172 bytes of scratch; one wave per SIMD fits)
-    if (d->dx) return bwdf_launch<32, 64, 4, 1, true, false>(d, st, query, ws_bytes, job);
-    return bwdf_launch<32, 32, 8, 2, true, true, 16>(d, st, query, ws_bytes, job);
+    if (d->dx) return bwdf_launch<32, 64, 4, 1, true, false>(d, st, query, ws_bytes, job, ncu, plan);
+    return bwdf_launch<32, 32, 8, 2, true, true, 16>(d, st, query, ws_bytes, job, ncu, plan);
   }
   // (32 -> 32: 8 waves x 1 workgroup per CU measured equal to 4 waves x 2 workgroups and leaves registers for the fused sums; with the
   //  weight-gradient products balanced over the waves the 4-wave form -- 256 registers, 32 bytes of scratch -- measured 365 vs 346 us)
-  if (cin_s == 32 && d->hg_dlogits) return bwdf_launch<32, 32, 8, 2, false, false, 32, true>(d, st, query, ws_bytes, job);
+  if (cin_s == 32 && d->hg_dlogits) return bwdf_launch<32, 32, 8, 2, false, false, 32, true>(d, st, query, ws_bytes, job, ncu, plan);
   if (d->hg_dlogits) return SATCV_ERR_UNSUPPORTED;
-  if (cin_s == 32) return bwdf_launch<32, 32, 8, 2>(d, st, query, ws_bytes, job);
-  if (d->cout == 32) return bwdf_launch<64, 32, 8, 2>(d, st, query, ws_bytes, job);
-  return bwdf_launch<64, 64, 4, 1>(d, st, query, ws_bytes, job);
+  if (cin_s == 32) return bwdf_launch<32, 32, 8, 2>(d, st, query, ws_bytes, job, ncu, plan);
+  if (d->cout == 32) return bwdf_launch<64, 32, 8, 2>(d, st, query, ws_bytes, job, ncu, plan);
+  return bwdf_launch<64, 64, 4, 1>(d, st, query, ws_bytes, job, ncu, plan);
 }
 
 extern "C" int satcv_conv2d_bwd_fused_reduce_job(const satcv_bwdf_desc* d, satcv_reduce_job* job) {
   SATCV_CHECK(d && job && d->dw && d->workspace, "bwd_fused_reduce_job: null pointer");
   return bwdf_dispatch(d, nullptr, false, nullptr, job);
+}
+
+extern "C" int satcv_conv2d_bwd_fused_plan_info(const satcv_bwdf_desc* d, int32_t ncu, satcv_bwdf_plan_info* info) {
+  SATCV_CHECK(d && info && ncu >= 0, "bwd_fused_plan_info: null pointer or negative CU count");
+  const int rc = bwdf_dispatch(d, nullptr, true, nullptr, nullptr, ncu, info);
+  if (rc == SATCV_ERR_UNSUPPORTED) satcv_set_error("bwd_fused_plan_info: shape outside the kernel's limits");
+  return rc;
 }
 
 extern "C" int64_t satcv_conv2d_bwd_fused_workspace(const satcv_bwdf_desc* d) {

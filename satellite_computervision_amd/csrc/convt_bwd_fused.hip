@@ -365,19 +365,31 @@ __global__ __launch_bounds__(768, 1) void convt_bwd_fused_kernel(const CtbfArgs 
 // ------------------------------------------------------------------ host side
 static int g_ct_ncu = 0;
 template <int COUT4, int PX, int CBLK>
-static int ctbf_launch(const satcv_ctbf_desc* d, hipStream_t st, bool query, int64_t* ws_bytes, satcv_reduce_job* job) {
+static int ctbf_launch(const satcv_ctbf_desc* d, hipStream_t st, bool query, int64_t* ws_bytes, satcv_reduce_job* job, int ncu, satcv_ctbf_plan_info* plan) {
   using G = CtbfGeom<COUT4, PX, CBLK>;
   static_assert(G::LDS <= 160 * 1024, "buffers + operand image exceed the LDS");
   if (d->w_ % PX != 0 || d->cin % CBLK != 0) return SATCV_ERR_UNSUPPORTED;
-  if (!g_ct_ncu) {
-    int dev = 0; hipDeviceProp_t p;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) { (void)hipGetLastError(); g_ct_ncu = 256; }
-    else g_ct_ncu = p.multiProcessorCount;
+  if (ncu <= 0) {                        // (ncu > 0: the plan query's CU count -- the HIP runtime is not touched)
+    if (!g_ct_ncu) {
+      int dev = 0; hipDeviceProp_t p;
+      if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) { (void)hipGetLastError(); g_ct_ncu = 256; }
+      else g_ct_ncu = p.multiProcessorCount;
+    }
+    ncu = g_ct_ncu;
   }
   const int nblk = d->cin / CBLK;
   const long long tiles = (long long)d->n * d->h * (d->w_ / PX);
-  long long slabs = g_ct_ncu / nblk; if (slabs < 1) slabs = 1; if (slabs > tiles) slabs = tiles;
+  long long slabs = ncu / nblk; if (slabs < 1) slabs = 1; if (slabs > tiles) slabs = tiles;
   const size_t need = (size_t)slabs * d->cin * COUT4 * sizeof(float);
+  if (plan) {
+    // the instantiation and the tile ranges the kernel derives from (tiles, slabs): tiles / slabs per slab, the first tiles % slabs one more
+    *plan = satcv_ctbf_plan_info{};
+    plan->cout4 = COUT4; plan->px = PX; plan->cblk = CBLK; plan->nblk = nblk;
+    plan->slabs = slabs; plan->tiles = tiles;
+    plan->tiles_min = tiles / slabs; plan->tiles_max = tiles / slabs + (tiles % slabs ? 1 : 0);
+    plan->lds_bytes = (int64_t)G::LDS; plan->ws_bytes = (int64_t)need;
+    return SATCV_OK;
+  }
   if (job) { reduce_job_fill(job, d->workspace, d->dw, (int)slabs, 1, d->cin, COUT4, d->cin, COUT4, 1, d->accumulate); return SATCV_OK; }
   if (query) { *ws_bytes = (int64_t)need; return SATCV_OK; }
   SATCV_CHECK((size_t)d->workspace_bytes >= need, "convt_bwd_fused: workspace %lld < %zu", (long long)d->workspace_bytes, need);
@@ -402,7 +414,8 @@ static int ctbf_launch(const satcv_ctbf_desc* d, hipStream_t st, bool query, int
   return wgrad_reduce_slabs_t(d->workspace, d->dw, (int)slabs, d->cin, COUT4, d->cin, COUT4, d->accumulate, st);
 }
 
-static int ctbf_dispatch(const satcv_ctbf_desc* d, hipStream_t st, bool query, int64_t* ws_bytes, satcv_reduce_job* job = nullptr) {
+static int ctbf_dispatch(const satcv_ctbf_desc* d, hipStream_t st, bool query, int64_t* ws_bytes, satcv_reduce_job* job = nullptr, int ncu = 0,
+                         satcv_ctbf_plan_info* plan = nullptr) {
   if (!d || d->dtype != SATCV_BF16 || d->f != 2 || d->cin <= 0 || d->cin % 64 != 0 || d->n <= 0 || d->h <= 0 || d->w_ <= 0) return SATCV_ERR_UNSUPPORTED;
   if (!satcv_pixels_ok(d->n, d->h, d->w_, 2) || d->cin > (1 << 16)) return SATCV_ERR_UNSUPPORTED;
   if (d->ldg % 8 || d->ldy % 8 || d->ldx % 8 || d->lddx % 8 || d->w_npad < d->cin || d->w_npad % 8) return SATCV_ERR_UNSUPPORTED;
@@ -414,10 +427,17 @@ static int ctbf_dispatch(const satcv_ctbf_desc* d, hipStream_t st, bool query, i
   // Cout 128 (512 gradient channels: 64 KB of operand image per 64 input channels, four blocks each re-forming the tile) measured no
   // faster than the three launches it would replace (141 us against 152 at batch 64) and is not instantiated
   switch (d->cout) {
-    case 32: return ctbf_launch<128, 64, 64>(d, st, query, ws_bytes, job);
-    case 64: return d->cin % 128 == 0 ? ctbf_launch<256, 32, 128>(d, st, query, ws_bytes, job) : ctbf_launch<256, 32, 64>(d, st, query, ws_bytes, job);
+    case 32: return ctbf_launch<128, 64, 64>(d, st, query, ws_bytes, job, ncu, plan);
+    case 64: return d->cin % 128 == 0 ? ctbf_launch<256, 32, 128>(d, st, query, ws_bytes, job, ncu, plan) : ctbf_launch<256, 32, 64>(d, st, query, ws_bytes, job, ncu, plan);
     default: return SATCV_ERR_UNSUPPORTED;
   }
+}
+
+extern "C" int satcv_convt_bwd_fused_plan_info(const satcv_ctbf_desc* d, int32_t ncu, satcv_ctbf_plan_info* info) {
+  SATCV_CHECK(d && info && ncu >= 0, "convt_bwd_fused_plan_info: null pointer or negative CU count");
+  const int rc = ctbf_dispatch(d, nullptr, true, nullptr, nullptr, ncu, info);
+  if (rc == SATCV_ERR_UNSUPPORTED) satcv_set_error("convt_bwd_fused_plan_info: shape outside the kernel's limits");
+  return rc;
 }
 
 extern "C" int64_t satcv_convt_bwd_fused_workspace(const satcv_ctbf_desc* d) {

@@ -201,7 +201,7 @@ def make_wgrad_desc(*, x0, c0, dy, lddy, dw, cin, cout, n, h, w_, dtype, x1=None
 def make_bwdf_desc(*, g, yraw, ldg, bn_scale, bn_shift, bn_mean, bn_rstd, bn_coef, x0, c0, w_dgrad, dx, lddx, dw, cin, cout, n, h, w_, dtype,
                    linear=0, x1=None, c1=0, in_scale=None, in_shift=None, in_relu=0, kh=3, kw=3, dil=1, workspace=None, workspace_bytes=0,
                    accumulate=0, bst_sums=None, bst_sums_ld=0, bst_mean=None, bst_rstd=None, bst_act_form=0, dpool=None, lddp=0, amax=None,
-                   hg_dlogits=None, hg_w=None, hg_ncls=0):
+                   hg_dlogits=None, hg_w=None, hg_ncls=0, defer_reduce=0):
     from ._lib import BwdfDesc
     d = BwdfDesc()
     d.g, d.yraw, d.ldg = g, yraw, ldg
@@ -214,6 +214,7 @@ def make_bwdf_desc(*, g, yraw, ldg, bn_scale, bn_shift, bn_mean, bn_rstd, bn_coe
     d.bst_sums, d.bst_sums_ld, d.bst_mean, d.bst_rstd, d.bst_act_form = bst_sums, bst_sums_ld, bst_mean, bst_rstd, int(bst_act_form)
     d.dpool, d.lddp, d.amax = dpool, lddp, amax
     d.hg_dlogits, d.hg_w, d.hg_ncls = hg_dlogits, hg_w, int(hg_ncls)
+    d.defer_reduce = int(defer_reduce)
     return d
 
 

@@ -119,6 +119,52 @@ int main(void) {
   satcv_bwdf_desc fd; memset(&fd, 0, sizeof(fd));
   EXPECT(satcv_conv2d_bwd_fused(NULL, NULL) != 0 && satcv_conv2d_bwd_fused(&fd, NULL) != 0, "invalid fused desc");
   EXPECT(satcv_conv2d_bwd_fused_workspace(NULL) < 0 && satcv_conv2d_bwd_fused_workspace(&fd) < 0, "fused workspace of an invalid desc");
+  {
+    /* the fused backward kernels' plan queries: null / zeroed / out-of-limits descriptors are refused with a message; a served one reports a
+     * geometry that adds up, for any CU count, with no device */
+    satcv_bwdf_plan_info fi; satcv_ctbf_plan_info ti;
+    satcv_ctbf_desc td; memset(&td, 0, sizeof(td));
+    EXPECT(satcv_conv2d_bwd_fused_plan_info(NULL, 256, &fi) != 0 && satcv_conv2d_bwd_fused_plan_info(&fd, 256, NULL) != 0 &&
+           satcv_conv2d_bwd_fused_plan_info(&fd, 256, &fi) != 0 && satcv_conv2d_bwd_fused_plan_info(&fd, -1, &fi) != 0, "invalid fused plan query");
+    EXPECT(satcv_convt_bwd_fused_plan_info(NULL, 256, &ti) != 0 && satcv_convt_bwd_fused_plan_info(&td, 256, NULL) != 0 &&
+           satcv_convt_bwd_fused_plan_info(&td, 256, &ti) != 0 && satcv_convt_bwd_fused_plan_info(&td, -1, &ti) != 0, "invalid convT fused plan query");
+    EXPECT(satcv_convt_bwd_fused_workspace(NULL) < 0 && satcv_convt_bwd_fused_workspace(&td) < 0 && satcv_convt_bwd_fused(&td, NULL) != 0, "invalid convT fused desc");
+    void* fk = (void*)(uintptr_t)0x7f0000001000ull;
+    static const int FC[][2] = {{32, 32}, {64, 32}, {64, 64}, {32, 64}, {48, 32}, {64, 128}};
+    static const int NCU[] = {1, 8, 255, 256, 304, 0x7fffffff};
+    int served = 0;
+    for (unsigned c = 0; c < sizeof(FC) / sizeof(FC[0]); ++c)
+      for (int n = 1; n <= 64; n *= 4)
+        for (int h = 8; h <= 264; h += 64)
+          for (int w = 32; w <= 288; w += 64)
+            for (unsigned k = 0; k < sizeof(NCU) / sizeof(NCU[0]); ++k) {
+              satcv_bwdf_desc d; memset(&d, 0, sizeof(d));
+              d.g = fk; d.yraw = fk; d.ldg = FC[c][1]; d.x0 = fk; d.c0 = FC[c][0]; d.w_dgrad = fk; d.dx = fk; d.lddx = FC[c][0]; d.dw = (float*)fk;
+              d.cin = FC[c][0]; d.cout = FC[c][1]; d.n = n; d.h = h; d.w_ = w; d.kh = d.kw = 3; d.dil = 1; d.dtype = SATCV_BF16;
+              (void)satcv_set_option("no_such_option", 1);
+              if (satcv_conv2d_bwd_fused_plan_info(&d, NCU[k], &fi) == 0) {
+                ++served;
+                EXPECT(fi.workgroups > 0 && fi.workgroups <= fi.tiles && fi.tiles == (int64_t)n * (h / 8) * (w / 32) && fi.tiles_min >= 1 &&
+                       fi.tiles_max - fi.tiles_min <= 1 && fi.tiles_min * fi.workgroups <= fi.tiles && fi.tiles_max * fi.workgroups >= fi.tiles &&
+                       fi.lds_bytes > 0 && fi.lds_bytes <= 160 * 1024 && fi.ws_bytes == fi.workgroups * 9 * fi.cin * fi.cout * 4, "fused plan geometry");
+              } else EXPECT(!strstr(satcv_last_error(), "no_such_option"), "a refused fused plan query says why");
+              satcv_ctbf_desc t; memset(&t, 0, sizeof(t));
+              t.g = fk; t.ldg = 2 * FC[c][1]; t.yup = fk; t.ldy = FC[c][1]; t.x = fk; t.ldx = 2 * FC[c][0]; t.w_dgrad = fk; t.w_npad = 2 * FC[c][0]; t.dx = fk; t.lddx = 2 * FC[c][0];
+              t.dw = (float*)fk; t.cin = 2 * FC[c][0]; t.cout = FC[c][1]; t.n = n; t.h = h; t.w_ = w; t.f = 2; t.dtype = SATCV_BF16;
+              (void)satcv_set_option("no_such_option", 1);
+              if (satcv_convt_bwd_fused_plan_info(&t, NCU[k], &ti) == 0) {
+                ++served;
+                EXPECT(ti.slabs > 0 && ti.slabs <= ti.tiles && ti.nblk * ti.cblk == t.cin && ti.tiles == (int64_t)n * h * (w / ti.px) && ti.tiles_min >= 1 &&
+                       ti.tiles_max - ti.tiles_min <= 1 && ti.tiles_min * ti.slabs <= ti.tiles && ti.tiles_max * ti.slabs >= ti.tiles &&
+                       ti.lds_bytes > 0 && ti.lds_bytes <= 160 * 1024 && ti.ws_bytes == ti.slabs * t.cin * ti.cout4 * 4, "convT fused plan geometry");
+              } else EXPECT(!strstr(satcv_last_error(), "no_such_option"), "a refused convT fused plan query says why");
+            }
+    EXPECT(served > 500, "fused plan queries answered (%d)", served);
+    satcv_bwdf_desc d; memset(&d, 0, sizeof(d));
+    d.g = fk; d.yraw = fk; d.ldg = 32; d.x0 = fk; d.c0 = 32; d.w_dgrad = fk; d.dx = fk; d.lddx = 32; d.dw = (float*)fk; d.cin = 32; d.cout = 32;
+    d.n = 0x7fffffff; d.h = 0x7ffffff8; d.w_ = 32; d.kh = d.kw = 3; d.dil = 1; d.dtype = SATCV_BF16;
+    EXPECT(satcv_conv2d_bwd_fused_plan_info(&d, 256, &fi) != 0 && satcv_conv2d_bwd_fused_workspace(&d) < 0, "fused plan: extents beyond 2^31 pixels");
+  }
   satcv_bnbwd_desc bd; memset(&bd, 0, sizeof(bd));
   EXPECT(satcv_bn_bwd_reduce(&bd, NULL) != 0 && satcv_bn_bwd_apply(&bd, NULL) != 0, "zeroed bn-backward desc");
   satcv_head_desc hd; memset(&hd, 0, sizeof(hd));
