@@ -875,6 +875,30 @@ typedef struct satcv_dense_desc {
  * dx_dtype other than float32 / bf16.  The nearest index is evaluated in float32, floorf((i + 0.5f) * ((float) in / (float) out)). */
 int satcv_dense_small_fwd(const satcv_dense_desc* d, void* stream);
 int satcv_dense_small_bwd(const satcv_dense_desc* d, void* stream);
+/* satcv_dense_scene_fwd: the fusion head of a scene prediction.  It is satcv_dense_small_fwd restricted to the centre crop of every
+ * chip, storing straight into the prediction map: the last Conv2D(k, [1, 1]) of get_hybrid_model / get_hierarchical_model
+ * (utils/model_tools.py:902-911, 1047-1049) together with the crop and placement of the chip loop of
+ * utils/prediction_tools.py:133-156 -- bit-equal to satcv_dense_small_fwd followed by satcv_scene_scatter (accumulate 0), without
+ * the (n, h, w_, cout) probability tensor in between and without the arithmetic of the pixels the crop throws away.
+ *   head:  sources, w, b, cout, activation, max_value as for satcv_dense_small_fwd; h, w_ the CHIP grid and npix = n * h * w_ (n chips);
+ *          out, classes, z_out and the backward fields (dout, dz_out, dw, db, src[i].dx) must be NULL
+ *   crop_h x crop_w pixels starting at (crop_y, crop_x) of chip k go to map position origins[first + k] (origins, total, first as for
+ *          satcv_scene_scatter), clipped to [0, map_h) x [0, map_w).  A resized source is read through the nearest index of the CHIP
+ *          grid (h, w_ against hs, ws) at chip coordinates (crop_y + v, crop_x + u), exactly as satcv_dense_small_fwd reads it
+ *   map:   float32 (map_h, map_w, ldm); output channels [c0, c0 + nc) are stored at map channels 0 .. nc - 1 (nc <= ldm)
+ *   class_map: optional uint8 (map_h, map_w), the argmax (first of equals) of a softmax head (activation 0 only)
+ * Contract: the placed windows of the chips of ONE launch are pairwise disjoint (plain stores, no accumulation).
+ * Refused, naming the entry point and writing nothing: a NULL map or origin table, c0 + nc > cout, nc > ldm, a crop outside the chip
+ * grid, class_map with a non-softmax activation, first + n > total, a non-NULL head.out / classes / z_out / backward field, and
+ * everything satcv_dense_small_fwd refuses of the sources and the grid. */
+typedef struct satcv_dense_scene_desc {
+  satcv_dense_desc head;
+  int32_t crop_y, crop_x, crop_h, crop_w;
+  const int32_t* origins; int32_t total, first;
+  float* map; int32_t map_h, map_w, ldm, c0, nc;
+  uint8_t* class_map;
+} satcv_dense_scene_desc;
+int satcv_dense_scene_fwd(const satcv_dense_scene_desc* d, void* stream);
 
 /* ------------------------------------------------------- stream utilities */
 int satcv_graph_begin(void* stream);

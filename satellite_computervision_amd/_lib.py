@@ -219,6 +219,15 @@ class DenseDesc(C.Structure):
                 ('dout', c_vp), ('dz_out', c_vp), ('dw', c_vp), ('db', c_vp)]
 
 
+class DenseSceneDesc(C.Structure):
+    """satcv_dense_scene_desc: a DenseDesc (out / classes / z_out / backward fields NULL) + the crop, the origin table and the scene map"""
+    _fields_ = [('head', DenseDesc),
+                ('crop_y', c_i32), ('crop_x', c_i32), ('crop_h', c_i32), ('crop_w', c_i32),
+                ('origins', c_vp), ('total', c_i32), ('first', c_i32),
+                ('map', c_vp), ('map_h', c_i32), ('map_w', c_i32), ('ldm', c_i32), ('c0', c_i32), ('nc', c_i32),
+                ('class_map', c_vp)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/satcv.h
 _SIGS = {
     'satcv_version': (C.c_char_p, []),
@@ -302,6 +311,7 @@ _SIGS = {
     'satcv_convlstm_step_supported': (C.c_int, [c_i32, c_i32]),
     'satcv_dense_small_fwd': (C.c_int, [C.POINTER(DenseDesc), c_vp]),
     'satcv_dense_small_bwd': (C.c_int, [C.POINTER(DenseDesc), c_vp]),
+    'satcv_dense_scene_fwd': (C.c_int, [C.POINTER(DenseSceneDesc), c_vp]),
     'satcv_zero2': (C.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp]),
     'satcv_graph_begin': (C.c_int, [c_vp]),
     'satcv_graph_end': (C.c_int, [c_vp, C.POINTER(c_vp)]),

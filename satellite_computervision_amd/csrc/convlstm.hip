@@ -12,6 +12,8 @@
 //   * satcv_dense_small_fwd/_bwd  Conv2D(k, 1x1) on one or two sources (concatenated), each optionally with a pending BatchNorm + ReLU and
 //                                 a nearest-neighbour resize (tf.image.resize(..., 'nearest')), activation softmax / sigmoid / linear /
 //                                 ReLU(max_value): the 1x1 `dense` layers and the three-way fusion head of get_hybrid_model.
+//   * satcv_dense_scene_fwd       the same head on the centre crop of every chip only, stored straight into a scene map (the fusion head of
+//                                 prediction_tools.predict_hybrid_scene): dense_small_fwd + scene_scatter without the tensor in between
 #include "common.hpp"
 
 #define EW_BLOCK 256
@@ -205,47 +207,142 @@ __device__ __forceinline__ float dense_src_val(const satcv_dense_src& s, long lo
   if (s.in_scale) { v = v * s.in_scale[c] + s.in_shift[c]; if (s.in_relu) v = fmaxf(v, 0.f); }
   return v;
 }
+// source pixel of pixel (n, y, x) of the output grid h x w
+__device__ __forceinline__ long long dense_src_pix_at(const satcv_dense_src& s, long long n, int y, int x, int h, int w) {
+  if (s.hs == 0) return (n * h + y) * w + x;
+  return (n * s.hs + nn_src(y, s.hs, h)) * s.ws + nn_src(x, s.ws, w);
+}
 // source pixel of output pixel p (n, y, x on the output grid h x w)
 __device__ __forceinline__ long long dense_src_pix(const satcv_dense_src& s, long long p, int h, int w) {
   if (s.hs == 0) return p;
   const int x = (int)(p % w); long long r = p / w;
   const int y = (int)(r % h); const long long n = r / h;
-  return (n * s.hs + nn_src(y, s.hs, h)) * s.ws + nn_src(x, s.ws, w);
+  return dense_src_pix_at(s, n, y, x, h, w);
 }
 
 #define DENSE_KMAX 16
-__global__ __launch_bounds__(EW_BLOCK) void dense_small_fwd_kernel(const satcv_dense_desc d) {
+// The per-pixel arithmetic of BOTH forward kernels (dense_small_fwd_kernel, dense_scene_fwd_kernel): bias seed, the sources in order,
+// their channels ascending, then the activation, with the softmax's `best` / first-of-equals argmax.  The kernel's side is `sink`:
+// sink.pix(s) the pixel's index in source s; the results leave through sink.z(j, v) (the pre-activation of output j, asked for with
+// sink.wants_z()), sink.out(j, v) (its activated value) and sink.cls(am) (the argmax of a softmax head) -- the loops over the outputs
+// stay the rolled loops they were, each kernel stores where it must.
+// WIDE: every source is read 16 bytes at a time (8 bf16 / 4 f32 channels; the host has checked ld and the alignment) -- the same values
+// summed in the same order as the one-load-per-channel form, so the two give equal bits.  A 16-byte item may reach into the channels
+// [cin, ld) of the pixel's own row; those elements are loaded and never used.
+template <bool WIDE, typename Sink>
+__device__ __forceinline__ void dense_pixel(const satcv_dense_desc& d, const Sink& sink) {
   const int k = d.cout;
-  for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < d.npix; p += (long long)gridDim.x * blockDim.x) {
-    float z[DENSE_KMAX];
+  float z[DENSE_KMAX];
 #pragma unroll
-    for (int j = 0; j < DENSE_KMAX; ++j) z[j] = j < k ? d.b[j] : 0.f;
-    int row = 0;
-    for (int si = 0; si < d.nsrc; ++si) {
-      const satcv_dense_src& s = d.src[si];
-      const long long q = dense_src_pix(s, p, d.h, d.w_);
+  for (int j = 0; j < DENSE_KMAX; ++j) z[j] = j < k ? d.b[j] : 0.f;
+  int row = 0;
+  for (int si = 0; si < d.nsrc; ++si) {
+    const satcv_dense_src& s = d.src[si];
+    const long long q = sink.pix(s);
+    if constexpr (WIDE) {
+      if (s.dtype == SATCV_BF16) {
+        const bf16* px = reinterpret_cast<const bf16*>(s.x) + q * s.ld;
+        for (int c0 = 0; c0 < s.cin; c0 += 8) {
+          const bf16x8 v = *reinterpret_cast<const bf16x8*>(px + c0);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int c = c0 + e;
+            if (c < s.cin) {
+              float a = (float)v[e];
+              if (s.in_scale) { a = a * s.in_scale[c] + s.in_shift[c]; if (s.in_relu) a = fmaxf(a, 0.f); }
+#pragma unroll
+              for (int j = 0; j < DENSE_KMAX; ++j) if (j < k) z[j] += a * d.w[(row + c) * k + j];
+            }
+          }
+        }
+      } else {
+        const float* px = reinterpret_cast<const float*>(s.x) + q * s.ld;
+        for (int c0 = 0; c0 < s.cin; c0 += 4) {
+          const float4 v4 = *reinterpret_cast<const float4*>(px + c0);
+          const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int c = c0 + e;
+            if (c < s.cin) {
+              float a = v[e];
+              if (s.in_scale) { a = a * s.in_scale[c] + s.in_shift[c]; if (s.in_relu) a = fmaxf(a, 0.f); }
+#pragma unroll
+              for (int j = 0; j < DENSE_KMAX; ++j) if (j < k) z[j] += a * d.w[(row + c) * k + j];
+            }
+          }
+        }
+      }
+    } else {
       for (int c = 0; c < s.cin; ++c) {
         const float a = dense_src_val(s, q, c);
 #pragma unroll
         for (int j = 0; j < DENSE_KMAX; ++j) if (j < k) z[j] += a * d.w[(row + c) * k + j];
       }
-      row += s.cin;
     }
-    if (d.z_out) { for (int j = 0; j < k; ++j) d.z_out[p * k + j] = z[j]; }
-    if (d.activation == 0) {
-      float mx = z[0]; for (int j = 1; j < k; ++j) mx = fmaxf(mx, z[j]);
-      float sum = 0.f, ex[DENSE_KMAX];
-      for (int j = 0; j < k; ++j) { ex[j] = expf(z[j] - mx); sum += ex[j]; }
-      float best = -1.f; int am = 0;
-      for (int j = 0; j < k; ++j) { const float pr = ex[j] / sum; d.out[p * k + j] = pr; if (pr > best) { best = pr; am = j; } }
-      if (d.classes) d.classes[p] = am;
-    } else if (d.activation == 1) {
-      for (int j = 0; j < k; ++j) d.out[p * k + j] = 1.f / (1.f + expf(-z[j]));
-    } else if (d.activation == 2) {
-      for (int j = 0; j < k; ++j) d.out[p * k + j] = z[j];
-    } else {
-      for (int j = 0; j < k; ++j) { float v = fmaxf(z[j], 0.f); if (d.max_value > 0.f) v = fminf(v, d.max_value); d.out[p * k + j] = v; }
-    }
+    row += s.cin;
+  }
+  if (sink.wants_z()) { for (int j = 0; j < k; ++j) sink.z(j, z[j]); }
+  if (d.activation == 0) {
+    float mx = z[0]; for (int j = 1; j < k; ++j) mx = fmaxf(mx, z[j]);
+    float sum = 0.f, ex[DENSE_KMAX];
+    for (int j = 0; j < k; ++j) { ex[j] = expf(z[j] - mx); sum += ex[j]; }
+    float best = -1.f; int am = 0;
+    for (int j = 0; j < k; ++j) { const float pr = ex[j] / sum; sink.out(j, pr); if (pr > best) { best = pr; am = j; } }
+    sink.cls(am);
+  } else if (d.activation == 1) {
+    for (int j = 0; j < k; ++j) sink.out(j, 1.f / (1.f + expf(-z[j])));
+  } else if (d.activation == 2) {
+    for (int j = 0; j < k; ++j) sink.out(j, z[j]);
+  } else {
+    for (int j = 0; j < k; ++j) { float v = fmaxf(z[j], 0.f); if (d.max_value > 0.f) v = fminf(v, d.max_value); sink.out(j, v); }
+  }
+}
+
+// sink of satcv_dense_small_fwd: (npix, cout) tensors
+struct dense_tensor_sink {
+  const satcv_dense_desc& d; long long p;
+  __device__ __forceinline__ long long pix(const satcv_dense_src& s) const { return dense_src_pix(s, p, d.h, d.w_); }
+  __device__ __forceinline__ bool wants_z() const { return d.z_out != nullptr; }
+  __device__ __forceinline__ void z(int j, float v) const { d.z_out[p * d.cout + j] = v; }
+  __device__ __forceinline__ void out(int j, float v) const { d.out[p * d.cout + j] = v; }
+  __device__ __forceinline__ void cls(int am) const { if (d.classes) d.classes[p] = am; }
+};
+__global__ __launch_bounds__(EW_BLOCK) void dense_small_fwd_kernel(const satcv_dense_desc d) {
+  for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < d.npix; p += (long long)gridDim.x * blockDim.x) {
+    const dense_tensor_sink sink{d, p};
+    dense_pixel<false>(d, sink);
+  }
+}
+
+// sink of satcv_dense_scene_fwd: output channels [c0, c0 + nc) at channels 0 .. nc - 1 of one map pixel, the class into the class map
+struct dense_map_sink {
+  const satcv_dense_desc& d; long long chip; int y, x;       // (y, x): chip coordinates of the crop pixel
+  float* dst; uint8_t* cls_dst; int c0, nc;
+  __device__ __forceinline__ long long pix(const satcv_dense_src& s) const { return dense_src_pix_at(s, chip, y, x, d.h, d.w_); }
+  __device__ __forceinline__ bool wants_z() const { return false; }
+  __device__ __forceinline__ void z(int, float) const {}
+  __device__ __forceinline__ void out(int j, float v) const { const int e = j - c0; if (e >= 0 && e < nc) dst[e] = v; }
+  __device__ __forceinline__ void cls(int am) const { if (cls_dst) *cls_dst = (uint8_t)am; }
+};
+// The same head restricted to the centre crop of every chip, stored straight into the scene map (satcv_dense_scene_fwd).  One item is one
+// crop pixel of one chip; x of the crop row runs fastest across lanes (a crop row is crop_w contiguous map pixels and, for a source on the
+// chip grid, crop_w contiguous source pixels), then the rows, then the chips.  Items whose destination lies outside the map are skipped
+// before any arithmetic.  Plain stores: the placed windows of one launch are pairwise disjoint (contract).  No LDS.
+template <bool WIDE>
+__global__ __launch_bounds__(EW_BLOCK) void dense_scene_fwd_kernel(const satcv_dense_scene_desc sd) {
+  const satcv_dense_desc& d = sd.head;
+  const int cw = sd.crop_w, chh = sd.crop_h;
+  const long long total = (d.npix / ((long long)d.h * d.w_)) * chh * cw;
+  for (long long it = blockIdx.x * (long long)blockDim.x + threadIdx.x; it < total; it += (long long)gridDim.x * blockDim.x) {
+    const int u = (int)(it % cw);
+    const int v = (int)((it / cw) % chh);
+    const long long kc = it / ((long long)cw * chh);
+    const int* og = sd.origins + 2 * (size_t)(sd.first + kc);
+    const long long y = (long long)og[0] + v, x = (long long)og[1] + u;
+    if (y < 0 || y >= sd.map_h || x < 0 || x >= sd.map_w) continue;           // clipped to the map
+    const size_t mp = (size_t)y * sd.map_w + (size_t)x;
+    const dense_map_sink sink{d, kc, sd.crop_y + v, sd.crop_x + u, sd.map + mp * sd.ldm, sd.class_map ? sd.class_map + mp : nullptr, sd.c0, sd.nc};
+    dense_pixel<WIDE>(d, sink);
   }
 }
 // what both directions ask of the sources and of the output grid (the kernels index with ld / cin, divide by h and w_, and read in_shift
@@ -266,6 +363,40 @@ extern "C" int satcv_dense_small_fwd(const satcv_dense_desc* d, void* stream) {
   if (const int rc = dense_check_sources(d, "dense_small_fwd")) return rc;
   hipLaunchKernelGGL(dense_small_fwd_kernel, dim3(lstm_grid(d->npix)), dim3(EW_BLOCK), 0, (hipStream_t)stream, *d);
   LSTM_OK("dense_small_fwd");
+  return SATCV_OK;
+}
+
+// every source readable 16 bytes at a time: the base and every pixel row on a 16-byte boundary
+static bool dense_sources_wide(const satcv_dense_desc* d) {
+  for (int i = 0; i < d->nsrc; ++i) {
+    const satcv_dense_src& s = d->src[i];
+    const size_t es = s.dtype == SATCV_BF16 ? 2 : 4;
+    if ((uintptr_t)s.x % 16 != 0 || ((size_t)s.ld * es) % 16 != 0) return false;
+  }
+  return true;
+}
+extern "C" int satcv_dense_scene_fwd(const satcv_dense_scene_desc* sd, void* stream) {
+  SATCV_CHECK(sd, "dense_scene_fwd: null descriptor");
+  const satcv_dense_desc* d = &sd->head;
+  SATCV_CHECK(d->w && d->b && d->npix > 0 && d->nsrc >= 1 && d->nsrc <= 2 && d->cout >= 1 && d->cout <= DENSE_KMAX, "dense_scene_fwd: bad args");
+  SATCV_CHECK(d->activation >= 0 && d->activation <= 3, "dense_scene_fwd: activation must be 0 softmax, 1 sigmoid, 2 linear or 3 ReLU");
+  SATCV_CHECK(!d->out && !d->classes && !d->z_out, "dense_scene_fwd: head.out, head.classes and head.z_out must be NULL (the map is the output)");
+  SATCV_CHECK(!d->dout && !d->dz_out && !d->dw && !d->db && !d->src[0].dx && !(d->nsrc > 1 && d->src[1].dx), "dense_scene_fwd: the backward fields of head must be NULL");
+  SATCV_CHECK(sd->map && sd->origins, "dense_scene_fwd: null map or origin table");
+  if (const int rc = dense_check_sources(d, "dense_scene_fwd")) return rc;
+  SATCV_CHECK(sd->map_h > 0 && sd->map_w > 0 && sd->ldm > 0 && satcv_pixels_ok(1, sd->map_h, sd->map_w, 1), "dense_scene_fwd: map sizes must be positive, below 2^31 pixels");
+  SATCV_CHECK(sd->c0 >= 0 && sd->nc >= 1 && (long long)sd->c0 + sd->nc <= d->cout, "dense_scene_fwd: output channel range (c0 + nc <= cout)");
+  SATCV_CHECK(sd->nc <= sd->ldm, "dense_scene_fwd: nc channels do not fit a map pixel of ldm");
+  SATCV_CHECK(sd->crop_y >= 0 && sd->crop_x >= 0 && sd->crop_h > 0 && sd->crop_w > 0 && (long long)sd->crop_y + sd->crop_h <= d->h &&
+              (long long)sd->crop_x + sd->crop_w <= d->w_, "dense_scene_fwd: crop outside the chip grid");
+  SATCV_CHECK(!sd->class_map || d->activation == 0, "dense_scene_fwd: class_map needs a softmax head (activation 0)");
+  const long long n = d->npix / ((long long)d->h * d->w_);
+  SATCV_CHECK(sd->first >= 0 && sd->total > 0 && (long long)sd->first + n <= sd->total, "dense_scene_fwd: chips [first, first + n) outside the origin table");
+  SATCV_CHECK(d->npix < (1LL << 31), "dense_scene_fwd: chips beyond 2^31 pixels");
+  const dim3 grid(lstm_grid(n * sd->crop_h * sd->crop_w)), block(EW_BLOCK);
+  if (dense_sources_wide(d)) hipLaunchKernelGGL(dense_scene_fwd_kernel<true>, grid, block, 0, (hipStream_t)stream, *sd);
+  else hipLaunchKernelGGL(dense_scene_fwd_kernel<false>, grid, block, 0, (hipStream_t)stream, *sd);
+  LSTM_OK("dense_scene_fwd");
   return SATCV_OK;
 }
 

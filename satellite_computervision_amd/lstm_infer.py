@@ -146,6 +146,50 @@ class _PlannedBN:
         return lt.Act(a.t, a.c, (self.scale, self.shift, None, None), relu)
 
 
+def _stage_prefix(dst, src, lead, B, what):
+    """copy an input into its static tensor `dst` ((lead * B, ...)); `src` may hold fewer chips than the plan (a short last batch): they
+    fill a prefix of every one of the `lead` time steps, the stale rest is computed and ignored (inference BatchNorm uses moving
+    statistics: chips are independent).  -> the number of chips staged"""
+    if src.dtype != dst.dtype or not src.is_cuda or src.dim() != dst.dim() or tuple(src.shape[1:]) != tuple(dst.shape[1:]) or not src.is_contiguous():
+        raise ValueError(f'{what}: expected a contiguous {dst.dtype} CUDA tensor {tuple(dst.shape)}, got {src.dtype} {tuple(src.shape)}')
+    if src.shape[0] == dst.shape[0]:
+        if src.data_ptr() != dst.data_ptr():
+            dst.copy_(src, non_blocking=True)
+        return B
+    n = src.shape[0] // lead
+    if n * lead != src.shape[0] or not 0 < n < B:
+        raise ValueError(f'{what}: {src.shape[0]} images do not make {lead} steps of at most {B} chips')
+    dst.view(lead, B, *dst.shape[1:])[:, :n].copy_(src.view(lead, n, *src.shape[1:]), non_blocking=True)
+    return n
+
+
+def _run_captured(plan, what):
+    """One run of `plan._launch` (SeriesInferPlan, HybridInferPlan): the first run is eager, the second captures the launch list into a
+    graph, later runs replay it on the current stream.  State on the plan: _runs, _graph, _graph_off."""
+    plan._runs += 1
+    if plan._graph is None and plan._runs > 1 and not plan._graph_off and lt.graph_enabled():
+        try:
+            # The launch list runs once, eagerly, ON THE CAPTURE STREAM first: the library keeps per-stream workspaces (split-K slabs)
+            # that it never allocates inside a capture, and a convolution that finds none takes another kernel form -- the replay
+            # would differ from the eager run in the last bits.  Then the same list is captured there, one linear chain.
+            g, cap, cur = torch.cuda.CUDAGraph(), _capture_stream(), torch.cuda.current_stream()
+            cap.wait_stream(cur)
+            with torch.cuda.stream(cap):
+                plan._launch()
+            cur.wait_stream(cap)
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g, stream=cap):
+                plan._launch()
+            plan._graph = g
+        except Exception as e:           # a forward that cannot be captured stays eager (and says so once)
+            warnings.warn(f'{what}: forward not captured ({e}); running eagerly')
+            plan._graph_off = True
+    if plan._graph is not None and lt.graph_enabled():
+        plan._graph.replay()
+    else:
+        plan._launch()
+
+
 class SeriesInferPlan:
     """SeriesInferPlan(model, shape=(B, T, H, W), fused=...) for an LSTMModel or an LSTMAutoencoder, in the model's storage type at the time
     it is built.  `run(xt, want_classes=False)` takes what `predict_on_device(..., shape=shape)` takes -- the ingested time-major tensor
@@ -218,20 +262,8 @@ class SeriesInferPlan:
 
     # ------------------------------------------------------------------ run
     def _stage(self, dst, src, lead, what):
-        """copy an input into its static tensor; `src` may hold fewer chips than the plan (a short last batch): they fill a prefix of every
-        time step, the stale rest is computed and ignored (inference BatchNorm uses moving statistics: chips are independent)"""
-        B = self.shape[0]
-        if src.dtype != dst.dtype or not src.is_cuda or src.dim() != dst.dim() or tuple(src.shape[1:]) != tuple(dst.shape[1:]) or not src.is_contiguous():
-            raise ValueError(f'{what}: expected a contiguous {dst.dtype} CUDA tensor {tuple(dst.shape)}, got {src.dtype} {tuple(src.shape)}')
-        if src.shape[0] == dst.shape[0]:
-            if src.data_ptr() != dst.data_ptr():
-                dst.copy_(src, non_blocking=True)
-            return B
-        n = src.shape[0] // lead
-        if n * lead != src.shape[0] or not 0 < n < B:
-            raise ValueError(f'{what}: {src.shape[0]} images do not make {lead} steps of at most {B} chips')
-        dst.view(lead, B, *dst.shape[1:])[:, :n].copy_(src.view(lead, n, *src.shape[1:]), non_blocking=True)
-        return n
+        """copy an input into its static tensor; a short last batch fills a prefix of every time step (_stage_prefix)"""
+        return _stage_prefix(dst, src, lead, self.shape[0], what)
 
     def run(self, xt, want_classes=False):
         """-> (B, H, W, n_classes) float32 (with want_classes also the (B, H, W) int32 class tensor of a softmax head); the autoencoder takes
@@ -251,31 +283,99 @@ class SeriesInferPlan:
             self._stage(self.x_in, xt, T, 'xt')
         if self._ver != self.model.P.version:
             self._refresh()
-        self._runs += 1
-        if self._graph is None and self._runs > 1 and not self._graph_off and lt.graph_enabled():
-            try:
-                # The launch list runs once, eagerly, ON THE CAPTURE STREAM first: the library keeps per-stream workspaces (split-K slabs)
-                # that it never allocates inside a capture, and a convolution that finds none takes another kernel form -- the replay
-                # would differ from the eager run in the last bits.  Then the same list is captured there, one linear chain.
-                g, cap, cur = torch.cuda.CUDAGraph(), _capture_stream(), torch.cuda.current_stream()
-                cap.wait_stream(cur)
-                with torch.cuda.stream(cap):
-                    self._launch()
-                cur.wait_stream(cap)
-                torch.cuda.synchronize()
-                with torch.cuda.graph(g, stream=cap):
-                    self._launch()
-                self._graph = g
-            except Exception as e:           # a forward that cannot be captured stays eager (and says so once)
-                warnings.warn(f'SeriesInferPlan: forward not captured ({e}); running eagerly')
-                self._graph_off = True
-        if self._graph is not None and lt.graph_enabled():
-            self._graph.replay()
-        else:
-            self._launch()
+        _run_captured(self, 'SeriesInferPlan')
         return (self.out, self.classes) if want_classes else self.out
 
     @property
     def replaying(self):
         """whether the next run replays a captured graph"""
+        return self._graph is not None and bool(lt.graph_enabled())
+
+
+class HybridInferPlan:
+    """HybridInferPlan(model, batch, side, side_lo, fused=False): the inference plan of a lstm_tools.HybridModel for scene prediction
+    (prediction_tools.predict_hybrid_scene), in the model's storage type at the time it is built; also HybridModel.scene_plan(...).
+
+    The plan owns the ConvLSTM branch the way SeriesInferPlan does: the static input x_in (T * batch, side_lo, side_lo, cpad), both
+    ConvLSTM2D layers and BatchNorms as planned launches on preallocated buffers, and the `lstm_dense` launch into a static
+    (batch, side_lo, side_lo, k) tensor.  That chain, and only that chain, is captured into a graph after one eager run and replayed
+    (SATCV_LSTM_GRAPH=0 keeps it eager; a capture that fails warns once and stays eager).  The U-Net branch (the engine's static plan for
+    the n chips of the batch) and the fusion head are launched eagerly on the current stream around the replay: the head's `first`
+    changes with every batch, so it cannot live in the graph.  fused=True runs a time step as satcv_convlstm_step_fwd where that kernel
+    was built for the layer (`fused_layers`); fused=False issues the tape's launches and is bit-equal to predict_on_device.
+    Parameters changed after the plan was built are repacked at the next run, into the same buffers.
+
+    NOTHING `run` RETURNS OUTLIVES THE NEXT RUN of this plan: the tensors are the plan's own."""
+
+    def __init__(self, model, batch, side, side_lo, fused=False):
+        if not isinstance(model, lt.HybridModel):
+            raise NotImplementedError(f'HybridInferPlan covers HybridModel; {type(model).__name__} has no plan of this kind')
+        B, S, SL = int(batch), int(side), int(side_lo)
+        if min(B, S, SL) < 1:
+            raise ValueError(f'bad plan sizes batch={batch}, side={side}, side_lo={side_lo}')
+        self.model, self.shape, self.dtype = model, (B, S, SL), model.dtype_code
+        T = self.T = model.n_time
+        td, dev = ops.TORCH_DTYPE[self.dtype], lt._dev()
+        self.cpad = ops.rup(model.n_channels, 16)
+        self.x_in = torch.zeros(T * B, SL, SL, self.cpad, dtype=td, device=dev)
+        stack = model.lstm
+        self.l1 = _PlannedLayer(stack.l1, T, B, SL, SL, self.dtype, fused)
+        self.bn1 = _PlannedBN(stack.bn1, self.l1.Fp)
+        self.l2 = _PlannedLayer(stack.l2, T, B, SL, SL, self.dtype, fused)
+        self.bn2 = _PlannedBN(stack.bn2, self.l2.Fp)
+        self.fused_layers = tuple(n for n, l in (('conv_lstm', self.l1), ('dilated_conv_lstm', self.l2)) if l.fused)
+        k = model.n_classes
+        self.zl = torch.empty(B, SL, SL, k, dtype=torch.float32, device=dev)
+        self.out = self.classes = None                                      # (allocated by the first run without scene_head)
+        self._ver = None
+        self._runs, self._graph, self._graph_off = 0, None, False
+
+    def _refresh(self):
+        for p in (self.l1, self.bn1, self.l2, self.bn2):
+            p.refresh()
+        self._ver = self.model.P.version
+
+    def _launch(self):
+        """the captured chain: conv_lstm -> batch_norm -> dilated_conv_lstm -> batch_norm2 -> lstm_dense (ReLU), into self.zl"""
+        m, (B, S, SL) = self.model, self.shape
+        s1 = self.l1.launch(lt.Act(self.x_in, m.n_channels))
+        a1 = self.bn1.apply(s1)                                             # (Dropout passes through at inference)
+        feats = self.bn2.apply(self.l2.launch(a1))
+        d = m.lstm_dense._desc([(feats, False)], (SL, SL))
+        d.out, d.npix = self.zl.data_ptr(), B * SL * SL
+        check(lib.satcv_dense_small_fwd(C.byref(d), ops.stream_ptr()))
+
+    def run(self, xu, xt, scene_head=None, want_classes=False):
+        """xu: (n, side, side, C) float32 CUDA tensor, xt: the ingested time-major tensor (T * n, side_lo, side_lo, cpad), n <= batch (a
+        short last batch fills a prefix of every time step of x_in; the U-Net branch and the head run on the n chips).
+        scene_head=<callable>: receives the descriptor of the `probabilities` layer (as HybridModel.predict_on_device passes it) and its
+        result is returned; without it -> (n, side, side, n_classes) float32 probabilities, with want_classes also the int32 classes.
+        Everything returned, and everything the descriptor points to, belongs to the plan and is overwritten by its next run."""
+        m, (B, S, SL) = self.model, self.shape
+        if m.dtype_code != self.dtype:
+            raise ValueError('the model\'s compute_dtype changed since this plan was built; build a new plan')
+        if not (isinstance(xu, torch.Tensor) and xu.is_cuda and xu.dtype == torch.float32 and xu.dim() == 4 and tuple(xu.shape[1:]) == (S, S, m.hi_channels)):
+            raise ValueError(f'xu: expected an (n, {S}, {S}, {m.hi_channels}) float32 CUDA tensor, got {getattr(xu, "dtype", None)} {tuple(getattr(xu, "shape", ()))}')
+        n = _stage_prefix(self.x_in, xt, self.T, B, 'xt')
+        if xu.shape[0] != n:
+            raise ValueError(f'xu and xt hold different numbers of chips: {xu.shape[0]} and {n}')
+        if self._ver != m.P.version:
+            self._refresh()
+        _, zu = m._unet_branch(xu, False)
+        _run_captured(self, 'HybridInferPlan')
+        srcs = m._fusion_sources(self.zl[:n], zu)
+        d = m.fusion._desc(srcs, (S, S))
+        d.npix = n * S * S
+        if scene_head is not None:
+            return scene_head(d)
+        if self.out is None:
+            self.out = torch.empty(B, S, S, m.n_classes, dtype=torch.float32, device=self.zl.device)
+            self.classes = torch.empty(B, S, S, dtype=torch.int32, device=self.zl.device)
+        d.out, d.classes = self.out.data_ptr(), self.classes.data_ptr()
+        check(lib.satcv_dense_small_fwd(C.byref(d), ops.stream_ptr()))
+        return (self.out[:n], self.classes[:n]) if want_classes else self.out[:n]
+
+    @property
+    def replaying(self):
+        """whether the next run replays the captured ConvLSTM chain"""
         return self._graph is not None and bool(lt.graph_enabled())

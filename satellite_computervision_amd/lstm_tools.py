@@ -967,6 +967,8 @@ class HybridModel(_SeqModelBase):
     def __init__(self, unet_dim, lstm_dim, n_classes, filters=(32, 64, 128, 256), factors=(3, 2, 2, 2), dropout=None, seed=None):
         rng = np.random.default_rng(seed if seed is not None else mt._RNG.integers(1 << 31))
         self.unet_dim, self.lstm_dim, self.n_classes = tuple(unet_dim), tuple(lstm_dim), n_classes
+        self.factors = tuple(int(f) for f in factors)
+        self.hi_channels, self.n_time, self.n_channels = self.unet_dim[-1], self.lstm_dim[0], self.lstm_dim[-1]
         inp = mt.Input(shape=(None, None, unet_dim[-1]))
         dec = mt.build_unet_layers(inp, list(filters), list(factors), dropout=dropout)
         if dropout is not None:                       # layers.SpatialDropout2D(dropout)(unet_output), :899-900
@@ -989,8 +991,8 @@ class HybridModel(_SeqModelBase):
         mt.reset_slots_on_recompile(self.unet.runtime, prev, self.optimizer)
         self.unet.runtime.adam_state[0:1].fill_(self.optimizer._lr)
 
-    def _forward(self, xs, training):
-        xu, xl = xs
+    def _unet_branch(self, xu, training):
+        """the U-Net branch on the static engine -> (plan, zu float32 (n, h, w, k): pre-activation of the U-Net's relu dense layer)"""
         self.unet.compute_dtype = self.compute_dtype
         n, h, w, _ = self.unet._shape_of(xu)
         plan = self.unet.runtime.plan(n, h, w, training)
@@ -998,16 +1000,69 @@ class HybridModel(_SeqModelBase):
         if training:
             plan.step_count += 1
         plan.run_forward(ops.stream_ptr())
-        zu = plan.outputs[self.unet.outputs[0].id]                    # float32 (n, h, w, k): pre-activation of the U-Net's relu dense layer
-        xt, (B, T, hh, ww) = _ingest_seq(xl, ops.rup(self.lstm_dim[-1], 16), self.dtype_code)
+        return plan, plan.outputs[self.unet.outputs[0].id]
+
+    def _fusion_sources(self, zl, zu):
+        """the sources of the `probabilities` layer: [nearest-resized lstm_dense output, relu(unet_dense pre-activation)]"""
+        return [(Act(zl, self.n_classes), True), (Act(zu, self.n_classes, relu=True), False)]
+
+    def _forward_ingested(self, xu, xt, shape, training, scene_head=None):
+        """xu: the fine batch (n, h, w, C); xt: the time-major storage tensor (T * B, hh, ww, cpad), shape = (B, T, hh, ww).  With
+        `scene_head` the `probabilities` layer is not launched: the callable receives its descriptor (sources, weights, grid, npix)."""
+        plan, zu = self._unet_branch(xu, training)
+        B, T, hh, ww = shape
         feats = self.lstm.forward(Act(xt, self.lstm_dim[-1]), T, B, training, self.dtype_code)
         if self.lstm_drop is not None:
             feats = self.lstm_drop.forward(feats, training)
         zl = self.lstm_dense.forward([(feats, False)])                # float32 (B, hh, ww, k), already through its ReLU
-        probs, classes = self.fusion.forward([(Act(zl, self.n_classes), True), (Act(zu, self.n_classes, relu=True), False)], out_hw=(h, w),
-                                             want_classes=True)
+        n, h, w, _ = zu.shape
+        srcs = self._fusion_sources(zl, zu)
         self._plan, self._zu = plan, zu
-        return probs, classes
+        if scene_head is not None:
+            d = self.fusion._desc(srcs, (h, w))
+            d.npix = n * h * w
+            return scene_head(d)
+        return self.fusion.forward(srcs, out_hw=(h, w), want_classes=True)
+
+    def _forward(self, xs, training):
+        xu, xl = xs
+        xt, shape = _ingest_seq(xl, ops.rup(self.lstm_dim[-1], 16), self.dtype_code)
+        return self._forward_ingested(xu, xt, shape, training)
+
+    def _device_inputs(self, xs, shape):
+        """[xu, xt] as the gathers leave them -> (xu, xt, (B, T, hh, ww)), checked"""
+        if not isinstance(xs, (list, tuple)) or len(xs) != 2:
+            raise ValueError('predict_on_device takes the pair [fine batch, coarse sequence]')
+        xu, xl = xs
+        if not (isinstance(xu, torch.Tensor) and xu.is_cuda and xu.dtype == torch.float32 and xu.dim() == 4 and xu.shape[-1] == self.hi_channels):
+            raise ValueError(f'predict_on_device takes the fine batch as an (n, h, w, {self.hi_channels}) float32 CUDA tensor')
+        xt, shape = self._ingested_input(xl, shape)
+        if shape[1] != self.n_time:
+            raise ValueError(f'model was built for {self.n_time} time steps, got {shape[1]}')
+        if shape[0] != xu.shape[0]:
+            raise ValueError(f'the two inputs hold different numbers of chips: {xu.shape[0]} and {shape[0]}')
+        return xu, xt, shape
+
+    def predict_on_device(self, xs, shape=None, want_classes=False, scene_head=None):
+        """Inference that stays on the device.  xs = [xu, xt]: the fine batch, an (n, side, side, C) float32 CUDA tensor, and the coarse
+        sequence -- with shape=(n, T, side_lo, side_lo) the already ingested time-major storage tensor (T * n, side_lo, side_lo, cpad)
+        (what satcv_series_gather writes), read in place; without shape an (n, T, side_lo, side_lo, c) float32 CUDA tensor.
+        -> (n, side, side, n_classes) float32 CUDA tensor, with want_classes also the (n, side, side) int32 class tensor.  The launches
+        are those of predict (the U-Net branch on the same engine plan): equal bits for equal host values.  No host synchronisation.
+        scene_head=<callable>: the last dense layer (`probabilities`) is not launched; the callable receives its descriptor -- a
+        _lib.DenseDesc with the sources, weights, the (side, side) grid and npix set, out NULL -- and its result is returned
+        (prediction_tools.predict_hybrid_scene launches satcv_dense_scene_fwd with it)."""
+        xu, xt, shape = self._device_inputs(xs, shape)
+        res = self._forward_ingested(xu, xt, shape, False, scene_head=scene_head)
+        if scene_head is not None:
+            return res
+        return res if want_classes else res[0]
+
+    def scene_plan(self, batch, side, side_lo, fused=False):
+        """lstm_infer.HybridInferPlan(self, batch, side, side_lo, fused): the preallocated, graph-replayed ConvLSTM branch for scene
+        prediction (prediction_tools.predict_hybrid_scene(..., plan=...))"""
+        from .lstm_infer import HybridInferPlan
+        return HybridInferPlan(self, batch, side, side_lo, fused=fused)
 
     def predict(self, x, batch_size=None, verbose=0, **kw):
         n = x[0].shape[0]
@@ -1270,6 +1325,7 @@ class HierarchicalModel(_SeqModelBase):
         rng = np.random.default_rng(seed if seed is not None else mt._RNG.integers(1 << 31))
         self.P = _Params()
         self.acnn_dim, self.lstm_dim, self.depth, self.mid = tuple(acnn_dim), tuple(lstm_dim), depth, (depth - 1) // 2
+        self.hi_channels, self.n_time, self.n_channels = self.acnn_dim[-1], self.lstm_dim[0], self.lstm_dim[-1]
         self.trunk = ACNN2Trunk(self.P, rng, acnn_dim[-1], depth, nfilters)
         self.lstm = LSTMLayers(self.P, rng, lstm_dim[-1])
         self.sub = Dense1x1(self.P, rng, 'sub_probs', [nfilters], acnn_sub_nclasses, 'softmax')
@@ -1290,6 +1346,43 @@ class HierarchicalModel(_SeqModelBase):
 
     def predict(self, x, batch_size=None, verbose=0, **kw):
         return [o.cpu().numpy() for o in self._forward(x, False)]
+
+    def predict_on_device(self, xs, shape=None, output='lstm_probs', scene_head=None):
+        """Inference of ONE head that stays on the device.  xs = [xa, xt]: the fine batch, an (n, side, side, C) float32 CUDA tensor, and
+        the coarse sequence -- with shape=(n, T, side_lo, side_lo) the already ingested time-major storage tensor, read in place; without
+        shape an (n, T, side_lo, side_lo, c) float32 CUDA tensor.  output: any of output_names.  -> (n, side, side, classes of that head)
+        float32 CUDA tensor, equal to the bit to that output of predict on the same host values; the ConvLSTM branch runs for
+        'lstm_probs' only.  No host synchronisation.
+        scene_head=<callable>: the head's dense layer is not launched; the callable receives its descriptor (a _lib.DenseDesc with the
+        sources, weights, grid and npix set, out NULL) and its result is returned."""
+        if output not in self.output_names:
+            raise ValueError(f'output must be one of {self.output_names}, got {output!r}')
+        if not isinstance(xs, (list, tuple)) or len(xs) != 2:
+            raise ValueError('predict_on_device takes the pair [fine batch, coarse sequence]')
+        xa, xl = xs
+        if not (isinstance(xa, torch.Tensor) and xa.is_cuda and xa.dtype == torch.float32 and xa.dim() == 4 and xa.shape[-1] == self.hi_channels):
+            raise ValueError(f'predict_on_device takes the fine batch as an (n, h, w, {self.hi_channels}) float32 CUDA tensor')
+        xt, shape = self._ingested_input(xl, shape)
+        B, T, hh, ww = shape
+        if T != self.n_time:
+            raise ValueError(f'model was built for {self.n_time} time steps, got {T}')
+        if B != xa.shape[0]:
+            raise ValueError(f'the two inputs hold different numbers of chips: {xa.shape[0]} and {B}')
+        x = ops.ingest_nhwc(xa.contiguous(), ops.rup(self.acnn_dim[-1], 16), self.dtype_code)
+        feats = self.trunk.forward(Act(x, self.acnn_dim[-1]), False, self.dtype_code)
+        n, H, W = x.shape[0], x.shape[1], x.shape[2]
+        if output == 'sub_probs':
+            head, srcs = self.sub, [(feats[self.mid], False)]
+        elif output == 'acnn_probs':
+            head, srcs = self.acnn, [(feats[-1], False)]
+        else:
+            lf = self.lstm.forward(Act(xt, self.lstm_dim[-1]), T, B, False, self.dtype_code)
+            head, srcs = self.fuse, [(lf, True), (feats[-1], False)]
+        if scene_head is not None:
+            d = head._desc(srcs, (H, W))
+            d.npix = n * H * W
+            return scene_head(d)
+        return head.forward(srcs, out_hw=(H, W))
 
     output_names = ('sub_probs', 'acnn_probs', 'lstm_probs')
 

@@ -342,8 +342,8 @@ def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=
     chips (m.inference_plan), a SeriesInferPlan built for (batch_size, m.n_time, kernel + buff, kernel + buff) is used as given: the
     batches run through its preallocated, graph-replayed forward; a short last batch fills a prefix of the plan's input, the stale rest
     is computed and ignored.
-    The returned arrays are the only device-to-host traffic; hybrid and hierarchical models (two inputs at two resolutions) are not
-    covered."""
+    The returned arrays are the only device-to-host traffic; hybrid and hierarchical models (two inputs at two resolutions) go through
+    `predict_hybrid_scene`."""
     from .lstm_tools import LSTMAutoencoder
     _check_geometry(kernel, buff, batch_size)
     if getattr(stack, 'ndim', None) != 4:
@@ -460,6 +460,209 @@ def _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, want_classe
             _scatter(res[0], a - s, e - a, (off, off, kernel, kernel), origins, total, a, out, 0, c0, nc, True)
             if cls is not None:
                 _scatter(res[1], a - s, e - a, (off, off, kernel, kernel), origins, total, a, cls, 0, 0, 1, False)
+    return out, cls
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Scene prediction for the two-resolution models (lstm_tools.HybridModel / HierarchicalModel): a fine (H, W, C) scene and a coarse
+# (T, c, h, w) time stack with H = r h, W = r w.  Per batch one satcv_scene_gather on the fine grid, one satcv_series_gather on the coarse
+# grid, the model up to its last dense layer, and satcv_dense_scene_fwd, which computes that layer on the chip centres only and stores
+# them into the map.  DESIGN.md, "Scene prediction for the hybrid and hierarchical models".
+def hybrid_chip_tables(hi_shape, lo_shape, kernel, buff, cover, multiple=1):
+    """Chip geometry on two grids.  hi_shape = (H, W[, ...]) of the fine plane, lo_shape = (h, w) of the coarse one, with one integer ratio
+    r >= 1: H == r h and W == r w.  -> (hi, lo, geo): int32 (total, 2) tables of the (y, x) centre origins on the fine grid
+    (`generate_chip_indices` for cover='reference', `full_cover_indices` for cover='full') and of the same chips on the coarse grid
+    (hi // r), and geo = dict(r, off, side, off_lo, side_lo): a fine window starts at origin - off and is side = kernel + 2 (buff // 2)
+    wide, a coarse window starts at origin_lo - off_lo and is side_lo = side // r wide.
+
+    ValueError unless kernel % r == 0, (buff // 2) % r == 0 and side % multiple == 0 (multiple: the product of the pooling factors of the
+    U-Net branch of a hybrid model, 1 for the hierarchical model); cover='full' needs H, W >= side.  With these conditions every fine
+    window starts on a multiple of r, so the nearest resize inside the model maps fine chip pixel u to coarse chip pixel u // r: the
+    coarse chip is exactly the coarse footprint of the fine chip."""
+    H, W = int(hi_shape[0]), int(hi_shape[1])
+    h, w = int(lo_shape[0]), int(lo_shape[1])
+    kernel, buff, multiple = int(kernel), int(buff), int(multiple)
+    if kernel < 1 or buff < 0 or multiple < 1:
+        raise ValueError(f'kernel and multiple must be positive and buff non-negative, got kernel={kernel}, buff={buff}, multiple={multiple}')
+    if min(H, W, h, w) < 1 or H % h or W % w:
+        raise ValueError(f'ratio: the fine plane {H} x {W} is not an integer multiple of the coarse plane {h} x {w}')
+    r = H // h
+    if W // w != r:
+        raise ValueError(f'ratio: rows {H} / {h} = {r} and columns {W} / {w} = {W // w} differ')
+    off = buff // 2
+    side = kernel + 2 * off
+    if kernel % r:
+        raise ValueError(f'kernel = {kernel} is not a multiple of the resolution ratio r = {r}')
+    if off % r:
+        raise ValueError(f'buff // 2 = {off} is not a multiple of the resolution ratio r = {r}')
+    if side % multiple:
+        raise ValueError(f'side = kernel + 2 (buff // 2) = {side} is not a multiple of {multiple}')
+    if cover == 'reference':
+        idx = generate_chip_indices(np.empty((H, W, 0)), buff, kernel)
+    elif cover == 'full':
+        if H < side or W < side:
+            raise ValueError(f"cover='full' needs a scene of at least side = {side} pixels a side, got {H} x {W}")
+        idx = full_cover_indices((H, W), kernel)
+    else:
+        raise ValueError(f"cover must be 'reference' or 'full', got {cover!r}")
+    hi = np.asarray(idx, np.int32).reshape(len(idx), 2)
+    assert not (hi % r).any()
+    return hi, hi // r, dict(r=r, off=off, side=side, off_lo=off // r, side_lo=side // r)
+
+
+def _hybrid_head(m, output):
+    """(the last dense layer that writes the map, multiple of the chip side) of a two-resolution model"""
+    from .lstm_tools import HierarchicalModel, HybridModel
+    if isinstance(m, HybridModel):
+        if output not in (None,) + tuple(m.output_names):
+            raise ValueError(f'output must be one of {m.output_names}, got {output!r}')
+        return m.fusion, int(np.prod(m.factors))
+    if isinstance(m, HierarchicalModel):
+        output = 'lstm_probs' if output is None else output
+        if output not in m.output_names:
+            raise ValueError(f'output must be one of {m.output_names}, got {output!r}')
+        return {'sub_probs': m.sub, 'acnn_probs': m.acnn, 'lstm_probs': m.fuse}[output], 1
+    raise ValueError(f'predict_hybrid_scene covers HybridModel and HierarchicalModel, got {type(m).__name__}')
+
+
+def predict_hybrid_scene(scene, stack, m, kernel=256, buff=128, batch_size=16, channel=0, cover='reference', classes=False, rescale=None,
+                         maxval=10000, output=None, plan=None):
+    """Prediction map of a fine (H, W, C) scene together with a coarse (T, c, h, w) time stack by a two-resolution model
+    (get_hybrid_model, get_hierarchical_model), stitched on the device; returns new arrays.
+
+    scene: as for `predict_scene` -- a host array (uint8 / uint16 / int16 / float32, `rescale` divides in float64 and rounds to float32;
+    anything else is cast to float32) or a contiguous float32 CUDA tensor read in place.  stack: as for `predict_series_scene` -- the first
+    m.n_time acquisitions, float32(float64(v) / maxval) with NaN -> 0, a host array or a contiguous int16 / float32 CUDA tensor.
+    Geometry: `hybrid_chip_tables` (H == r h, W == r w, kernel and buff // 2 multiples of r, the chip side a multiple of the U-Net
+    branch's pooling product); ValueError otherwise.  kernel, buff, batch_size, channel, cover, classes: as for `predict_scene`; the border
+    the reference cover leaves out stays 0 (255 in the class map).
+    output: the head that is mapped -- None: 'probabilities' (hybrid) / 'lstm_probs' (hierarchical); the hierarchical model also takes
+    'sub_probs' and 'acnn_probs'.  classes=True needs a softmax head.
+    plan: None runs every batch through m.predict_on_device; True builds a lstm_infer.HybridInferPlan(m, batch_size, side, side_lo), a
+    HybridInferPlan of this model and these sizes is used as given (HybridModel only: NotImplementedError for a hierarchical model, whose
+    ACNN trunk lives on the tape).
+    Per batch the model stops before its last dense layer; satcv_dense_scene_fwd computes that layer on the chip centres and stores
+    them into the map.  The returned arrays are the only device-to-host traffic."""
+    import torch
+    from .lstm_tools import HierarchicalModel
+    head, multiple = _hybrid_head(m, output)
+    _check_geometry(kernel, buff, batch_size)
+    if getattr(scene, 'ndim', None) != 3:
+        raise ValueError(f'expected an (H, W, C) scene, got shape {tuple(getattr(scene, "shape", ()))}')
+    if getattr(stack, 'ndim', None) != 4:
+        raise ValueError(f'expected a (T, c, h, w) time stack, got shape {tuple(getattr(stack, "shape", ()))}')
+    H, W, C_ = (int(v) for v in scene.shape)
+    T, c_, h, w = (int(v) for v in stack.shape)
+    if C_ != m.hi_channels:
+        raise ValueError(f'the model reads {m.hi_channels} fine bands, the scene holds {C_}')
+    if T < m.n_time:
+        raise ValueError(f'the model reads {m.n_time} acquisitions, the stack holds {T}')
+    if c_ != m.n_channels:
+        raise ValueError(f'the model reads {m.n_channels} coarse bands, the stack holds {c_}')
+    if not float(maxval) or float(maxval) != float(maxval):
+        raise ValueError(f'maxval must be a non-zero number, got {maxval}')
+    hi, lo, geo = hybrid_chip_tables((H, W), (h, w), kernel, buff, cover, multiple)
+    ncls = head.cout
+    if classes and head.activation != head.ACT['softmax']:
+        raise ValueError(f'classes=True needs a head with a class output (softmax); {head.name!r} has none')
+    if channel is not None and not -ncls <= int(channel) < ncls:
+        raise IndexError(f'channel {channel} of a {ncls}-class output')
+    if plan is not None and plan is not False and isinstance(m, HierarchicalModel):
+        raise NotImplementedError('plan: HybridInferPlan covers HybridModel; the ACNN trunk of a HierarchicalModel lives on the tape')
+    if not len(hi):                          # (a scene too small for one reference chip: nothing is predicted)
+        probs = np.zeros((H, W) if channel is not None else (H, W, ncls), np.float32)
+        return (probs, np.full((H, W), 255, np.uint8)) if classes else probs
+    if plan is not None and plan is not False:
+        want = (min(int(batch_size), len(hi)), geo['side'], geo['side_lo'])
+        if plan is True:
+            try:
+                plan = m.scene_plan(*want)
+            except torch.cuda.OutOfMemoryError as e:
+                raise MemoryError(f'a HybridInferPlan for (batch, side, side_lo) = {want} does not fit in device memory; lower batch_size') from e
+        elif getattr(plan, 'model', None) is not m or tuple(getattr(plan, 'shape', ())) != want:
+            raise ValueError(f'plan must be a HybridInferPlan of this model for (batch, side, side_lo) = {want}, got {getattr(plan, "shape", plan)!r}')
+    else:
+        plan = None
+    out, cls = _stitch_hybrid(scene, stack, hi, lo, geo, m, head, output, int(kernel), int(batch_size), None if channel is None else int(channel),
+                              bool(classes), rescale, float(maxval), plan)
+    probs = (out if channel is None else out[..., 0]).cpu().numpy()
+    return (probs, cls.cpu().numpy()) if classes else probs
+
+
+def _stitch_hybrid(scene, stack, hi, lo, geo, m, head, output, kernel, batch_size, channel, want_classes, rescale, maxval, plan):
+    """the batch loop of predict_hybrid_scene: -> (device map (H, W, nc) float32, device class map (H, W) uint8 or None)"""
+    import ctypes as C
+    import torch
+    from . import ops
+    from ._lib import DenseSceneDesc, SceneGatherDesc, SeriesGatherDesc, check, lib
+    from .lstm_tools import HybridModel
+    H, W, C_ = scene.shape
+    T, c_, h, w = stack.shape
+    steps, off, side, off_lo, side_lo = m.n_time, geo['off'], geo['side'], geo['off_lo'], geo['side_lo']
+    if isinstance(scene, torch.Tensor):      # a scene that is already resident: read where it lies
+        if not (scene.is_cuda and scene.dtype == torch.float32 and scene.is_contiguous()):
+            raise ValueError(f'a tensor scene must be a contiguous float32 CUDA tensor (H, W, C), got {scene.dtype} {tuple(scene.shape)} on {scene.device}')
+        sdev, skind = scene, _SCENE_KIND[np.dtype(np.float32)]
+    else:
+        sc = np.asarray(scene)
+        if sc.dtype not in _SCENE_KIND:
+            if rescale:
+                raise ValueError(f'rescale needs a uint8 / uint16 / int16 / float32 scene, got {sc.dtype}')
+            sc = sc.astype(np.float32)
+        sdev, skind = _to_device(sc, 'the scene'), _SCENE_KIND[sc.dtype]
+    if isinstance(stack, torch.Tensor):
+        if not (stack.is_cuda and stack.dtype in (torch.int16, torch.float32) and stack.is_contiguous()):
+            raise ValueError(f'a tensor stack must be a contiguous int16 / float32 CUDA tensor (T, c, h, w), got {stack.dtype} on {stack.device}')
+        tdev, tkind = stack, _SERIES_KIND[np.dtype(np.int16 if stack.dtype == torch.int16 else np.float32)]
+    else:
+        st_ = np.asarray(stack)[:steps]      # (only the acquisitions the model reads are cast and uploaded: a contiguous prefix)
+        T = steps
+        if st_.dtype not in _SERIES_KIND:
+            st_ = st_.astype(np.float32)
+        tdev, tkind = _to_device(st_, 'the time stack'), _SERIES_KIND[st_.dtype]
+    total = len(hi)
+    org_hi, org_lo = _to_device(hi, 'the origin table'), _to_device(np.ascontiguousarray(lo, np.int32), 'the origin table')
+    nb = min(batch_size, total)
+    cpad, dtype = ops.rup(c_, 16), m.dtype_code
+    td = ops.TORCH_DTYPE[dtype]
+    buf_hi = _device_empty((nb, side, side, C_), torch.float32, 'the fine chip batch')
+    # with a plan, full batches are gathered straight into its static input; a short last batch goes through a buffer of its own and is
+    # spread over a prefix of every time step by plan.run
+    buf_lo = plan.x_in.view(-1) if plan is not None else _device_empty((steps * nb * side_lo * side_lo * cpad,), td, 'the coarse chip batch')
+    short = _device_empty((steps * (total % nb) * side_lo * side_lo * cpad,), td, 'the coarse chip batch') if plan is not None and total % nb else None
+    ncls = head.cout
+    c0, nc = (0, ncls) if channel is None else (channel % ncls, 1)
+    out = _device_empty((H, W, nc), torch.float32, 'the prediction map', 0.0)
+    cls = _device_empty((H, W), torch.uint8, 'the class map', 255) if want_classes else None
+    st = ops.stream_ptr()
+    kw = {} if isinstance(m, HybridModel) else {'output': output or 'lstm_probs'}
+    first = [0]
+
+    def scene_head(d):
+        """the model's last dense layer (its sources in `d`) on the chip centres, stored into the map"""
+        sd = DenseSceneDesc(head=d, crop_y=off, crop_x=off, crop_h=kernel, crop_w=kernel, origins=org_hi.data_ptr(), total=total, first=first[0],
+                            map=out.data_ptr(), map_h=H, map_w=W, ldm=nc, c0=c0, nc=nc, class_map=cls.data_ptr() if cls is not None else None)
+        check(lib.satcv_dense_scene_fwd(C.byref(sd), st))
+    # No host synchronisation inside this loop.  Every launch -- the gathers, the model's kernels, the head -- goes to the current stream, so
+    # stream order alone keeps the gathers of batch i + 1 from overwriting the chip buffers while batch i still reads them.  The windows
+    # of both covers are pairwise disjoint, so one head launch per batch meets the kernel's contract.
+    for s in range(0, total, batch_size):
+        n = min(batch_size, total - s)
+        first[0] = s
+        d = SceneGatherDesc(src=sdev.data_ptr(), src_kind=skind, h=H, w_=W, c=C_, rescale=float(rescale or 0.0), origins=org_hi.data_ptr(), total=total,
+                            first=s, n=n, off=off, side=side, dst=buf_hi.data_ptr(), ldc=C_, coff=0)
+        check(lib.satcv_scene_gather(C.byref(d), st))
+        xt = (buf_lo if n == nb or short is None else short)[:steps * n * side_lo * side_lo * cpad].view(steps * n, side_lo, side_lo, cpad)
+        d = SeriesGatherDesc(src=tdev.data_ptr(), src_kind=tkind, t=T, c=c_, h=h, w_=w, steps=steps, maxval=maxval, origins=org_lo.data_ptr(),
+                             total=total, first=s, n=n, off=off_lo, side=side_lo, dst=xt.data_ptr(), dtype=dtype, cpad=cpad)
+        check(lib.satcv_series_gather(C.byref(d), st))
+        try:
+            if plan is not None:
+                plan.run(buf_hi[:n], xt, scene_head=scene_head)
+            else:
+                m.predict_on_device([buf_hi[:n], xt], shape=(n, steps, side_lo, side_lo), scene_head=scene_head, **kw)
+        except torch.cuda.OutOfMemoryError as e:
+            raise MemoryError(f'a batch of {n} chips of {side} x {side} and {steps} x {side_lo} x {side_lo} does not fit in device memory; lower batch_size') from e
     return out, cls
 
 
