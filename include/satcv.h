@@ -684,6 +684,76 @@ typedef struct satcv_composite_desc {
 } satcv_composite_desc;
 int satcv_median_composite(const satcv_composite_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ Sentinel-2 quality masks of a time stack
+ * The per-sample masks of utils/ee_tools.py on a resident (t, cs, h, w_) planar stack, ONE launch: basicQA (:159-180),
+ * sentinelCloudScore (:218-255) with the `cloudScore <= 15` of maskTOA (:288-306), waterScore (:115-157) with the `<= 0.25` and the
+ * `B11 > 900` shadow test of mask (:257-268), and the scene classification of maskSR (:270-286).  The Cloud Displacement Index and
+ * the JRC water history that mask also consults are external products and stay out, as maskTOA leaves them out.
+ *   src:     (t, cs, h, w_) planar, contiguous, of kind 1 u16, 2 f32 or 3 i16; cs <= 16, t <= SATCV_COMPOSITE_MAX_T, h * w_ < 2^31
+ *   offsets: as for the composite; applied to the REFLECTANCE roles only, before anything else, as max(v, off) - off
+ *   band:    the plane of each role in the order B1, B2, B3, B4, B8, B10, B11, B12, QA60, SCL (SATCV_Q_ROLE_*); -1 = absent.  A rule
+ *            or an output whose roles are absent is an error before any launch.  Only the planes of the selected rules are read
+ *   rules:   a set of SATCV_Q_* bits; cloud_max (reference: 15) and shadow_min (reference: 900) are their thresholds
+ *   clear:   uint32 bit-planes (ceil(t / 32), h, w_): bit j % 32 of word j / 32 is 1 when acquisition j passes every selected rule
+ *            at that pixel; unused high bits are 0.  Or NULL
+ *   cloud_score: (t, h, w_) uint8, 0 ... 100, 255 where a band the score reads is nodata; or NULL
+ *   water_score: (t, h, w_) fp32 in [0, 1], NaN where a band the score reads is nodata; or NULL.  At least one output is non-null
+ * Nodata: a sample passes a rule only if every reflectance band that rule reads is valid (> 0, not NaN) at that acquisition and
+ * pixel -- in Earth Engine a masked input masks the result.  QA60 and SCL are codes: the nodata rule does not apply to them; in an
+ * f32 stack a NaN code fails the rule and other values are truncated to integers.
+ * Rules, on the harmonised DN x (the reference divides by 10000 in sentinel2toa :90; the constants are multiplied through):
+ *   QA60    (qa & 1024) == 0 && (qa & 2048) == 0
+ *   CLOUD   s100 = min(100, (B2 - 1000) / 40, (B1 - 1000) / 20, (B1 + B10 - 1500) / 5, (B2 + B3 + B4 - 2000) / 60,
+ *                      500 (B8 - B11) / (B8 + B11) + 50, 400 - 500 (B3 - B11) / (B3 + B11));
+ *           cloud_score = floor(s100) limited to 0 ... 100 (`.multiply(100).byte()`: saturating, truncating); clear when
+ *           cloud_score <= cloud_max
+ *   SHADOW  B11 > shadow_min
+ *   WATER   w1 = clamp((3500 - (B8 + B11 + B12)) / 1500, 0, 1); w2 = clamp((B2 - sd) / mean, 0, 1), mean and sd (ddof 0: the
+ *           population form is taken for ee.Reducer.stdDev) over B3, B4, B8, B11, B12; w3 = ((B3 - B11) / (B3 + B11) - 0.3) / 0.5;
+ *           water_score = clamp(min(1, w1, w2, w3), 0, 1); the sample is water when all three terms exceed 1/4, and passes when
+ *           it is not water
+ *   SCL     the code is none of 0 (nodata), 2, 3, 8, 9, 10, 11
+ *   A quotient whose denominator is 0 (both bands of a normalised difference 0 after the harmonisation, mean 0) is 0, Earth Engine's
+ *   convention for a division by zero.
+ * Numerics: decisions are exact on the stored sample values, not the result of a floating-point evaluation order.  The 16-bit kinds
+ * use integer arithmetic (division-free cross-multiplied inequalities, 64-bit products for w2, floor divisions for the score); f32
+ * stacks evaluate the same cross-multiplied inequalities in double, which is exact for integer-valued data below 2^22 -- fractional
+ * f32 data are decided by those double expressions.  water_score is computed in double and rounded once to fp32. */
+#define SATCV_Q_QA60 1
+#define SATCV_Q_CLOUD 2
+#define SATCV_Q_SHADOW 4
+#define SATCV_Q_WATER 8
+#define SATCV_Q_SCL 16
+#define SATCV_Q_ROLES 10
+typedef struct satcv_quality_desc {
+  const void* src; int32_t src_kind;
+  int32_t t, cs, h, w_;
+  const float* offsets;
+  int32_t band[SATCV_Q_ROLES];
+  int32_t rules;
+  int32_t cloud_max; float shadow_min;
+  uint32_t* clear;
+  uint8_t* cloud_score;
+  float* water_score;
+} satcv_quality_desc;
+int satcv_quality_mask(const satcv_quality_desc* d, void* stream);
+
+/* Median composite under a clear mask and a band selection (the composites the reference's models were trained on: every
+ * acquisition masked by utils/ee_tools.py before the median).  Everything of satcv_median_composite holds, with
+ *   base:     its descriptor; base.c is the number of OUTPUT bands (<= 16), base.src has cs planes per acquisition
+ *   clear:    the bit-planes satcv_quality_mask writes, or NULL (every sample clear).  A sample is valid iff v > 0 and its bit is set
+ *   cs:       planes per acquisition in base.src (<= 16)
+ *   band_idx: the plane of output band b, 0 <= band_idx[b] < cs for b < base.c -- a 14-plane quality stack yields a 4-band composite
+ *             without a copy
+ * With clear = NULL and the identity table the results equal satcv_median_composite's bit for bit. */
+typedef struct satcv_composite_masked_desc {
+  satcv_composite_desc base;
+  const uint32_t* clear;
+  int32_t cs;
+  int32_t band_idx[16];
+} satcv_composite_masked_desc;
+int satcv_median_composite_masked(const satcv_composite_masked_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ losses
  * Each writes loss_out[0] += mean loss contribution (caller zeroes) and
  * dlogits = dL/dlogits (through the head activation).

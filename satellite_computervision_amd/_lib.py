@@ -74,6 +74,20 @@ class CompositeDesc(C.Structure):
                 ('use_fill', c_i32), ('fill', c_f32)]
 
 
+Q_QA60, Q_CLOUD, Q_SHADOW, Q_WATER, Q_SCL = 1, 2, 4, 8, 16     # SATCV_Q_* of include/satcv.h
+Q_ROLES = ('B1', 'B2', 'B3', 'B4', 'B8', 'B10', 'B11', 'B12', 'QA60', 'SCL')      # the order of satcv_quality_desc.band
+
+
+class QualityDesc(C.Structure):
+    _fields_ = [('src', c_vp), ('src_kind', c_i32), ('t', c_i32), ('cs', c_i32), ('h', c_i32), ('w_', c_i32), ('offsets', c_vp),
+                ('band', c_i32 * len(Q_ROLES)), ('rules', c_i32), ('cloud_max', c_i32), ('shadow_min', c_f32),
+                ('clear', c_vp), ('cloud_score', c_vp), ('water_score', c_vp)]
+
+
+class CompositeMaskedDesc(C.Structure):
+    _fields_ = [('base', CompositeDesc), ('clear', c_vp), ('cs', c_i32), ('band_idx', c_i32 * 16)]
+
+
 RECORD_MAX_PLANES = 32     # SATCV_RECORD_MAX_PLANES of include/satcv.h
 RECORD_STAT_SPLITS = 16    # SATCV_RECORD_STAT_SPLITS
 _i32p, _f32p = c_i32 * RECORD_MAX_PLANES, c_f32 * RECORD_MAX_PLANES
@@ -281,6 +295,8 @@ _SIGS = {
     'satcv_scene_scatter': (C.c_int, [C.POINTER(SceneScatterDesc), c_vp]),
     'satcv_series_gather': (C.c_int, [C.POINTER(SeriesGatherDesc), c_vp]),
     'satcv_median_composite': (C.c_int, [C.POINTER(CompositeDesc), c_vp]),
+    'satcv_quality_mask': (C.c_int, [C.POINTER(QualityDesc), c_vp]),
+    'satcv_median_composite_masked': (C.c_int, [C.POINTER(CompositeMaskedDesc), c_vp]),
     'satcv_record_stats': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_record_to_tuple': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_label_onehot': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),

@@ -18,6 +18,12 @@
 // General path (32 < t <= SATCV_COMPOSITE_MAX_T, and maps of a single pixel): 64 lanes per workgroup, the samples of a band as ordered
 // 32-bit keys in LDS, the k-th smallest found bit by bit (32 counting passes over LDS) -- exact, same trip count in every lane.
 // No lane-dependent branch surrounds a load: lanes past the end of the map repeat the last item and skip their stores.
+//
+// satcv_median_composite_masked is a second instantiation of the same kernels (MaskedArgs): the composites the reference's models were
+// trained on took the median over acquisitions masked by utils/ee_tools.py (basicQA :159, maskTOA :288, maskSR :270, mask :257).  A sample
+// is valid iff v > 0 and its bit in the clear bit-planes of satcv_quality_mask (csrc/quality.hip) is set; the plane of output band b comes
+// from a band table, so a stack that carries its quality planes is composited without a copy.  Register paths load the pixel's mask word
+// once, outside the band loop; the packed 16-bit path folds the bit into the validity `m`.  The unmasked instantiations are unchanged.
 #include "common.hpp"
 #include <cmath>
 #include <utility>
@@ -36,7 +42,33 @@ struct Args {
   int npix;          // h * w
   int items;         // lanes of work: ceil(npix / pixels per lane)
   int vec_med, vec_norm;      // 16-byte stores possible (c, ld, coff multiples of 4, base 16-byte aligned)
+  static constexpr bool masked = false;
 };
+// satcv_median_composite_masked: the same kernels, instantiated with a band table and the clear bit-planes of satcv_quality_mask
+struct MaskedArgs : Args {
+  const unsigned* clear;      // (ceil(t / 32), h, w) words, or null: every sample clear
+  int cs;                     // planes per acquisition in src
+  unsigned long long bands;   // the plane of output band b in bits [4 b, 4 b + 4): a scalar shift, no table in registers
+  static constexpr bool masked = true;
+};
+// the plane of (acquisition j, output band b)
+template <typename A>
+__device__ __forceinline__ size_t plane_of(const A& a, int j, int c, int b) {
+  if constexpr (A::masked) return (size_t)j * a.cs + (unsigned)((a.bands >> (4 * b)) & 15u);
+  else return (size_t)j * c + b;
+}
+// an f32 sample takes part: > 0, and clear under a mask
+template <typename A>
+__device__ __forceinline__ int valid_of(float v, unsigned w, int j) {
+  if constexpr (A::masked) return (v > 0.f) & (int)((w >> j) & 1u);
+  else return v > 0.f;
+}
+// word k of pixel p's clear mask (a wave-uniform branch: all ones without a mask)
+template <typename A>
+__device__ __forceinline__ unsigned clear_word(const A& a, int k, size_t p) {
+  if constexpr (A::masked) return a.clear ? a.clear[(size_t)k * a.npix + p] : 0xffffffffu;
+  else return 0xffffffffu;
+}
 
 // ---------------------------------------------------------------- Batcher's merge-exchange network for N = 2^k slots
 template <int N>
@@ -144,8 +176,8 @@ __device__ __forceinline__ void finish_pixel(const Args& a, const double* med, i
 // ---------------------------------------------------------------- register path, 16-bit stacks: two pixels per lane
 struct __attribute__((packed, aligned(2))) Pair16 { unsigned v; };     // a plane of an odd map starts on a 2-byte boundary
 
-template <bool SIGNED, int N>
-__global__ __launch_bounds__(CP_BLOCK) void composite16_kernel(const Args a) {
+template <bool SIGNED, int N, typename A>
+__global__ __launch_bounds__(CP_BLOCK) void composite16_kernel(const A a) {
   extern __shared__ double cp_med[];                     // [c][2][CP_BLOCK]
   const satcv_composite_desc& d = a.d;
   const unsigned short* __restrict__ src = reinterpret_cast<const unsigned short*>(d.src);
@@ -160,23 +192,34 @@ __global__ __launch_bounds__(CP_BLOCK) void composite16_kernel(const Args a) {
     // the last lane of an odd map holds ONE pixel: it loads the pair that ends on it and shifts (npix >= 2 on this path)
     const bool tail = 2 * it + 1 >= npix;
     const size_t e0 = tail ? (size_t)npix - 2 : (size_t)2 * it;
+    // the clear bits of the lane's two pixels, loaded once (N <= 32: one word each) and interleaved by halves, so that a shift by
+    // j % 16 brings acquisition j's two bits to bit 0 of the two 16-bit fields: w01[j / 16] >> (j % 16) & 0x00010001
+    unsigned w01[2] = {0, 0};
+    if constexpr (A::masked) {
+      const unsigned wx = clear_word(a, 0, tail ? (size_t)npix - 1 : e0), wy = clear_word(a, 0, tail ? (size_t)npix - 1 : e0 + 1);
+      w01[0] = (wx & 0xffffu) | (wy << 16);
+      w01[1] = (wx >> 16) | (wy & 0xffff0000u);
+    }
     for (int b = 0; b < c; ++b) {
       u16x2 s[N];
       u16x2 par = zero, cnt = zero;
 #pragma unroll
       for (int j = 0; j < N; ++j) {
         unsigned raw = 0;
-        if (j < t) raw = reinterpret_cast<const Pair16*>(src + ((size_t)j * c + b) * npix + e0)->v;      // wave-uniform condition
+        if (j < t) raw = reinterpret_cast<const Pair16*>(src + plane_of(a, j, c, b) * npix + e0)->v;      // wave-uniform condition
         raw = tail ? raw >> 16 : raw;
         u16x2 v = __builtin_bit_cast(u16x2, raw);
         if (SIGNED) v = __builtin_bit_cast(u16x2, __builtin_elementwise_max(__builtin_bit_cast(i16x2, v), __builtin_bit_cast(i16x2, zero)));
-        const u16x2 m = __builtin_elementwise_min(v, one);        // 1 = valid (x > 0)
+        u16x2 valid = one;
+        if constexpr (A::masked) valid = __builtin_bit_cast(u16x2, (w01[j / 16] >> (j % 16)) & 0x00010001u);      // the clear bits are part of `m`
+        const u16x2 m = __builtin_elementwise_min(v, valid);      // 1 = valid (x > 0, and clear)
         const u16x2 inv = m ^ one;
         const u16x2 top = inv & par;                               // the 2nd, 4th, ... nodata sample goes to the top
         par ^= inv;
         cnt += m;
         const u16x2 o = __builtin_bit_cast(u16x2, off[j]);
-        const u16x2 u = __builtin_elementwise_max(v, o) - o;       // nodata stays 0: the bottom key
+        u16x2 u = __builtin_elementwise_max(v, o) - o;             // nodata stays 0: the bottom key
+        if constexpr (A::masked) u *= m;                           // ... and a sample that is not clear becomes it
         s[j] = u | (zero - top);
       }
       net_sort<N>(s);
@@ -191,8 +234,8 @@ __global__ __launch_bounds__(CP_BLOCK) void composite16_kernel(const Args a) {
 }
 
 // ---------------------------------------------------------------- register path, f32 stacks: one pixel per lane
-template <int N>
-__global__ __launch_bounds__(CP_BLOCK) void composite32_kernel(const Args a) {
+template <int N, typename A>
+__global__ __launch_bounds__(CP_BLOCK) void composite32_kernel(const A a) {
   extern __shared__ double cp_med[];                     // [c][CP_BLOCK]
   const satcv_composite_desc& d = a.d;
   const float* __restrict__ src = reinterpret_cast<const float*>(d.src);
@@ -203,14 +246,16 @@ __global__ __launch_bounds__(CP_BLOCK) void composite32_kernel(const Args a) {
   for (int base = blockIdx.x * CP_BLOCK; base < a.items; base += gridDim.x * CP_BLOCK) {
     const bool live = base + tid < a.items;
     const int it = live ? base + tid : a.items - 1;
+    unsigned w = 0;                                       // the pixel's clear bits, loaded once (N <= 32: one word)
+    if constexpr (A::masked) w = clear_word(a, 0, (size_t)it);
     for (int b = 0; b < c; ++b) {
       float s[N];
       int par = 0, cnt = 0;
 #pragma unroll
       for (int j = 0; j < N; ++j) {
         float v = 0.f;
-        if (j < t) v = src[((size_t)j * c + b) * npix + it];       // wave-uniform condition
-        const int valid = v > 0.f;                                 // NaN and negative values are nodata
+        if (j < t) v = src[plane_of(a, j, c, b) * npix + it];         // wave-uniform condition
+        const int valid = valid_of<A>(v, w, j);                    // NaN and negative values are nodata
         const int top = (valid ^ 1) & par;
         par ^= valid ^ 1;
         cnt += valid;
@@ -225,8 +270,8 @@ __global__ __launch_bounds__(CP_BLOCK) void composite32_kernel(const Args a) {
 
 // ---------------------------------------------------------------- general path: any t up to SATCV_COMPOSITE_MAX_T
 // keys: the float bits of a valid sample after the harmonisation (>= +0, so they order as unsigned integers), all ones for nodata
-template <typename S>
-__global__ __launch_bounds__(CP_GBLOCK) void composite_general_kernel(const Args a) {
+template <typename S, typename A>
+__global__ __launch_bounds__(CP_GBLOCK) void composite_general_kernel(const A a) {
   extern __shared__ double cp_med[];                     // [c][CP_GBLOCK] doubles, then [t][CP_GBLOCK] keys
   const satcv_composite_desc& d = a.d;
   const S* __restrict__ src = reinterpret_cast<const S*>(d.src);
@@ -237,10 +282,15 @@ __global__ __launch_bounds__(CP_GBLOCK) void composite_general_kernel(const Args
     const int it = live ? base + tid : a.items - 1;
     for (int b = 0; b < c; ++b) {
       int n = 0;
+      unsigned w = 0xffffffffu;
       for (int j = 0; j < t; ++j) {
-        const float v = (float)src[((size_t)j * c + b) * npix + it];
+        const float v = (float)src[plane_of(a, j, c, b) * npix + it];
         const float off = offset_of<!std::is_same<S, float>::value>(d.offsets, j, t);
-        const bool valid = v > 0.f;
+        bool valid = v > 0.f;
+        if constexpr (A::masked) {
+          if ((j & 31) == 0) w = clear_word(a, j >> 5, (size_t)it);      // wave-uniform condition
+          valid = valid && ((w >> (j & 31)) & 1u);
+        }
         n += valid;
         key[j * CP_GBLOCK] = valid ? __float_as_uint(fmaxf(v, off) - off) : 0xffffffffu;
       }
@@ -266,8 +316,8 @@ __global__ __launch_bounds__(CP_GBLOCK) void composite_general_kernel(const Args
   }
 }
 
-template <typename K>
-int launch(K kern, const Args& a, int block, size_t lds, hipStream_t st) {
+template <typename K, typename A>
+int launch(K kern, const A& a, int block, size_t lds, hipStream_t st) {
   const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds);
   if (rc != SATCV_OK) return rc;
   int grid = (a.items + block - 1) / block;
@@ -276,41 +326,46 @@ int launch(K kern, const Args& a, int block, size_t lds, hipStream_t st) {
   return SATCV_OK;
 }
 
-template <bool SIGNED>
-int launch16(const Args& a, hipStream_t st) {
+template <bool SIGNED, typename A>
+int launch16(const A& a, hipStream_t st) {
   const size_t lds = (size_t)a.d.c * 2 * CP_BLOCK * sizeof(double);
   const int t = a.d.t;
-  if (t <= 4) return launch(composite16_kernel<SIGNED, 4>, a, CP_BLOCK, lds, st);
-  if (t <= 8) return launch(composite16_kernel<SIGNED, 8>, a, CP_BLOCK, lds, st);
-  if (t <= 16) return launch(composite16_kernel<SIGNED, 16>, a, CP_BLOCK, lds, st);
-  return launch(composite16_kernel<SIGNED, 32>, a, CP_BLOCK, lds, st);
+  if (t <= 4) return launch(composite16_kernel<SIGNED, 4, A>, a, CP_BLOCK, lds, st);
+  if (t <= 8) return launch(composite16_kernel<SIGNED, 8, A>, a, CP_BLOCK, lds, st);
+  if (t <= 16) return launch(composite16_kernel<SIGNED, 16, A>, a, CP_BLOCK, lds, st);
+  return launch(composite16_kernel<SIGNED, 32, A>, a, CP_BLOCK, lds, st);
 }
 
-int launch32(const Args& a, hipStream_t st) {
+template <typename A>
+int launch32(const A& a, hipStream_t st) {
   const size_t lds = (size_t)a.d.c * CP_BLOCK * sizeof(double);
   const int t = a.d.t;
-  if (t <= 4) return launch(composite32_kernel<4>, a, CP_BLOCK, lds, st);
-  if (t <= 8) return launch(composite32_kernel<8>, a, CP_BLOCK, lds, st);
-  if (t <= 16) return launch(composite32_kernel<16>, a, CP_BLOCK, lds, st);
-  return launch(composite32_kernel<32>, a, CP_BLOCK, lds, st);
+  if (t <= 4) return launch(composite32_kernel<4, A>, a, CP_BLOCK, lds, st);
+  if (t <= 8) return launch(composite32_kernel<8, A>, a, CP_BLOCK, lds, st);
+  if (t <= 16) return launch(composite32_kernel<16, A>, a, CP_BLOCK, lds, st);
+  return launch(composite32_kernel<32, A>, a, CP_BLOCK, lds, st);
 }
 
-}  // namespace
-
-extern "C" int satcv_median_composite(const satcv_composite_desc* d, void* stream) {
-  SATCV_CHECK(d && d->src, "median_composite: null pointer (src)");
-  SATCV_CHECK(d->median || d->norm, "median_composite: both outputs are null");
-  SATCV_CHECK(d->t > 0 && d->c > 0 && d->h > 0 && d->w_ > 0, "median_composite: sizes must be positive");
-  SATCV_CHECK(d->c <= 16, "median_composite: c = %d bands (at most 16)", d->c);
-  SATCV_CHECK(d->src_kind >= 1 && d->src_kind <= 3, "median_composite: src_kind %d (1 u16, 2 f32, 3 i16)", d->src_kind);
+// the checks both entry points share
+int check_desc(const satcv_composite_desc* d, const char* who) {
+  SATCV_CHECK(d && d->src, "%s: null pointer (src)", who);
+  SATCV_CHECK(d->median || d->norm, "%s: both outputs are null", who);
+  SATCV_CHECK(d->t > 0 && d->c > 0 && d->h > 0 && d->w_ > 0, "%s: sizes must be positive", who);
+  SATCV_CHECK(d->c <= 16, "%s: c = %d bands (at most 16)", who, d->c);
+  SATCV_CHECK(d->src_kind >= 1 && d->src_kind <= 3, "%s: src_kind %d (1 u16, 2 f32, 3 i16)", who, d->src_kind);
   SATCV_CHECK(!d->median || (d->coff_med >= 0 && d->ld_med > 0 && (long long)d->coff_med + d->c <= d->ld_med),
-              "median_composite: median channel range (coff_med + c <= ld_med)");
+              "%s: median channel range (coff_med + c <= ld_med)", who);
   SATCV_CHECK(!d->norm || (d->coff_norm >= 0 && d->ld_norm > 0 && (long long)d->coff_norm + d->c <= d->ld_norm),
-              "median_composite: norm channel range (coff_norm + c <= ld_norm)");
-  SATCV_CHECK(d->t <= SATCV_COMPOSITE_MAX_T, "median_composite: t = %d acquisitions (at most %d)", d->t, SATCV_COMPOSITE_MAX_T);
-  SATCV_CHECK(satcv_pixels_ok(1, d->h, d->w_, 1), "median_composite: map beyond 2^31 pixels");
-  Args a;
-  a.d = *d;
+              "%s: norm channel range (coff_norm + c <= ld_norm)", who);
+  SATCV_CHECK(d->t <= SATCV_COMPOSITE_MAX_T, "%s: t = %d acquisitions (at most %d)", who, d->t, SATCV_COMPOSITE_MAX_T);
+  SATCV_CHECK(satcv_pixels_ok(1, d->h, d->w_, 1), "%s: map beyond 2^31 pixels", who);
+  return SATCV_OK;
+}
+
+// a is complete but for the fields set here
+template <typename A>
+int run(A& a, const char* who, void* stream) {
+  const satcv_composite_desc* d = &a.d;
   a.npix = d->h * d->w_;
   const bool c4 = d->c % 4 == 0;
   a.vec_med = d->median && c4 && d->ld_med % 4 == 0 && d->coff_med % 4 == 0 && (uintptr_t)d->median % 16 == 0;
@@ -320,9 +375,9 @@ extern "C" int satcv_median_composite(const satcv_composite_desc* d, void* strea
   if (d->t > 32 || a.npix < 2) {
     a.items = a.npix;
     const size_t lds = (size_t)CP_GBLOCK * (d->c * sizeof(double) + d->t * sizeof(unsigned));
-    if (d->src_kind == 1) rc = launch(composite_general_kernel<uint16_t>, a, CP_GBLOCK, lds, st);
-    else if (d->src_kind == 2) rc = launch(composite_general_kernel<float>, a, CP_GBLOCK, lds, st);
-    else rc = launch(composite_general_kernel<int16_t>, a, CP_GBLOCK, lds, st);
+    if (d->src_kind == 1) rc = launch(composite_general_kernel<uint16_t, A>, a, CP_GBLOCK, lds, st);
+    else if (d->src_kind == 2) rc = launch(composite_general_kernel<float, A>, a, CP_GBLOCK, lds, st);
+    else rc = launch(composite_general_kernel<int16_t, A>, a, CP_GBLOCK, lds, st);
   } else if (d->src_kind == 2) {
     a.items = a.npix;
     rc = launch32(a, st);
@@ -333,8 +388,34 @@ extern "C" int satcv_median_composite(const satcv_composite_desc* d, void* strea
   if (rc != SATCV_OK) return rc;
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    satcv_set_error("median_composite launch: %s", hipGetErrorString(e));
+    satcv_set_error("%s launch: %s", who, hipGetErrorString(e));
     return SATCV_ERR_HIP;
   }
   return SATCV_OK;
+}
+
+}  // namespace
+
+extern "C" int satcv_median_composite(const satcv_composite_desc* d, void* stream) {
+  const int rc = check_desc(d, "median_composite");
+  if (rc != SATCV_OK) return rc;
+  Args a;
+  a.d = *d;
+  return run(a, "median_composite", stream);
+}
+
+extern "C" int satcv_median_composite_masked(const satcv_composite_masked_desc* d, void* stream) {
+  SATCV_CHECK(d, "median_composite_masked: null pointer (descriptor)");
+  const int rc = check_desc(&d->base, "median_composite_masked");
+  if (rc != SATCV_OK) return rc;
+  SATCV_CHECK(d->cs >= 1 && d->cs <= 16, "median_composite_masked: cs = %d planes per acquisition (1 ... 16)", d->cs);
+  for (int b = 0; b < d->base.c; ++b)
+    SATCV_CHECK(d->band_idx[b] >= 0 && d->band_idx[b] < d->cs, "median_composite_masked: band_idx[%d] = %d out of range (cs = %d)", b, d->band_idx[b], d->cs);
+  MaskedArgs a;
+  a.d = d->base;
+  a.clear = d->clear;
+  a.cs = d->cs;
+  a.bands = 0;
+  for (int b = 0; b < d->base.c; ++b) a.bands |= (unsigned long long)d->band_idx[b] << (4 * b);
+  return run(a, "median_composite_masked", stream);
 }

@@ -7,6 +7,10 @@
 The first four arrows are ONE kernel (satcv_median_composite, csrc/composite.hip) on a stack that is uploaded once; its output is the
 (H, W, C) float32 scene the device-resident prediction loop of prediction_tools reads in place.  Acquisition (STAC search, stackstac,
 rioxarray), reprojection and clipping stay with the caller.
+
+The composites the reference's models were trained on were masked per acquisition first (utils/ee_tools.py: basicQA :159, maskTOA
+:288, maskSR :270, mask :257).  `median_composite(clear=...)` / `predict_change(quality=...)` take those masks from `ee_tools` as bit-planes
+on the device (satcv_median_composite_masked): a sample is valid iff it is > 0 and its clear bit is set.
 """
 from datetime import datetime
 
@@ -57,7 +61,81 @@ def _stack_to_device(stack):
     return _to_device(stack, 'the time stack'), kinds[stack.dtype]
 
 
-def median_composite(stack, times=None, offsets=None, fill=None, out=None, channel_offset=0):
+def _band_selection(bands, band_names, nplanes):
+    """`bands` (indices, or names together with `band_names`) -> plane indices; None: every plane in order"""
+    if bands is None:
+        return list(range(nplanes))
+    bands = list(bands)
+    if not bands:
+        raise ValueError('an empty band selection')
+    if all(isinstance(b, (int, np.integer)) for b in bands):
+        idx = [int(b) for b in bands]
+    else:
+        if band_names is None:
+            raise ValueError('bands given by name need band_names, the names of the planes of the stack')
+        from .ee_tools import canonical_band
+        names = [canonical_band(b) for b in band_names]
+        if len(names) != nplanes:
+            raise ValueError(f'{nplanes} planes need {nplanes} band_names, got {len(names)}')
+        missing = [b for b in bands if canonical_band(b) not in names]
+        if missing:
+            raise ValueError(f'bands {missing} are not among band_names {list(band_names)}')
+        idx = [names.index(canonical_band(b)) for b in bands]
+    if any(i < 0 or i >= nplanes for i in idx):
+        raise ValueError(f'band selection {idx} outside the {nplanes} planes of the stack')
+    if len(idx) > 16:
+        raise ValueError(f'{len(idx)} bands: the composite kernel takes at most 16')
+    return idx
+
+
+def _offsets_to_device(T, times, offsets):
+    from .prediction_tools import _to_device
+    if times is not None and offsets is not None:
+        raise ValueError('give times or offsets, not both')
+    if times is not None:
+        offsets = harmonize_offsets(times)
+    if offsets is None:
+        return None
+    offsets = np.ascontiguousarray(offsets, np.float32)
+    if offsets.shape != (T,):
+        raise ValueError(f'{T} acquisitions need {T} offsets / times, got shape {offsets.shape}')
+    return _to_device(offsets, 'the offset table') if offsets.any() else None
+
+
+def _composite(src, kind, off_dev, fill, out, channel_offset, clear=None, idx=None):
+    """the launch of `median_composite` on a resident stack (src, kind); clear: a ClearMask or None, idx: plane indices or None.
+    With neither it is satcv_median_composite, otherwise satcv_median_composite_masked."""
+    import ctypes as C
+    import torch
+    from . import ops
+    from ._lib import CompositeDesc, CompositeMaskedDesc, check, lib
+    from .prediction_tools import _device_empty
+    T, cs, H, W = (int(v) for v in src.shape)
+    nb = cs if idx is None else len(idx)
+    median = _device_empty((H, W, nb), torch.float32, 'the median composite')
+    if out is None:
+        if channel_offset:
+            raise ValueError('channel_offset needs out')
+        out = _device_empty((H, W, nb), torch.float32, 'the normalised composite')
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and out.is_contiguous()
+              and tuple(out.shape[:2]) == (H, W)):
+        raise ValueError(f'out must be a contiguous float32 CUDA tensor ({H}, {W}, ld)')
+    d = CompositeDesc(src=src.data_ptr(), src_kind=kind, t=T, c=nb, h=H, w_=W, offsets=off_dev.data_ptr() if off_dev is not None else None,
+                      median=median.data_ptr(), ld_med=nb, coff_med=0, norm=out.data_ptr(), ld_norm=out.shape[2], coff_norm=int(channel_offset),
+                      use_fill=int(fill is not None), fill=float(fill or 0.0))
+    if clear is None and idx is None:
+        check(lib.satcv_median_composite(C.byref(d), ops.stream_ptr()))
+    else:
+        if clear is not None and clear.shape != (T, H, W):
+            raise ValueError(f'the clear mask is for a stack {clear.shape}, the stack is {(T, H, W)}')
+        table = list(idx if idx is not None else range(cs)) + [0] * 16
+        md = CompositeMaskedDesc(base=d, clear=clear.words.data_ptr() if clear is not None else None, cs=cs, band_idx=(C.c_int32 * 16)(*table[:16]))
+        check(lib.satcv_median_composite_masked(C.byref(md), ops.stream_ptr()))
+    # `src`, `off_dev` and the mask may be released on return: the caching allocator hands their memory to later work of this same stream only
+    return median, out[..., channel_offset:channel_offset + nb]
+
+
+def median_composite(stack, times=None, offsets=None, fill=None, out=None, channel_offset=0, clear=None, bands=None, band_names=None):
     """Median composite of a time stack and its per-pixel normalisation over bands, on the device: `(median, norm)`, float32 CUDA
     tensors (H, W, C).
 
@@ -70,47 +148,27 @@ def median_composite(stack, times=None, offsets=None, fill=None, out=None, chann
     out, channel_offset: write `norm` into channels [channel_offset, channel_offset + C) of an existing contiguous float32 CUDA tensor
     (H, W, ld) -- with ld = 2 C the before / after composites of `run_local` land in one scene without a concatenation pass (:650);
     the returned `norm` is that slice.
+    clear: an `ee_tools.ClearMask` of the stack (basicQA / maskTOA / maskSR / mask): a sample takes part iff it is > 0 and clear.
+    bands: the planes that make the composite, by index, or by name together with band_names (the names of the stack's planes) --
+    a 14-plane stack with its QA60 plane yields a 4-band composite without a copy; C above is then len(bands).
+    With neither `clear` nor `bands` the launch is the unmasked kernel's, unchanged.
     Nothing here synchronises with the host.  T <= 256, C <= 16; a stack that does not fit in device memory raises MemoryError."""
-    import ctypes as C
-    import torch
-    from . import ops
-    from ._lib import COMPOSITE_MAX_T, CompositeDesc, check, lib
-    from .prediction_tools import _device_empty, _to_device
+    from ._lib import COMPOSITE_MAX_T
     if getattr(stack, 'ndim', 0) != 4:
         raise ValueError(f'expected a (T, C, H, W) stack, got shape {tuple(getattr(stack, "shape", ()))}')
     T, nb, H, W = (int(v) for v in stack.shape)
     if T > COMPOSITE_MAX_T:
         raise ValueError(f'{T} acquisitions: the composite kernel takes at most {COMPOSITE_MAX_T}')
-    if times is not None and offsets is not None:
-        raise ValueError('give times or offsets, not both')
-    if times is not None:
-        offsets = harmonize_offsets(times)
-    off_dev = None
-    if offsets is not None:
-        offsets = np.ascontiguousarray(offsets, np.float32)
-        if offsets.shape != (T,):
-            raise ValueError(f'{T} acquisitions need {T} offsets / times, got shape {offsets.shape}')
-        if offsets.any():
-            off_dev = _to_device(offsets, 'the offset table')
+    idx = _band_selection(bands, band_names, nb) if bands is not None else None
+    if clear is not None and not hasattr(clear, 'words'):
+        raise ValueError('clear is an ee_tools.ClearMask')
+    off_dev = _offsets_to_device(T, times, offsets)
     src, kind = _stack_to_device(stack)
-    median = _device_empty((H, W, nb), torch.float32, 'the median composite')
-    if out is None:
-        if channel_offset:
-            raise ValueError('channel_offset needs out')
-        out = _device_empty((H, W, nb), torch.float32, 'the normalised composite')
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and out.is_contiguous()
-              and tuple(out.shape[:2]) == (H, W)):
-        raise ValueError(f'out must be a contiguous float32 CUDA tensor ({H}, {W}, ld)')
-    d = CompositeDesc(src=src.data_ptr(), src_kind=kind, t=T, c=nb, h=H, w_=W, offsets=off_dev.data_ptr() if off_dev is not None else None,
-                      median=median.data_ptr(), ld_med=nb, coff_med=0, norm=out.data_ptr(), ld_norm=out.shape[2], coff_norm=int(channel_offset),
-                      use_fill=int(fill is not None), fill=float(fill or 0.0))
-    check(lib.satcv_median_composite(C.byref(d), ops.stream_ptr()))
-    # `src` and `off_dev` may be released on return: the caching allocator hands their memory to later work of this same stream only
-    return median, out[..., channel_offset:channel_offset + nb]
+    return _composite(src, kind, off_dev, fill, out, channel_offset, clear, idx)
 
 
 def predict_change(before, after, m, before_times=None, after_times=None, buff=128, kernel=256, batch_size=16, channel=0,
-                   cover='reference', fill=None):
+                   cover='reference', fill=None, quality=None, band_names=None, bands=None):
     """`run_local` (utils/pc_tools.py:620-668) from the two time stacks on: `(output, bef_median, aft_median)` -- the change map
     (H, W) float32 and the two median composites (H, W, C) float32 as host arrays (the reference's return without the geotransform).
 
@@ -119,20 +177,47 @@ def predict_change(before, after, m, before_times=None, after_times=None, buff=1
     two-input model (make_siamese_unet) gets the pair in its own input order (a = after / T2, b = before / T1, as `predict_chips`
     documents).  buff, kernel, batch_size, channel, cover: as `prediction_tools.predict_scene`.  fill: see `median_composite`; with
     None a pixel without a valid sample sends NaN into every chip that contains it, as in the reference.
+    quality: masks both stacks before their composites, as the reference's training composites were (utils/ee_tools.py) -- 'toa'
+    (maskTOA :288), 'sr' (maskSR :270), 'mask' (mask :257), any rule set `ee_tools.rule_set` takes (these need band_names, the names of
+    the planes), or a pair of `ee_tools.ClearMask`s (before, after).  bands: the planes the model sees, see `median_composite`; the
+    returned medians are the masked composites of those bands.
     The composites stay on the device from the composite kernel to the stitch; the three returned arrays are the only copies back."""
     import torch
     from . import prediction_tools as pt
     from .prediction_tools import _device_empty
     if getattr(before, 'ndim', 0) != 4 or getattr(after, 'ndim', 0) != 4 or tuple(before.shape[1:]) != tuple(after.shape[1:]):
         raise ValueError(f'before and after must be (T, C, H, W) stacks of equal C, H, W, got {tuple(before.shape)} and {tuple(after.shape)}')
-    nb, H, W = (int(v) for v in before.shape[1:])
-    if len(getattr(m, 'inputs', ())) > 1:
-        bef_median, bef_norm = median_composite(before, times=before_times, fill=fill)
-        aft_median, aft_norm = median_composite(after, times=after_times, fill=fill)
-        scene = (aft_norm, bef_norm)
-    else:
-        scene = _device_empty((H, W, 2 * nb), torch.float32, 'the two-date scene')
-        bef_median, _ = median_composite(before, times=before_times, fill=fill, out=scene, channel_offset=0)
-        aft_median, _ = median_composite(after, times=after_times, fill=fill, out=scene, channel_offset=nb)
+    cs, H, W = (int(v) for v in before.shape[1:])
+    idx = _band_selection(bands, band_names, cs) if bands is not None else None
+    nb = cs if idx is None else len(idx)
+    masks = (None, None)
+    rules = table = None
+    if quality is not None:
+        from . import ee_tools as ee
+        if isinstance(quality, (tuple, list)) and len(quality) == 2 and all(hasattr(q, 'words') for q in quality):
+            masks = tuple(quality)
+        else:
+            rules = ee.rule_set(quality)
+            if band_names is None:
+                raise ValueError('quality rules need band_names, the names of the planes of the stacks')
+            if len(band_names) != cs:
+                raise ValueError(f'{cs} planes need {cs} band_names, got {len(band_names)}')
+            table = ee.band_table(band_names)
+            ee._require(table, rules, band_names)
+    two_inputs = len(getattr(m, 'inputs', ())) > 1
+    scene = None if two_inputs else _device_empty((H, W, 2 * nb), torch.float32, 'the two-date scene')
+    medians, norms = [], []
+    for k, (stack, times, clear) in enumerate(((before, before_times, masks[0]), (after, after_times, masks[1]))):
+        off_dev = _offsets_to_device(int(stack.shape[0]), times, None)
+        src, kind = _stack_to_device(stack)                  # uploaded once: the mask kernel and the composite read the same copy
+        if rules is not None:
+            clear = ee._quality(src, kind, table, rules, off_dev, clear=True)[0]
+        median, norm = _composite(src, kind, off_dev, fill, scene, 0 if two_inputs else k * nb, clear, idx)
+        medians.append(median)
+        norms.append(norm)
+        del src, clear                                       # one stack resident at a time, as before
+    bef_median, aft_median = medians
+    if two_inputs:
+        scene = (norms[1], norms[0])
     output = pt.predict_scene(scene, m, kernel=kernel, buff=buff, batch_size=batch_size, channel=channel, cover=cover)
     return output, bef_median.cpu().numpy(), aft_median.cpu().numpy()
