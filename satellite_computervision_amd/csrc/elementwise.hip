@@ -1552,12 +1552,16 @@ __global__ void loss_kernel(int kind, const float* __restrict__ probs, const flo
         gp[k] = inside ? (-t[k] * pw / yp + (1.f - t[k]) / (1.f - yp)) * inv_e : 0.f;
       }
     }
-    if (activation == 0) {      // softmax Jacobian
-      float dot = 0.f;
+    if (activation == 0) {      // softmax Jacobian p_k (gp_k - sum_j gp_j p_j), written as p_k (gp_k (1 - p_k) - sum_{j != k} gp_j p_j):
+      // gp_k never meets its own share of the sum.  Under weighted BCE a probability just below the upper clip has gp ~ 1e5 / n, and
+      // gp_k - gp_k p_k in float32 lost three digits of p_k gp_k (1 - p_k) (7.8e-4 of the largest gradient at one class).
 #pragma unroll
-      for (int k = 0; k < HEAD_NCMAX; ++k) dot += gp[k] * pr[k];
+      for (int k = 0; k < HEAD_NCMAX; ++k) if (k < nc) {
+        float rest = 0.f;
 #pragma unroll
-      for (int k = 0; k < HEAD_NCMAX; ++k) if (k < nc) dlogits[p * nc + k] = grad_scale * pr[k] * (gp[k] - dot);
+        for (int j = 0; j < HEAD_NCMAX; ++j) if (j != k) rest += gp[j] * pr[j];
+        dlogits[p * nc + k] = grad_scale * pr[k] * (gp[k] * (1.f - pr[k]) - rest);
+      }
     } else if (activation == 2) {   // linear head (regression): the outputs are the logits
 #pragma unroll
       for (int k = 0; k < HEAD_NCMAX; ++k) if (k < nc) dlogits[p * nc + k] = grad_scale * gp[k];
@@ -1571,9 +1575,11 @@ __global__ void loss_kernel(int kind, const float* __restrict__ probs, const flo
   __syncthreads();
   if (threadIdx.x == 0) { float s = 0.f; for (int i = 0; i < EW_BLOCK / 64; ++i) s += red[i]; atomicAdd(loss_out, s); }
 }
-// Round 6: the same arithmetic, statement for statement, with the class count at compile time (2 or 4: one 8- / 16-byte load and store per
-// tensor and pixel instead of a scalar one per class behind a run-time `k < nc`) for the case every U-Net of the reference trains with --
-// weighted categorical cross-entropy on a softmax head (utils/model_tools.py:25, 414).  42 -> ~25 us per step at batch 64.
+// Round 6: the same loss and gradient with the class count at compile time (2 or 4: one 8- / 16-byte load and store per tensor and pixel
+// instead of a scalar one per class behind a run-time `k < nc`) for the case every U-Net of the reference trains with -- weighted
+// categorical cross-entropy on a softmax head (utils/model_tools.py:25, 414).  42 -> ~25 us per step at batch 64.  Statement for
+// statement loss_kernel's arithmetic up to the softmax Jacobian, which loss_kernel now forms without gp_k's own share of the sum: the
+// same number, and cross-entropy has no large gp_k to cancel, so this kernel keeps p_k (gp_k - sum_j gp_j p_j).
 template <int NC>
 __global__ __launch_bounds__(EW_BLOCK) void loss_cce_softmax_kernel(const float* __restrict__ probs, const float* __restrict__ yt, const float* __restrict__ wts,
                                                                     long long npix, float grad_scale, float* loss_out, float* dlogits) {
