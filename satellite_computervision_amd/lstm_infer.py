@@ -163,34 +163,74 @@ def _stage_prefix(dst, src, lead, B, what):
     return n
 
 
-def _run_captured(plan, what):
-    """One run of `plan._launch` (SeriesInferPlan, HybridInferPlan): the first run is eager, the second captures the launch list into a
-    graph, later runs replay it on the current stream.  State on the plan: _runs, _graph, _graph_off."""
-    plan._runs += 1
-    if plan._graph is None and plan._runs > 1 and not plan._graph_off and lt.graph_enabled():
-        try:
-            # The launch list runs once, eagerly, ON THE CAPTURE STREAM first: the library keeps per-stream workspaces (split-K slabs)
-            # that it never allocates inside a capture, and a convolution that finds none takes another kernel form -- the replay
-            # would differ from the eager run in the last bits.  Then the same list is captured there, one linear chain.
-            g, cap, cur = torch.cuda.CUDAGraph(), _capture_stream(), torch.cuda.current_stream()
-            cap.wait_stream(cur)
-            with torch.cuda.stream(cap):
-                plan._launch()
-            cur.wait_stream(cap)
-            torch.cuda.synchronize()
-            with torch.cuda.graph(g, stream=cap):
-                plan._launch()
-            plan._graph = g
-        except Exception as e:           # a forward that cannot be captured stays eager (and says so once)
-            warnings.warn(f'{what}: forward not captured ({e}); running eagerly')
-            plan._graph_off = True
-    if plan._graph is not None and lt.graph_enabled():
-        plan._graph.replay()
-    else:
-        plan._launch()
+class _ConvLstmPlan:
+    """What SeriesInferPlan and HybridInferPlan share -- the ConvLSTM branch of `model` (its layers in `stack`) for B chips of H x W pixels:
+    the static input x_in (T * B, H, W, cpad), both ConvLSTM2D layers and their BatchNorms as planned launches on preallocated buffers,
+    the repack of parameters that changed, and the capture of the subclass's launch list (`_launch`) into a graph."""
+
+    def __init__(self, model, stack, B, H, W, fused):
+        self.model, self.dtype = model, model.dtype_code
+        T = self.T = model.n_time
+        self.cpad = ops.rup(model.n_channels, 16)
+        self.x_in = torch.zeros(T * B, H, W, self.cpad, dtype=ops.TORCH_DTYPE[self.dtype], device=lt._dev())
+        self.l1 = _PlannedLayer(stack.l1, T, B, H, W, self.dtype, fused)
+        self.bn1 = _PlannedBN(stack.bn1, self.l1.Fp)
+        self.l2 = _PlannedLayer(stack.l2, T, B, H, W, self.dtype, fused)
+        self.bn2 = _PlannedBN(stack.bn2, self.l2.Fp)
+        self.fused_layers = tuple(n for n, l in (('conv_lstm', self.l1), ('dilated_conv_lstm', self.l2)) if l.fused)
+        self._ver = None
+        self._runs, self._graph, self._graph_off = 0, None, False
+
+    def _check_dtype(self):
+        if self.model.dtype_code != self.dtype:
+            raise ValueError('the model\'s compute_dtype changed since this plan was built; build a new plan')
+
+    def _refresh(self):
+        """parameters changed since the last run (set_weights, training) are repacked, into the same buffers"""
+        if self._ver != self.model.P.version:
+            for p in (self.l1, self.bn1, self.l2, self.bn2):
+                p.refresh()
+            self._ver = self.model.P.version
+
+    def _launch_lstm(self):
+        """the head of both launch lists: conv_lstm -> batch_norm -> dilated_conv_lstm; -> Act of the second layer's raw output"""
+        s1 = self.l1.launch(lt.Act(self.x_in, self.model.n_channels))
+        a1 = self.bn1.apply(s1)                                             # (Dropout passes through at inference)
+        return self.l2.launch(a1)
+
+    def _run_captured(self):
+        """One run of `self._launch`: the first run is eager, the second captures the launch list into a graph, later runs replay it on
+        the current stream."""
+        self._runs += 1
+        if self._graph is None and self._runs > 1 and not self._graph_off and lt.graph_enabled():
+            try:
+                # The launch list runs once, eagerly, ON THE CAPTURE STREAM first: the library keeps per-stream workspaces (split-K slabs)
+                # that it never allocates inside a capture, and a convolution that finds none takes another kernel form -- the replay
+                # would differ from the eager run in the last bits.  Then the same list is captured there, one linear chain.
+                g, cap, cur = torch.cuda.CUDAGraph(), _capture_stream(), torch.cuda.current_stream()
+                cap.wait_stream(cur)
+                with torch.cuda.stream(cap):
+                    self._launch()
+                cur.wait_stream(cap)
+                torch.cuda.synchronize()
+                with torch.cuda.graph(g, stream=cap):
+                    self._launch()
+                self._graph = g
+            except Exception as e:           # a forward that cannot be captured stays eager (and says so once)
+                warnings.warn(f'{type(self).__name__}: forward not captured ({e}); running eagerly')
+                self._graph_off = True
+        if self._graph is not None and lt.graph_enabled():
+            self._graph.replay()
+        else:
+            self._launch()
+
+    @property
+    def replaying(self):
+        """whether the next run replays a captured graph"""
+        return self._graph is not None and bool(lt.graph_enabled())
 
 
-class SeriesInferPlan:
+class SeriesInferPlan(_ConvLstmPlan):
     """SeriesInferPlan(model, shape=(B, T, H, W), fused=...) for an LSTMModel or an LSTMAutoencoder, in the model's storage type at the time
     it is built.  `run(xt, want_classes=False)` takes what `predict_on_device(..., shape=shape)` takes -- the ingested time-major tensor
     (T * B, H, W, cpad); for the autoencoder the pair [xt, sincos] -- and returns what it returns.
@@ -212,38 +252,21 @@ class SeriesInferPlan:
             raise ValueError(f'model was built for {model.n_time} time steps, got {T}')
         if min(B, H, W) < 1:
             raise ValueError(f'bad plan shape {shape}')
-        self.model, self.shape, self.dtype = model, (B, T, H, W), model.dtype_code
+        self.shape = (B, T, H, W)
         self.is_ae = isinstance(model, lt.LSTMAutoencoder)
-        stack = model.enc if self.is_ae else model.layers_
+        super().__init__(model, model.enc if self.is_ae else model.layers_, B, H, W, fused)
         td, dev = ops.TORCH_DTYPE[self.dtype], lt._dev()
-        self.cpad = ops.rup(model.n_channels, 16)
-        self.x_in = torch.zeros(T * B, H, W, self.cpad, dtype=td, device=dev)
-        self.l1 = _PlannedLayer(stack.l1, T, B, H, W, self.dtype, fused)
-        self.bn1 = _PlannedBN(stack.bn1, self.l1.Fp)
-        self.l2 = _PlannedLayer(stack.l2, T, B, H, W, self.dtype, fused)
-        self.bn2 = _PlannedBN(stack.bn2, self.l2.Fp)
-        self.fused_layers = tuple(n for n, l in (('conv_lstm', self.l1), ('dilated_conv_lstm', self.l2)) if l.fused)
         self.head = model.single if self.is_ae else model.dense
         self.out = torch.empty(B, H, W, self.head.cout, dtype=torch.float32, device=dev)
         self.classes = torch.empty(B, H, W, dtype=torch.int32, device=dev) if (not self.is_ae and model.class_output) else None
         if self.is_ae:
             self.sc_in = torch.zeros(B, H, W, 2, dtype=torch.float32, device=dev)
             self.enc_out = torch.empty(B, H, W, self.l1.Fp, dtype=td, device=dev)
-        self._ver = None
-        self._runs, self._graph, self._graph_off = 0, None, False
-
-    # ------------------------------------------------------------------ parameters
-    def _refresh(self):
-        for p in (self.l1, self.bn1, self.l2, self.bn2):
-            p.refresh()
-        self._ver = self.model.P.version
 
     # ------------------------------------------------------------------ the launch list (the structure of _forward_ingested, inference)
     def _launch(self):
-        m, (B, T, H, W) = self.model, self.shape
-        s1 = self.l1.launch(lt.Act(self.x_in, m.n_channels))
-        a1 = self.bn1.apply(s1)                                             # (Dropout passes through at inference)
-        h2 = self.l2.launch(a1)
+        B, T, H, W = self.shape
+        h2 = self._launch_lstm()
         if not self.is_ae:
             feats = self.bn2.apply(h2)
             srcs = [(feats, False)]
@@ -271,9 +294,8 @@ class SeriesInferPlan:
         first n chips of the result are its prediction.  The tensors returned belong to the plan and are overwritten by its next run."""
         if want_classes and self.classes is None:
             raise ValueError("want_classes needs a model with activation='softmax'")
-        if self.model.dtype_code != self.dtype:
-            raise ValueError('the model\'s compute_dtype changed since this plan was built; build a new plan')
-        T = self.shape[1]
+        self._check_dtype()
+        T = self.T
         if self.is_ae:
             xt, sincos = xt
             n = self._stage(self.x_in, xt, T, 'xt')
@@ -281,24 +303,18 @@ class SeriesInferPlan:
                 raise ValueError('xt and sincos hold different numbers of chips')
         else:
             self._stage(self.x_in, xt, T, 'xt')
-        if self._ver != self.model.P.version:
-            self._refresh()
-        _run_captured(self, 'SeriesInferPlan')
+        self._refresh()
+        self._run_captured()
         return (self.out, self.classes) if want_classes else self.out
 
-    @property
-    def replaying(self):
-        """whether the next run replays a captured graph"""
-        return self._graph is not None and bool(lt.graph_enabled())
 
-
-class HybridInferPlan:
+class HybridInferPlan(_ConvLstmPlan):
     """HybridInferPlan(model, batch, side, side_lo, fused=False): the inference plan of a lstm_tools.HybridModel for scene prediction
     (prediction_tools.predict_hybrid_scene), in the model's storage type at the time it is built; also HybridModel.scene_plan(...).
 
-    The plan owns the ConvLSTM branch the way SeriesInferPlan does: the static input x_in (T * batch, side_lo, side_lo, cpad), both
-    ConvLSTM2D layers and BatchNorms as planned launches on preallocated buffers, and the `lstm_dense` launch into a static
-    (batch, side_lo, side_lo, k) tensor.  That chain, and only that chain, is captured into a graph after one eager run and replayed
+    The ConvLSTM branch is the base class's, as for SeriesInferPlan: the static input x_in (T * batch, side_lo, side_lo, cpad) and both
+    ConvLSTM2D layers and BatchNorms as planned launches on preallocated buffers.  The plan's own tail is the `lstm_dense` launch into a
+    static (batch, side_lo, side_lo, k) tensor.  That chain, and only that chain, is captured into a graph after one eager run and replayed
     (SATCV_LSTM_GRAPH=0 keeps it eager; a capture that fails warns once and stays eager).  The U-Net branch (the engine's static plan for
     the n chips of the batch) and the fusion head are launched eagerly on the current stream around the replay: the head's `first`
     changes with every batch, so it cannot live in the graph.  fused=True runs a time step as satcv_convlstm_step_fwd where that kernel
@@ -313,34 +329,15 @@ class HybridInferPlan:
         B, S, SL = int(batch), int(side), int(side_lo)
         if min(B, S, SL) < 1:
             raise ValueError(f'bad plan sizes batch={batch}, side={side}, side_lo={side_lo}')
-        self.model, self.shape, self.dtype = model, (B, S, SL), model.dtype_code
-        T = self.T = model.n_time
-        td, dev = ops.TORCH_DTYPE[self.dtype], lt._dev()
-        self.cpad = ops.rup(model.n_channels, 16)
-        self.x_in = torch.zeros(T * B, SL, SL, self.cpad, dtype=td, device=dev)
-        stack = model.lstm
-        self.l1 = _PlannedLayer(stack.l1, T, B, SL, SL, self.dtype, fused)
-        self.bn1 = _PlannedBN(stack.bn1, self.l1.Fp)
-        self.l2 = _PlannedLayer(stack.l2, T, B, SL, SL, self.dtype, fused)
-        self.bn2 = _PlannedBN(stack.bn2, self.l2.Fp)
-        self.fused_layers = tuple(n for n, l in (('conv_lstm', self.l1), ('dilated_conv_lstm', self.l2)) if l.fused)
-        k = model.n_classes
-        self.zl = torch.empty(B, SL, SL, k, dtype=torch.float32, device=dev)
+        self.shape = (B, S, SL)
+        super().__init__(model, model.lstm, B, SL, SL, fused)
+        self.zl = torch.empty(B, SL, SL, model.n_classes, dtype=torch.float32, device=lt._dev())
         self.out = self.classes = None                                      # (allocated by the first run without scene_head)
-        self._ver = None
-        self._runs, self._graph, self._graph_off = 0, None, False
-
-    def _refresh(self):
-        for p in (self.l1, self.bn1, self.l2, self.bn2):
-            p.refresh()
-        self._ver = self.model.P.version
 
     def _launch(self):
         """the captured chain: conv_lstm -> batch_norm -> dilated_conv_lstm -> batch_norm2 -> lstm_dense (ReLU), into self.zl"""
         m, (B, S, SL) = self.model, self.shape
-        s1 = self.l1.launch(lt.Act(self.x_in, m.n_channels))
-        a1 = self.bn1.apply(s1)                                             # (Dropout passes through at inference)
-        feats = self.bn2.apply(self.l2.launch(a1))
+        feats = self.bn2.apply(self._launch_lstm())
         d = m.lstm_dense._desc([(feats, False)], (SL, SL))
         d.out, d.npix = self.zl.data_ptr(), B * SL * SL
         check(lib.satcv_dense_small_fwd(C.byref(d), ops.stream_ptr()))
@@ -352,17 +349,15 @@ class HybridInferPlan:
         result is returned; without it -> (n, side, side, n_classes) float32 probabilities, with want_classes also the int32 classes.
         Everything returned, and everything the descriptor points to, belongs to the plan and is overwritten by its next run."""
         m, (B, S, SL) = self.model, self.shape
-        if m.dtype_code != self.dtype:
-            raise ValueError('the model\'s compute_dtype changed since this plan was built; build a new plan')
+        self._check_dtype()
         if not (isinstance(xu, torch.Tensor) and xu.is_cuda and xu.dtype == torch.float32 and xu.dim() == 4 and tuple(xu.shape[1:]) == (S, S, m.hi_channels)):
             raise ValueError(f'xu: expected an (n, {S}, {S}, {m.hi_channels}) float32 CUDA tensor, got {getattr(xu, "dtype", None)} {tuple(getattr(xu, "shape", ()))}')
         n = _stage_prefix(self.x_in, xt, self.T, B, 'xt')
         if xu.shape[0] != n:
             raise ValueError(f'xu and xt hold different numbers of chips: {xu.shape[0]} and {n}')
-        if self._ver != m.P.version:
-            self._refresh()
+        self._refresh()
         _, zu = m._unet_branch(xu, False)
-        _run_captured(self, 'HybridInferPlan')
+        self._run_captured()
         srcs = m._fusion_sources(self.zl[:n], zu)
         d = m.fusion._desc(srcs, (S, S))
         d.npix = n * S * S
@@ -374,8 +369,3 @@ class HybridInferPlan:
         d.out, d.classes = self.out.data_ptr(), self.classes.data_ptr()
         check(lib.satcv_dense_small_fwd(C.byref(d), ops.stream_ptr()))
         return (self.out[:n], self.classes[:n]) if want_classes else self.out[:n]
-
-    @property
-    def replaying(self):
-        """whether the next run replays the captured ConvLSTM chain"""
-        return self._graph is not None and bool(lt.graph_enabled())

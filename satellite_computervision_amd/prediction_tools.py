@@ -91,8 +91,10 @@ def predict_chips_sharded(arr, chip_indices, template, m, kernel=256, buff=128, 
 # ---------------------------------------------------------------------------------------------------------------------------------
 # Device-resident scene prediction: the scene goes to the device once, windows are cut there (satcv_scene_gather), the model reads them
 # in place (Model.predict_on_device) and the centres are stitched into a device-resident map (satcv_scene_scatter).  Layout, the
-# reflect rule and the disjointness contract: DESIGN.md, "Device-resident scene prediction".
+# reflect rule and the disjointness contract: DESIGN.md, "Device-resident scene prediction".  The pieces from here to `_stitch_batches`
+# are shared by the three predictors of this file (predict_scene, predict_series_scene, predict_hybrid_scene).
 _SCENE_KIND = {np.dtype(np.uint8): 0, np.dtype(np.uint16): 1, np.dtype(np.float32): 2, np.dtype(np.int16): 3}     # kinds of satcv_tile_desc
+_SERIES_KIND = {np.dtype(np.uint16): 1, np.dtype(np.float32): 2, np.dtype(np.int16): 3}     # kinds of satcv_tile_desc the series gather reads
 
 
 def _disjoint_runs(origins, height, width):
@@ -116,6 +118,18 @@ def full_cover_indices(shape, kernel=256):
     return [(y, x) for y in range(0, H, kernel) for x in range(0, W, kernel)]
 
 
+def _cover_indices(H, W, kernel, buff, cover, need, need_name):
+    """The chip list [(y, x)] of a cover of an H x W plane: `generate_chip_indices` for 'reference', `full_cover_indices` for 'full', which
+    needs H, W >= need (the caller's window size, named `need_name` in the error: one reflection then fills an overhanging window)."""
+    if cover == 'reference':
+        return generate_chip_indices(np.empty((H, W, 0)), buff, kernel)
+    if cover == 'full':
+        if H < need or W < need:
+            raise ValueError(f"cover='full' needs a scene of at least {need_name} = {need} pixels a side, got {H} x {W}")
+        return full_cover_indices((H, W), kernel)
+    raise ValueError(f"cover must be 'reference' or 'full', got {cover!r}")
+
+
 def _check_geometry(kernel, buff, batch_size):
     if int(kernel) < 1 or int(buff) < 0 or int(batch_size) < 1:
         raise ValueError(f'kernel and batch_size must be positive and buff non-negative, got kernel={kernel}, buff={buff}, batch_size={batch_size}')
@@ -126,6 +140,45 @@ def _check_windows(idx, H, W, kernel, off):
         if y - off < 0 or x - off < 0 or y + kernel + off > H or x + kernel + off > W:
             raise ValueError(f'chip index ({y}, {x}): its window rows {y - off}:{y + kernel + off}, columns {x - off}:{x + kernel + off} '
                              f'leaves the {H} x {W} scene')
+
+
+def _check_stack(stack, m, layout='(T, C, H, W)', bands='bands'):
+    """-> (C, H, W) of a time stack a ConvLSTM model can read: 4-D, at least m.n_time acquisitions of m.n_channels bands"""
+    if getattr(stack, 'ndim', None) != 4:
+        raise ValueError(f'expected a {layout} time stack, got shape {tuple(getattr(stack, "shape", ()))}')
+    T, C_, H, W = (int(v) for v in stack.shape)
+    if T < m.n_time:
+        raise ValueError(f'the model reads {m.n_time} acquisitions, the stack holds {T}')
+    if C_ != m.n_channels:
+        raise ValueError(f'the model reads {m.n_channels} {bands}, the stack holds {C_}')
+    return C_, H, W
+
+
+def _check_maxval(maxval):
+    if not float(maxval) or float(maxval) != float(maxval):
+        raise ValueError(f'maxval must be a non-zero number, got {maxval}')
+    return float(maxval)
+
+
+def _channel_range(channel, ncls):
+    """(c0, nc): the channels of an ncls-class output that the map holds -- all of them for channel None, else the one (negative from the end)"""
+    if channel is None:
+        return 0, ncls
+    if not -ncls <= int(channel) < ncls:
+        raise IndexError(f'channel {channel} of a {ncls}-class output')
+    return int(channel) % ncls, 1
+
+
+def _resolve_plan(plan, m, want, build, kind, sizes):
+    """The `plan` argument of a predictor: None / False -> None (the eager tape), True -> build(), a plan object -> itself if it was built
+    for this model and for `want` (its `shape`), else ValueError."""
+    if plan is None or plan is False:
+        return None
+    if plan is True:
+        return build()
+    if getattr(plan, 'model', None) is not m or tuple(getattr(plan, 'shape', ())) != want:
+        raise ValueError(f'plan must be a {kind} of this model for {sizes} {want}, got {getattr(plan, "shape", plan)!r}')
+    return plan
 
 
 def _patch_grid(patches, cols, patch_hw, kernel_shape, kernel_buffer):
@@ -170,6 +223,90 @@ def _device_empty(shape, dtype, what, fill=None):
         raise MemoryError(f'{what} of shape {tuple(shape)} does not fit in device memory (scenes are not tiled into strips)') from e
 
 
+def _origin_table(idx):
+    """the (y, x) origins of a chip list as an int32 (total, 2) device tensor: uploaded once, every launch reads its rows [first, first + n)"""
+    return _to_device(np.asarray(idx, np.int32).reshape(len(idx), 2), 'the origin table')
+
+
+def _resident_scene(sc, rescale):
+    """(device tensor (H, W, C), its kind of satcv_tile_desc) of one scene: a host array goes up once in its own dtype, a contiguous
+    float32 CUDA tensor (pc_tools.median_composite) is used where it lies"""
+    import torch
+    if isinstance(sc, torch.Tensor):
+        if not (sc.is_cuda and sc.dtype == torch.float32 and sc.dim() == 3 and sc.is_contiguous()):
+            raise ValueError(f'a tensor scene must be a contiguous float32 CUDA tensor (H, W, C), got {sc.dtype} {tuple(sc.shape)} on {sc.device}')
+        return sc, _SCENE_KIND[np.dtype(np.float32)]
+    sc = np.asarray(sc)
+    if sc.dtype not in _SCENE_KIND:
+        if rescale:
+            raise ValueError(f'rescale needs a uint8 / uint16 / int16 / float32 scene, got {sc.dtype}')
+        sc = sc.astype(np.float32)            # what Model.predict does with a host batch
+    return _to_device(sc, 'the scene'), _SCENE_KIND[sc.dtype]
+
+
+def _resident_stack(stack, steps, layout):
+    """(device tensor (T, C, H, W), its kind of satcv_tile_desc) of a time stack: of a host array the first `steps` acquisitions go up (the
+    tensor's T is then `steps`), a contiguous int16 / float32 CUDA tensor is read where it lies"""
+    import torch
+    if isinstance(stack, torch.Tensor):
+        if not (stack.is_cuda and stack.dtype in (torch.int16, torch.float32) and stack.is_contiguous()):
+            raise ValueError(f'a tensor stack must be a contiguous int16 / float32 CUDA tensor {layout}, got {stack.dtype} on {stack.device}')
+        return stack, _SERIES_KIND[np.dtype(np.int16 if stack.dtype == torch.int16 else np.float32)]
+    st_ = np.asarray(stack)[:steps]          # (only the acquisitions the model reads are cast and uploaded: a contiguous prefix)
+    if st_.dtype not in _SERIES_KIND:
+        st_ = st_.astype(np.float32)
+    return _to_device(st_, 'the time stack'), _SERIES_KIND[st_.dtype]
+
+
+def _scene_gatherer(src, kind, rescale, origins, off, dst):
+    """-> gather(first, n): one satcv_scene_gather of the windows of chips [first, first + n) of the resident scene `src` into the
+    (nb, side, side, C) float32 buffer `dst`; returns dst[:n].  The descriptor is filled once, a launch sets `first` and `n`."""
+    import ctypes as C
+    from . import ops
+    from ._lib import SceneGatherDesc, check, lib
+    H, W, C_ = src.shape
+    d = SceneGatherDesc(src=src.data_ptr(), src_kind=kind, h=H, w_=W, c=C_, rescale=float(rescale or 0.0), origins=origins.data_ptr(),
+                        total=origins.shape[0], first=0, n=0, off=off, side=dst.shape[1], dst=dst.data_ptr(), ldc=C_, coff=0)
+    ref, st = C.byref(d), ops.stream_ptr()
+
+    def gather(first, n):
+        d.first, d.n = first, n
+        check(lib.satcv_scene_gather(ref, st))
+        return dst[:n]
+    return gather
+
+
+def _series_buffers(plan, per_chip, nb, total, dtype, what):
+    """(buf, short): the flat buffers the series gather fills, per_chip = steps * side * side * cpad elements a chip.  Without a plan one
+    buffer of nb chips.  With a plan, full batches are gathered straight into its static input; a short last batch goes through a buffer
+    of its own and is spread over a prefix of every time step by plan.run."""
+    from . import ops
+    td = ops.TORCH_DTYPE[dtype]
+    if plan is None:
+        return _device_empty((nb * per_chip,), td, what), None
+    return plan.x_in.view(-1), (_device_empty(((total % nb) * per_chip,), td, what) if total % nb else None)
+
+
+def _series_gatherer(src, kind, maxval, origins, off, side, steps, dtype, cpad, nb, buf, short):
+    """-> gather(first, n): one satcv_series_gather of chips [first, first + n) of the resident stack `src` -- cut, normalised, ingested --
+    into the buffers of `_series_buffers`; returns the time-major (steps * n, side, side, cpad) tensor a ConvLSTM model reads.  The
+    descriptor is filled once, a launch sets `first`, `n` and the destination."""
+    import ctypes as C
+    from . import ops
+    from ._lib import SeriesGatherDesc, check, lib
+    T, C_, H, W = src.shape
+    d = SeriesGatherDesc(src=src.data_ptr(), src_kind=kind, t=T, c=C_, h=H, w_=W, steps=steps, maxval=maxval, origins=origins.data_ptr(),
+                         total=origins.shape[0], first=0, n=0, off=off, side=side, dst=None, dtype=dtype, cpad=cpad)
+    ref, st = C.byref(d), ops.stream_ptr()
+
+    def gather(first, n):
+        xt = (buf if n == nb or short is None else short)[:steps * n * side * side * cpad].view(steps * n, side, side, cpad)      # (steps, n, ...) is contiguous for every n
+        d.first, d.n, d.dst = first, n, xt.data_ptr()
+        check(lib.satcv_series_gather(ref, st))
+        return xt
+    return gather
+
+
 def _scatter(src, src_first, n, crop, origins_dev, total, first, dst, doff, c0, nc, accumulate):
     """centres of chips [src_first, src_first + n) of the (N, sh, sw[, lds]) tensor `src` -> map `dst` (H, W, ldd) at origins[first:first + n]"""
     import ctypes as C
@@ -185,71 +322,82 @@ def _scatter(src, src_first, n, crop, origins_dev, total, first, dst, doff, c0, 
     check(lib.satcv_scene_scatter(C.byref(d), ops.stream_ptr()))
 
 
+class _Maps:
+    """The device-resident result of a scene predictor: `out` (H, W, nc) float32, channels [c0, c0 + nc) of the model's output, 0 where
+    nothing is predicted; `cls` (H, W, 1) uint8, 255 there, or None.  `alloc` runs before the batch loop where the class count is known
+    from the model, inside the first batch where only its output tells it (predict_chips_device takes any object with predict_on_device)."""
+    out = cls = None
+
+    def alloc(self, H, W, channel, ncls, want_classes):
+        import torch
+        self.c0, self.nc = _channel_range(channel, ncls)
+        self.out = _device_empty((H, W, self.nc), torch.float32, 'the prediction map', 0.0)
+        self.cls = _device_empty((H, W, 1), torch.uint8, 'the class map', 255) if want_classes else None
+
+    def host(self, channel):
+        """the one copy back: the (H, W) map of an int channel or (H, W, n_classes), with a class map the pair (map, (H, W) uint8)"""
+        probs = (self.out if channel is None else self.out[..., 0]).cpu().numpy()
+        return probs if self.cls is None else (probs, self.cls[..., 0].cpu().numpy())
+
+
+def _empty_result(H, W, channel, ncls, classes):
+    """what a predictor returns for a scene too small for one reference chip: nothing is predicted"""
+    probs = np.zeros((H, W) if channel is not None else (H, W, ncls), np.float32)
+    return (probs, np.full((H, W), 255, np.uint8)) if classes else probs
+
+
+def _stitch_batches(idx, origins, batch_size, kernel, off, maps, gather, forward):
+    """The batch loop of the three scene predictors.  gather(first, n) launches the gathers of chips [first, first + n) and returns the
+    model's inputs; forward(inputs, first, n) runs the model on them and returns (probs, classes or None) -- (n, side, side, k) and
+    (n, side, side) tensors whose centres are scattered into `maps` here, one launch per run of pairwise disjoint chips -- or None where
+    the model's head has stored the centres itself."""
+    total = len(idx)
+    crop = (off, off, kernel, kernel)
+    # No host synchronisation inside this loop.  Every launch -- gather, the model's or the plan's kernels, scatter -- goes to the current
+    # stream, so stream order alone keeps the gather of batch i + 1 from overwriting the chip buffers (and the model or the plan from
+    # overwriting its output tensors) while batch i still reads them.
+    for s in range(0, total, batch_size):
+        n = min(batch_size, total - s)
+        res = forward(gather(s, n), s, n)
+        if res is None:
+            continue
+        for a, e in _disjoint_runs(idx[s:s + n], kernel, kernel):
+            _scatter(res[0], a, e - a, crop, origins, total, s + a, maps.out, 0, maps.c0, maps.nc, True)
+            if maps.cls is not None:
+                _scatter(res[1], a, e - a, crop, origins, total, s + a, maps.cls, 0, 0, 1, False)
+    return maps
+
+
 def _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, channel, want_classes, rescale):
-    """Shared loop of predict_chips_device / predict_scene: -> (device map (H, W, nc) float32, device class map (H, W, 1) uint8 or
-    None).  channel: int, or None for every class.  A scene is a host array, or a contiguous float32 CUDA tensor (H, W, C) that is
-    read where it lies."""
-    import ctypes as C
+    """predict_chips_device / predict_scene on the device: -> _Maps.  channel: int, or None for every class.  A scene is a host array,
+    or a contiguous float32 CUDA tensor (H, W, C) that is read where it lies."""
     import torch
-    from . import ops
-    from ._lib import SceneGatherDesc, check, lib
     H, W = scenes[0].shape[:2]
     off = buff // 2
     side = kernel + 2 * off                  # the window of predict_chips; kernel + buff for an even buff
-    dev, kinds = [], []
-    for sc in scenes:
-        if isinstance(sc, torch.Tensor):     # a scene that is already resident (pc_tools.median_composite): used in place
-            if not (sc.is_cuda and sc.dtype == torch.float32 and sc.dim() == 3 and sc.is_contiguous()):
-                raise ValueError(f'a tensor scene must be a contiguous float32 CUDA tensor (H, W, C), got {sc.dtype} {tuple(sc.shape)} on {sc.device}')
-            dev.append(sc)
-            kinds.append(_SCENE_KIND[np.dtype(np.float32)])
-            continue
-        sc = np.asarray(sc)
-        if sc.dtype not in _SCENE_KIND:
-            if rescale:
-                raise ValueError(f'rescale needs a uint8 / uint16 / int16 / float32 scene, got {sc.dtype}')
-            sc = sc.astype(np.float32)        # what Model.predict does with a host batch
-        dev.append(_to_device(sc, 'the scene'))
-        kinds.append(_SCENE_KIND[sc.dtype])
-    total = len(idx)
-    origins = _to_device(np.asarray(idx, np.int32).reshape(total, 2), 'the origin table')
-    runs = [[(s + a, s + b) for a, b in _disjoint_runs(idx[s:s + batch_size], kernel, kernel)] for s in range(0, total, batch_size)]
-    nb = min(batch_size, total)
-    bufs = [_device_empty((nb, side, side, sc.shape[2]), torch.float32, 'the chip batch') for sc in dev]
-    st = ops.stream_ptr()
-    out = cls = None
-    # No host synchronisation inside this loop.  Every launch -- gather, the plan's kernels, scatter -- goes to the current stream, so
-    # stream order alone keeps the gather of batch i + 1 from overwriting `bufs` (and the plan from overwriting its output tensors) while
-    # batch i still reads them.
-    for b, s in enumerate(range(0, total, batch_size)):
-        n = min(batch_size, total - s)
-        xs = []
-        for sc, kind, buf in zip(dev, kinds, bufs):
-            d = SceneGatherDesc(src=sc.data_ptr(), src_kind=kind, h=H, w_=W, c=sc.shape[2], rescale=float(rescale or 0.0),
-                                origins=origins.data_ptr(), total=total, first=s, n=n, off=off, side=side,
-                                dst=buf.data_ptr(), ldc=sc.shape[2], coff=0)
-            check(lib.satcv_scene_gather(C.byref(d), st))
-            xs.append(buf[:n])
+    dev = [_resident_scene(sc, rescale) for sc in scenes]
+    origins = _origin_table(idx)
+    nb = min(batch_size, len(idx))
+    bufs = [_device_empty((nb, side, side, sc.shape[2]), torch.float32, 'the chip batch') for sc, _ in dev]
+    gathers = [_scene_gatherer(sc, kind, rescale, origins, off, buf) for (sc, kind), buf in zip(dev, bufs)]
+    maps = _Maps()
+
+    def gather(first, n):
+        return [g(first, n) for g in gathers]
+
+    def forward(xs, first, n):
         res = m.predict_on_device(xs if len(xs) > 1 else xs[0])
         res = list(res) if isinstance(res, (list, tuple)) else [res]
         probs = res[0]
         if probs.dtype != torch.float32 or not probs.is_contiguous():
             probs = probs.to(torch.float32).contiguous()
-        if out is None:
-            ncls = probs.shape[-1]
-            if channel is not None and not -ncls <= channel < ncls:
-                raise IndexError(f'channel {channel} of a {ncls}-class output')
-            c0, nc = (0, ncls) if channel is None else (channel % ncls, 1)
-            out = _device_empty((H, W, nc), torch.float32, 'the prediction map', 0.0)
-            if want_classes:
-                if len(res) < 2 or res[1].dim() != 3:
-                    raise ValueError('classes=True needs a model with an (n, h, w) class output next to its probabilities')
-                cls = _device_empty((H, W, 1), torch.uint8, 'the class map', 255)
-        for a, e in runs[b]:
-            _scatter(probs, a - s, e - a, (off, off, kernel, kernel), origins, total, a, out, 0, c0, nc, True)
-            if cls is not None:
-                _scatter(res[1], a - s, e - a, (off, off, kernel, kernel), origins, total, a, cls, 0, 0, 1, False)
-    return out, cls
+        if maps.out is None:                 # (the class count is the model's to tell: known with its first output)
+            _channel_range(channel, probs.shape[-1])
+            if want_classes and (len(res) < 2 or res[1].dim() != 3):
+                raise ValueError('classes=True needs a model with an (n, h, w) class output next to its probabilities')
+            maps.alloc(H, W, channel, probs.shape[-1], want_classes)
+        return probs, (res[1] if want_classes else None)
+    return _stitch_batches(idx, origins, batch_size, kernel, off, maps, gather, forward)
 
 
 def predict_chips_device(arr, chip_indices, template, m, kernel=256, buff=128, batch_size=16, channel=0, rescale=None):
@@ -275,8 +423,7 @@ def predict_chips_device(arr, chip_indices, template, m, kernel=256, buff=128, b
     if scenes[0].ndim != 3:
         raise ValueError(f'expected an (H, W, C) scene, got shape {scenes[0].shape}')
     _check_windows(idx, scenes[0].shape[0], scenes[0].shape[1], kernel, buff // 2)
-    out, _ = _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, int(channel), False, rescale)
-    template += out[..., 0].cpu().numpy()
+    template += _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, int(channel), False, rescale).host(int(channel))
     return template
 
 
@@ -296,23 +443,13 @@ def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover=
     if scenes[0].ndim != 3:
         raise ValueError(f'expected an (H, W, C) scene, got shape {scenes[0].shape}')
     H, W = scenes[0].shape[:2]
-    if cover == 'reference':
-        idx = generate_chip_indices(scenes[0], buff, kernel)
-    elif cover == 'full':
-        if H < kernel + buff or W < kernel + buff:
-            raise ValueError(f"cover='full' needs a scene of at least kernel + buff = {kernel + buff} pixels a side, got {H} x {W}")
-        idx = full_cover_indices((H, W), kernel)
-    else:
-        raise ValueError(f"cover must be 'reference' or 'full', got {cover!r}")
+    idx = _cover_indices(H, W, kernel, buff, cover, kernel + buff, 'kernel + buff')
     if classes and len(getattr(m, 'outputs', ())) < 2:
         raise ValueError('classes=True needs a model with a class output next to its probabilities')
-    if not idx:                              # (a scene too small for one reference chip: nothing is predicted)
-        ncls = m.outputs[0].channels
-        probs = np.zeros((H, W) if channel is not None else (H, W, ncls), np.float32)
-        return (probs, np.full((H, W), 255, np.uint8)) if classes else probs
-    out, cls = _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, None if channel is None else int(channel), classes, rescale)
-    probs = (out if channel is None else out[..., 0]).cpu().numpy()
-    return (probs, cls[..., 0].cpu().numpy()) if classes else probs
+    if not idx:
+        return _empty_result(H, W, channel, m.outputs[0].channels, classes)
+    channel = None if channel is None else int(channel)
+    return _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, channel, classes, rescale).host(channel)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -320,9 +457,6 @@ def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover=
 # device once, satcv_series_gather cuts, normalises and ingests a chip batch in one launch, the model reads the result in place
 # (predict_on_device(..., shape=...)) and satcv_scene_scatter stitches the centres.  DESIGN.md, "Scene prediction for the time-series
 # models".
-_SERIES_KIND = {np.dtype(np.uint16): 1, np.dtype(np.float32): 2, np.dtype(np.int16): 3}     # kinds of satcv_tile_desc the gather reads
-
-
 def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=0, cover='reference', classes=False, maxval=10000,
                          harmonics=None, plan=None):
     """Prediction map of a (T, C, H, W) time stack -- the layout of the LSTMDataGenerator files and of `pc_tools.median_composite`'s
@@ -346,23 +480,9 @@ def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=
     `predict_hybrid_scene`."""
     from .lstm_tools import LSTMAutoencoder
     _check_geometry(kernel, buff, batch_size)
-    if getattr(stack, 'ndim', None) != 4:
-        raise ValueError(f'expected a (T, C, H, W) time stack, got shape {tuple(getattr(stack, "shape", ()))}')
-    T, C_, H, W = (int(v) for v in stack.shape)
-    if T < m.n_time:
-        raise ValueError(f'the model reads {m.n_time} acquisitions, the stack holds {T}')
-    if C_ != m.n_channels:
-        raise ValueError(f'the model reads {m.n_channels} bands, the stack holds {C_}')
-    if not float(maxval) or float(maxval) != float(maxval):
-        raise ValueError(f'maxval must be a non-zero number, got {maxval}')
-    if cover == 'reference':
-        idx = generate_chip_indices(np.empty((H, W, 0)), buff, kernel)
-    elif cover == 'full':
-        if H < kernel + buff or W < kernel + buff:
-            raise ValueError(f"cover='full' needs a scene of at least kernel + buff = {kernel + buff} pixels a side, got {H} x {W}")
-        idx = full_cover_indices((H, W), kernel)
-    else:
-        raise ValueError(f"cover must be 'reference' or 'full', got {cover!r}")
+    _, H, W = _check_stack(stack, m)
+    maxval = _check_maxval(maxval)
+    idx = _cover_indices(H, W, kernel, buff, cover, kernel + buff, 'kernel + buff')
     is_ae = isinstance(m, LSTMAutoencoder)
     if is_ae and harmonics is None:
         raise ValueError('an LSTMAutoencoder needs harmonics=(sin, cos), its second input')
@@ -374,93 +494,52 @@ def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=
         harmonics = (float(harmonics[0]), float(harmonics[1]))
     if classes and (is_ae or not getattr(m, 'class_output', True)):
         raise ValueError("classes=True needs a model with a class output: an LSTMModel with activation='softmax'")
-    ncls = m.n_classes if idx else None
-    if idx and channel is not None and not -ncls <= int(channel) < ncls:
-        raise IndexError(f'channel {channel} of a {ncls}-class output')
-    if not idx:                              # (a scene too small for one reference chip: nothing is predicted)
-        probs = np.zeros((H, W) if channel is not None else (H, W, m.n_classes), np.float32)
-        return (probs, np.full((H, W), 255, np.uint8)) if classes else probs
-    if plan is not None and plan is not False:
-        side = kernel + 2 * (buff // 2)
-        want = (min(batch_size, len(idx)), m.n_time, side, side)
-        if plan is True:
-            plan = m.inference_plan(want)
-        elif getattr(plan, 'model', None) is not m or tuple(plan.shape) != want:
-            raise ValueError(f'plan must be a SeriesInferPlan of this model for shape {want}, got {getattr(plan, "shape", plan)!r}')
-    else:
-        plan = None
-    out, cls = _stitch_series(stack, idx, m, kernel, buff, batch_size, None if channel is None else int(channel), classes, float(maxval), harmonics,
-                              plan)
-    probs = (out if channel is None else out[..., 0]).cpu().numpy()
-    return (probs, cls[..., 0].cpu().numpy()) if classes else probs
+    if not idx:
+        return _empty_result(H, W, channel, m.n_classes, classes)
+    channel = None if channel is None else int(channel)
+    _channel_range(channel, m.n_classes)
+    side = kernel + 2 * (buff // 2)
+    want = (min(batch_size, len(idx)), m.n_time, side, side)
+    plan = _resolve_plan(plan, m, want, lambda: m.inference_plan(want), 'SeriesInferPlan', 'shape')
+    return _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, classes, maxval, harmonics, plan).host(channel)
 
 
 def _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, want_classes, maxval, harmonics, plan=None):
-    """the batch loop of predict_series_scene: -> (device map (H, W, nc) float32, device class map (H, W, 1) uint8 or None)"""
-    import ctypes as C
+    """predict_series_scene on the device: -> _Maps"""
     import torch
     from . import ops
-    from ._lib import SeriesGatherDesc, check, lib
-    T, C_, H, W = stack.shape
-    steps = m.n_time
-    off = buff // 2
+    _, C_, H, W = stack.shape
+    steps, off = m.n_time, buff // 2
     side = kernel + 2 * off
-    if isinstance(stack, torch.Tensor):      # a stack that is already resident: read where it lies
-        if not (stack.is_cuda and stack.dtype in (torch.int16, torch.float32) and stack.is_contiguous()):
-            raise ValueError(f'a tensor stack must be a contiguous int16 / float32 CUDA tensor (T, C, H, W), got {stack.dtype} on {stack.device}')
-        dev, kind = stack, _SERIES_KIND[np.dtype(np.int16 if stack.dtype == torch.int16 else np.float32)]
-    else:
-        st_ = np.asarray(stack)[:steps]      # (only the acquisitions the model reads are cast and uploaded: a contiguous prefix)
-        T = steps
-        if st_.dtype not in _SERIES_KIND:
-            st_ = st_.astype(np.float32)
-        kind = _SERIES_KIND[st_.dtype]
-        dev = _to_device(st_, 'the time stack')
+    dev, kind = _resident_stack(stack, steps, '(T, C, H, W)')
+    origins = _origin_table(idx)
     total = len(idx)
-    origins = _to_device(np.asarray(idx, np.int32).reshape(total, 2), 'the origin table')
-    runs = [[(s + a, s + b) for a, b in _disjoint_runs(idx[s:s + batch_size], kernel, kernel)] for s in range(0, total, batch_size)]
     nb = min(batch_size, total)
     cpad, dtype = ops.rup(C_, 16), m.dtype_code
-    # with a plan, full batches are gathered straight into its static input; a short last batch goes through a buffer of its own and
-    # is spread over a prefix of every time step by plan.run
-    buf = plan.x_in.view(-1) if plan is not None else _device_empty((steps * nb * side * side * cpad,), ops.TORCH_DTYPE[dtype], 'the chip batch')
-    short = _device_empty((steps * (total % nb) * side * side * cpad,), ops.TORCH_DTYPE[dtype], 'the chip batch') if plan is not None and total % nb else None
+    buf, short = _series_buffers(plan, steps * side * side * cpad, nb, total, dtype, 'the chip batch')
     sincos = None
     if harmonics is not None:
         sincos = _device_empty((nb, side, side, 2), torch.float32, 'the harmonics')
         sincos[..., 0] = harmonics[0]
         sincos[..., 1] = harmonics[1]
-    ncls = m.n_classes
-    c0, nc = (0, ncls) if channel is None else (channel % ncls, 1)
-    out = _device_empty((H, W, nc), torch.float32, 'the prediction map', 0.0)
-    cls = _device_empty((H, W, 1), torch.uint8, 'the class map', 255) if want_classes else None
-    st = ops.stream_ptr()
-    # No host synchronisation inside this loop.  Every launch -- gather, the model's kernels, scatter -- goes to the current stream, so
-    # stream order alone keeps the gather of batch i + 1 from overwriting `buf` (and the model from overwriting its output tensors) while
-    # batch i still reads them.
-    for b, s in enumerate(range(0, total, batch_size)):
-        n = min(batch_size, total - s)
-        xt = (buf if n == nb or short is None else short)[:steps * n * side * side * cpad].view(steps * n, side, side, cpad)      # (steps, n, ...) is contiguous for every n
-        d = SeriesGatherDesc(src=dev.data_ptr(), src_kind=kind, t=T, c=C_, h=H, w_=W, steps=steps, maxval=maxval, origins=origins.data_ptr(),
-                             total=total, first=s, n=n, off=off, side=side, dst=xt.data_ptr(), dtype=dtype, cpad=cpad)
-        check(lib.satcv_series_gather(C.byref(d), st))
+    maps = _Maps()
+    maps.alloc(H, W, channel, m.n_classes, want_classes)
+
+    gather = _series_gatherer(dev, kind, maxval, origins, off, side, steps, dtype, cpad, nb, buf, short)
+
+    def forward(xt, first, n):
         try:
             if plan is not None:
                 res = plan.run(xt if sincos is None else [xt, sincos[:n]], want_classes=want_classes)
-                res = res if want_classes else (res,)
-            elif sincos is not None:
-                res = (m.predict_on_device([xt, sincos[:n]], shape=(n, steps, side, side)),)
-            elif want_classes:
-                res = m.predict_on_device(xt, shape=(n, steps, side, side), want_classes=True)
-            else:
-                res = (m.predict_on_device(xt, shape=(n, steps, side, side)),)
+                return res if want_classes else (res, None)
+            if sincos is not None:
+                return m.predict_on_device([xt, sincos[:n]], shape=(n, steps, side, side)), None
+            if want_classes:
+                return m.predict_on_device(xt, shape=(n, steps, side, side), want_classes=True)
+            return m.predict_on_device(xt, shape=(n, steps, side, side)), None
         except torch.cuda.OutOfMemoryError as e:
             raise MemoryError(f'a batch of {n} chips of {steps} x {side} x {side} does not fit in device memory; lower batch_size') from e
-        for a, e in runs[b]:
-            _scatter(res[0], a - s, e - a, (off, off, kernel, kernel), origins, total, a, out, 0, c0, nc, True)
-            if cls is not None:
-                _scatter(res[1], a - s, e - a, (off, off, kernel, kernel), origins, total, a, cls, 0, 0, 1, False)
-    return out, cls
+    return _stitch_batches(idx, origins, batch_size, kernel, off, maps, gather, forward)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -497,14 +576,7 @@ def hybrid_chip_tables(hi_shape, lo_shape, kernel, buff, cover, multiple=1):
         raise ValueError(f'buff // 2 = {off} is not a multiple of the resolution ratio r = {r}')
     if side % multiple:
         raise ValueError(f'side = kernel + 2 (buff // 2) = {side} is not a multiple of {multiple}')
-    if cover == 'reference':
-        idx = generate_chip_indices(np.empty((H, W, 0)), buff, kernel)
-    elif cover == 'full':
-        if H < side or W < side:
-            raise ValueError(f"cover='full' needs a scene of at least side = {side} pixels a side, got {H} x {W}")
-        idx = full_cover_indices((H, W), kernel)
-    else:
-        raise ValueError(f"cover must be 'reference' or 'full', got {cover!r}")
+    idx = _cover_indices(H, W, kernel, buff, cover, side, 'side')
     hi = np.asarray(idx, np.int32).reshape(len(idx), 2)
     assert not (hi % r).any()
     return hi, hi // r, dict(r=r, off=off, side=side, off_lo=off // r, side_lo=side // r)
@@ -549,121 +621,78 @@ def predict_hybrid_scene(scene, stack, m, kernel=256, buff=128, batch_size=16, c
     _check_geometry(kernel, buff, batch_size)
     if getattr(scene, 'ndim', None) != 3:
         raise ValueError(f'expected an (H, W, C) scene, got shape {tuple(getattr(scene, "shape", ()))}')
-    if getattr(stack, 'ndim', None) != 4:
-        raise ValueError(f'expected a (T, c, h, w) time stack, got shape {tuple(getattr(stack, "shape", ()))}')
     H, W, C_ = (int(v) for v in scene.shape)
-    T, c_, h, w = (int(v) for v in stack.shape)
     if C_ != m.hi_channels:
         raise ValueError(f'the model reads {m.hi_channels} fine bands, the scene holds {C_}')
-    if T < m.n_time:
-        raise ValueError(f'the model reads {m.n_time} acquisitions, the stack holds {T}')
-    if c_ != m.n_channels:
-        raise ValueError(f'the model reads {m.n_channels} coarse bands, the stack holds {c_}')
-    if not float(maxval) or float(maxval) != float(maxval):
-        raise ValueError(f'maxval must be a non-zero number, got {maxval}')
+    _, h, w = _check_stack(stack, m, '(T, c, h, w)', 'coarse bands')
+    maxval = _check_maxval(maxval)
     hi, lo, geo = hybrid_chip_tables((H, W), (h, w), kernel, buff, cover, multiple)
     ncls = head.cout
     if classes and head.activation != head.ACT['softmax']:
         raise ValueError(f'classes=True needs a head with a class output (softmax); {head.name!r} has none')
-    if channel is not None and not -ncls <= int(channel) < ncls:
-        raise IndexError(f'channel {channel} of a {ncls}-class output')
+    channel = None if channel is None else int(channel)
+    _channel_range(channel, ncls)
     if plan is not None and plan is not False and isinstance(m, HierarchicalModel):
         raise NotImplementedError('plan: HybridInferPlan covers HybridModel; the ACNN trunk of a HierarchicalModel lives on the tape')
-    if not len(hi):                          # (a scene too small for one reference chip: nothing is predicted)
-        probs = np.zeros((H, W) if channel is not None else (H, W, ncls), np.float32)
-        return (probs, np.full((H, W), 255, np.uint8)) if classes else probs
-    if plan is not None and plan is not False:
-        want = (min(int(batch_size), len(hi)), geo['side'], geo['side_lo'])
-        if plan is True:
-            try:
-                plan = m.scene_plan(*want)
-            except torch.cuda.OutOfMemoryError as e:
-                raise MemoryError(f'a HybridInferPlan for (batch, side, side_lo) = {want} does not fit in device memory; lower batch_size') from e
-        elif getattr(plan, 'model', None) is not m or tuple(getattr(plan, 'shape', ())) != want:
-            raise ValueError(f'plan must be a HybridInferPlan of this model for (batch, side, side_lo) = {want}, got {getattr(plan, "shape", plan)!r}')
-    else:
-        plan = None
-    out, cls = _stitch_hybrid(scene, stack, hi, lo, geo, m, head, output, int(kernel), int(batch_size), None if channel is None else int(channel),
-                              bool(classes), rescale, float(maxval), plan)
-    probs = (out if channel is None else out[..., 0]).cpu().numpy()
-    return (probs, cls.cpu().numpy()) if classes else probs
+    if not len(hi):
+        return _empty_result(H, W, channel, ncls, classes)
+    want = (min(int(batch_size), len(hi)), geo['side'], geo['side_lo'])
+
+    def build():
+        try:
+            return m.scene_plan(*want)
+        except torch.cuda.OutOfMemoryError as e:
+            raise MemoryError(f'a HybridInferPlan for (batch, side, side_lo) = {want} does not fit in device memory; lower batch_size') from e
+    plan = _resolve_plan(plan, m, want, build, 'HybridInferPlan', '(batch, side, side_lo) =')
+    return _stitch_hybrid(scene, stack, hi, lo, geo, m, head, output, int(kernel), int(batch_size), channel, bool(classes), rescale, maxval,
+                          plan).host(channel)
 
 
 def _stitch_hybrid(scene, stack, hi, lo, geo, m, head, output, kernel, batch_size, channel, want_classes, rescale, maxval, plan):
-    """the batch loop of predict_hybrid_scene: -> (device map (H, W, nc) float32, device class map (H, W) uint8 or None)"""
+    """predict_hybrid_scene on the device: -> _Maps"""
     import ctypes as C
     import torch
     from . import ops
-    from ._lib import DenseSceneDesc, SceneGatherDesc, SeriesGatherDesc, check, lib
+    from ._lib import DenseSceneDesc, check, lib
     from .lstm_tools import HybridModel
     H, W, C_ = scene.shape
-    T, c_, h, w = stack.shape
     steps, off, side, off_lo, side_lo = m.n_time, geo['off'], geo['side'], geo['off_lo'], geo['side_lo']
-    if isinstance(scene, torch.Tensor):      # a scene that is already resident: read where it lies
-        if not (scene.is_cuda and scene.dtype == torch.float32 and scene.is_contiguous()):
-            raise ValueError(f'a tensor scene must be a contiguous float32 CUDA tensor (H, W, C), got {scene.dtype} {tuple(scene.shape)} on {scene.device}')
-        sdev, skind = scene, _SCENE_KIND[np.dtype(np.float32)]
-    else:
-        sc = np.asarray(scene)
-        if sc.dtype not in _SCENE_KIND:
-            if rescale:
-                raise ValueError(f'rescale needs a uint8 / uint16 / int16 / float32 scene, got {sc.dtype}')
-            sc = sc.astype(np.float32)
-        sdev, skind = _to_device(sc, 'the scene'), _SCENE_KIND[sc.dtype]
-    if isinstance(stack, torch.Tensor):
-        if not (stack.is_cuda and stack.dtype in (torch.int16, torch.float32) and stack.is_contiguous()):
-            raise ValueError(f'a tensor stack must be a contiguous int16 / float32 CUDA tensor (T, c, h, w), got {stack.dtype} on {stack.device}')
-        tdev, tkind = stack, _SERIES_KIND[np.dtype(np.int16 if stack.dtype == torch.int16 else np.float32)]
-    else:
-        st_ = np.asarray(stack)[:steps]      # (only the acquisitions the model reads are cast and uploaded: a contiguous prefix)
-        T = steps
-        if st_.dtype not in _SERIES_KIND:
-            st_ = st_.astype(np.float32)
-        tdev, tkind = _to_device(st_, 'the time stack'), _SERIES_KIND[st_.dtype]
+    sdev, skind = _resident_scene(scene, rescale)
+    tdev, tkind = _resident_stack(stack, steps, '(T, c, h, w)')
     total = len(hi)
-    org_hi, org_lo = _to_device(hi, 'the origin table'), _to_device(np.ascontiguousarray(lo, np.int32), 'the origin table')
+    org_hi, org_lo = _origin_table(hi), _origin_table(lo)
     nb = min(batch_size, total)
-    cpad, dtype = ops.rup(c_, 16), m.dtype_code
-    td = ops.TORCH_DTYPE[dtype]
+    cpad, dtype = ops.rup(stack.shape[1], 16), m.dtype_code
     buf_hi = _device_empty((nb, side, side, C_), torch.float32, 'the fine chip batch')
-    # with a plan, full batches are gathered straight into its static input; a short last batch goes through a buffer of its own and is
-    # spread over a prefix of every time step by plan.run
-    buf_lo = plan.x_in.view(-1) if plan is not None else _device_empty((steps * nb * side_lo * side_lo * cpad,), td, 'the coarse chip batch')
-    short = _device_empty((steps * (total % nb) * side_lo * side_lo * cpad,), td, 'the coarse chip batch') if plan is not None and total % nb else None
-    ncls = head.cout
-    c0, nc = (0, ncls) if channel is None else (channel % ncls, 1)
-    out = _device_empty((H, W, nc), torch.float32, 'the prediction map', 0.0)
-    cls = _device_empty((H, W), torch.uint8, 'the class map', 255) if want_classes else None
-    st = ops.stream_ptr()
+    buf_lo, short = _series_buffers(plan, steps * side_lo * side_lo * cpad, nb, total, dtype, 'the coarse chip batch')
+    maps = _Maps()
+    maps.alloc(H, W, channel, head.cout, want_classes)
     kw = {} if isinstance(m, HybridModel) else {'output': output or 'lstm_probs'}
-    first = [0]
+    st = ops.stream_ptr()
 
-    def scene_head(d):
-        """the model's last dense layer (its sources in `d`) on the chip centres, stored into the map"""
-        sd = DenseSceneDesc(head=d, crop_y=off, crop_x=off, crop_h=kernel, crop_w=kernel, origins=org_hi.data_ptr(), total=total, first=first[0],
-                            map=out.data_ptr(), map_h=H, map_w=W, ldm=nc, c0=c0, nc=nc, class_map=cls.data_ptr() if cls is not None else None)
-        check(lib.satcv_dense_scene_fwd(C.byref(sd), st))
-    # No host synchronisation inside this loop.  Every launch -- the gathers, the model's kernels, the head -- goes to the current stream, so
-    # stream order alone keeps the gathers of batch i + 1 from overwriting the chip buffers while batch i still reads them.  The windows
-    # of both covers are pairwise disjoint, so one head launch per batch meets the kernel's contract.
-    for s in range(0, total, batch_size):
-        n = min(batch_size, total - s)
-        first[0] = s
-        d = SceneGatherDesc(src=sdev.data_ptr(), src_kind=skind, h=H, w_=W, c=C_, rescale=float(rescale or 0.0), origins=org_hi.data_ptr(), total=total,
-                            first=s, n=n, off=off, side=side, dst=buf_hi.data_ptr(), ldc=C_, coff=0)
-        check(lib.satcv_scene_gather(C.byref(d), st))
-        xt = (buf_lo if n == nb or short is None else short)[:steps * n * side_lo * side_lo * cpad].view(steps * n, side_lo, side_lo, cpad)
-        d = SeriesGatherDesc(src=tdev.data_ptr(), src_kind=tkind, t=T, c=c_, h=h, w_=w, steps=steps, maxval=maxval, origins=org_lo.data_ptr(),
-                             total=total, first=s, n=n, off=off_lo, side=side_lo, dst=xt.data_ptr(), dtype=dtype, cpad=cpad)
-        check(lib.satcv_series_gather(C.byref(d), st))
+    gather_hi = _scene_gatherer(sdev, skind, rescale, org_hi, off, buf_hi)
+    gather_lo = _series_gatherer(tdev, tkind, maxval, org_lo, off_lo, side_lo, steps, dtype, cpad, nb, buf_lo, short)
+
+    def gather(first, n):
+        return [gather_hi(first, n), gather_lo(first, n)]
+
+    def forward(xs, first, n):
+        """the model up to its last dense layer; that layer runs in `scene_head`, so nothing is left to scatter.  The windows of both
+        covers are pairwise disjoint, so one head launch per batch meets the kernel's contract."""
+        def scene_head(d):
+            """the model's last dense layer (its sources in `d`) on the chip centres, stored into the map"""
+            sd = DenseSceneDesc(head=d, crop_y=off, crop_x=off, crop_h=kernel, crop_w=kernel, origins=org_hi.data_ptr(), total=total, first=first,
+                                map=maps.out.data_ptr(), map_h=H, map_w=W, ldm=maps.nc, c0=maps.c0, nc=maps.nc,
+                                class_map=maps.cls.data_ptr() if maps.cls is not None else None)
+            check(lib.satcv_dense_scene_fwd(C.byref(sd), st))
         try:
             if plan is not None:
-                plan.run(buf_hi[:n], xt, scene_head=scene_head)
+                plan.run(*xs, scene_head=scene_head)
             else:
-                m.predict_on_device([buf_hi[:n], xt], shape=(n, steps, side_lo, side_lo), scene_head=scene_head, **kw)
+                m.predict_on_device(xs, shape=(n, steps, side_lo, side_lo), scene_head=scene_head, **kw)
         except torch.cuda.OutOfMemoryError as e:
             raise MemoryError(f'a batch of {n} chips of {side} x {side} and {steps} x {side_lo} x {side_lo} does not fit in device memory; lower batch_size') from e
-    return out, cls
+    return _stitch_batches(hi, org_hi, batch_size, kernel, off, maps, gather, forward)
 
 
 def callback_predictions(imageDataset, model, mixer, kernel_shape=[256, 256], kernel_buffer=[128, 128]):
@@ -692,7 +721,7 @@ def callback_predictions(imageDataset, model, mixer, kernel_shape=[256, 256], ke
             if probs.shape[-1] < 2:
                 raise ValueError('callback_predictions writes the probability of class 1: the model has a single output channel')
             grid, place, hw = _patch_grid(patches, cols, probs.shape[1:3], kernel_shape, kernel_buffer)
-            origins = _to_device(np.asarray(place, np.int32).reshape(-1, 2), 'the origin table')
+            origins = _origin_table(place)
             mosaic = _device_empty(hw + (1,), torch.float32, 'the mosaic', 0.0)
         n = min(probs.shape[0], len(place) - filled)
         _scatter(probs, 0, n, grid, origins, len(place), filled, mosaic, 0, 1, 1, False)

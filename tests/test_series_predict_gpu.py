@@ -308,14 +308,15 @@ def _softmax_model(env, stack):
     return m
 
 
+@pytest.mark.parametrize('plan', [None, True])
 @pytest.mark.parametrize('cover', ['reference', 'full'])
-def test_class_map_is_the_argmax_of_the_probability_map(env, scene, cover):
+def test_class_map_is_the_argmax_of_the_probability_map(env, scene, cover, plan):
     """a softmax head (the default clipped ReLU ties at 0 and 2 wholesale).  Pixels whose two largest probabilities are exactly equal are
-    left out of the comparison; they may be at most 1 % of the predicted pixels."""
+    left out of the comparison; they may be at most 1 % of the predicted pixels.  plan=True: the class tensor of a SeriesInferPlan."""
     pt = env['pt']
     m = _softmax_model(env, scene['stack'])
     probs, cls = pt.predict_series_scene(scene['stack'], m, kernel=KERNEL, buff=BUFF, batch_size=BATCH[cover], channel=None, cover=cover,
-                                         classes=True, maxval=MAXVAL)
+                                         classes=True, maxval=MAXVAL, plan=plan)
     assert probs.shape == (H, W, 3) and cls.shape == (H, W) and cls.dtype == np.uint8
     seen = np.zeros((H, W), bool)
     for y, x in _indices(pt, cover):
@@ -334,12 +335,15 @@ def test_class_map_is_the_argmax_of_the_probability_map(env, scene, cover):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 6. autoencoder
-def test_autoencoder_scene_equals_the_host_loop(env, scene):
+@pytest.mark.parametrize('plan', [None, True])
+def test_autoencoder_scene_equals_the_host_loop(env, scene, plan):
+    """plan=True: the unfused SeriesInferPlan is bit-equal to predict_on_device; the short last batch is staged as a prefix of both of the
+    plan's inputs, the time-major chips and the harmonics"""
     pt, pr = env['pt'], env['pr']
     ae = _autoencoder(env, 'bfloat16')
     harm = pr.sin_cos(2, T)
     want = _host_map(env, ae, scene['stack'], 'full', harmonics=harm)
     got = pt.predict_series_scene(scene['stack'], ae, kernel=KERNEL, buff=BUFF, batch_size=BATCH['full'], channel=None, cover='full',
-                                  maxval=MAXVAL, harmonics=harm)
+                                  maxval=MAXVAL, harmonics=harm, plan=plan)
     assert got.shape == (H, W, NB) and got.dtype == np.float32 and np.ptp(want) > 0
     assert np.array_equal(got, want)
