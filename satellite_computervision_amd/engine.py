@@ -14,7 +14,7 @@ There is no CPU path: everything here requires the HIP library and a ROCm device
 """
 import ctypes as C
 import itertools
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 from fractions import Fraction
 
 import numpy as np
@@ -240,16 +240,7 @@ class Runtime:
             else:
                 jobs.append(PackJob(src, pk['fwd'].data_ptr(), 2, taps, cin, cout, cp, rup(taps * cout, 32)))
                 jobs.append(PackJob(src, pk['dgrad'].data_ptr(), 3, taps, cin, cout, rup(taps * cout, 16), rup(cin, 32)))
-        if not jobs:
-            return None
-        prefix, tot = [], 0
-        for j in jobs:
-            prefix.append(tot)
-            tot += int(lib.satcv_pack_job_items(C.byref(j)))
-        arr = (PackJob * len(jobs))(*jobs)
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.dev)
-        pre = torch.tensor(prefix, dtype=torch.int64, device=self.dev)
-        return dict(jobs=raw, prefix=pre, n=len(jobs), total=tot)
+        return ops.job_table(jobs, lib.satcv_pack_job_items, self.dev) if jobs else None
 
     def repack(self, lo=0, hi=None, stream=None):
         """fp32 Keras-layout kernels -> MFMA operand images (after every weight update), one launch for all layers (or for the layers whose
@@ -319,7 +310,7 @@ class Plan:
         self.frozen = set(frozen)
         self.raw_bn = set(raw_bn)             # BatchNorms (zero gamma) whose backward sums no activation-based producer may form
         self.tile_policy = 2 if (training and _M16_DEFAULT == 1) else 0      # satcv_conv_desc.tile_policy of this plan's convolution launches
-        self.eo_lo, self.early_opt, self.eo_done = None, None, False          # split optimizer step (see _build_backward: `early`)
+        self.eo_lo, self.early_opt, self.eo_done = None, None, False          # split optimizer step (see _SlabSums.layer_done: `early`)
         self.fwd, self.bwd = [], []
         self.keep = []                        # ctypes descriptors / tensors kept alive
         self.dropouts = []                    # dropout masks (regenerated every training step)
@@ -438,1137 +429,14 @@ class Plan:
 
     # -- lowering
     def _build(self):
-        rt, m, n = self.rt, self.rt.model, self.n
-        T, dt, es = rt.tdtype, rt.dtype, rt.esize
-        training = self.training
-        consumers = defaultdict(list)
-        for node in m.nodes:
-            for t in node.inputs:
-                consumers[t.id].append(node)
-        vals, acts, ctx = {}, {}, {}
-        sinks, cat_stats = {}, {}
-        order = {id(nd): i for i, nd in enumerate(m.nodes)}
-        fused_join = {}                            # add_relu node id -> the shortcut tensor its sum was written into
-        folded_plain = {}                          # tensor id -> a conv -> BatchNorm branch stored normalised, waiting for the join's other branch
-        for node in m.nodes:
-            if node.op == 'concat_bn_relu':
-                a, b = node.inputs
-                ctot = a.channels + b.channels
-                st = self._z(STAT_ROWS, 2, ctot, dtype=torch.float64)
-                cat_stats[id(node)] = st
-                sinks[a.id] = (st, 0, ctot)
-                sinks[b.id] = (st, a.channels, ctot)
+        fw = _ForwardLowering(self)
+        fw.run()
+        self.vals, self.node_ctx = fw.vals, fw.ctx
+        if self.training:
+            self._build_backward(fw.consumers, fw.vals, fw.ctx)
 
-        slots, actslots = {}, {}
-        for node in m.nodes:
-            if node.op == 'concat':
-                if all(t.node.op == 'cba' and len(consumers[t.id]) > 1 for t in node.inputs):
-                    # concatenation of ACTIVATED encoder outputs that are also pooled (Siamese skips): the pool kernels write
-                    # their activation straight into channel slices of one tensor
-                    ctot = sum(t.channels for t in node.inputs)
-                    hh, ww = self._dims(node.inputs[0])
-                    shared = self._z(n, hh, ww, ctot)
-                    off = 0
-                    for t in node.inputs:
-                        actslots[t.id] = (shared, off, ctot)
-                        if node.outputs[0].id in sinks:                      # statistics for the decoder's concat BatchNorm
-                            st_, so_, sl_ = sinks[node.outputs[0].id]
-                            sinks[t.id] = (st_, so_ + off, sl_)
-                        off += t.channels
-                    ctx[id(node)] = dict(act=shared, ctot=ctot)
-                    continue
-                if not all(t.node.op == 'cba' and len(consumers[t.id]) == 1 for t in node.inputs):
-                    raise NotImplementedError('concatenate is supported for conv_batch_act outputs consumed only by the concat (ASPP)')
-                ctot = sum(t.channels for t in node.inputs)
-                hh, ww = self._dims(node.inputs[0])
-                yshared = self._z(n, hh, ww, ctot)
-                stshared = self._z(STAT_ROWS, 2, ctot, dtype=torch.float64) if training else None
-                aff = dict(scale=self._z(ctot, dtype=torch.float32), shift=self._z(ctot, dtype=torch.float32),
-                           mean=self._z(ctot, dtype=torch.float32), rstd=self._z(ctot, dtype=torch.float32))
-                off = 0
-                for t in node.inputs:
-                    slots[t.id] = dict(y=yshared, off=off, ctot=ctot, stats=stshared, aff=aff)
-                    off += t.channels
-                ctx[id(node)] = dict(y=yshared, ctot=ctot, aff=aff)
-
-        for node in m.nodes:
-            op = node.op
-            if op == 'input':
-                t = node.outputs[0]
-                cp = rup(t.channels, 16)
-                x = self._z(n, self.h, self.w, cp)
-                xin = self._z(n, self.h, self.w, t.channels, dtype=torch.float32)
-                self.x_f32 = xin
-                self.x_inputs.append(xin)
-                self.x_by_tid[t.id] = xin
-                npix = n * self.h * self.w
-                cc = t.channels
-                self.fwd.append(lambda st, xin=xin, x=x, npix=npix, cc=cc, cp=cp, tid=t.id: check(lib.satcv_ingest_nhwc(
-                    self.x_src.get(tid) or xin.data_ptr(), x.data_ptr(), npix, cc, cp, dt, st)))
-                vals[t.id] = TRef([(x, cp)], n, self.h, self.w)
-            elif op == 'cba':
-                tin, tout = node.inputs[0], node.outputs[0]
-                r = vals[tin.id]
-                lay = node.layer
-                pk = rt.packed[lay.name]
-                cout = tout.channels
-                if cout % 16:
-                    raise NotImplementedError(f'{lay.name}: filters must be a multiple of 16 (got {cout})')
-                if r.c != pk['cin_pad']:
-                    raise ValueError(f'{lay.name}: input has {r.c} stored channels, kernel expects {pk["cin_pad"]}')
-                k, dil = node.attrs['k'], node.attrs['dil']
-                stride, relu_out = node.attrs.get('stride', 1), node.attrs.get('relu', True)
-                hin, win = r.h, r.w
-                if stride > 1:
-                    if training:
-                        raise NotImplementedError('strided convolutions are inference-only (DeepLab backbone)')
-                    r = TRef(r.srcs, r.n, (hin - 1) // stride + 1, (win - 1) // stride + 1, r.affine, r.relu)   # output grid
-                sl = slots.get(tout.id)
-                if not node.attrs.get('bn', True):
-                    # plain Conv2D + bias, no normalisation (atrous CNN family): consumers read the stored values as they are
-                    if sl is not None or stride > 1:
-                        raise NotImplementedError('a convolution without BatchNormalization as a concatenation branch / with a stride')
-                    y = self._z(n, r.h, r.w, cout)
-                    self.fwd.append(self._conv_step(w=pk['fwd'].data_ptr(), bias=rt.pptr(lay.name + '/bias'), y=y.data_ptr(), ldy=cout, n=n, h=r.h, w_=r.w,
-                                                    cout=cout, cout_pad=rup(cout, 32), kh=k, kw=k, dil=dil, dtype=dt, **self._src_args(r)))
-                    vals[tout.id] = TRef([(y, cout)], n, r.h, r.w)
-                    ctx[id(node)] = dict(r=r, y=y, yoff=0, ldy=cout, aff=None, aoff=0, cout=cout, k=k, dil=dil)
-                    continue
-                # inference, residual join (ResNet bottleneck: ReLU(BN(conv) + shortcut), utils-free build-defined DeepLab backbone): when this
-                # block's output only feeds the join and nothing reads the shortcut afterwards, the convolution applies its own
-                # BatchNormalization in the epilogue (out_scale / bias_eff from the batched affine launch) and writes
-                # ReLU(shortcut + result) IN PLACE over the shortcut (accumulate = 2): no add_relu launch, no third tensor
-                # (20 launches of ~10 us on a single 512 x 512 tile, 11 % of the kernel time at batch 16; SATCV_FUSE_RESIDUAL=0: separate)
-                join = consumers[tout.id][0] if (not training and sl is None and not relu_out and FUSE_RESIDUAL
-                                                 and len(consumers[tout.id]) == 1 and consumers[tout.id][0].op == 'add_relu'
-                                                 and tout in consumers[tout.id][0].inputs) else None
-                if join is not None:
-                    tsc = join.inputs[1] if join.inputs[0] is tout else join.inputs[0]      # the join's other addend
-                    rs_ = vals.get(tsc.id)
-                    fold_args = None
-                    if rs_ is None:
-                        # (B) the other addend is a conv -> BatchNorm branch that runs LATER in the list (the projection shortcut of a stage's
-                        # first block): store this branch normalised (its BatchNorm in the epilogue, nothing pending), the later branch
-                        # then adds itself in place (A)
-                        if (stride == 1 and tsc.node is not None and tsc.node.op == 'cba' and len(consumers[tsc.id]) == 1
-                                and tsc.node.attrs.get('bn', True) and not tsc.node.attrs.get('relu', True) and tsc.channels == cout):
-                            y = self._z(n, r.h, r.w, cout)
-                            fold_args = dict(y=y.data_ptr(), accumulate=0)
-                            folded_plain[tout.id] = y
-                            sb = y
-                    else:
-                        # (A) the other addend is final: a plain activated tensor written by an earlier join, or a branch stored normalised (B)
-                        src_ok = (tsc.id in folded_plain) or (tsc.node is not None and tsc.node.op == 'add_relu' and stride == 1)
-                        if (src_ok and not rs_.affine and len(rs_.srcs) == 1 and rs_.srcs[0][1] == cout and rs_.srcs[0][0].shape[-1] == cout
-                                and (rs_.h, rs_.w) == (r.h, r.w)
-                                and all(cn is join or order[id(cn)] < order[id(node)] for cn in consumers[tsc.id])):
-                            sb = rs_.srcs[0][0]
-                            fold_args = dict(y=sb.data_ptr(), accumulate=2)
-                            fused_join[id(join)] = sb
-                    if fold_args is not None:
-                        be = self._z(cout, dtype=torch.float32)
-                        aff = self._bn_forward(lay.bn_name, None, cout, 0, cout, n * r.h * r.w, node.attrs.get('bn_updates', 1),
-                                               conv_bias=rt.pptr(lay.name + '/bias'), bias_eff=_fp(be))
-                        self.fwd.append(self._conv_step(w=pk['fwd'].data_ptr(), bias=_fp(be), out_scale=_fp(aff['scale']), ldy=cout,
-                                                        n=n, h=r.h, w_=r.w, cout=cout, cout_pad=rup(cout, 32), kh=k, kw=k, dil=dil, dtype=dt,
-                                                        stride=stride, hin=hin if stride > 1 else 0, win=win if stride > 1 else 0,
-                                                        **fold_args, **self._src_args(r)))
-                        vals[tout.id] = TRef([(sb, cout)], n, r.h, r.w)
-                        ctx[id(node)] = dict(r=r, y=sb, yoff=0, ldy=cout, aff=None, aoff=0, cout=cout, k=k, dil=dil)
-                        continue
-                if sl is None:
-                    y = self._z(n, r.h, r.w, cout)
-                    stats = self._z(STAT_ROWS, 2, cout, dtype=torch.float64) if training else None
-                    yoff, ldy, aoff, aff_in = 0, cout, 0, None
-                else:           # branch of a concatenation: write into the channel slice of the shared tensor
-                    y, stats, yoff, ldy, aoff, aff_in = sl['y'], sl['stats'], sl['off'], sl['ctot'], sl['off'], sl['aff']
-                self.fwd.append(self._conv_step(w=pk['fwd'].data_ptr(), bias=rt.pptr(lay.name + '/bias'), y=y.data_ptr() + yoff * es, ldy=ldy,
-                                                stats=_fp(stats, aoff), stats_ld=ldy, n=n, h=r.h, w_=r.w, cout=cout, cout_pad=rup(cout, 32),
-                                                kh=k, kw=k, dil=dil, dtype=dt, stride=stride, hin=hin if stride > 1 else 0,
-                                                win=win if stride > 1 else 0, **self._src_args(r)))
-                aff = self._bn_forward(lay.bn_name, stats, ldy, aoff, cout, n * r.h * r.w, node.attrs.get('bn_updates', 1), aff_in, aoff)
-                if sl is None:
-                    vals[tout.id] = TRef([(y, cout)], n, r.h, r.w, affine=aff, relu=relu_out)
-                ctx[id(node)] = dict(r=r, y=y, yoff=yoff, ldy=ldy, aff=aff, aoff=aoff, cout=cout, k=k, dil=dil)
-            elif op == 'concat':
-                cx = ctx[id(node)]
-                hh, ww = self._dims(node.inputs[0])
-                if 'act' in cx:
-                    vals[node.outputs[0].id] = TRef([(cx['act'], cx['ctot'])], n, hh, ww)
-                else:
-                    vals[node.outputs[0].id] = TRef([(cx['y'], cx['ctot'])], n, hh, ww, affine=cx['aff'], relu=True)
-            elif op == 'pool':
-                tin, tout = node.inputs[0], node.outputs[0]
-                r = vals[tin.id]
-                f = node.attrs['f']
-                if not (r.affine and len(r.srcs) == 1):
-                    raise NotImplementedError('max-pool expects the output of a conv_batch_act block')
-                c = r.c
-                if r.h % f or r.w % f:
-                    raise ValueError(f'input {self.h}x{self.w} is not divisible by the model downsampling (a {r.h}x{r.w} map meets a {f}x{f} pool)')
-                pooled = self._z(n, r.h // f, r.w // f, c)
-                others = [cn for cn in consumers[tin.id] if cn is not node]
-                if others:
-                    acts[tin.id] = self._materialize(tin, r, f, pooled, sinks.get(tin.id), actslots.get(tin.id))
-                else:
-                    (y, _) = r.srcs[0]
-                    a = r.affine
-                    hh, ww = r.h, r.w
-                    self.fwd.append(lambda st, y=y, a=a, pooled=pooled, hh=hh, ww=ww, c=c, f=f: check(lib.satcv_bn_relu_pool(
-                        y.data_ptr(), _fp(a['scale']), _fp(a['shift']), None, 0, pooled.data_ptr(), None, 0, n, hh, ww, c, f, dt, st)))
-                vals[tout.id] = TRef([(pooled, c)], n, r.h // f, r.w // f)
-                ctx[id(node)] = dict(f=f)
-            elif op == 'convT':
-                tin, tout = node.inputs[0], node.outputs[0]
-                r = vals[tin.id]
-                if len(r.srcs) != 1:
-                    raise NotImplementedError('transposed conv on a concatenated input')
-                lay = node.layer
-                pk = rt.packed[lay.name]
-                cout, f = tout.channels, node.attrs['f']
-                if cout % 16:
-                    raise NotImplementedError(f'{lay.name}: transposed-conv filters must be a multiple of 16')
-                u = self._z(n, r.h * f, r.w * f, cout)
-                sink = sinks.get(tout.id) if training else None
-                self.fwd.append(self._conv_step(w=pk['fwd'].data_ptr(), bias=rt.pptr(lay.name + '/bias'), y=u.data_ptr(), ldy=cout,
-                                                stats=_fp(sink[0], sink[1]) if sink else None, stats_ld=sink[2] if sink else 0,
-                                                n=n, h=r.h, w_=r.w, cout=f * f * cout, cout_pad=rup(f * f * cout, 32), kh=1, kw=1, dil=1,
-                                                mode_out=1, f=f, cstat=cout, dtype=dt, **self._src_args(r)))
-                vals[tout.id] = TRef([(u, cout)], n, r.h * f, r.w * f)
-                ctx[id(node)] = dict(r=r, u=u, cout=cout, f=f)
-            elif op == 'concat_bn_relu':
-                ta, tb = node.inputs
-                tout = node.outputs[0]
-                if ta.id not in acts:
-                    ra0 = vals[ta.id]
-                    acts[ta.id] = self._materialize(ta, ra0, 1, None, sinks.get(ta.id)) if ra0.affine else ra0
-                ra, rb = acts[ta.id], vals[tb.id]
-                if (ra.h, ra.w) != (rb.h, rb.w):
-                    raise ValueError(f'concatenation of a {ra.h}x{ra.w} skip with a {rb.h}x{rb.w} up-sampled map: the input size must be divisible by the model downsampling')
-                if rb.affine or len(rb.srcs) != 1 or len(ra.srcs) != 1:
-                    raise NotImplementedError('concat+BN expects (activated skip, transposed-conv output)')
-                ca, cb = ra.c, rb.c
-                st = cat_stats[id(node)]
-                aff = self._bn_forward(node.layer.name, st, ca + cb, 0, ca + cb, n * ra.h * ra.w, 1)
-                vals[tout.id] = TRef([ra.srcs[0], rb.srcs[0]], n, ra.h, ra.w, affine=aff, relu=True)
-                ctx[id(node)] = dict(ra=ra, rb=rb, aff=aff, ca=ca, cb=cb)
-            elif op == 'maxpool':
-                tin, tout = node.inputs[0], node.outputs[0]
-                r = vals[tin.id]
-                if r.affine:
-                    r = self._materialize(tin, r)
-                (src, c) = r.srcs[0]
-                kk, ss, pp = node.attrs['k'], node.attrs['s'], node.attrs['pad']
-                ho, wo = (r.h + 2 * pp - kk) // ss + 1, (r.w + 2 * pp - kk) // ss + 1
-                out = self._z(n, ho, wo, c)
-                self.fwd.append(lambda st, src=src, out=out, hh=r.h, ww=r.w, c=c, kk=kk, ss=ss, pp=pp: check(lib.satcv_maxpool(
-                    src.data_ptr(), out.data_ptr(), n, hh, ww, c, kk, ss, pp, dt, st)))
-                vals[tout.id] = TRef([(out, c)], n, ho, wo)
-            elif op == 'raw':
-                # the convolution output BEFORE its BatchNormalization (build_acnn_layers feeds it to the next Conv2D, utils/model_tools.py:930)
-                r = vals[node.inputs[0].id]
-                if len(r.srcs) != 1 or node.inputs[0].node.op != 'cba':
-                    raise NotImplementedError('raw view of a tensor that is not a single convolution output')
-                vals[node.outputs[0].id] = TRef(r.srcs, n, r.h, r.w)
-            elif op == 'add_relu':
-                ty, tsc = node.inputs
-                tout = node.outputs[0]
-                if id(node) in fused_join:            # written in place by the block's last convolution (above)
-                    sb = fused_join[id(node)]
-                    c = sb.shape[-1]
-                    vals[tout.id] = TRef([(sb, c)], n, vals[ty.id].h, vals[ty.id].w)
-                    ctx[id(node)] = dict(out=sb, c=c, h=vals[ty.id].h, w=vals[ty.id].w)
-                    continue
-                ry, rs = vals[ty.id], vals[tsc.id]
-                if rs.affine and rs.relu and len(rs.srcs) == 1:       # shortcut = ReLU(BN(conv)) kept in raw form: activate it once
-                    if tsc.id not in acts:
-                        acts[tsc.id] = self._materialize(tsc, rs)
-                    rs = acts[tsc.id]
-                if len(ry.srcs) != 1 or len(rs.srcs) != 1 or ry.relu or (rs.affine and rs.relu):
-                    raise NotImplementedError('residual join expects linear (BN without ReLU) branches')
-                (yb, c), (sb, c2) = ry.srcs[0], rs.srcs[0]
-                assert c == c2 and (ry.h, ry.w) == (rs.h, rs.w)
-                out = self._z(n, ry.h, ry.w, c)
-                ya, sa = ry.affine, rs.affine
-                npx = n * ry.h * ry.w
-                self.fwd.append(lambda st, yb=yb, sb=sb, out=out, ya=ya, sa=sa, npx=npx, c=c: check(lib.satcv_add_act(
-                    yb.data_ptr(), _fp(ya['scale']) if ya else None, _fp(ya['shift']) if ya else None, sb.data_ptr(),
-                    _fp(sa['scale']) if sa else None, _fp(sa['shift']) if sa else None, 1, out.data_ptr(), npx, c, dt, st)))
-                vals[tout.id] = TRef([(out, c)], n, ry.h, ry.w)
-                ctx[id(node)] = dict(out=out, c=c, h=ry.h, w=ry.w)
-            elif op == 'upsample_head':
-                tin, tout = node.inputs[0], node.outputs[0]
-                lg = self.outputs[tin.id]                         # fp32 logits written by the linear head
-                hctx = ctx[id(tin.node)]
-                f = node.attrs['factor']
-                act = 0 if node.attrs['activation'] == 'softmax' else 1
-                hh, ww, ncls = hctx['r'].h, hctx['r'].w, hctx['ncls']
-                probs = self._z(n, hh * f, ww * f, ncls, dtype=torch.float32)
-                classes = self._z(*((n, hh * f, ww * f) if act == 0 else (n, hh * f, ww * f, ncls)), dtype=torch.int32)
-                th = float(node.attrs.get('thresh', 0.5))
-                self.fwd.append(lambda st, lg=lg, probs=probs, classes=classes, hh=hh, ww=ww, ncls=ncls, f=f, act=act, th=th: check(
-                    lib.satcv_upsample_head(lg.data_ptr(), n, hh, ww, ncls, f, act, th, probs.data_ptr(), classes.data_ptr(), st)))
-                self.outputs[tout.id] = probs
-                ctx[id(node)] = dict(classes=classes)
-                if training:
-                    raise NotImplementedError('the up-sampling head is inference-only')
-            elif op == 'dropout':
-                tin, tout = node.inputs[0], node.outputs[0]
-                r = vals[tin.id]
-                if not training:                     # identity at inference (Keras semantics)
-                    vals[tout.id] = r
-                    if tin.id in acts:
-                        acts[tout.id] = acts[tin.id]
-                    continue
-                ctot = r.c
-                spatial = node.attrs['spatial']
-                hw = r.h * r.w
-                mask = self._z(*((n, ctot) if spatial else (n * hw, ctot)), dtype=torch.float32)
-                out = self._z(n, r.h, r.w, ctot)
-                rate = float(node.attrs['rate'])
-                slot = len(self.dropouts)
-                self.dropouts.append(dict(mask=mask, node=node))
-                cnt = mask.numel()
-
-                def gen(st, mask=mask, rate=rate, cnt=cnt, slot=slot):
-                    # a fresh mask every step: counter = (step, dropout slot)
-                    check(lib.satcv_dropout_mask(self.rt.dropout_seed, (self.step_count << 8) + slot, rate, cnt, mask.data_ptr(), st))
-                self.fwd.append(gen)
-                off = 0
-                mode = 0 if spatial else 1
-                for (src, cs) in r.srcs:             # dual-source (concat) inputs: one launch per source / channel slice
-                    a = r.affine
-                    self.fwd.append(lambda st, src=src, cs=cs, off=off, a=a, rl=1 if r.relu else 0, mask=mask, ctot=ctot, mode=mode, out=out,
-                                    hw=hw: check(lib.satcv_dropout_apply(
-                        src.data_ptr(), cs, _fp(a['scale'], off) if a else None, _fp(a['shift'], off) if a else None, rl,
-                        _fp(mask, off), ctot, mode, out.data_ptr() + off * es, ctot, n, hw, cs, dt, st)))
-                    off += cs
-                vals[tout.id] = TRef([(out, ctot)], n, r.h, r.w)
-                ctx[id(node)] = dict(mask=mask, spatial=spatial, ctot=ctot, hw=hw, r=r)
-            elif op == 'head':
-                tin, tout = node.inputs[0], node.outputs[0]
-                r = vals[tin.id]
-                if len(r.srcs) != 1:
-                    raise NotImplementedError('head on concatenated input')
-                lay = node.layer
-                ncls = tout.channels
-                act = {'softmax': 0, 'sigmoid': 1, 'linear': 2}[node.attrs['activation']]
-                (y, c) = r.srcs[0]
-                npix = n * r.h * r.w
-                probs = self._z(n, r.h, r.w, ncls, dtype=torch.float32)
-                classes = self._z(*((n, r.h, r.w) if act != 1 else (n, r.h, r.w, ncls)), dtype=torch.int32)
-                hd = ops.make_head_desc(x=y.data_ptr(), ldx=c, cin=c, w=rt.pptr(lay.name + '/kernel'), b=rt.pptr(lay.name + '/bias'),
-                                        ncls=ncls, activation=act, npix=npix, dtype=dt,
-                                        in_scale=_fp(r.affine['scale']) if r.affine else None,
-                                        in_shift=_fp(r.affine['shift']) if r.affine else None,
-                                        thresh=node.attrs.get('thresh', 0.5), probs=probs.data_ptr(), classes=classes.data_ptr())
-                self.keep.append(hd)
-                self.fwd.append(lambda st, hd=hd: check(lib.satcv_head_fwd(C.byref(hd), st)))
-                self.outputs[tout.id] = probs
-                ctx[id(node)] = dict(r=r, probs=probs, classes=classes, act=act, ncls=ncls)
-                self.head = ctx[id(node)]
-                self.head_node = node
-            elif op == 'classes':
-                hctx = ctx[id(node.inputs[0].node)]
-                if 'thresh' in node.attrs:
-                    node.inputs[0].node.attrs['thresh'] = node.attrs['thresh']
-                self.outputs[node.outputs[0].id] = hctx['classes']
-            else:
-                raise NotImplementedError(f'op {op}')
-        self.vals = vals
-        self.node_ctx = ctx
-        if training:
-            self._build_backward(consumers, vals, acts, ctx, cat_stats)
-
-    def _build_backward(self, consumers, vals, acts, ctx, cat_stats):
-        rt, m, n = self.rt, self.rt.model, self.n
-        dt, es = rt.dtype, rt.esize
-        gact, gpool, gpool_f, graw = {}, {}, {}, {}
-        self.dbg = {}                       # layer name -> intermediate gradient tensors (diagnostics only)
-        _cnt = defaultdict(int)
-        for nd in m.nodes:
-            if nd.layer is not None:
-                _cnt[nd.layer.name] += 1
-        shared_layers = {k for k, v in _cnt.items() if v > 1}      # layers applied to several inputs (Siamese encoders)
-        ws_need = 0
-        wdescs = []
-        # DEFER: deferred, batched slab sums (satcv_reduce_slabs_batched; otherwise one sum launch behind every weight-gradient launch):
-        # a deferring launch keeps a workspace of its own; the sums run in groups, one launch per ~16 MiB of finished gradients (the bucket size
-        # of the gradient exchange, whose checkpoints move to the group boundaries)
-        DEFER = switches.read('defer_reduce') != 0
-        # RED3: the slab sum of a side-stream weight gradient on a THIRD stream, behind an event of its launch; with a workspace of its own per
-        # layer the next weight gradient does not have to wait for the sum of the previous one
-        RED3 = (not DEFER) and self.side is not None and switches.read('reduce_stream')
-        self.rstream = torch.cuda.Stream() if RED3 else None
-        self._last_red_ev = None
-        rpending = []                       # (descriptor, 'w' | 'f', gradient bytes) of launches whose sum has not been scheduled yet
-        rgroups = []                        # {'items': [(desc, kind)], 'tab': device job table, filled once the workspaces are assigned}
-        fused_ws_need = 0                   # the fused thin-layer backward launches run on the MAIN stream: a workspace of their own
-        fdescs = []
-        # loss -> dlogits is written by Model.train step into this buffer
-        h = self.head
-        self.dlogits = self._z(n * h['r'].h * h['r'].w, h['ncls'], dtype=torch.float32)
-        self.loss_buf = self._z(1, dtype=torch.float32)
-
-        def bn_bwd_steps(da, ldda, dp, lddp, f, yraw, ldy, aff, aoff, sums, sums_off, sums_ld, c, hh, ww, dy, lddy, dbias,
-                         dgamma, dbeta, accum=0, linear=0, frozen=False, second=None, act=None):
-            """act: dict(buf=[ROWS][2][c] rows in the ACTIVATED form, parts={'skip', 'pool'}) -- the parts of this layer's gradient whose
-            sums a producer already formed (the decoder's concat-BN apply pass for the skip gradient `da`, the data gradient of the next
-            encoder block for the pooled gradient `dp`); the separate reduce pass then only covers what is left."""
-            coef = self._z(2, c, dtype=torch.float32)
-            common = dict(yraw=yraw, ldy=ldy, scale=_fp(aff['scale'], aoff), shift=_fp(aff['shift'], aoff),
-                          mean=_fp(aff['mean'], aoff), rstd=_fp(aff['rstd'], aoff), n=n, h=hh, w_=ww, c=c, dtype=dt,
-                          f=f, sums=_fp(sums, sums_off), sums_ld=sums_ld, coef=_fp(coef), dy=dy, lddy_out=lddy, dbias=dbias, linear=linear)
-            d = ops.make_bnbwd_desc(da=da, ldda=ldda, dpool=dp, lddp=lddp, **common, **(second or {}))
-            self.keep.append(d)
-            parts = act['parts'] if (act and not frozen) else set()
-            need_da, need_dp = da is not None and 'skip' not in parts, dp is not None and 'pool' not in parts
-            dr = d
-            if parts and (need_da or need_dp):          # reduce pass over the part no producer covered
-                dr = ops.make_bnbwd_desc(da=da if need_da else None, ldda=ldda if need_da else 0, dpool=dp if need_dp else None,
-                                         lddp=lddp if need_dp else 0, **common)
-                self.keep.append(dr)
-            cnt = float(n * hh * ww)
-            red = lambda st: check(lib.satcv_bn_bwd_reduce(C.byref(dr), st))
-            red.label = f"bn_bwd_reduce n{n} {hh}x{ww} c{c} f{f}{' (part)' if dr is not d else ''}"
-            red.work = dict(kind='bn_bwd_reduce', px=n * hh * ww, c=c, esize=es)
-            if parts and not (need_da or need_dp):
-                red = None
-            if parts:
-                abuf = act['buf']
-                fin0 = lambda st: check(lib.satcv_bn_bwd_finalize2(_fp(sums, sums_off) if red is not None else None, sums_ld, _fp(abuf), c, c, cnt,
-                                                                   _fp(aff['scale'], aoff), _fp(aff['shift'], aoff), _fp(aff['mean'], aoff),
-                                                                   _fp(aff['rstd'], aoff), dgamma, dbeta, _fp(coef), accum, st))
-            else:
-                fin0 = lambda st: check(lib.satcv_bn_bwd_finalize(_fp(sums, sums_off), sums_ld, c, cnt, dgamma, dbeta, _fp(coef), accum, st))
-            if self.sync_bn:
-                def fin(st):            # SyncBN: Σdy, Σdy·x̂ averaged over replicas (linear + idempotent, so the whole buffer is reduced)
-                    parallel.allreduce_mean_(sums)
-                    if parts:
-                        parallel.allreduce_mean_(act['buf'])
-                    fin0(st)
-            else:
-                fin = fin0
-            app = lambda st: check(lib.satcv_bn_bwd_apply(C.byref(d), st))
-            app.label = f"bn_bwd_apply n{n} {hh}x{ww} c{c} f{f}"
-            app.work = dict(kind='bn_bwd_apply', px=n * hh * ww, c=c, esize=es)
-            app.coef = coef
-            if frozen:
-                # inference-mode BatchNormalization: dy = scale * g * mask, no batch-statistics terms (coef stays 0), no dgamma / dbeta
-                def fin_frozen(st):
-                    sums.zero_()
-                    coef.zero_()
-                    if act:
-                        act['buf'].zero_()
-                return None, fin_frozen, app
-            return red, fin, app
-
-        # ---- sums of an ENCODER block's BatchNorm backward formed by the producers of its two gradients (activated form, see
-        # satcv_bn_bwd_finalize2): encoder conv output tensor id -> dict(buf, parts)
-        act_sums = {}
-        POOL_SUMS = getattr(rt.model, 'fuse_pool_bn_sums', True) and dt == ops.BF16
-        ident = {}
-
-        def ident_vecs(c):
-            if c not in ident:
-                ident[c] = (torch.ones(c, dtype=torch.float32, device=rt.dev), torch.zeros(c, dtype=torch.float32, device=rt.dev))
-                self.keep.append(ident[c])
-            return ident[c]
-
-        def act_sums_for(t):
-            """the registry entry of encoder output t (a conv -> BN -> ReLU node that is pooled AND used as a skip), or None"""
-            if not POOL_SUMS or t.node.op != 'cba' or not t.node.attrs.get('bn', True) or not t.node.attrs.get('relu', True):
-                return None
-            if t.node.layer.bn_name in self.frozen or t.node.layer.bn_name in self.raw_bn or t.node.layer.name in shared_layers:
-                return None
-            if t.id not in act_sums:
-                act_sums[t.id] = dict(buf=self._z(STAT_ROWS, 2, t.channels, dtype=torch.float64), parts=set())
-            return act_sums[t.id]
-
-        seen_layers = set()     # layers applied more than once (shared weights): later visits accumulate their gradients
-        fused = {}      # tensor id -> sums buffer whose BN-backward reduce pass was done by the producer of the gradient
-        HEAD_FAST = {(1, 16), (2, 16), (1, 32), (2, 32), (3, 32), (4, 32), (1, 64), (2, 64)}
-
-        def fuse_target(t):
-            """bnr_* fields (and the sums buffer) if the head's backward kernel can also do the reduce pass of the BN+ReLU
-            that produced its input tensor `t` (the raw values are in its registers anyway); None otherwise."""
-            if not rt.model.fuse_head_bn_bwd or t.id in gact or len(consumers[t.id]) != 1:
-                return None
-            P, pc = t.node, ctx.get(id(t.node))
-            if P.op != 'cba' or pc['yoff'] != 0 or pc['ldy'] != pc['cout']:
-                return None
-            c, aff = pc['cout'], pc['aff']
-            sums = self._z(STAT_ROWS, 2, c, dtype=torch.float64)
-            return dict(mean=_fp(aff['mean']), rstd=_fp(aff['rstd']), sums=_fp(sums), sums_ld=c), sums
-
-        def bst_target(t):
-            """(bst fields, sums buffer, channels) if the data-gradient launch that writes dL/d t -- t the activated output of a
-            conv -> BN -> ReLU node or of the decoder's BN over [skip, up] -- may also form the sums of that BatchNorm's backward
-            (satcv.h: bst_*): the gradient has this one contributor, so the tile in the accumulators IS the whole gradient."""
-            if not getattr(rt.model, 'fuse_dgrad_bn_bwd', True) or dt != ops.BF16 or t.id in gact or t.id in gpool or len(consumers[t.id]) != 1:
-                return None
-            P, pc = t.node, ctx.get(id(t.node))
-            if P.op == 'cba' and P.attrs.get('bn', True) and P.layer.bn_name not in self.frozen:
-                c, aff, aoff = pc['cout'], pc['aff'], pc['aoff']
-                b = dict(y=pc['y'].data_ptr() + pc['yoff'] * es, ld=pc['ldy'], relu=1 if P.attrs.get('relu', True) else 0)
-            elif P.op == 'concat_bn_relu' and P.layer.name not in self.frozen:
-                ra, rb, aff, ca, cb = pc['ra'], pc['rb'], pc['aff'], pc['ca'], pc['cb']
-                if (P.inputs[1].node.op == 'convT' and BIAS_NOISE) or ca % 8:
-                    return None            # (the two-launch form of that BN backward keeps its own reduce passes)
-                c, aoff = ca + cb, 0
-                b = dict(y=ra.srcs[0][0].data_ptr(), ld=ca, y1=rb.srcs[0][0].data_ptr(), ld1=cb, split=ca, relu=1)
-            else:
-                return None
-            b.update(scale=_fp(aff['scale'], aoff), shift=_fp(aff['shift'], aoff), mean=_fp(aff['mean'], aoff), rstd=_fp(aff['rstd'], aoff))
-            return b, c
-
-        def act_form_unfit(t):
-            """t is the output of a BatchNorm with a zero gamma: its backward sums cannot be rebuilt from the activation (the fused
-            backward kernels' in-loader activation included) -- the separate reduce pass over the raw output forms them"""
-            P = t.node
-            return (P.op == 'cba' and P.layer.bn_name in self.raw_bn) or (P.op == 'concat_bn_relu' and P.layer.name in self.raw_bn)
-
-        def dgrad_step(t, **kw):
-            """data-gradient launch writing the activation gradient of tensor t (and, where the kernel can, the sums of the
-            BatchNorm backward of the node that produced t: one pass over two tensors less per such layer)"""
-            # the gradient of a max-pooled encoder output: this launch sees the pooled activation p = maxpool(relu(BN(y_enc))) (its own
-            # input), so its epilogue can form the pooled part of that BatchNorm's backward sums in the activated form -- sum dp [p > 0],
-            # sum dp p (bst_* with unit scale / rstd and zero shift / mean on the pooled tensor)
-            kw.setdefault('tile_policy', self.tile_policy)        # (the dry-run probes below must ask for the tile family the launch will get)
-            if (POOL_SUMS and not kw.get('accumulate') and t.node.op == 'pool' and len(consumers[t.id]) == 1 and t.id not in gact
-                    and len(vals[t.id].srcs) == 1 and vals[t.id].affine is None):
-                ent = act_sums_for(t.node.inputs[0])
-                if ent is not None and vals[t.id].srcs[0][1] == kw['cout'] == t.node.inputs[0].channels:
-                    one, zero = ident_vecs(kw['cout'])
-                    kwp = dict(kw, bst=dict(y=vals[t.id].srcs[0][0].data_ptr(), ld=kw['cout'], scale=_fp(one), shift=_fp(zero), mean=_fp(zero),
-                                            rstd=_fp(one), relu=1), stats=_fp(ent['buf']), stats_ld=kw['cout'])
-                    probe = ops.make_conv_desc(**kwp)
-                    if lib.satcv_conv2d_igemm_pipelined(C.byref(probe)) == 1:
-                        ent['parts'].add('pool')
-                        fn = self._conv_step(role='dgrad', **kwp)
-                        fn.label += ' +poolsums'
-                        return fn
-            bt = None if kw.get('accumulate') else bst_target(t)
-            # where it pays (measured per layer of the five-level U-Net, batch 64; DESIGN.md §3): the extra tile read hides under a
-            # K loop of >= 1152 (3x3 x 128 channels) and under the 1x1 kernels.  The thin and middle layers are HBM-bound
-            # themselves -- there the read costs the conv what the separate pass had cost -- and the thin ones run on the
-            # persistent weights-stationary kernel, which does not carry the sums.
-            kdepth = kw.get('kh', 1) * kw.get('kw', 1) * (kw.get('c0', 0) + (kw.get('c1', 0) or 0))
-            # (128 -> 256 at 64 x 64, the one K = 1152 layer whose output is wider than its input, measured +49 us against -41 us)
-            pays = FUSE_DGRAD_ALL or kdepth >= 2304 or (kdepth >= 1152 and kw['cout'] <= kw.get('c0', 0)) or kw.get('kh', 1) == 1
-            if bt is not None and bt[1] == kw['cout'] and pays:
-                sums = self._z(STAT_ROWS, 2, bt[1], dtype=torch.float64)
-                kw2 = dict(kw, bst=bt[0], stats=_fp(sums), stats_ld=bt[1])
-                probe = ops.make_conv_desc(**kw2)
-                if lib.satcv_conv2d_igemm_pipelined(C.byref(probe)) == 1:
-                    fused[t.id] = sums
-                    fn = self._conv_step(role='dgrad', **kw2)
-                    fn.label += ' +bnred'
-                    return fn
-            return self._conv_step(role='dgrad', **kw)
-
-        def wgrad_step(r, dy, lddy, lay, cin_real, cout, hh, ww, k, dil, f=0, accum=0, last=False):
-            nonlocal ws_need
-            sa = self._src_args(r)
-            if sa['x1'] is not None and sa['c0'] % 8:
-                raise NotImplementedError(f'{lay.name}: training a convolution over a concatenation needs a first part of a multiple of 8 channels '
-                                          f'(got {sa["c0"]}); inference has no such limit')
-            d = ops.make_wgrad_desc(dy=dy, lddy=lddy, dw=rt.gptr(lay.name + '/kernel'), cin=cin_real, cout=cout, n=n, h=hh, w_=ww,
-                                    dtype=dt, kh=k, kw=k, dil=dil, mode_dy=1 if f else 0, f=f if f else 1, transposed=1 if f else 0, accumulate=accum,
-                                    whole_chip=1 if last else 0, **sa)
-            nb = lib.satcv_conv2d_wgrad_workspace(C.byref(d))
-            if nb < 0:
-                raise RuntimeError(lib.satcv_last_error().decode())
-            nvalid = (f * f if f else 1) * cout
-            grp = None
-            if DEFER and not accum and lay.name not in shared_layers and nvalid % 4 == 0 and not (k == 3 and dil > 1):
-                d.defer_reduce = 1
-                d._own_ws = nb
-                rpending.append((d, 'w', 4 * k * k * cin_real * nvalid))
-            elif RED3 and not accum and lay.name not in shared_layers and nvalid % 4 == 0 and not (k == 3 and dil > 1):
-                d.defer_reduce = 1
-                d._own_ws = nb
-                grp = {'items': [(d, 'w')], 'tab': None}       # (a one-job table, built with the others once the workspaces are assigned)
-                rgroups.append(grp)
-            else:
-                ws_need = max(ws_need, nb)
-            wdescs.append(d)
-            self.keep.append(d)
-            label = f"wgrad k{k} d{dil} n{n} {hh}x{ww} {sa['c0']}+{sa['c1']}->{cout}{' convT f%d' % f if f else ''}"
-            work = dict(kind='wgrad', taps=(f * f if f else k * k), px=n * hh * ww, cin=cin_real, cout=cout, esize=es)
-            if self.side is None:
-                fn = lambda st: check(lib.satcv_conv2d_wgrad(C.byref(d), st))
-                fn.label, fn.work = label, work
-                return fn
-            # weight gradient and data gradient of a layer only share their INPUT (dy): run the weight gradients on a
-            # second HIP stream so that their load/MFMA/store phases interleave with the main stream's kernels
-            ev = torch.cuda.Event()
-            side, sptr = self.side, C.c_void_p(self.side.cuda_stream)
-
-            evw, evr = (torch.cuda.Event(), torch.cuda.Event()) if grp is not None else (None, None)
-
-            def run(st, d=d, ev=ev, grp=grp, evw=evw, evr=evr):
-                ev.record(torch.cuda.current_stream())
-                side.wait_event(ev)
-                check(lib.satcv_conv2d_wgrad(C.byref(d), sptr))
-                if grp is not None:
-                    t = grp['tab']
-                    evw.record(side)
-                    self.rstream.wait_event(evw)
-                    check(lib.satcv_reduce_slabs_batched(t['jobs'].data_ptr(), t['prefix'].data_ptr(), t['n'], t['total'], C.c_void_p(self.rstream.cuda_stream)))
-                    evr.record(self.rstream)
-                    self._last_red_ev = evr
-            run.label, run.work = label, work
-            return run
-
-        # data-parallel overlap: after every parameter-bearing node tell the gradient exchange which tail of the flat
-        # gradient buffer is final (parallel.GradSync.ready_above)
-        pending = {}                                   # layer name -> remaining visits
-        for node in m.nodes:
-            if node.layer is not None and any(ps.name in rt.offsets for ps in node.layer.specs):
-                pending[node.layer.name] = pending.get(node.layer.name, 0) + 1
-        layer_hi = {l.name: max(rt.offsets[ps.name] + ps.size for ps in l.specs if ps.name in rt.offsets)
-                    for l in m.layers if l.name in pending}
-        # a conv_batch_act node also writes the gamma / beta gradients of ITS BatchNormalization (a layer of its own, directly
-        # above the convolution in the flat buffer): until the node has run, nothing below the end of that layer is final
-        by_name = {l.name: l for l in m.layers}
-        for node in m.nodes:
-            bn = getattr(node.layer, 'bn_name', None) if node.op == 'cba' else None
-            if bn in by_name and node.layer.name in layer_hi:
-                his = [rt.offsets[ps.name] + ps.size for ps in by_name[bn].specs if ps.name in rt.offsets]
-                if his:
-                    layer_hi[node.layer.name] = max(layer_hi[node.layer.name], max(his))
-
-        def flush_reduces(force=False):
-            """schedule the batched slab sum of the launches recorded so far (on the weight-gradient stream, behind an event of the main
-            stream: the fused thin-layer launches write their slabs there).  Returns False while a group is still being collected."""
-            if not rpending:
-                return True
-            if not force and sum(b for _, _, b in rpending) < (16 << 20):
-                return False
-            grp = {'items': [(d, kind) for d, kind, _ in rpending], 'tab': None}
-            rpending.clear()
-            rgroups.append(grp)
-            ev = torch.cuda.Event() if self.side is not None else None
-
-            def flush(st, grp=grp, ev=ev):
-                t = grp['tab']
-                if self.side is not None:
-                    ev.record(torch.cuda.current_stream())
-                    self.side.wait_event(ev)
-                    st = C.c_void_p(self.side.cuda_stream)
-                check(lib.satcv_reduce_slabs_batched(t['jobs'].data_ptr(), t['prefix'].data_ptr(), t['n'], t['total'], st))
-            flush.label = f"wgrad_reduce_batched {len(grp['items'])} layers"
-            self.bwd.append(flush)
-            return True
-
-        def grads_ready(node):
-            lay = node.layer
-            if lay is None or lay.name not in pending:
-                return
-            pending[lay.name] -= 1
-            if pending[lay.name] == 0:
-                del pending[lay.name]
-            if not flush_reduces(force=not pending):
-                return                                  # (the gradients above `lo` are not final before their slabs are summed)
-            lo = max((layer_hi[k] for k in pending), default=0)
-            # ---- round 6: the optimizer step of the parameters in [lo, n) beside the REST of the backward pass.  When what is still pending is a
-            # few per cent of the parameters (the three thin encoder blocks of get_unet_model hold 0.5 %), everything above `lo` is final: Adam
-            # and the operand repack of that range run on the weight-gradient stream -- idle from here on: the thin layers' weight gradients
-            # are part of the fused launches of the main stream -- while the main stream finishes the encoder's backward pass; the step's tail
-            # then only updates [0, lo).  Single replica only (a gradient exchange must see every gradient first): Model.train_step_device
-            # sets plan.early_opt per step.
-            if EARLY_OPT and self.side is not None and self.eo_lo is None and pending and 0 < lo <= EARLY_OPT_FRAC * rt.n_train and lo % 4 == 0:
-                self.eo_lo = lo
-                evo = torch.cuda.Event()
-
-                def early(st, lo=lo, evo=evo):
-                    eo = self.early_opt
-                    if eo is None:
-                        return
-                    evo.record(torch.cuda.current_stream())
-                    self.side.wait_event(evo)
-                    if self._last_red_ev is not None:
-                        self.side.wait_event(self._last_red_ev)
-                    sp = C.c_void_p(self.side.cuda_stream)
-                    n = rt.n_train - lo
-                    check(lib.satcv_adam_step_part(_fp(rt.pflat, lo), _fp(rt.gflat, lo), _fp(rt.adam_m, lo), _fp(rt.adam_v, lo), n, eo['beta_1'], eo['beta_2'],
-                                                   eo['epsilon'], rt.adam_state.data_ptr(), _fp(rt.lr_mul, lo) if rt.lr_mul is not None else None, 0, sp))
-                    rt.repack(lo, None, stream=sp)
-                    self.eo_done = True
-                early.label = f'early optimizer step [{lo}, {rt.n_train}) on the side stream'
-                self.bwd.append(early)
-
-            def ckpt(st, lo=lo):
-                sync = getattr(m, '_sync_grads', None)
-                if sync is not None and hasattr(sync, 'ready_above'):
-                    if self._last_red_ev is not None:            # (gradients are final behind their slab sums on the third stream)
-                        self.side.wait_event(self._last_red_ev)
-                    sync.ready_above(rt.gflat, lo, self.side)
-            self.bwd.append(ckpt)
-
-        head_feed = {}                                 # tensor id -> the head launch that writes its gradient
-        prev_node = None
-        for node in reversed(m.nodes):
-            if prev_node is not None:
-                grads_ready(prev_node)                 # (the branches below `continue`: bookkeeping of the node just finished)
-            prev_node = node
-            op = node.op
-            cx = ctx.get(id(node))
-            if op == 'head':
-                r = cx['r']
-                (y, c) = r.srcs[0]
-                dx = self._z(n, r.h, r.w, c)
-                lay = node.layer
-                hb = None
-                ft = fuse_target(node.inputs[0]) if (cx['ncls'], c) in HEAD_FAST and r.affine else None
-                if ft is not None:
-                    hb = dict(mean=ft[0]['mean'], rstd=ft[0]['rstd'], sums=ft[0]['sums'], sums_ld=ft[0]['sums_ld'])
-                    fused[node.inputs[0].id] = ft[1]
-                hd = ops.make_head_desc(x=y.data_ptr(), ldx=c, cin=c, w=rt.pptr(lay.name + '/kernel'), b=rt.pptr(lay.name + '/bias'),
-                                        ncls=cx['ncls'], activation=cx['act'], npix=n * r.h * r.w, dtype=dt,
-                                        in_scale=_fp(r.affine['scale']) if r.affine else None,
-                                        in_shift=_fp(r.affine['shift']) if r.affine else None,
-                                        dlogits=self.dlogits.data_ptr(), dx=dx.data_ptr(), lddx=c,
-                                        dw=rt.gptr(lay.name + '/kernel'), db=rt.gptr(lay.name + '/bias'), bnr=hb)
-                self.keep.append(hd)
-                self.bwd.append(lambda st, hd=hd: check(lib.satcv_head_bwd(C.byref(hd), st)))
-                nb = lib.satcv_head_bwd_workspace(C.byref(hd))
-                if nb > 0:            # per-workgroup partial rows + an ordered sum instead of float atomics: reproducible dW / db
-                    part = self._z(nb // 4, dtype=torch.float32)
-                    hd.partials = part.data_ptr()
-                    self.bwd.append(lambda st, hd=hd: check(lib.satcv_head_bwd_finalize(C.byref(hd), st)))
-                gact[node.inputs[0].id] = (dx, 0, c)
-                # (the block under the head may form this gradient itself from the logit gradients: see the fused launch below)
-                head_feed[node.inputs[0].id] = dict(hd=hd, ncls=cx['ncls'], c=c, w=rt.pptr(lay.name + '/kernel'), wname=lay.name + '/kernel',
-                                                    fused_reduce=ft is not None)
-            elif op == 'add_relu':
-                # out = ReLU(BN(conv) + shortcut): the masked gradient g * (out > 0) belongs to BOTH addends.  It is formed in place
-                # and handed to the branch's (linear) BN backward and to the shortcut; a tensor that already holds a gradient
-                # (several consumers) receives it by addition.
-                ty, tsc = node.inputs
-                g = gact.get(node.outputs[0].id)
-                if g is None or cx is None:
-                    continue
-                c, hh, ww, out = cx['c'], cx['h'], cx['w'], cx['out']
-                if g[1] != 0 or g[2] != c:
-                    raise NotImplementedError('residual-join gradient in a channel slice')
-                gb, cnt = g[0], n * hh * ww * c
-                self.bwd.append(lambda st, out=out, gb=gb, cnt=cnt: check(lib.satcv_relu_bwd(out.data_ptr(), gb.data_ptr(), cnt, dt, st)))
-                for t in (ty, tsc):
-                    prev = gact.get(t.id)
-                    if prev is None:
-                        gact[t.id] = (gb, 0, c)
-                    else:
-                        if prev[1] != 0 or prev[2] != c:
-                            raise NotImplementedError('gradient fan-in into a channel slice')
-                        self.bwd.append(lambda st, pb=prev[0], gb=gb, npx=n * hh * ww, c=c: check(lib.satcv_add_act(
-                            pb.data_ptr(), None, None, gb.data_ptr(), None, None, 0, pb.data_ptr(), npx, c, dt, st)))
-            elif op == 'cba' and not node.attrs.get('bn', True):
-                # plain Conv2D: the gradient of its stored output is the incoming one as it is
-                tin, tout = node.inputs[0], node.outputs[0]
-                da = gact.get(tout.id)
-                if da is None:
-                    continue
-                lay, r, cout = node.layer, cx['r'], cx['cout']
-                if da[1] != 0 or da[2] != cout:
-                    raise NotImplementedError('plain-convolution gradient in a channel slice')
-                hh, ww, dyb = r.h, r.w, da[0]
-                accum = 1 if lay.name in seen_layers else 0
-                seen_layers.add(lay.name)
-                bpart = self._z(max(lib.satcv_bias_grad_workspace(n * hh * ww, cout) // 4, 1), dtype=torch.float32)
-                self.bwd.append(lambda st, dyb=dyb, cout=cout, npx=n * hh * ww, db=rt.gptr(lay.name + '/bias'), bpart=bpart: check(lib.satcv_bias_grad(
-                    dyb.data_ptr(), cout, npx, cout, dt, db, bpart.data_ptr(), st)))
-                pk = rt.packed[lay.name]
-                self.bwd.append(wgrad_step(r, dyb.data_ptr(), cout, lay, pk['cin'], cout, hh, ww, cx['k'], cx['dil'], accum=accum))
-                if tin.node.op != 'input':
-                    cinp = r.c
-                    prev = gact.get(tin.id)
-                    if prev is not None and (prev[1] != 0 or prev[2] != cinp):
-                        raise NotImplementedError('gradient fan-in into a channel slice')
-                    gin = prev[0] if prev is not None else self._z(n, hh, ww, cinp)
-                    self.bwd.append(dgrad_step(tin, x0=dyb.data_ptr(), c0=cout, w=pk['dgrad'].data_ptr(), y=gin.data_ptr(), ldy=cinp,
-                                               n=n, h=hh, w_=ww, cout=cinp, cout_pad=rup(cinp, 32), kh=cx['k'], kw=cx['k'],
-                                               dil=cx['dil'], dtype=dt, accumulate=1 if prev is not None else 0))
-                    gact[tin.id] = (gin, 0, cinp)
-            elif op == 'cba':
-                tin, tout = node.inputs[0], node.outputs[0]
-                da, dp = gact.get(tout.id), gpool.get(tout.id)
-                graws = [gact[cn.outputs[0].id] for cn in consumers.get(tout.id, []) if cn.op == 'raw' and cn.outputs[0].id in gact]
-                if da is None and dp is None:
-                    if graws:
-                        raise NotImplementedError('a convolution consumed only through its un-normalised output')
-                    continue
-                lay, r, y, aff, cout = node.layer, cx['r'], cx['y'], cx['aff'], cx['cout']
-                yoff, ldy, aoff = cx['yoff'], cx['ldy'], cx['aoff']
-                hh, ww = r.h, r.w
-                pre = fused.get(tout.id)
-                sums = pre if pre is not None else self._z(STAT_ROWS, 2, cout, dtype=torch.float64)
-                accum = 1 if lay.name in seen_layers else 0
-                seen_layers.add(lay.name)
-                da_ptr = da[0].data_ptr() + da[1] * es if da is not None else None
-                # ---- thin full- / half-resolution layers: ONE launch forms dy = BN-backward(g, y) in registers and uses the tile for
-                # the data gradient AND the weight gradient (csrc/conv_bwd_fused.hip): 4 tensor passes instead of 7, no dy tensor
-                fz = None
-                if (getattr(rt.model, 'fuse_thin_bwd', True) and dt == ops.BF16 and da is not None and dp is None and not graws and not BIAS_NOISE
-                        and tin.node.op != 'input' and gact.get(tin.id) is None and cx['k'] == 3 and cx['dil'] == 1 and da[2] == ldy
-                        and lay.name not in shared_layers):      # (a shared layer's other visit may have its weight gradient in flight on the side stream)
-                    pk = rt.packed[lay.name]
-                    cinp = r.c
-                    sa = self._src_args(r)
-                    coef = self._z(2, cout, dtype=torch.float32)
-                    gin = self._z(n, hh, ww, cinp)
-                    fz = ops.make_bwdf_desc(g=da_ptr, yraw=y.data_ptr() + yoff * es, ldg=ldy, bn_scale=_fp(aff['scale'], aoff), bn_shift=_fp(aff['shift'], aoff),
-                                            bn_mean=_fp(aff['mean'], aoff), bn_rstd=_fp(aff['rstd'], aoff), bn_coef=_fp(coef),
-                                            linear=0 if node.attrs.get('relu', True) else 1, w_dgrad=pk['dgrad'].data_ptr(), dx=gin.data_ptr(), lddx=cinp,
-                                            dw=rt.gptr(lay.name + '/kernel'), cin=pk['cin'], cout=cout, n=n, h=hh, w_=ww, dtype=dt, accumulate=accum, **sa)
-                    # ... and, where the layer below is a BatchNorm + ReLU fed only by this gradient, the sums of ITS backward
-                    # (what satcv_bn_bwd_reduce would compute in a pass over dx and that layer's raw output): bst_*
-                    bt = bst_target(tin) if (sa['in_relu'] and sa['in_scale'] is not None and not act_form_unfit(tin)) else None
-                    sums_below = None
-                    if bt is not None and bt[1] == cinp and bt[0].get('relu', 0) == 1:
-                        sums_below = self._z(STAT_ROWS, 2, cinp, dtype=torch.float64)
-                        fz.bst_sums, fz.bst_sums_ld, fz.bst_mean, fz.bst_rstd = _fp(sums_below), cinp, bt[0]['mean'], bt[0]['rstd']
-                    # ... and, for the block under the 1 x 1 head, the gradient g itself: two logit gradients per pixel instead of the
-                    # head's dx tensor written and read back (2 x 64 bytes per pixel)
-                    hf = head_feed.get(tout.id)
-                    if (hf is not None and getattr(rt.model, 'fuse_head_grad', True) and hf['ncls'] == 2 and hf['c'] == cout == 32 and cinp == 32
-                            and hf['fused_reduce'] and pre is not None and len(consumers.get(tout.id, [])) == 1):
-                        fz.hg_dlogits, fz.hg_w, fz.hg_ncls = self.dlogits.data_ptr(), hf['w'], 2
-                        if lib.satcv_conv2d_bwd_fused_workspace(C.byref(fz)) < 0:
-                            fz.hg_dlogits, fz.hg_w, fz.hg_ncls = None, None, 0
-                        else:
-                            hf['hd'].dx = None                      # satcv_head_bwd keeps its dW / db and the fused sums, stores no dx
-                    nbf = lib.satcv_conv2d_bwd_fused_workspace(C.byref(fz))
-                    if nbf < 0 and sums_below is not None:              # (the 64 -> 64 form does not carry the sums)
-                        fz.bst_sums, fz.bst_sums_ld, fz.bst_mean, fz.bst_rstd = None, 0, None, None
-                        sums_below = None
-                        nbf = lib.satcv_conv2d_bwd_fused_workspace(C.byref(fz))
-                    if nbf < 0:
-                        fz = None
-                    elif sums_below is not None:
-                        fused[tin.id] = sums_below
-                if fz is not None:
-                    if DEFER and not accum and lay.name not in shared_layers:
-                        fz.defer_reduce = 1
-                        fz._own_ws = nbf
-                        rpending.append((fz, 'f', 4 * 9 * pk['cin'] * cout))
-                    else:
-                        fused_ws_need = max(fused_ws_need, nbf)
-                    fdescs.append(fz)
-                    self.keep.append(fz)
-                    cnt = float(n * hh * ww)
-                    frozen_bn = lay.bn_name in self.frozen
-                    dg_, db_ = rt.gptr(lay.bn_name + '/gamma'), rt.gptr(lay.bn_name + '/beta')
-                    bd = ops.make_bnbwd_desc(yraw=y.data_ptr() + yoff * es, ldy=ldy, scale=_fp(aff['scale'], aoff), shift=_fp(aff['shift'], aoff),
-                                             mean=_fp(aff['mean'], aoff), rstd=_fp(aff['rstd'], aoff), n=n, h=hh, w_=ww, c=cout, dtype=dt,
-                                             da=da_ptr, ldda=da[2], sums=_fp(sums), sums_ld=cout, coef=_fp(coef), linear=fz.linear)
-                    self.keep.append(bd)
-                    if frozen_bn:
-                        def fin(st, sums=sums, coef=coef):
-                            sums.zero_(); coef.zero_()
-                    else:
-                        if pre is None:
-                            red = lambda st, bd=bd: check(lib.satcv_bn_bwd_reduce(C.byref(bd), st))
-                            red.label = f"bn_bwd_reduce n{n} {hh}x{ww} c{cout} f1"
-                            red.work = dict(kind='bn_bwd_reduce', px=n * hh * ww, c=cout, esize=es)
-                            self.bwd.append(red)
-                        fin0 = lambda st, sums=sums, coef=coef, cnt=cnt, dg_=dg_, db_=db_, accum=accum, c_=cout: check(lib.satcv_bn_bwd_finalize(
-                            _fp(sums), c_, c_, cnt, dg_, db_, _fp(coef), accum, st))
-                        if self.sync_bn:
-                            def fin(st, fin0=fin0, sums=sums):
-                                parallel.allreduce_mean_(sums)
-                                fin0(st)
-                        else:
-                            fin = fin0
-                    self.bwd.append(fin)
-                    fstep = lambda st, fz=fz: check(lib.satcv_conv2d_bwd_fused(C.byref(fz), st))
-                    fstep.label = f"bwd_fused k3 n{n} {hh}x{ww} {sa['c0']}+{sa['c1']}->{cout}{' +bnred' if fz.bst_sums else ''}{' +headgrad' if fz.hg_dlogits else ''}"
-                    fstep.work = dict(kind='bwd_fused', taps=9, px=n * hh * ww, cin=pk['cin'], cout=cout, esize=es)
-                    self.bwd.append(fstep)
-                    gact[tin.id] = (gin, 0, cinp)
-                    self.dbg['dx:' + lay.name] = gin
-                    self.dbg['dyparts:' + lay.name] = dict(g=da, y=y, yoff=yoff, ldy=ldy, aff=aff, aoff=aoff, cout=cout, coef=coef, linear=fz.linear)
-                    if fz.hg_dlogits:
-                        self.dbg['dyparts:' + lay.name]['head'] = (self.dlogits, head_feed[tout.id]['wname'])
-                    self.dbg['_ctx:' + lay.name] = dict(da=da, dp=dp, y=y, yoff=yoff, ldy=ldy, aff=aff, aoff=aoff, cout=cout)
-                    continue
-                dy = self._z(n, hh, ww, cout)
-                red, fin, app = bn_bwd_steps(da_ptr, da[2] if da is not None else 0, dp[0].data_ptr() if dp is not None else None,
-                                             cout, gpool_f.get(tout.id, 1), y.data_ptr() + yoff * es, ldy, aff, aoff, sums, 0, cout, cout, hh, ww,
-                                             dy.data_ptr(), cout, rt.gptr(lay.name + '/bias') if BIAS_NOISE else None,
-                                             rt.gptr(lay.bn_name + '/gamma'), rt.gptr(lay.bn_name + '/beta'), accum,
-                                             linear=0 if node.attrs.get('relu', True) else 1, frozen=lay.bn_name in self.frozen,
-                                             act=act_sums.get(tout.id) if (act_sums.get(tout.id) or {}).get('parts') else None)
-                # ---- encoder blocks of the full- / half-resolution levels: the pooled BatchNorm apply + weight gradient (+ data gradient)
-                # in ONE launch (satcv_conv2d_bwd_fused with dpool / amax): no dy tensor, no separate weight-gradient launch
-                fzp = None
-                amax = self.amax_of.get(tout.id)
-                if (amax is not None and getattr(rt.model, 'fuse_pool_bwd', True) and dt == ops.BF16 and da is not None and dp is not None
-                        and gpool_f.get(tout.id, 1) == 2 and not graws and not BIAS_NOISE and cx['k'] == 3 and cx['dil'] == 1 and da[2] == ldy
-                        and dp[1] == 0 and lay.bn_name not in self.frozen and gact.get(tin.id) is None and lay.name not in shared_layers):
-                    pkp = rt.packed[lay.name]
-                    sa = self._src_args(r)
-                    want_dx = tin.node.op != 'input'
-                    cinp = r.c
-                    ginp = self._z(n, hh, ww, cinp) if want_dx else None
-                    fzp = ops.make_bwdf_desc(g=da_ptr, yraw=y.data_ptr() + yoff * es, ldg=ldy, bn_scale=_fp(aff['scale'], aoff), bn_shift=_fp(aff['shift'], aoff),
-                                             bn_mean=_fp(aff['mean'], aoff), bn_rstd=_fp(aff['rstd'], aoff), bn_coef=_fp(app.coef), linear=0,
-                                             w_dgrad=pkp['dgrad'].data_ptr() if want_dx else None, dx=ginp.data_ptr() if want_dx else None,
-                                             lddx=cinp if want_dx else 0, dw=rt.gptr(lay.name + '/kernel'), cin=pkp['cin'], cout=cout, n=n, h=hh, w_=ww,
-                                             dtype=dt, accumulate=accum, dpool=dp[0].data_ptr(), lddp=dp[2], amax=amax.data_ptr(), **sa)
-                    # its input is the max-pooled output of the block below: the pooled part of THAT block's sums, activated form
-                    ent = None
-                    if (want_dx and POOL_SUMS and tin.node.op == 'pool' and len(consumers[tin.id]) == 1 and sa['in_scale'] is None
-                            and len(vals[tin.id].srcs) == 1 and tin.node.inputs[0].channels == cinp):
-                        ent = act_sums_for(tin.node.inputs[0])
-                    if ent is not None:
-                        fzp.bst_sums, fzp.bst_sums_ld, fzp.bst_act_form = _fp(ent['buf']), cinp, 1
-                    nbp = lib.satcv_conv2d_bwd_fused_workspace(C.byref(fzp))
-                    if nbp < 0:
-                        fzp = None
-                    elif ent is not None:
-                        ent['parts'].add('pool')
-                if fzp is not None:
-                    if DEFER and not accum and lay.name not in shared_layers:
-                        fzp.defer_reduce = 1
-                        fzp._own_ws = nbp
-                        rpending.append((fzp, 'f', 4 * 9 * pkp['cin'] * cout))
-                    else:
-                        fused_ws_need = max(fused_ws_need, nbp)
-                    fdescs.append(fzp)
-                    self.keep.append(fzp)
-                    self.bwd += [fin] if (pre is not None or red is None) else [red, fin]
-                    fstep = lambda st, fzp=fzp: check(lib.satcv_conv2d_bwd_fused(C.byref(fzp), st))
-                    fstep.label = f"bwd_fused k3 n{n} {hh}x{ww} {sa['c0']}+{sa['c1']}->{cout} pooled{'' if want_dx else ' nodx'}{' +poolsums' if fzp.bst_sums else ''}"
-                    fstep.work = dict(kind='bwd_fused', taps=9, px=n * hh * ww, cin=pkp['cin'], cout=cout, esize=es, nodx=not want_dx, pooled=True)
-                    self.bwd.append(fstep)
-                    if want_dx:
-                        gact[tin.id] = (ginp, 0, cinp)
-                        self.dbg['dx:' + lay.name] = ginp
-                    self.dbg['dyparts:' + lay.name] = dict(g=da, y=y, yoff=yoff, ldy=ldy, aff=aff, aoff=aoff, cout=cout, coef=app.coef, linear=0,
-                                                           dp=dp, amax=amax)
-                    self.dbg['_ctx:' + lay.name] = dict(da=da, dp=dp, y=y, yoff=yoff, ldy=ldy, aff=aff, aoff=aoff, cout=cout)
-                    continue
-                self.bwd += [fin, app] if (pre is not None or red is None) else [red, fin, app]
-                for gr in graws:            # consumers of the un-normalised output add their gradient to dy (and to the bias gradient)
-                    if gr[1] != 0 or gr[2] != cout:
-                        raise NotImplementedError('raw-output gradient in a channel slice')
-                    bpart = self._z(max(lib.satcv_bias_grad_workspace(n * hh * ww, cout) // 4, 1), dtype=torch.float32)
-                    self.bwd.append(lambda st, dy=dy, gb=gr[0], npx=n * hh * ww, cout=cout, db=rt.gptr(lay.name + '/bias'), bpart=bpart: (
-                        check(lib.satcv_bias_grad(gb.data_ptr(), cout, npx, cout, dt, db, bpart.data_ptr(), st)),
-                        check(lib.satcv_add_act(dy.data_ptr(), None, None, gb.data_ptr(), None, None, 0, dy.data_ptr(), npx, cout, dt, st))))
-                self.dbg['dy:' + lay.name] = dy
-                self.dbg['_ctx:' + lay.name] = dict(da=da, dp=dp, y=y, yoff=yoff, ldy=ldy, aff=aff, aoff=aoff, cout=cout)
-                pk = rt.packed[lay.name]
-                # (the weight gradient of a layer fed by a model input is the last launch of the backward pass: nothing runs beside it)
-                wstep = wgrad_step(r, dy.data_ptr(), cout, lay, pk['cin'], cout, hh, ww, cx['k'], cx['dil'], accum=accum,
-                                   last=tin.node.op == 'input' and len(m.inputs) == 1 and switches.read('wgrad_last_full'))
-                if not WGRAD_LATE:
-                    self.bwd.append(wstep)
-                if tin.node.op != 'input':
-                    cinp = r.c
-                    prev = gact.get(tin.id)
-                    if prev is not None and (prev[1] != 0 or prev[2] != cinp):
-                        raise NotImplementedError('gradient fan-in into a channel slice')
-                    gin = prev[0] if prev is not None else self._z(n, hh, ww, cinp)
-                    self.bwd.append(dgrad_step(tin, x0=dy.data_ptr(), c0=cout, w=pk['dgrad'].data_ptr(), y=gin.data_ptr(), ldy=cinp,
-                                               n=n, h=hh, w_=ww, cout=cinp, cout_pad=rup(cinp, 32), kh=cx['k'], kw=cx['k'],
-                                               dil=cx['dil'], dtype=dt, accumulate=1 if prev is not None else 0))
-                    gact[tin.id] = (gin, 0, cinp)
-                    self.dbg['dx:' + lay.name] = gin
-                if WGRAD_LATE:
-                    self.bwd.append(wstep)
-            elif op == 'dropout':
-                tin, tout = node.inputs[0], node.outputs[0]
-                g = gact.get(tout.id)
-                if g is None or cx is None:
-                    continue
-                if g[1] != 0 or g[2] != cx['ctot']:
-                    raise NotImplementedError('dropout gradient in a channel slice')
-                gt, mask, ctot, hw = g[0], cx['mask'], cx['ctot'], cx['hw']
-                mode = 0 if cx['spatial'] else 1
-                self.bwd.append(lambda st, gt=gt, mask=mask, ctot=ctot, hw=hw, mode=mode: check(lib.satcv_dropout_apply(
-                    gt.data_ptr(), ctot, None, None, 0, _fp(mask), ctot, mode, gt.data_ptr(), ctot, n, hw, ctot, dt, st)))
-                gact[tin.id] = (gt, 0, ctot)
-            elif op == 'concat':
-                g = gact.get(node.outputs[0].id)
-                if g is None:
-                    continue
-                off = 0
-                for t in node.inputs:          # each branch sees its channel slice of the gradient
-                    gact[t.id] = (g[0], g[1] + off, g[2])
-                    off += t.channels
-            elif op == 'pool':
-                tin, tout = node.inputs[0], node.outputs[0]
-                if tout.id in gact:
-                    if gact[tout.id][1] != 0:
-                        raise NotImplementedError('pooled gradient in a channel slice')
-                    gpool[tin.id] = gact[tout.id]
-                    gpool_f[tin.id] = cx['f']
-            elif op == 'concat_bn_relu':
-                ta, tb = node.inputs
-                tout = node.outputs[0]
-                g = gact.get(tout.id)
-                if g is None:
-                    continue
-                ra, rb, aff, ca, cb = cx['ra'], cx['rb'], cx['aff'], cx['ca'], cx['cb']
-                ctot = ca + cb
-                hh, ww = ra.h, ra.w
-                pre = fused.get(tout.id)
-                sums = pre if pre is not None else self._z(STAT_ROWS, 2, ctot, dtype=torch.float64)
-                dskip = self._z(n, hh, ww, ca)
-                du = self._z(n, hh, ww, cb)
-                bn = node.layer.name
-                upl = tb.node.layer
-                if g[2] != ctot:
-                    raise NotImplementedError('decoder concat gradient in a channel slice')
-                gptr_ = g[0].data_ptr() + g[1] * es
-                if not (tb.node.op == 'convT' and BIAS_NOISE) and ca % 8 == 0:
-                    # ONE reduce / finalize / apply over the whole concatenation: the gradient of the concatenated tensor is read
-                    # once per pass in full lines (the two half launches each touched every line of it for half of its bytes)
-                    # the skip is the activated output of an encoder block that is also max-pooled: this apply pass has dskip and that
-                    # activation in registers -- it also forms the skip part of the encoder BatchNorm's backward sums (sk_sums)
-                    sec = dict(yraw1=rb.srcs[0][0].data_ptr(), ldy1=cb, dy1=du.data_ptr(), lddy1=cb, c_split=ca)
-                    # round 5: the `up` channels' part of this apply pass, the transposed convolution's data gradient and its weight gradient as ONE
-                    # launch (satcv_convt_bwd_fused, built at the convT node below): the apply pass then covers the skip channels only
-                    ctbf = None
-                    cxt = ctx.get(id(tb.node)) if tb.node.op == 'convT' else None
-                    if (CTBF and dt == ops.BF16 and cxt is not None and bn not in self.frozen and upl.name not in shared_layers and cxt['f'] == 2
-                            and cb in CTBF_COUTS and len(consumers.get(tb.id, [])) == 1):
-                        rT = cxt['r']
-                        saT = self._src_args(rT)
-                        probe = ops.make_ctbf_desc(g=gptr_ + ca * es, ldg=ctot, yup=rb.srcs[0][0].data_ptr(), ldy=cb, bn_scale=None, bn_shift=None, bn_mean=None,
-                                                   bn_rstd=None, bn_c1=None, bn_c2=None, x=saT['x0'], ldx=saT['c0'], w_dgrad=rt.packed[upl.name]['dgrad'].data_ptr(),
-                                                   w_npad=rup(rT.c, 32), dx=saT['x0'], lddx=rT.c, dw=rt.gptr(upl.name + '/kernel'), cin=rT.c, cout=cb, n=n,
-                                                   h=rT.h, w_=rT.w, dtype=dt)
-                        if saT['x1'] is None and saT['c0'] == rT.c == rt.packed[upl.name]['cin'] and lib.satcv_convt_bwd_fused_workspace(C.byref(probe)) > 0:
-                            ctbf = dict(g=gptr_ + ca * es, ldg=ctot, yup=rb.srcs[0][0].data_ptr(), ldy=cb, aff=aff, aoff=ca, ctot=ctot)
-                            sec['dy1'] = None
-                    ent = None
-                    if (bn not in self.frozen and ta.id not in gact and any(cn.op == 'pool' for cn in consumers[ta.id])
-                            and len([cn for cn in consumers[ta.id] if cn.op != 'pool']) == 1 and ta.channels == ca):
-                        ent = act_sums_for(ta)
-                    if ent is not None:
-                        sec.update(sk_sums=_fp(ent['buf']), sk_sums_ld=ca)
-                        ent['parts'].add('skip')
-                    r_, f_, a_ = bn_bwd_steps(gptr_, ctot, None, 0, 1, ra.srcs[0][0].data_ptr(), ca, aff, 0, sums, 0, ctot, ctot, hh, ww,
-                                              dskip.data_ptr(), ca, None, rt.gptr(bn + '/gamma'), rt.gptr(bn + '/beta'), frozen=bn in self.frozen,
-                                              second=sec)
-                    if ent is not None:
-                        a_.label += ' +skipsums'
-                    if ctbf is not None:
-                        a_.label += ' (skip half)'
-                        a_.work = dict(kind='bn_bwd_apply', px=n * hh * ww, c=ca, esize=es)
-                        ctbf['coef'] = a_.coef
-                    self.bwd += [f_, a_] if (pre is not None or r_ is None) else [r_, f_, a_]
-                    gact[ta.id] = (dskip, 0, ca)
-                    self.dbg['dskip:' + bn] = dskip
-                    self.dbg['du:' + bn] = du
-                    graw[tb.id] = ctbf if ctbf is not None else du
-                    continue
-                ra_, fa_, aa_ = bn_bwd_steps(gptr_, ctot, None, 0, 1, ra.srcs[0][0].data_ptr(), ca, aff, 0, sums, 0, ctot, ca, hh, ww,
-                                             dskip.data_ptr(), ca, None, rt.gptr(bn + '/gamma'), rt.gptr(bn + '/beta'), frozen=bn in self.frozen)
-                rb_, fb_, ab_ = bn_bwd_steps(gptr_ + ca * es, ctot, None, 0, 1, rb.srcs[0][0].data_ptr(), cb, aff, ca, sums, ca, ctot, cb,
-                                             hh, ww, du.data_ptr(), cb, rt.gptr(upl.name + '/bias') if (tb.node.op == 'convT' and BIAS_NOISE) else None,
-                                             rt.gptr(bn + '/gamma') + 4 * ca, rt.gptr(bn + '/beta') + 4 * ca, frozen=bn in self.frozen)
-                self.bwd += [fa_, fb_, aa_, ab_] if (pre is not None or ra_ is None) else [ra_, rb_, fa_, fb_, aa_, ab_]
-                # the skip is the activated output of an encoder conv_batch_act block
-                gact[ta.id] = (dskip, 0, ca)
-                self.dbg['dskip:' + bn] = dskip
-                self.dbg['du:' + bn] = du
-                graw[tb.id] = du
-            elif op == 'convT':
-                tin, tout = node.inputs[0], node.outputs[0]
-                du = graw.get(tout.id)
-                if du is None:
-                    continue
-                lay, r, cout, f = node.layer, cx['r'], cx['cout'], cx['f']
-                pk = rt.packed[lay.name]
-                if isinstance(du, dict):
-                    # fused: BatchNorm-backward apply of the `up` channels + data gradient + weight gradient (csrc/convt_bwd_fused.hip)
-                    cb_, sa = du, self._src_args(r)
-                    cinp = r.c
-                    gin = self._z(n, r.h, r.w, cinp)
-                    af_, ao_, ct_ = cb_['aff'], cb_['aoff'], cb_['ctot']
-                    fz = ops.make_ctbf_desc(g=cb_['g'], ldg=cb_['ldg'], yup=cb_['yup'], ldy=cb_['ldy'], bn_scale=_fp(af_['scale'], ao_), bn_shift=_fp(af_['shift'], ao_),
-                                            bn_mean=_fp(af_['mean'], ao_), bn_rstd=_fp(af_['rstd'], ao_), bn_c1=_fp(cb_['coef'], ao_), bn_c2=_fp(cb_['coef'], ct_ + ao_),
-                                            x=sa['x0'], ldx=sa['c0'], in_scale=sa['in_scale'], in_shift=sa['in_shift'], in_relu=sa['in_relu'],
-                                            w_dgrad=pk['dgrad'].data_ptr(), w_npad=rup(cinp, 32), dx=gin.data_ptr(), lddx=cinp, dw=rt.gptr(lay.name + '/kernel'),
-                                            cin=cinp, cout=cout, n=n, h=r.h, w_=r.w, dtype=dt)
-                    bt = bst_target(tin) if (sa['in_relu'] and sa['in_scale'] is not None and not act_form_unfit(tin)) else None
-                    if bt is not None and bt[1] == cinp and bt[0].get('relu', 0) == 1:
-                        sums_below = self._z(STAT_ROWS, 2, cinp, dtype=torch.float64)
-                        fz.bst_sums, fz.bst_sums_ld, fz.bst_mean, fz.bst_rstd = _fp(sums_below), cinp, bt[0]['mean'], bt[0]['rstd']
-                        fused[tin.id] = sums_below
-                    nbc = lib.satcv_convt_bwd_fused_workspace(C.byref(fz))
-                    if nbc <= 0:
-                        raise RuntimeError('convt_bwd_fused: the probe accepted this shape, the final descriptor did not')
-                    wsc = self._z(max(nbc // 4, 1), dtype=torch.float32)
-                    fz.workspace, fz.workspace_bytes = wsc.data_ptr(), nbc
-                    self.keep.append(fz)
-                    cstep = lambda st, fz=fz: check(lib.satcv_convt_bwd_fused(C.byref(fz), st))
-                    cstep.label = f"convt_bwd_fused n{n} {r.h}x{r.w} {cinp}<-4x{cout}{' +bnred' if fz.bst_sums else ''}"
-                    cstep.work = dict(kind='convt_bwd_fused', px=n * r.h * r.w, cin=cinp, cout=cout, esize=es)
-                    self.bwd.append(cstep)
-                    gact[tin.id] = (gin, 0, cinp)
-                    self.dbg['dx:' + lay.name] = gin
-                    continue
-                wstep = wgrad_step(r, du.data_ptr(), cout, lay, pk['cin'], cout, r.h, r.w, 1, 1, f=f)
-                if not WGRAD_LATE:
-                    self.bwd.append(wstep)
-                cinp = r.c
-                gin = self._z(n, r.h, r.w, cinp)
-                self.bwd.append(dgrad_step(tin, x0=du.data_ptr(), c0=cout, w=pk['dgrad'].data_ptr(), y=gin.data_ptr(), ldy=cinp, n=n, h=r.h,
-                                           w_=r.w, cout=cinp, cout_pad=rup(cinp, 32), kh=1, kw=1, dil=1, mode_in=1, f=f, dtype=dt))
-                if WGRAD_LATE:
-                    self.bwd.append(wstep)
-                gact[tin.id] = (gin, 0, cinp)
-                self.dbg['dx:' + lay.name] = gin
-        if prev_node is not None:
-            grads_ready(prev_node)
-        if ws_need:
-            ws = self._z(max(ws_need // 4, 1), dtype=torch.float32)
-            for d in wdescs:
-                if not d.defer_reduce:
-                    d.workspace, d.workspace_bytes = ws.data_ptr(), ws_need
-        if fused_ws_need:
-            wsf = self._z(max(fused_ws_need // 4, 1), dtype=torch.float32)
-            for d in fdescs:
-                if not d.defer_reduce:
-                    d.workspace, d.workspace_bytes = wsf.data_ptr(), fused_ws_need
-        flush_reduces(force=True)
-        if rgroups:
-            from ._lib import ReduceJob
-            own = [d for g in rgroups for d, _ in g['items']]
-            arena = self._z(max(sum((d._own_ws + 255) // 256 * 256 for d in own) // 4, 1), dtype=torch.float32)
-            off = 0
-            for d in own:
-                d.workspace, d.workspace_bytes = arena.data_ptr() + off, d._own_ws
-                off += (d._own_ws + 255) // 256 * 256
-            for g in rgroups:
-                jobs, prefix, tot = [], [], 0
-                for d, kind in g['items']:
-                    j = ReduceJob()
-                    check((lib.satcv_conv2d_wgrad_reduce_job if kind == 'w' else lib.satcv_conv2d_bwd_fused_reduce_job)(C.byref(d), C.byref(j)))
-                    prefix.append(tot)
-                    tot += int(lib.satcv_reduce_job_items(C.byref(j)))
-                    jobs.append(j)
-                arr = (ReduceJob * len(jobs))(*jobs)
-                g['tab'] = dict(jobs=torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(rt.dev),
-                                prefix=torch.tensor(prefix, dtype=torch.int64, device=rt.dev), n=len(jobs), total=tot)
-        if self.side is not None:
-            evj = torch.cuda.Event()
-
-            evj2 = torch.cuda.Event()
-
-            def join(st, evj=evj, evj2=evj2):          # the optimizer (main stream) must see every weight gradient
-                evj.record(self.side)
-                torch.cuda.current_stream().wait_event(evj)
-                if self.rstream is not None:
-                    evj2.record(self.rstream)
-                    torch.cuda.current_stream().wait_event(evj2)
-            self.bwd.append(join)
+    def _build_backward(self, consumers, vals, ctx):
+        _BackwardLowering(self, consumers, vals, ctx).run()
 
     # -- execution
     # (a training plan lets EVERY eligible deep 3x3 launch -- also the data gradients that carry no statistics -- run on the 16x16x32 tile;
@@ -1584,3 +452,1237 @@ class Plan:
     def run_backward(self, st):
         self._run(self.bwd, st)
 
+
+class _ForwardLowering:
+    """Lowers model.nodes into plan.fwd: two preparation passes over the concatenations, then one method per op."""
+    OPS = ('input', 'cba', 'concat', 'pool', 'convT', 'concat_bn_relu', 'maxpool', 'raw', 'add_relu', 'upsample_head', 'dropout', 'head', 'classes')
+
+    def __init__(self, plan):
+        self.plan, self.rt, self.m, self.n = plan, plan.rt, plan.rt.model, plan.n
+        self.dt, self.es, self.training = plan.rt.dtype, plan.rt.esize, plan.training
+        # the plan's lists and helpers under the names the lowering code uses
+        self.fwd, self.keep, self.outputs = plan.fwd, plan.keep, plan.outputs
+        self._z, self._dims, self._conv_step, self._src_args = plan._z, plan._dims, plan._conv_step, plan._src_args
+        self._bn_forward, self._materialize = plan._bn_forward, plan._materialize
+        self.consumers = defaultdict(list)         # tensor id -> the nodes that read it
+        for node in self.m.nodes:
+            for t in node.inputs:
+                self.consumers[t.id].append(node)
+        self.vals = {}                             # tensor id -> TRef (stored form: raw + pending affine, or final)
+        self.acts = {}                             # tensor id -> TRef of its materialised activation
+        self.ctx = {}                              # node id -> what the backward lowering needs of the node (plan.node_ctx)
+        self.sinks = {}                            # tensor id -> (statistics rows, channel offset, row stride) of the decoder concat BatchNorm it feeds
+        self.cat_stats = {}                        # concat_bn_relu node id -> its statistics rows
+        self.slots = {}                            # tensor id -> channel slice of a shared raw concatenation (ASPP branches)
+        self.actslots = {}                         # tensor id -> (tensor, channel offset, channel stride) of a shared ACTIVATED concatenation
+        self.order = {id(nd): i for i, nd in enumerate(self.m.nodes)}
+        self.fused_join = {}                       # add_relu node id -> the shortcut tensor its sum was written into
+        self.folded_plain = {}                     # tensor id -> a conv -> BatchNorm branch stored normalised, waiting for the join's other branch
+
+    def run(self):
+        self._prepare_concat_stats()
+        self._prepare_concat_slots()
+        for node in self.m.nodes:
+            if node.op not in self.OPS:
+                raise NotImplementedError(f'op {node.op}')
+            getattr(self, node.op)(node)
+
+    def _prepare_concat_stats(self):
+        for node in self.m.nodes:
+            if node.op == 'concat_bn_relu':
+                a, b = node.inputs
+                ctot = a.channels + b.channels
+                st = self._z(STAT_ROWS, 2, ctot, dtype=torch.float64)
+                self.cat_stats[id(node)] = st
+                self.sinks[a.id] = (st, 0, ctot)
+                self.sinks[b.id] = (st, a.channels, ctot)
+
+    def _prepare_concat_slots(self):
+        n, consumers, sinks = self.n, self.consumers, self.sinks
+        for node in self.m.nodes:
+            if node.op != 'concat':
+                continue
+            if all(t.node.op == 'cba' and len(consumers[t.id]) > 1 for t in node.inputs):
+                # concatenation of ACTIVATED encoder outputs that are also pooled (Siamese skips): the pool kernels write
+                # their activation straight into channel slices of one tensor
+                ctot = sum(t.channels for t in node.inputs)
+                hh, ww = self._dims(node.inputs[0])
+                shared = self._z(n, hh, ww, ctot)
+                off = 0
+                for t in node.inputs:
+                    self.actslots[t.id] = (shared, off, ctot)
+                    if node.outputs[0].id in sinks:                      # statistics for the decoder's concat BatchNorm
+                        st_, so_, sl_ = sinks[node.outputs[0].id]
+                        sinks[t.id] = (st_, so_ + off, sl_)
+                    off += t.channels
+                self.ctx[id(node)] = dict(act=shared, ctot=ctot)
+                continue
+            if not all(t.node.op == 'cba' and len(consumers[t.id]) == 1 for t in node.inputs):
+                raise NotImplementedError('concatenate is supported for conv_batch_act outputs consumed only by the concat (ASPP)')
+            ctot = sum(t.channels for t in node.inputs)
+            hh, ww = self._dims(node.inputs[0])
+            yshared = self._z(n, hh, ww, ctot)
+            stshared = self._z(STAT_ROWS, 2, ctot, dtype=torch.float64) if self.training else None
+            aff = dict(scale=self._z(ctot, dtype=torch.float32), shift=self._z(ctot, dtype=torch.float32),
+                       mean=self._z(ctot, dtype=torch.float32), rstd=self._z(ctot, dtype=torch.float32))
+            off = 0
+            for t in node.inputs:
+                self.slots[t.id] = dict(y=yshared, off=off, ctot=ctot, stats=stshared, aff=aff)
+                off += t.channels
+            self.ctx[id(node)] = dict(y=yshared, ctot=ctot, aff=aff)
+
+    def input(self, node):
+        p, n, dt = self.plan, self.n, self.dt
+        t = node.outputs[0]
+        cp = rup(t.channels, 16)
+        x = self._z(n, p.h, p.w, cp)
+        xin = self._z(n, p.h, p.w, t.channels, dtype=torch.float32)
+        p.x_f32 = xin
+        p.x_inputs.append(xin)
+        p.x_by_tid[t.id] = xin
+        npix = n * p.h * p.w
+        cc = t.channels
+        self.fwd.append(lambda st, xin=xin, x=x, npix=npix, cc=cc, cp=cp, tid=t.id: check(lib.satcv_ingest_nhwc(
+            p.x_src.get(tid) or xin.data_ptr(), x.data_ptr(), npix, cc, cp, dt, st)))
+        self.vals[t.id] = TRef([(x, cp)], n, p.h, p.w)
+
+    def cba(self, node):
+        rt, n, dt, es = self.rt, self.n, self.dt, self.es
+        tin, tout = node.inputs[0], node.outputs[0]
+        r = self.vals[tin.id]
+        lay = node.layer
+        pk = rt.packed[lay.name]
+        cout = tout.channels
+        if cout % 16:
+            raise NotImplementedError(f'{lay.name}: filters must be a multiple of 16 (got {cout})')
+        if r.c != pk['cin_pad']:
+            raise ValueError(f'{lay.name}: input has {r.c} stored channels, kernel expects {pk["cin_pad"]}')
+        k, dil = node.attrs['k'], node.attrs['dil']
+        stride, relu_out = node.attrs.get('stride', 1), node.attrs.get('relu', True)
+        hin, win = r.h, r.w
+        if stride > 1:
+            if self.training:
+                raise NotImplementedError('strided convolutions are inference-only (DeepLab backbone)')
+            r = TRef(r.srcs, r.n, (hin - 1) // stride + 1, (win - 1) // stride + 1, r.affine, r.relu)   # output grid
+        sl = self.slots.get(tout.id)
+        if not node.attrs.get('bn', True):
+            # plain Conv2D + bias, no normalisation (atrous CNN family): consumers read the stored values as they are
+            if sl is not None or stride > 1:
+                raise NotImplementedError('a convolution without BatchNormalization as a concatenation branch / with a stride')
+            y = self._z(n, r.h, r.w, cout)
+            self.fwd.append(self._conv_step(w=pk['fwd'].data_ptr(), bias=rt.pptr(lay.name + '/bias'), y=y.data_ptr(), ldy=cout, n=n, h=r.h, w_=r.w,
+                                            cout=cout, cout_pad=rup(cout, 32), kh=k, kw=k, dil=dil, dtype=dt, **self._src_args(r)))
+            self.vals[tout.id] = TRef([(y, cout)], n, r.h, r.w)
+            self.ctx[id(node)] = dict(r=r, y=y, yoff=0, ldy=cout, aff=None, aoff=0, cout=cout, k=k, dil=dil)
+            return
+        strided = dict(stride=stride, hin=hin if stride > 1 else 0, win=win if stride > 1 else 0)
+        fold = self._residual_fold(node, r, stride) if (sl is None and not relu_out) else None
+        if fold is not None:
+            fold_args, sb = fold
+            be = self._z(cout, dtype=torch.float32)
+            aff = self._bn_forward(lay.bn_name, None, cout, 0, cout, n * r.h * r.w, node.attrs.get('bn_updates', 1),
+                                   conv_bias=rt.pptr(lay.name + '/bias'), bias_eff=_fp(be))
+            self.fwd.append(self._conv_step(w=pk['fwd'].data_ptr(), bias=_fp(be), out_scale=_fp(aff['scale']), ldy=cout,
+                                            n=n, h=r.h, w_=r.w, cout=cout, cout_pad=rup(cout, 32), kh=k, kw=k, dil=dil, dtype=dt,
+                                            **strided, **fold_args, **self._src_args(r)))
+            self.vals[tout.id] = TRef([(sb, cout)], n, r.h, r.w)
+            self.ctx[id(node)] = dict(r=r, y=sb, yoff=0, ldy=cout, aff=None, aoff=0, cout=cout, k=k, dil=dil)
+            return
+        if sl is None:
+            y = self._z(n, r.h, r.w, cout)
+            stats = self._z(STAT_ROWS, 2, cout, dtype=torch.float64) if self.training else None
+            yoff, ldy, aoff, aff_in = 0, cout, 0, None
+        else:           # branch of a concatenation: write into the channel slice of the shared tensor
+            y, stats, yoff, ldy, aoff, aff_in = sl['y'], sl['stats'], sl['off'], sl['ctot'], sl['off'], sl['aff']
+        self.fwd.append(self._conv_step(w=pk['fwd'].data_ptr(), bias=rt.pptr(lay.name + '/bias'), y=y.data_ptr() + yoff * es, ldy=ldy,
+                                        stats=_fp(stats, aoff), stats_ld=ldy, n=n, h=r.h, w_=r.w, cout=cout, cout_pad=rup(cout, 32),
+                                        kh=k, kw=k, dil=dil, dtype=dt, **strided, **self._src_args(r)))
+        aff = self._bn_forward(lay.bn_name, stats, ldy, aoff, cout, n * r.h * r.w, node.attrs.get('bn_updates', 1), aff_in, aoff)
+        if sl is None:
+            self.vals[tout.id] = TRef([(y, cout)], n, r.h, r.w, affine=aff, relu=relu_out)
+        self.ctx[id(node)] = dict(r=r, y=y, yoff=yoff, ldy=ldy, aff=aff, aoff=aoff, cout=cout, k=k, dil=dil)
+
+    def _residual_fold(self, node, r, stride):
+        """inference, residual join (ResNet bottleneck: ReLU(BN(conv) + shortcut), utils-free build-defined DeepLab backbone): when this
+        block's output only feeds the join and nothing reads the shortcut afterwards, the convolution applies its own
+        BatchNormalization in the epilogue (out_scale / bias_eff from the batched affine launch) and writes
+        ReLU(shortcut + result) IN PLACE over the shortcut (accumulate = 2): no add_relu launch, no third tensor
+        (20 launches of ~10 us on a single 512 x 512 tile, 11 % of the kernel time at batch 16; SATCV_FUSE_RESIDUAL=0: separate).
+        Returns (the launch's y / accumulate arguments, the tensor it writes), or None when the join stays a launch of its own."""
+        consumers, vals = self.consumers, self.vals
+        tout = node.outputs[0]
+        cout, cons = tout.channels, consumers[tout.id]
+        if self.training or not FUSE_RESIDUAL or len(cons) != 1 or cons[0].op != 'add_relu' or tout not in cons[0].inputs:
+            return None
+        join = cons[0]
+        tsc = join.inputs[1] if join.inputs[0] is tout else join.inputs[0]      # the join's other addend
+        rs_ = vals.get(tsc.id)
+        if rs_ is None:
+            # (B) the other addend is a conv -> BatchNorm branch that runs LATER in the list (the projection shortcut of a stage's
+            # first block): store this branch normalised (its BatchNorm in the epilogue, nothing pending), the later branch
+            # then adds itself in place (A)
+            if (stride == 1 and tsc.node is not None and tsc.node.op == 'cba' and len(consumers[tsc.id]) == 1
+                    and tsc.node.attrs.get('bn', True) and not tsc.node.attrs.get('relu', True) and tsc.channels == cout):
+                y = self._z(self.n, r.h, r.w, cout)
+                self.folded_plain[tout.id] = y
+                return dict(y=y.data_ptr(), accumulate=0), y
+            return None
+        # (A) the other addend is final: a plain activated tensor written by an earlier join, or a branch stored normalised (B)
+        src_ok = (tsc.id in self.folded_plain) or (tsc.node is not None and tsc.node.op == 'add_relu' and stride == 1)
+        if (src_ok and not rs_.affine and len(rs_.srcs) == 1 and rs_.srcs[0][1] == cout and rs_.srcs[0][0].shape[-1] == cout
+                and (rs_.h, rs_.w) == (r.h, r.w)
+                and all(cn is join or self.order[id(cn)] < self.order[id(node)] for cn in consumers[tsc.id])):
+            sb = rs_.srcs[0][0]
+            self.fused_join[id(join)] = sb
+            return dict(y=sb.data_ptr(), accumulate=2), sb
+        return None
+
+    def concat(self, node):
+        cx = self.ctx[id(node)]
+        hh, ww = self._dims(node.inputs[0])
+        if 'act' in cx:
+            self.vals[node.outputs[0].id] = TRef([(cx['act'], cx['ctot'])], self.n, hh, ww)
+        else:
+            self.vals[node.outputs[0].id] = TRef([(cx['y'], cx['ctot'])], self.n, hh, ww, affine=cx['aff'], relu=True)
+
+    def pool(self, node):
+        p, n, dt = self.plan, self.n, self.dt
+        tin, tout = node.inputs[0], node.outputs[0]
+        r = self.vals[tin.id]
+        f = node.attrs['f']
+        if not (r.affine and len(r.srcs) == 1):
+            raise NotImplementedError('max-pool expects the output of a conv_batch_act block')
+        c = r.c
+        if r.h % f or r.w % f:
+            raise ValueError(f'input {p.h}x{p.w} is not divisible by the model downsampling (a {r.h}x{r.w} map meets a {f}x{f} pool)')
+        pooled = self._z(n, r.h // f, r.w // f, c)
+        others = [cn for cn in self.consumers[tin.id] if cn is not node]
+        if others:
+            self.acts[tin.id] = self._materialize(tin, r, f, pooled, self.sinks.get(tin.id), self.actslots.get(tin.id))
+        else:
+            (y, _) = r.srcs[0]
+            a = r.affine
+            hh, ww = r.h, r.w
+            self.fwd.append(lambda st, y=y, a=a, pooled=pooled, hh=hh, ww=ww, c=c, f=f: check(lib.satcv_bn_relu_pool(
+                y.data_ptr(), _fp(a['scale']), _fp(a['shift']), None, 0, pooled.data_ptr(), None, 0, n, hh, ww, c, f, dt, st)))
+        self.vals[tout.id] = TRef([(pooled, c)], n, r.h // f, r.w // f)
+        self.ctx[id(node)] = dict(f=f)
+
+    def convT(self, node):
+        rt, n = self.rt, self.n
+        tin, tout = node.inputs[0], node.outputs[0]
+        r = self.vals[tin.id]
+        if len(r.srcs) != 1:
+            raise NotImplementedError('transposed conv on a concatenated input')
+        lay = node.layer
+        pk = rt.packed[lay.name]
+        cout, f = tout.channels, node.attrs['f']
+        if cout % 16:
+            raise NotImplementedError(f'{lay.name}: transposed-conv filters must be a multiple of 16')
+        u = self._z(n, r.h * f, r.w * f, cout)
+        sink = self.sinks.get(tout.id) if self.training else None
+        self.fwd.append(self._conv_step(w=pk['fwd'].data_ptr(), bias=rt.pptr(lay.name + '/bias'), y=u.data_ptr(), ldy=cout,
+                                        stats=_fp(sink[0], sink[1]) if sink else None, stats_ld=sink[2] if sink else 0,
+                                        n=n, h=r.h, w_=r.w, cout=f * f * cout, cout_pad=rup(f * f * cout, 32), kh=1, kw=1, dil=1,
+                                        mode_out=1, f=f, cstat=cout, dtype=self.dt, **self._src_args(r)))
+        self.vals[tout.id] = TRef([(u, cout)], n, r.h * f, r.w * f)
+        self.ctx[id(node)] = dict(r=r, u=u, cout=cout, f=f)
+
+    def concat_bn_relu(self, node):
+        vals, acts = self.vals, self.acts
+        ta, tb = node.inputs
+        tout = node.outputs[0]
+        if ta.id not in acts:
+            ra0 = vals[ta.id]
+            acts[ta.id] = self._materialize(ta, ra0, 1, None, self.sinks.get(ta.id)) if ra0.affine else ra0
+        ra, rb = acts[ta.id], vals[tb.id]
+        if (ra.h, ra.w) != (rb.h, rb.w):
+            raise ValueError(f'concatenation of a {ra.h}x{ra.w} skip with a {rb.h}x{rb.w} up-sampled map: the input size must be divisible by the model downsampling')
+        if rb.affine or len(rb.srcs) != 1 or len(ra.srcs) != 1:
+            raise NotImplementedError('concat+BN expects (activated skip, transposed-conv output)')
+        ca, cb = ra.c, rb.c
+        st = self.cat_stats[id(node)]
+        aff = self._bn_forward(node.layer.name, st, ca + cb, 0, ca + cb, self.n * ra.h * ra.w, 1)
+        vals[tout.id] = TRef([ra.srcs[0], rb.srcs[0]], self.n, ra.h, ra.w, affine=aff, relu=True)
+        self.ctx[id(node)] = dict(ra=ra, rb=rb, aff=aff, ca=ca, cb=cb)
+
+    def maxpool(self, node):
+        n, dt = self.n, self.dt
+        tin, tout = node.inputs[0], node.outputs[0]
+        r = self.vals[tin.id]
+        if r.affine:
+            r = self._materialize(tin, r)
+        (src, c) = r.srcs[0]
+        kk, ss, pp = node.attrs['k'], node.attrs['s'], node.attrs['pad']
+        ho, wo = (r.h + 2 * pp - kk) // ss + 1, (r.w + 2 * pp - kk) // ss + 1
+        out = self._z(n, ho, wo, c)
+        self.fwd.append(lambda st, src=src, out=out, hh=r.h, ww=r.w, c=c, kk=kk, ss=ss, pp=pp: check(lib.satcv_maxpool(
+            src.data_ptr(), out.data_ptr(), n, hh, ww, c, kk, ss, pp, dt, st)))
+        self.vals[tout.id] = TRef([(out, c)], n, ho, wo)
+
+    def raw(self, node):
+        # the convolution output BEFORE its BatchNormalization (build_acnn_layers feeds it to the next Conv2D, utils/model_tools.py:930)
+        r = self.vals[node.inputs[0].id]
+        if len(r.srcs) != 1 or node.inputs[0].node.op != 'cba':
+            raise NotImplementedError('raw view of a tensor that is not a single convolution output')
+        self.vals[node.outputs[0].id] = TRef(r.srcs, self.n, r.h, r.w)
+
+    def add_relu(self, node):
+        n, dt, vals, acts = self.n, self.dt, self.vals, self.acts
+        ty, tsc = node.inputs
+        tout = node.outputs[0]
+        if id(node) in self.fused_join:            # written in place by the block's last convolution (_residual_fold)
+            sb = self.fused_join[id(node)]
+            c = sb.shape[-1]
+            vals[tout.id] = TRef([(sb, c)], n, vals[ty.id].h, vals[ty.id].w)
+            self.ctx[id(node)] = dict(out=sb, c=c, h=vals[ty.id].h, w=vals[ty.id].w)
+            return
+        ry, rs = vals[ty.id], vals[tsc.id]
+        if rs.affine and rs.relu and len(rs.srcs) == 1:       # shortcut = ReLU(BN(conv)) kept in raw form: activate it once
+            if tsc.id not in acts:
+                acts[tsc.id] = self._materialize(tsc, rs)
+            rs = acts[tsc.id]
+        if len(ry.srcs) != 1 or len(rs.srcs) != 1 or ry.relu or (rs.affine and rs.relu):
+            raise NotImplementedError('residual join expects linear (BN without ReLU) branches')
+        (yb, c), (sb, c2) = ry.srcs[0], rs.srcs[0]
+        assert c == c2 and (ry.h, ry.w) == (rs.h, rs.w)
+        out = self._z(n, ry.h, ry.w, c)
+        ya, sa = ry.affine, rs.affine
+        npx = n * ry.h * ry.w
+        self.fwd.append(lambda st, yb=yb, sb=sb, out=out, ya=ya, sa=sa, npx=npx, c=c: check(lib.satcv_add_act(
+            yb.data_ptr(), _fp(ya['scale']) if ya else None, _fp(ya['shift']) if ya else None, sb.data_ptr(),
+            _fp(sa['scale']) if sa else None, _fp(sa['shift']) if sa else None, 1, out.data_ptr(), npx, c, dt, st)))
+        vals[tout.id] = TRef([(out, c)], n, ry.h, ry.w)
+        self.ctx[id(node)] = dict(out=out, c=c, h=ry.h, w=ry.w)
+
+    def upsample_head(self, node):
+        n = self.n
+        tin, tout = node.inputs[0], node.outputs[0]
+        lg = self.outputs[tin.id]                         # fp32 logits written by the linear head
+        hctx = self.ctx[id(tin.node)]
+        f = node.attrs['factor']
+        act = 0 if node.attrs['activation'] == 'softmax' else 1
+        hh, ww, ncls = hctx['r'].h, hctx['r'].w, hctx['ncls']
+        probs = self._z(n, hh * f, ww * f, ncls, dtype=torch.float32)
+        classes = self._z(*((n, hh * f, ww * f) if act == 0 else (n, hh * f, ww * f, ncls)), dtype=torch.int32)
+        th = float(node.attrs.get('thresh', 0.5))
+        self.fwd.append(lambda st, lg=lg, probs=probs, classes=classes, hh=hh, ww=ww, ncls=ncls, f=f, act=act, th=th: check(
+            lib.satcv_upsample_head(lg.data_ptr(), n, hh, ww, ncls, f, act, th, probs.data_ptr(), classes.data_ptr(), st)))
+        self.outputs[tout.id] = probs
+        self.ctx[id(node)] = dict(classes=classes)
+        if self.training:
+            raise NotImplementedError('the up-sampling head is inference-only')
+
+    def dropout(self, node):
+        p, n, dt, es, vals = self.plan, self.n, self.dt, self.es, self.vals
+        tin, tout = node.inputs[0], node.outputs[0]
+        r = vals[tin.id]
+        if not self.training:                     # identity at inference (Keras semantics)
+            vals[tout.id] = r
+            if tin.id in self.acts:
+                self.acts[tout.id] = self.acts[tin.id]
+            return
+        ctot = r.c
+        spatial = node.attrs['spatial']
+        hw = r.h * r.w
+        mask = self._z(*((n, ctot) if spatial else (n * hw, ctot)), dtype=torch.float32)
+        out = self._z(n, r.h, r.w, ctot)
+        rate = float(node.attrs['rate'])
+        slot = len(p.dropouts)
+        p.dropouts.append(dict(mask=mask, node=node))
+        cnt = mask.numel()
+
+        def gen(st, mask=mask, rate=rate, cnt=cnt, slot=slot):
+            # a fresh mask every step: counter = (step, dropout slot)
+            check(lib.satcv_dropout_mask(p.rt.dropout_seed, (p.step_count << 8) + slot, rate, cnt, mask.data_ptr(), st))
+        self.fwd.append(gen)
+        off = 0
+        mode = 0 if spatial else 1
+        for (src, cs) in r.srcs:             # dual-source (concat) inputs: one launch per source / channel slice
+            a = r.affine
+            self.fwd.append(lambda st, src=src, cs=cs, off=off, a=a, rl=1 if r.relu else 0, mask=mask, ctot=ctot, mode=mode, out=out,
+                            hw=hw: check(lib.satcv_dropout_apply(
+                src.data_ptr(), cs, _fp(a['scale'], off) if a else None, _fp(a['shift'], off) if a else None, rl,
+                _fp(mask, off), ctot, mode, out.data_ptr() + off * es, ctot, n, hw, cs, dt, st)))
+            off += cs
+        vals[tout.id] = TRef([(out, ctot)], n, r.h, r.w)
+        self.ctx[id(node)] = dict(mask=mask, spatial=spatial, ctot=ctot, hw=hw, r=r)
+
+    def head(self, node):
+        rt, n = self.rt, self.n
+        tin, tout = node.inputs[0], node.outputs[0]
+        r = self.vals[tin.id]
+        if len(r.srcs) != 1:
+            raise NotImplementedError('head on concatenated input')
+        lay = node.layer
+        ncls = tout.channels
+        act = {'softmax': 0, 'sigmoid': 1, 'linear': 2}[node.attrs['activation']]
+        (y, c) = r.srcs[0]
+        npix = n * r.h * r.w
+        probs = self._z(n, r.h, r.w, ncls, dtype=torch.float32)
+        classes = self._z(*((n, r.h, r.w) if act != 1 else (n, r.h, r.w, ncls)), dtype=torch.int32)
+        hd = ops.make_head_desc(x=y.data_ptr(), ldx=c, cin=c, w=rt.pptr(lay.name + '/kernel'), b=rt.pptr(lay.name + '/bias'),
+                                ncls=ncls, activation=act, npix=npix, dtype=self.dt,
+                                in_scale=_fp(r.affine['scale']) if r.affine else None,
+                                in_shift=_fp(r.affine['shift']) if r.affine else None,
+                                thresh=node.attrs.get('thresh', 0.5), probs=probs.data_ptr(), classes=classes.data_ptr())
+        self.keep.append(hd)
+        self.fwd.append(lambda st, hd=hd: check(lib.satcv_head_fwd(C.byref(hd), st)))
+        self.outputs[tout.id] = probs
+        self.ctx[id(node)] = dict(r=r, probs=probs, classes=classes, act=act, ncls=ncls)
+        self.plan.head = self.ctx[id(node)]
+        self.plan.head_node = node
+
+    def classes(self, node):
+        hctx = self.ctx[id(node.inputs[0].node)]
+        if 'thresh' in node.attrs:
+            node.inputs[0].node.attrs['thresh'] = node.attrs['thresh']
+        self.outputs[node.outputs[0].id] = hctx['classes']
+
+
+class _SlabSums:
+    """Where the slab sums of the weight-gradient and fused launches run, and the early optimizer step: the three opt-in schedulers
+    (switches.py: defer_reduce, reduce_stream, early_opt; DESIGN.md section 6 holds their measurements).  With all three off every launch
+    sums its slabs itself from the shared workspace and this object emits nothing.
+      defer: deferred, batched slab sums (satcv_reduce_slabs_batched; otherwise one sum launch behind every weight-gradient launch): a
+        deferring launch keeps a workspace of its own; the sums run in groups, one launch per ~16 MiB of finished gradients (the bucket
+        size of the gradient exchange, whose checkpoints move to the group boundaries)
+      red3: the slab sum of a side-stream weight gradient on a THIRD stream, behind an event of its launch; with a workspace of its own
+        per layer the next weight gradient does not have to wait for the sum of the previous one"""
+
+    def __init__(self, plan):
+        self.plan = plan
+        self.defer = switches.read('defer_reduce') != 0
+        self.red3 = (not self.defer) and plan.side is not None and switches.read('reduce_stream')
+        plan.rstream = torch.cuda.Stream() if self.red3 else None
+        plan._last_red_ev = None
+        self.pending = []                   # (descriptor, 'w' | 'f', gradient bytes) of launches whose sum has not been scheduled yet
+        self.groups = []                    # {'items': [(desc, kind)], 'tab': device job table, filled once the workspaces are assigned}
+
+    def own_workspace(self, d, kind, nb, grad_bytes, eligible):
+        """a weight-gradient ('w') or fused ('f') descriptor was made: True when it keeps a workspace of `nb` bytes of its own and its
+        slab sum is scheduled here, False when it sums its slabs itself from the workspace all such launches share"""
+        if not eligible or not (self.defer or (self.red3 and kind == 'w')):
+            return False
+        d.defer_reduce = 1
+        d._own_ws = nb
+        if self.defer:
+            self.pending.append((d, kind, grad_bytes))
+        else:
+            self.groups.append({'items': [(d, kind)], 'tab': None})       # (a one-job table, built with the others once the workspaces are assigned)
+        return True
+
+    def behind_wgrad(self, run, d):
+        """the side-stream step of weight-gradient launch d; red3: followed by its slab sum on the third stream"""
+        if not (self.red3 and d.defer_reduce):
+            return run
+        p, grp = self.plan, self.groups[-1]
+        evw, evr = torch.cuda.Event(), torch.cuda.Event()
+
+        def run3(st):
+            run(st)
+            t = grp['tab']
+            evw.record(p.side)
+            p.rstream.wait_event(evw)
+            check(lib.satcv_reduce_slabs_batched(t['jobs'].data_ptr(), t['prefix'].data_ptr(), t['n'], t['total'], C.c_void_p(p.rstream.cuda_stream)))
+            evr.record(p.rstream)
+            p._last_red_ev = evr
+        return run3
+
+    def _flush(self, force=False):
+        """schedule the batched slab sum of the launches recorded so far (on the weight-gradient stream, behind an event of the main
+        stream: the fused thin-layer launches write their slabs there).  Returns False while a group is still being collected."""
+        p = self.plan
+        if not self.pending:
+            return True
+        if not force and sum(b for _, _, b in self.pending) < (16 << 20):
+            return False
+        grp = {'items': [(d, kind) for d, kind, _ in self.pending], 'tab': None}
+        self.pending.clear()
+        self.groups.append(grp)
+        ev = torch.cuda.Event() if p.side is not None else None
+
+        def flush(st, grp=grp, ev=ev):
+            t = grp['tab']
+            if p.side is not None:
+                ev.record(torch.cuda.current_stream())
+                p.side.wait_event(ev)
+                st = C.c_void_p(p.side.cuda_stream)
+            check(lib.satcv_reduce_slabs_batched(t['jobs'].data_ptr(), t['prefix'].data_ptr(), t['n'], t['total'], st))
+        flush.label = f"wgrad_reduce_batched {len(grp['items'])} layers"
+        p.bwd.append(flush)
+        return True
+
+    def layer_done(self, lo, more):
+        """a layer's gradients are complete; `more`: other layers are still pending.  False while the gradients above `lo` are not final
+        (their slabs are not summed yet)."""
+        if not self._flush(force=not more):
+            return False
+        p, rt = self.plan, self.plan.rt
+        # ---- round 6: the optimizer step of the parameters in [lo, n) beside the REST of the backward pass.  When what is still pending is a
+        # few per cent of the parameters (the three thin encoder blocks of get_unet_model hold 0.5 %), everything above `lo` is final: Adam
+        # and the operand repack of that range run on the weight-gradient stream -- idle from here on: the thin layers' weight gradients
+        # are part of the fused launches of the main stream -- while the main stream finishes the encoder's backward pass; the step's tail
+        # then only updates [0, lo).  Single replica only (a gradient exchange must see every gradient first): Model.train_step_device
+        # sets plan.early_opt per step.
+        if EARLY_OPT and p.side is not None and p.eo_lo is None and more and 0 < lo <= EARLY_OPT_FRAC * rt.n_train and lo % 4 == 0:
+            p.eo_lo = lo
+            evo = torch.cuda.Event()
+
+            def early(st, lo=lo, evo=evo):
+                eo = p.early_opt
+                if eo is None:
+                    return
+                evo.record(torch.cuda.current_stream())
+                p.side.wait_event(evo)
+                if p._last_red_ev is not None:
+                    p.side.wait_event(p._last_red_ev)
+                sp = C.c_void_p(p.side.cuda_stream)
+                n = rt.n_train - lo
+                check(lib.satcv_adam_step_part(_fp(rt.pflat, lo), _fp(rt.gflat, lo), _fp(rt.adam_m, lo), _fp(rt.adam_v, lo), n, eo['beta_1'], eo['beta_2'],
+                                               eo['epsilon'], rt.adam_state.data_ptr(), _fp(rt.lr_mul, lo) if rt.lr_mul is not None else None, 0, sp))
+                rt.repack(lo, None, stream=sp)
+                p.eo_done = True
+            early.label = f'early optimizer step [{lo}, {rt.n_train}) on the side stream'
+            p.bwd.append(early)
+        return True
+
+    def assign(self):
+        """all descriptors exist: the last group, one arena for the workspaces the launches keep for themselves, one job table per group"""
+        self._flush(force=True)
+        if not self.groups:
+            return
+        from ._lib import ReduceJob
+        p = self.plan
+        own = [d for g in self.groups for d, _ in g['items']]
+        arena = p._z(max(sum((d._own_ws + 255) // 256 * 256 for d in own) // 4, 1), dtype=torch.float32)
+        off = 0
+        for d in own:
+            d.workspace, d.workspace_bytes = arena.data_ptr() + off, d._own_ws
+            off += (d._own_ws + 255) // 256 * 256
+        for g in self.groups:
+            jobs = []
+            for d, kind in g['items']:
+                jobs.append(ReduceJob())
+                check((lib.satcv_conv2d_wgrad_reduce_job if kind == 'w' else lib.satcv_conv2d_bwd_fused_reduce_job)(C.byref(d), C.byref(jobs[-1])))
+            g['tab'] = ops.job_table(jobs, lib.satcv_reduce_job_items, p.rt.dev)
+
+    def behind_join(self, join):
+        """the step that lets the main stream wait for the weight-gradient stream; red3: and for the third stream"""
+        p = self.plan
+        if p.rstream is None:
+            return join
+        evj2 = torch.cuda.Event()
+
+        def join3(st):
+            join(st)
+            evj2.record(p.rstream)
+            torch.cuda.current_stream().wait_event(evj2)
+        return join3
+
+
+# one visit of a conv -> BatchNorm block by the backward lowering: its gradients (da activated, dp pooled, graws of raw consumers), the sums
+# buffer (pre: already filled by the producer of da) and whether its weight gradient accumulates
+_CbaVisit = namedtuple('_CbaVisit', 'node cx da dp da_ptr graws pre sums accum')
+
+
+class _BackwardLowering:
+    """Lowers the backward pass of a training plan into plan.bwd: one method per op, called for reversed(model.nodes)."""
+    OPS = ('head', 'add_relu', 'cba', 'dropout', 'concat', 'pool', 'concat_bn_relu', 'convT')
+    HEAD_FAST = {(1, 16), (2, 16), (1, 32), (2, 32), (3, 32), (4, 32), (1, 64), (2, 64)}
+
+    def __init__(self, plan, consumers, vals, ctx):
+        self.plan, self.consumers, self.vals, self.ctx = plan, consumers, vals, ctx
+        rt = self.rt = plan.rt
+        self.m, self.n, self.dt, self.es = rt.model, plan.n, rt.dtype, rt.esize
+        plan.dbg = {}                       # layer name -> intermediate gradient tensors (diagnostics only)
+        # the plan's lists and helpers under the names the lowering code uses
+        self.bwd, self.keep, self.dbg, self.amax_of = plan.bwd, plan.keep, plan.dbg, plan.amax_of
+        self._z, self._conv_step, self._src_args = plan._z, plan._conv_step, plan._src_args
+        self.frozen, self.raw_bn, self.side, self.sync_bn, self.tile_policy = plan.frozen, plan.raw_bn, plan.side, plan.sync_bn, plan.tile_policy
+        self.gact = {}                      # tensor id -> (tensor, channel offset, channels) of the gradient of its activated form
+        self.gpool, self.gpool_f = {}, {}   # tensor id -> gradient of its max-pooled form (same triple); -> the pooling factor
+        self.graw = {}                      # transposed-conv output id -> gradient of its raw values (a tensor; a dict: what the fused launch needs)
+        _cnt = defaultdict(int)
+        for nd in self.m.nodes:
+            if nd.layer is not None:
+                _cnt[nd.layer.name] += 1
+        self.shared_layers = {k for k, v in _cnt.items() if v > 1}      # layers applied to several inputs (Siamese encoders)
+        self.seen_layers = set()            # layers applied more than once (shared weights): later visits accumulate their gradients
+        self.ws_need, self.wdescs = 0, []   # the workspace the weight-gradient launches (side stream) share: bytes, descriptors
+        self.fused_ws_need, self.fdescs = 0, []     # the fused thin-layer backward launches run on the MAIN stream: a workspace of their own
+        self.sums = _SlabSums(plan)
+        # loss -> dlogits is written by Model.train step into this buffer
+        h = plan.head
+        self.dlogits = plan.dlogits = self._z(self.n * h['r'].h * h['r'].w, h['ncls'], dtype=torch.float32)
+        plan.loss_buf = self._z(1, dtype=torch.float32)
+        # ---- sums of an ENCODER block's BatchNorm backward formed by the producers of its two gradients (activated form, see
+        # satcv_bn_bwd_finalize2): encoder conv output tensor id -> dict(buf, parts)
+        self.act_sums = {}
+        self.POOL_SUMS = getattr(rt.model, 'fuse_pool_bn_sums', True) and self.dt == ops.BF16
+        self.ident = {}                     # channels -> (ones, zeros) vectors
+        self.fused = {}                     # tensor id -> sums buffer whose BN-backward reduce pass was done by the producer of the gradient
+        self.head_feed = {}                 # tensor id -> the head launch that writes its gradient
+        # data-parallel overlap: after every parameter-bearing node tell the gradient exchange which tail of the flat
+        # gradient buffer is final (parallel.GradSync.ready_above)
+        pending = self.pending = {}         # layer name -> remaining visits
+        for node in self.m.nodes:
+            if node.layer is not None and any(ps.name in rt.offsets for ps in node.layer.specs):
+                pending[node.layer.name] = pending.get(node.layer.name, 0) + 1
+        # layer name -> end of its parameters in the flat buffer
+        self.layer_hi = {l.name: max(rt.offsets[ps.name] + ps.size for ps in l.specs if ps.name in rt.offsets)
+                         for l in self.m.layers if l.name in pending}
+        # a conv_batch_act node also writes the gamma / beta gradients of ITS BatchNormalization (a layer of its own, directly
+        # above the convolution in the flat buffer): until the node has run, nothing below the end of that layer is final
+        by_name = {l.name: l for l in self.m.layers}
+        for node in self.m.nodes:
+            bn = getattr(node.layer, 'bn_name', None) if node.op == 'cba' else None
+            if bn in by_name and node.layer.name in self.layer_hi:
+                his = [rt.offsets[ps.name] + ps.size for ps in by_name[bn].specs if ps.name in rt.offsets]
+                if his:
+                    self.layer_hi[node.layer.name] = max(self.layer_hi[node.layer.name], max(his))
+
+    def run(self):
+        for node in reversed(self.m.nodes):
+            if node.op in self.OPS:
+                getattr(self, node.op)(node, self.ctx.get(id(node)))
+            self.grads_ready(node)
+        if self.ws_need:
+            ws = self._z(max(self.ws_need // 4, 1), dtype=torch.float32)
+            for d in self.wdescs:
+                if not d.defer_reduce:
+                    d.workspace, d.workspace_bytes = ws.data_ptr(), self.ws_need
+        if self.fused_ws_need:
+            wsf = self._z(max(self.fused_ws_need // 4, 1), dtype=torch.float32)
+            for d in self.fdescs:
+                if not d.defer_reduce:
+                    d.workspace, d.workspace_bytes = wsf.data_ptr(), self.fused_ws_need
+        self.sums.assign()
+        if self.side is not None:
+            side, evj = self.side, torch.cuda.Event()
+
+            def join(st):          # the optimizer (main stream) must see every weight gradient
+                evj.record(side)
+                torch.cuda.current_stream().wait_event(evj)
+            self.bwd.append(self.sums.behind_join(join))
+
+    # -- helpers
+    def bn_bwd_steps(self, da, ldda, dp, lddp, f, yraw, ldy, aff, aoff, sums, sums_off, sums_ld, c, hh, ww, dy, lddy, dbias,
+                     dgamma, dbeta, accum=0, linear=0, frozen=False, second=None, act=None, coef=None):
+        """(reduce, finalize, apply) steps of one BatchNorm backward; reduce is None where nothing is left for it.
+        act: dict(buf=[ROWS][2][c] rows in the ACTIVATED form, parts={'skip', 'pool'}) -- the parts of this layer's gradient whose
+        sums a producer already formed (the decoder's concat-BN apply pass for the skip gradient `da`, the data gradient of the next
+        encoder block for the pooled gradient `dp`); the separate reduce pass then only covers what is left.
+        coef: the coefficient rows where the caller made them (a fused launch reads them), else allocated here."""
+        n, dt, es = self.n, self.dt, self.es
+        if coef is None:
+            coef = self._z(2, c, dtype=torch.float32)
+        common = dict(yraw=yraw, ldy=ldy, scale=_fp(aff['scale'], aoff), shift=_fp(aff['shift'], aoff),
+                      mean=_fp(aff['mean'], aoff), rstd=_fp(aff['rstd'], aoff), n=n, h=hh, w_=ww, c=c, dtype=dt,
+                      f=f, sums=_fp(sums, sums_off), sums_ld=sums_ld, coef=_fp(coef), dy=dy, lddy_out=lddy, dbias=dbias, linear=linear)
+        d = ops.make_bnbwd_desc(da=da, ldda=ldda, dpool=dp, lddp=lddp, **common, **(second or {}))
+        self.keep.append(d)
+        parts = act['parts'] if (act and not frozen) else set()
+        need_da, need_dp = da is not None and 'skip' not in parts, dp is not None and 'pool' not in parts
+        dr = d
+        if parts and (need_da or need_dp):          # reduce pass over the part no producer covered
+            dr = ops.make_bnbwd_desc(da=da if need_da else None, ldda=ldda if need_da else 0, dpool=dp if need_dp else None,
+                                     lddp=lddp if need_dp else 0, **common)
+            self.keep.append(dr)
+        cnt = float(n * hh * ww)
+        red = lambda st: check(lib.satcv_bn_bwd_reduce(C.byref(dr), st))
+        red.label = f"bn_bwd_reduce n{n} {hh}x{ww} c{c} f{f}{' (part)' if dr is not d else ''}"
+        red.work = dict(kind='bn_bwd_reduce', px=n * hh * ww, c=c, esize=es)
+        if parts and not (need_da or need_dp):
+            red = None
+        if parts:
+            abuf = act['buf']
+            fin0 = lambda st: check(lib.satcv_bn_bwd_finalize2(_fp(sums, sums_off) if red is not None else None, sums_ld, _fp(abuf), c, c, cnt,
+                                                               _fp(aff['scale'], aoff), _fp(aff['shift'], aoff), _fp(aff['mean'], aoff),
+                                                               _fp(aff['rstd'], aoff), dgamma, dbeta, _fp(coef), accum, st))
+        else:
+            fin0 = lambda st: check(lib.satcv_bn_bwd_finalize(_fp(sums, sums_off), sums_ld, c, cnt, dgamma, dbeta, _fp(coef), accum, st))
+        if self.sync_bn:
+            def fin(st):            # SyncBN: Σdy, Σdy·x̂ averaged over replicas (linear + idempotent, so the whole buffer is reduced)
+                parallel.allreduce_mean_(sums)
+                if parts:
+                    parallel.allreduce_mean_(act['buf'])
+                fin0(st)
+        else:
+            fin = fin0
+        app = lambda st: check(lib.satcv_bn_bwd_apply(C.byref(d), st))
+        app.label = f"bn_bwd_apply n{n} {hh}x{ww} c{c} f{f}"
+        app.work = dict(kind='bn_bwd_apply', px=n * hh * ww, c=c, esize=es)
+        app.coef = coef
+        if frozen:
+            # inference-mode BatchNormalization: dy = scale * g * mask, no batch-statistics terms (coef stays 0), no dgamma / dbeta
+            def fin_frozen(st):
+                sums.zero_()
+                coef.zero_()
+                if act:
+                    act['buf'].zero_()
+            return None, fin_frozen, app
+        return red, fin, app
+
+    def ident_vecs(self, c):
+        if c not in self.ident:
+            self.ident[c] = (torch.ones(c, dtype=torch.float32, device=self.rt.dev), torch.zeros(c, dtype=torch.float32, device=self.rt.dev))
+            self.keep.append(self.ident[c])
+        return self.ident[c]
+
+    def act_sums_for(self, t):
+        """the registry entry of encoder output t (a conv -> BN -> ReLU node that is pooled AND used as a skip), or None"""
+        if not self.POOL_SUMS or t.node.op != 'cba' or not t.node.attrs.get('bn', True) or not t.node.attrs.get('relu', True):
+            return None
+        if t.node.layer.bn_name in self.frozen or t.node.layer.bn_name in self.raw_bn or t.node.layer.name in self.shared_layers:
+            return None
+        if t.id not in self.act_sums:
+            self.act_sums[t.id] = dict(buf=self._z(STAT_ROWS, 2, t.channels, dtype=torch.float64), parts=set())
+        return self.act_sums[t.id]
+
+    def fuse_target(self, t):
+        """bnr_* fields (and the sums buffer) if the head's backward kernel can also do the reduce pass of the BN+ReLU
+        that produced its input tensor `t` (the raw values are in its registers anyway); None otherwise."""
+        if not self.rt.model.fuse_head_bn_bwd or t.id in self.gact or len(self.consumers[t.id]) != 1:
+            return None
+        P, pc = t.node, self.ctx.get(id(t.node))
+        if P.op != 'cba' or pc['yoff'] != 0 or pc['ldy'] != pc['cout']:
+            return None
+        c, aff = pc['cout'], pc['aff']
+        sums = self._z(STAT_ROWS, 2, c, dtype=torch.float64)
+        return dict(mean=_fp(aff['mean']), rstd=_fp(aff['rstd']), sums=_fp(sums), sums_ld=c), sums
+
+    def bst_target(self, t):
+        """(bst fields, channels) if the data-gradient launch that writes dL/d t -- t the activated output of a
+        conv -> BN -> ReLU node or of the decoder's BN over [skip, up] -- may also form the sums of that BatchNorm's backward
+        (satcv.h: bst_*): the gradient has this one contributor, so the tile in the accumulators IS the whole gradient."""
+        if (not getattr(self.rt.model, 'fuse_dgrad_bn_bwd', True) or self.dt != ops.BF16 or t.id in self.gact or t.id in self.gpool
+                or len(self.consumers[t.id]) != 1):
+            return None
+        P, pc = t.node, self.ctx.get(id(t.node))
+        if P.op == 'cba' and P.attrs.get('bn', True) and P.layer.bn_name not in self.frozen:
+            c, aff, aoff = pc['cout'], pc['aff'], pc['aoff']
+            b = dict(y=pc['y'].data_ptr() + pc['yoff'] * self.es, ld=pc['ldy'], relu=1 if P.attrs.get('relu', True) else 0)
+        elif P.op == 'concat_bn_relu' and P.layer.name not in self.frozen:
+            ra, rb, aff, ca, cb = pc['ra'], pc['rb'], pc['aff'], pc['ca'], pc['cb']
+            if (P.inputs[1].node.op == 'convT' and BIAS_NOISE) or ca % 8:
+                return None            # (the two-launch form of that BN backward keeps its own reduce passes)
+            c, aoff = ca + cb, 0
+            b = dict(y=ra.srcs[0][0].data_ptr(), ld=ca, y1=rb.srcs[0][0].data_ptr(), ld1=cb, split=ca, relu=1)
+        else:
+            return None
+        b.update(scale=_fp(aff['scale'], aoff), shift=_fp(aff['shift'], aoff), mean=_fp(aff['mean'], aoff), rstd=_fp(aff['rstd'], aoff))
+        return b, c
+
+    def act_form_unfit(self, t):
+        """t is the output of a BatchNorm with a zero gamma: its backward sums cannot be rebuilt from the activation (the fused
+        backward kernels' in-loader activation included) -- the separate reduce pass over the raw output forms them"""
+        P = t.node
+        return (P.op == 'cba' and P.layer.bn_name in self.raw_bn) or (P.op == 'concat_bn_relu' and P.layer.name in self.raw_bn)
+
+    def sums_below(self, fz, tin, sa, cinp):
+        """offer a fused launch fz, whose input tin is a BatchNorm + ReLU fed only by this gradient, the sums of THAT layer's backward
+        (what satcv_bn_bwd_reduce would compute in a pass over dx and that layer's raw output): bst_*.  Returns the sums buffer or None."""
+        bt = self.bst_target(tin) if (sa['in_relu'] and sa['in_scale'] is not None and not self.act_form_unfit(tin)) else None
+        if bt is None or bt[1] != cinp or bt[0].get('relu', 0) != 1:
+            return None
+        sums = self._z(STAT_ROWS, 2, cinp, dtype=torch.float64)
+        fz.bst_sums, fz.bst_sums_ld, fz.bst_mean, fz.bst_rstd = _fp(sums), cinp, bt[0]['mean'], bt[0]['rstd']
+        return sums
+
+    def dgrad_step(self, t, **kw):
+        """data-gradient launch writing the activation gradient of tensor t (and, where the kernel can, the sums of the
+        BatchNorm backward of the node that produced t: one pass over two tensors less per such layer)"""
+        vals = self.vals
+        # the gradient of a max-pooled encoder output: this launch sees the pooled activation p = maxpool(relu(BN(y_enc))) (its own
+        # input), so its epilogue can form the pooled part of that BatchNorm's backward sums in the activated form -- sum dp [p > 0],
+        # sum dp p (bst_* with unit scale / rstd and zero shift / mean on the pooled tensor)
+        kw.setdefault('tile_policy', self.tile_policy)        # (the dry-run probes below must ask for the tile family the launch will get)
+        if (self.POOL_SUMS and not kw.get('accumulate') and t.node.op == 'pool' and len(self.consumers[t.id]) == 1 and t.id not in self.gact
+                and len(vals[t.id].srcs) == 1 and vals[t.id].affine is None):
+            ent = self.act_sums_for(t.node.inputs[0])
+            if ent is not None and vals[t.id].srcs[0][1] == kw['cout'] == t.node.inputs[0].channels:
+                one, zero = self.ident_vecs(kw['cout'])
+                kwp = dict(kw, bst=dict(y=vals[t.id].srcs[0][0].data_ptr(), ld=kw['cout'], scale=_fp(one), shift=_fp(zero), mean=_fp(zero),
+                                        rstd=_fp(one), relu=1), stats=_fp(ent['buf']), stats_ld=kw['cout'])
+                probe = ops.make_conv_desc(**kwp)
+                if lib.satcv_conv2d_igemm_pipelined(C.byref(probe)) == 1:
+                    ent['parts'].add('pool')
+                    fn = self._conv_step(role='dgrad', **kwp)
+                    fn.label += ' +poolsums'
+                    return fn
+        bt = None if kw.get('accumulate') else self.bst_target(t)
+        # where it pays (measured per layer of the five-level U-Net, batch 64; DESIGN.md §3): the extra tile read hides under a
+        # K loop of >= 1152 (3x3 x 128 channels) and under the 1x1 kernels.  The thin and middle layers are HBM-bound
+        # themselves -- there the read costs the conv what the separate pass had cost -- and the thin ones run on the
+        # persistent weights-stationary kernel, which does not carry the sums.
+        kdepth = kw.get('kh', 1) * kw.get('kw', 1) * (kw.get('c0', 0) + (kw.get('c1', 0) or 0))
+        # (128 -> 256 at 64 x 64, the one K = 1152 layer whose output is wider than its input, measured +49 us against -41 us)
+        pays = FUSE_DGRAD_ALL or kdepth >= 2304 or (kdepth >= 1152 and kw['cout'] <= kw.get('c0', 0)) or kw.get('kh', 1) == 1
+        if bt is not None and bt[1] == kw['cout'] and pays:
+            sums = self._z(STAT_ROWS, 2, bt[1], dtype=torch.float64)
+            kw2 = dict(kw, bst=bt[0], stats=_fp(sums), stats_ld=bt[1])
+            probe = ops.make_conv_desc(**kw2)
+            if lib.satcv_conv2d_igemm_pipelined(C.byref(probe)) == 1:
+                self.fused[t.id] = sums
+                fn = self._conv_step(role='dgrad', **kw2)
+                fn.label += ' +bnred'
+                return fn
+        return self._conv_step(role='dgrad', **kw)
+
+    def wgrad_step(self, r, dy, lddy, lay, cin_real, cout, hh, ww, k, dil, f=0, accum=0, last=False):
+        rt, n = self.rt, self.n
+        sa = self._src_args(r)
+        if sa['x1'] is not None and sa['c0'] % 8:
+            raise NotImplementedError(f'{lay.name}: training a convolution over a concatenation needs a first part of a multiple of 8 channels '
+                                      f'(got {sa["c0"]}); inference has no such limit')
+        d = ops.make_wgrad_desc(dy=dy, lddy=lddy, dw=rt.gptr(lay.name + '/kernel'), cin=cin_real, cout=cout, n=n, h=hh, w_=ww,
+                                dtype=self.dt, kh=k, kw=k, dil=dil, mode_dy=1 if f else 0, f=f if f else 1, transposed=1 if f else 0, accumulate=accum,
+                                whole_chip=1 if last else 0, **sa)
+        nb = lib.satcv_conv2d_wgrad_workspace(C.byref(d))
+        if nb < 0:
+            raise RuntimeError(lib.satcv_last_error().decode())
+        nvalid = (f * f if f else 1) * cout
+        if not self.sums.own_workspace(d, 'w', nb, 4 * k * k * cin_real * nvalid,
+                                       not accum and lay.name not in self.shared_layers and nvalid % 4 == 0 and not (k == 3 and dil > 1)):
+            self.ws_need = max(self.ws_need, nb)
+        self.wdescs.append(d)
+        self.keep.append(d)
+        if self.side is None:
+            run = lambda st: check(lib.satcv_conv2d_wgrad(C.byref(d), st))
+        else:
+            # weight gradient and data gradient of a layer only share their INPUT (dy): run the weight gradients on a
+            # second HIP stream so that their load/MFMA/store phases interleave with the main stream's kernels
+            ev = torch.cuda.Event()
+            side, sptr = self.side, C.c_void_p(self.side.cuda_stream)
+
+            def run(st):
+                ev.record(torch.cuda.current_stream())
+                side.wait_event(ev)
+                check(lib.satcv_conv2d_wgrad(C.byref(d), sptr))
+            run = self.sums.behind_wgrad(run, d)
+        run.label = f"wgrad k{k} d{dil} n{n} {hh}x{ww} {sa['c0']}+{sa['c1']}->{cout}{' convT f%d' % f if f else ''}"
+        run.work = dict(kind='wgrad', taps=(f * f if f else k * k), px=n * hh * ww, cin=cin_real, cout=cout, esize=self.es)
+        return run
+
+    def place_wgrad(self, wstep, at):
+        """default: a layer's weight gradient (second stream) sits at `at`, BEFORE its data gradient; WGRAD_LATE: behind it"""
+        self.bwd.insert(len(self.bwd) if WGRAD_LATE else at, wstep)
+
+    def conv_dgrad(self, tin, dy, cout, pk, r, k, dil):
+        """data gradient of a convolution into dL/d tin, added where that tensor already holds a gradient (several consumers)"""
+        n, hh, ww, cinp = self.n, r.h, r.w, r.c
+        prev = self.gact.get(tin.id)
+        if prev is not None and (prev[1] != 0 or prev[2] != cinp):
+            raise NotImplementedError('gradient fan-in into a channel slice')
+        gin = prev[0] if prev is not None else self._z(n, hh, ww, cinp)
+        self.bwd.append(self.dgrad_step(tin, x0=dy.data_ptr(), c0=cout, w=pk['dgrad'].data_ptr(), y=gin.data_ptr(), ldy=cinp,
+                                        n=n, h=hh, w_=ww, cout=cinp, cout_pad=rup(cinp, 32), kh=k, kw=k,
+                                        dil=dil, dtype=self.dt, accumulate=1 if prev is not None else 0))
+        return gin
+
+    def set_grad(self, tin, lay, gin, cinp):
+        self.gact[tin.id] = (gin, 0, cinp)
+        self.dbg['dx:' + lay.name] = gin
+
+    def dbg_ctx(self, lay, da, dp, cx):
+        self.dbg['_ctx:' + lay.name] = dict(da=da, dp=dp, **{k: cx[k] for k in ('y', 'yoff', 'ldy', 'aff', 'aoff', 'cout')})
+
+    def grads_ready(self, node):
+        """bookkeeping of the node just finished: once a layer has had all its visits, the tail of the flat gradient buffer above the
+        layers still pending is final"""
+        lay, pending = node.layer, self.pending
+        if lay is None or lay.name not in pending:
+            return
+        pending[lay.name] -= 1
+        if pending[lay.name] == 0:
+            del pending[lay.name]
+        lo = max((self.layer_hi[k] for k in pending), default=0)
+        if not self.sums.layer_done(lo, bool(pending)):
+            return
+        plan, rt, m = self.plan, self.rt, self.m
+
+        def ckpt(st, lo=lo):
+            sync = getattr(m, '_sync_grads', None)
+            if sync is not None and hasattr(sync, 'ready_above'):
+                if plan._last_red_ev is not None:            # (gradients are final behind their slab sums on the third stream)
+                    plan.side.wait_event(plan._last_red_ev)
+                sync.ready_above(rt.gflat, lo, plan.side)
+        self.bwd.append(ckpt)
+
+    # -- one method per op
+    def head(self, node, cx):
+        rt, n = self.rt, self.n
+        r = cx['r']
+        (y, c) = r.srcs[0]
+        dx = self._z(n, r.h, r.w, c)
+        lay = node.layer
+        hb = None
+        ft = self.fuse_target(node.inputs[0]) if (cx['ncls'], c) in self.HEAD_FAST and r.affine else None
+        if ft is not None:
+            hb = dict(mean=ft[0]['mean'], rstd=ft[0]['rstd'], sums=ft[0]['sums'], sums_ld=ft[0]['sums_ld'])
+            self.fused[node.inputs[0].id] = ft[1]
+        hd = ops.make_head_desc(x=y.data_ptr(), ldx=c, cin=c, w=rt.pptr(lay.name + '/kernel'), b=rt.pptr(lay.name + '/bias'),
+                                ncls=cx['ncls'], activation=cx['act'], npix=n * r.h * r.w, dtype=self.dt,
+                                in_scale=_fp(r.affine['scale']) if r.affine else None,
+                                in_shift=_fp(r.affine['shift']) if r.affine else None,
+                                dlogits=self.dlogits.data_ptr(), dx=dx.data_ptr(), lddx=c,
+                                dw=rt.gptr(lay.name + '/kernel'), db=rt.gptr(lay.name + '/bias'), bnr=hb)
+        self.keep.append(hd)
+        self.bwd.append(lambda st, hd=hd: check(lib.satcv_head_bwd(C.byref(hd), st)))
+        nb = lib.satcv_head_bwd_workspace(C.byref(hd))
+        if nb > 0:            # per-workgroup partial rows + an ordered sum instead of float atomics: reproducible dW / db
+            part = self._z(nb // 4, dtype=torch.float32)
+            hd.partials = part.data_ptr()
+            self.bwd.append(lambda st, hd=hd: check(lib.satcv_head_bwd_finalize(C.byref(hd), st)))
+        self.gact[node.inputs[0].id] = (dx, 0, c)
+        # (the block under the head may form this gradient itself from the logit gradients: see _thin_fused)
+        self.head_feed[node.inputs[0].id] = dict(hd=hd, ncls=cx['ncls'], c=c, w=rt.pptr(lay.name + '/kernel'), wname=lay.name + '/kernel',
+                                                 fused_reduce=ft is not None)
+
+    def add_relu(self, node, cx):
+        # out = ReLU(BN(conv) + shortcut): the masked gradient g * (out > 0) belongs to BOTH addends.  It is formed in place
+        # and handed to the branch's (linear) BN backward and to the shortcut; a tensor that already holds a gradient
+        # (several consumers) receives it by addition.
+        n, dt, gact = self.n, self.dt, self.gact
+        g = gact.get(node.outputs[0].id)
+        if g is None or cx is None:
+            return
+        c, hh, ww, out = cx['c'], cx['h'], cx['w'], cx['out']
+        if g[1] != 0 or g[2] != c:
+            raise NotImplementedError('residual-join gradient in a channel slice')
+        gb, cnt = g[0], n * hh * ww * c
+        self.bwd.append(lambda st, out=out, gb=gb, cnt=cnt: check(lib.satcv_relu_bwd(out.data_ptr(), gb.data_ptr(), cnt, dt, st)))
+        for t in node.inputs:
+            prev = gact.get(t.id)
+            if prev is None:
+                gact[t.id] = (gb, 0, c)
+            else:
+                if prev[1] != 0 or prev[2] != c:
+                    raise NotImplementedError('gradient fan-in into a channel slice')
+                self.bwd.append(lambda st, pb=prev[0], gb=gb, npx=n * hh * ww, c=c: check(lib.satcv_add_act(
+                    pb.data_ptr(), None, None, gb.data_ptr(), None, None, 0, pb.data_ptr(), npx, c, dt, st)))
+
+    def plain_cba(self, node, cx):
+        # plain Conv2D: the gradient of its stored output is the incoming one as it is
+        rt, n, dt = self.rt, self.n, self.dt
+        tin, tout = node.inputs[0], node.outputs[0]
+        da = self.gact.get(tout.id)
+        if da is None:
+            return
+        lay, r, cout = node.layer, cx['r'], cx['cout']
+        if da[1] != 0 or da[2] != cout:
+            raise NotImplementedError('plain-convolution gradient in a channel slice')
+        hh, ww, dyb = r.h, r.w, da[0]
+        accum = 1 if lay.name in self.seen_layers else 0
+        self.seen_layers.add(lay.name)
+        bpart = self._z(max(lib.satcv_bias_grad_workspace(n * hh * ww, cout) // 4, 1), dtype=torch.float32)
+        self.bwd.append(lambda st, dyb=dyb, cout=cout, npx=n * hh * ww, db=rt.gptr(lay.name + '/bias'), bpart=bpart: check(lib.satcv_bias_grad(
+            dyb.data_ptr(), cout, npx, cout, dt, db, bpart.data_ptr(), st)))
+        pk = rt.packed[lay.name]
+        self.bwd.append(self.wgrad_step(r, dyb.data_ptr(), cout, lay, pk['cin'], cout, hh, ww, cx['k'], cx['dil'], accum=accum))
+        if tin.node.op != 'input':
+            gin = self.conv_dgrad(tin, dyb, cout, pk, r, cx['k'], cx['dil'])
+            self.gact[tin.id] = (gin, 0, r.c)
+
+    def cba(self, node, cx):
+        if not node.attrs.get('bn', True):
+            return self.plain_cba(node, cx)
+        rt, es = self.rt, self.es
+        tout = node.outputs[0]
+        da, dp = self.gact.get(tout.id), self.gpool.get(tout.id)
+        graws = [self.gact[cn.outputs[0].id] for cn in self.consumers.get(tout.id, []) if cn.op == 'raw' and cn.outputs[0].id in self.gact]
+        if da is None and dp is None:
+            if graws:
+                raise NotImplementedError('a convolution consumed only through its un-normalised output')
+            return
+        lay, r, cout = node.layer, cx['r'], cx['cout']
+        pre = self.fused.get(tout.id)
+        sums = pre if pre is not None else self._z(STAT_ROWS, 2, cout, dtype=torch.float64)
+        accum = 1 if lay.name in self.seen_layers else 0
+        self.seen_layers.add(lay.name)
+        v = _CbaVisit(node, cx, da, dp, da[0].data_ptr() + da[1] * es if da is not None else None, graws, pre, sums, accum)
+        # what the two fused forms share: one input, no consumer of the raw output, no bias noise, a 3 x 3 undilated kernel, a gradient
+        # laid out like the raw output, no gradient of the input yet and a layer applied once (a shared layer's other visit may have its
+        # weight gradient in flight on the side stream)
+        fusable = (self.dt == ops.BF16 and da is not None and not graws and not BIAS_NOISE and cx['k'] == 3 and cx['dil'] == 1 and da[2] == cx['ldy']
+                   and self.gact.get(node.inputs[0].id) is None and lay.name not in self.shared_layers)
+        if fusable and dp is None and self._thin_fused(v) is not None:
+            return
+        dy = self._z(self.n, r.h, r.w, cout)
+        bn = self.bn_bwd_steps(v.da_ptr, da[2] if da is not None else 0, dp[0].data_ptr() if dp is not None else None,
+                               cout, self.gpool_f.get(tout.id, 1), cx['y'].data_ptr() + cx['yoff'] * es, cx['ldy'], cx['aff'], cx['aoff'], sums, 0, cout, cout,
+                               r.h, r.w, dy.data_ptr(), cout, rt.gptr(lay.name + '/bias') if BIAS_NOISE else None,
+                               rt.gptr(lay.bn_name + '/gamma'), rt.gptr(lay.bn_name + '/beta'), accum,
+                               linear=0 if node.attrs.get('relu', True) else 1, frozen=lay.bn_name in self.frozen,
+                               act=self.act_sums.get(tout.id) if (self.act_sums.get(tout.id) or {}).get('parts') else None)
+        if fusable and dp is not None and self._pooled_fused(v, bn) is not None:
+            return
+        self._separate(v, bn, dy)
+
+    def _fused_desc(self, v, coef, want_dx=True, **kw):
+        """(satcv_conv2d_bwd_fused descriptor, source arguments, data-gradient tensor or None) of a conv -> BN (-> ReLU) block"""
+        rt, n, es, cx = self.rt, self.n, self.es, v.cx
+        lay, r, aff, aoff, cout = v.node.layer, cx['r'], cx['aff'], cx['aoff'], cx['cout']
+        pk, sa = rt.packed[lay.name], self._src_args(r)
+        gin = self._z(n, r.h, r.w, r.c) if want_dx else None
+        fz = ops.make_bwdf_desc(g=v.da_ptr, yraw=cx['y'].data_ptr() + cx['yoff'] * es, ldg=cx['ldy'], bn_scale=_fp(aff['scale'], aoff), bn_shift=_fp(aff['shift'], aoff),
+                                bn_mean=_fp(aff['mean'], aoff), bn_rstd=_fp(aff['rstd'], aoff), bn_coef=_fp(coef),
+                                w_dgrad=pk['dgrad'].data_ptr() if want_dx else None, dx=gin.data_ptr() if want_dx else None, lddx=r.c if want_dx else 0,
+                                dw=rt.gptr(lay.name + '/kernel'), cin=pk['cin'], cout=cout, n=n, h=r.h, w_=r.w, dtype=self.dt, accumulate=v.accum, **kw, **sa)
+        return fz, sa, gin
+
+    def _emit_fused(self, v, fz, nb, red, fin, gin, suffix, dyparts, **work):
+        """the steps and records of an accepted fused backward launch: whose workspace, BatchNorm reduce / finalize, the launch itself"""
+        n, cx, lay = self.n, v.cx, v.node.layer
+        r, cout = cx['r'], cx['cout']
+        if not self.sums.own_workspace(fz, 'f', nb, 4 * 9 * fz.cin * cout, not v.accum and lay.name not in self.shared_layers):
+            self.fused_ws_need = max(self.fused_ws_need, nb)
+        self.fdescs.append(fz)
+        self.keep.append(fz)
+        self.bwd += [fin] if (v.pre is not None or red is None) else [red, fin]
+        fstep = lambda st: check(lib.satcv_conv2d_bwd_fused(C.byref(fz), st))
+        fstep.label = f"bwd_fused k3 n{n} {r.h}x{r.w} {fz.c0}+{fz.c1}->{cout}{suffix}"
+        fstep.work = dict(kind='bwd_fused', taps=9, px=n * r.h * r.w, cin=fz.cin, cout=cout, esize=self.es, **work)
+        self.bwd.append(fstep)
+        if gin is not None:
+            self.set_grad(v.node.inputs[0], lay, gin, r.c)
+        self.dbg['dyparts:' + lay.name] = dict(g=v.da, **{k: cx[k] for k in ('y', 'yoff', 'ldy', 'aff', 'aoff', 'cout')}, **dyparts)
+        self.dbg_ctx(lay, v.da, v.dp, cx)
+        return fstep
+
+    def _thin_fused(self, v):
+        """thin full- / half-resolution layers: ONE launch forms dy = BN-backward(g, y) in registers and uses the tile for
+        the data gradient AND the weight gradient (csrc/conv_bwd_fused.hip): 4 tensor passes instead of 7, no dy tensor.
+        None when the model or the library's workspace query refuses it."""
+        node, cx = v.node, v.cx
+        rt, tin, tout, lay, r, cout = self.rt, node.inputs[0], node.outputs[0], node.layer, cx['r'], cx['cout']
+        if not getattr(rt.model, 'fuse_thin_bwd', True) or tin.node.op == 'input':
+            return None
+        cinp = r.c
+        coef = self._z(2, cout, dtype=torch.float32)
+        fz, sa, gin = self._fused_desc(v, coef, linear=0 if node.attrs.get('relu', True) else 1)
+        sums_below = self.sums_below(fz, tin, sa, cinp)
+        # ... and, for the block under the 1 x 1 head, the gradient g itself: two logit gradients per pixel instead of the
+        # head's dx tensor written and read back (2 x 64 bytes per pixel)
+        hf = self.head_feed.get(tout.id)
+        if (hf is not None and getattr(rt.model, 'fuse_head_grad', True) and hf['ncls'] == 2 and hf['c'] == cout == 32 and cinp == 32
+                and hf['fused_reduce'] and v.pre is not None and len(self.consumers.get(tout.id, [])) == 1):
+            fz.hg_dlogits, fz.hg_w, fz.hg_ncls = self.dlogits.data_ptr(), hf['w'], 2
+            if lib.satcv_conv2d_bwd_fused_workspace(C.byref(fz)) < 0:
+                fz.hg_dlogits, fz.hg_w, fz.hg_ncls = None, None, 0
+            else:
+                hf['hd'].dx = None                      # satcv_head_bwd keeps its dW / db and the fused sums, stores no dx
+        nbf = lib.satcv_conv2d_bwd_fused_workspace(C.byref(fz))
+        if nbf < 0 and sums_below is not None:              # (the 64 -> 64 form does not carry the sums)
+            fz.bst_sums, fz.bst_sums_ld, fz.bst_mean, fz.bst_rstd = None, 0, None, None
+            sums_below = None
+            nbf = lib.satcv_conv2d_bwd_fused_workspace(C.byref(fz))
+        if nbf < 0:
+            return None
+        if sums_below is not None:
+            self.fused[tin.id] = sums_below
+        # (the launch applies the BatchNorm backward itself: of the three steps only reduce and finalize are used)
+        red, fin, _ = self.bn_bwd_steps(v.da_ptr, v.da[2], None, 0, 1, cx['y'].data_ptr() + cx['yoff'] * self.es, cx['ldy'], cx['aff'], cx['aoff'], v.sums, 0,
+                                        cout, cout, r.h, r.w, None, 0, None, rt.gptr(lay.bn_name + '/gamma'), rt.gptr(lay.bn_name + '/beta'), v.accum,
+                                        linear=fz.linear, frozen=lay.bn_name in self.frozen, coef=coef)
+        dyparts = dict(coef=coef, linear=fz.linear)
+        if fz.hg_dlogits:
+            dyparts['head'] = (self.dlogits, hf['wname'])
+        return self._emit_fused(v, fz, nbf, red, fin, gin, f"{' +bnred' if fz.bst_sums else ''}{' +headgrad' if fz.hg_dlogits else ''}", dyparts)
+
+    def _pooled_fused(self, v, bn):
+        """encoder blocks of the full- / half-resolution levels: the pooled BatchNorm apply + weight gradient (+ data gradient)
+        in ONE launch (satcv_conv2d_bwd_fused with dpool / amax): no dy tensor, no separate weight-gradient launch.  `bn`: the block's
+        (reduce, finalize, apply) steps -- the launch reads the coefficients the finalize writes.  None when refused."""
+        node, dp = v.node, v.dp
+        rt, tin, tout, lay = self.rt, node.inputs[0], node.outputs[0], node.layer
+        red, fin, app = bn
+        amax = self.amax_of.get(tout.id)
+        if (amax is None or not getattr(rt.model, 'fuse_pool_bwd', True) or self.gpool_f.get(tout.id, 1) != 2 or dp[1] != 0
+                or lay.bn_name in self.frozen):
+            return None
+        want_dx = tin.node.op != 'input'
+        cinp = v.cx['r'].c
+        fzp, sa, ginp = self._fused_desc(v, app.coef, want_dx, linear=0, dpool=dp[0].data_ptr(), lddp=dp[2], amax=amax.data_ptr())
+        # its input is the max-pooled output of the block below: the pooled part of THAT block's sums, activated form
+        ent = None
+        if (want_dx and self.POOL_SUMS and tin.node.op == 'pool' and len(self.consumers[tin.id]) == 1 and sa['in_scale'] is None
+                and len(self.vals[tin.id].srcs) == 1 and tin.node.inputs[0].channels == cinp):
+            ent = self.act_sums_for(tin.node.inputs[0])
+        if ent is not None:
+            fzp.bst_sums, fzp.bst_sums_ld, fzp.bst_act_form = _fp(ent['buf']), cinp, 1
+        nbp = lib.satcv_conv2d_bwd_fused_workspace(C.byref(fzp))
+        if nbp < 0:
+            return None
+        if ent is not None:
+            ent['parts'].add('pool')
+        return self._emit_fused(v, fzp, nbp, red, fin, ginp, f" pooled{'' if want_dx else ' nodx'}{' +poolsums' if fzp.bst_sums else ''}",
+                                dict(coef=app.coef, linear=0, dp=dp, amax=amax), nodx=not want_dx, pooled=True)
+
+    def _separate(self, v, bn, dy):
+        """BatchNorm reduce / finalize / apply into dy, then the weight gradient (side stream) and the data gradient as launches of their own"""
+        rt, n, dt, node, cx = self.rt, self.n, self.dt, v.node, v.cx
+        tin, lay, r, cout = node.inputs[0], node.layer, cx['r'], cx['cout']
+        red, fin, app = bn
+        hh, ww = r.h, r.w
+        self.bwd += [fin, app] if (v.pre is not None or red is None) else [red, fin, app]
+        for gr in v.graws:            # consumers of the un-normalised output add their gradient to dy (and to the bias gradient)
+            if gr[1] != 0 or gr[2] != cout:
+                raise NotImplementedError('raw-output gradient in a channel slice')
+            bpart = self._z(max(lib.satcv_bias_grad_workspace(n * hh * ww, cout) // 4, 1), dtype=torch.float32)
+            self.bwd.append(lambda st, dy=dy, gb=gr[0], npx=n * hh * ww, cout=cout, db=rt.gptr(lay.name + '/bias'), bpart=bpart: (
+                check(lib.satcv_bias_grad(gb.data_ptr(), cout, npx, cout, dt, db, bpart.data_ptr(), st)),
+                check(lib.satcv_add_act(dy.data_ptr(), None, None, gb.data_ptr(), None, None, 0, dy.data_ptr(), npx, cout, dt, st))))
+        self.dbg['dy:' + lay.name] = dy
+        self.dbg_ctx(lay, v.da, v.dp, cx)
+        pk = rt.packed[lay.name]
+        # (the weight gradient of a layer fed by a model input is the last launch of the backward pass: nothing runs beside it)
+        wstep = self.wgrad_step(r, dy.data_ptr(), cout, lay, pk['cin'], cout, hh, ww, cx['k'], cx['dil'], accum=v.accum,
+                                last=tin.node.op == 'input' and len(self.m.inputs) == 1 and switches.read('wgrad_last_full'))
+        at = len(self.bwd)
+        if tin.node.op != 'input':
+            self.set_grad(tin, lay, self.conv_dgrad(tin, dy, cout, pk, r, cx['k'], cx['dil']), r.c)
+        self.place_wgrad(wstep, at)
+
+    def dropout(self, node, cx):
+        n, dt = self.n, self.dt
+        tin, tout = node.inputs[0], node.outputs[0]
+        g = self.gact.get(tout.id)
+        if g is None or cx is None:
+            return
+        if g[1] != 0 or g[2] != cx['ctot']:
+            raise NotImplementedError('dropout gradient in a channel slice')
+        gt, mask, ctot, hw = g[0], cx['mask'], cx['ctot'], cx['hw']
+        mode = 0 if cx['spatial'] else 1
+        self.bwd.append(lambda st, gt=gt, mask=mask, ctot=ctot, hw=hw, mode=mode: check(lib.satcv_dropout_apply(
+            gt.data_ptr(), ctot, None, None, 0, _fp(mask), ctot, mode, gt.data_ptr(), ctot, n, hw, ctot, dt, st)))
+        self.gact[tin.id] = (gt, 0, ctot)
+
+    def concat(self, node, cx):
+        g = self.gact.get(node.outputs[0].id)
+        if g is None:
+            return
+        off = 0
+        for t in node.inputs:          # each branch sees its channel slice of the gradient
+            self.gact[t.id] = (g[0], g[1] + off, g[2])
+            off += t.channels
+
+    def pool(self, node, cx):
+        tin, tout = node.inputs[0], node.outputs[0]
+        if tout.id in self.gact:
+            if self.gact[tout.id][1] != 0:
+                raise NotImplementedError('pooled gradient in a channel slice')
+            self.gpool[tin.id] = self.gact[tout.id]
+            self.gpool_f[tin.id] = cx['f']
+
+    def concat_bn_relu(self, node, cx):
+        rt, n, dt, es, consumers = self.rt, self.n, self.dt, self.es, self.consumers
+        ta, tb = node.inputs
+        tout = node.outputs[0]
+        g = self.gact.get(tout.id)
+        if g is None:
+            return
+        ra, rb, aff, ca, cb = cx['ra'], cx['rb'], cx['aff'], cx['ca'], cx['cb']
+        ctot = ca + cb
+        hh, ww = ra.h, ra.w
+        pre = self.fused.get(tout.id)
+        sums = pre if pre is not None else self._z(STAT_ROWS, 2, ctot, dtype=torch.float64)
+        dskip = self._z(n, hh, ww, ca)
+        du = self._z(n, hh, ww, cb)
+        bn = node.layer.name
+        upl = tb.node.layer
+        if g[2] != ctot:
+            raise NotImplementedError('decoder concat gradient in a channel slice')
+        gptr_ = g[0].data_ptr() + g[1] * es
+        if not (tb.node.op == 'convT' and BIAS_NOISE) and ca % 8 == 0:
+            # ONE reduce / finalize / apply over the whole concatenation: the gradient of the concatenated tensor is read
+            # once per pass in full lines (the two half launches each touched every line of it for half of its bytes)
+            # the skip is the activated output of an encoder block that is also max-pooled: this apply pass has dskip and that
+            # activation in registers -- it also forms the skip part of the encoder BatchNorm's backward sums (sk_sums)
+            sec = dict(yraw1=rb.srcs[0][0].data_ptr(), ldy1=cb, dy1=du.data_ptr(), lddy1=cb, c_split=ca)
+            # round 5: the `up` channels' part of this apply pass, the transposed convolution's data gradient and its weight gradient as ONE
+            # launch (satcv_convt_bwd_fused, built at the convT node): the apply pass then covers the skip channels only
+            ctbf = None
+            cxt = self.ctx.get(id(tb.node)) if tb.node.op == 'convT' else None
+            if (CTBF and dt == ops.BF16 and cxt is not None and bn not in self.frozen and upl.name not in self.shared_layers and cxt['f'] == 2
+                    and cb in CTBF_COUTS and len(consumers.get(tb.id, [])) == 1):
+                rT = cxt['r']
+                saT = self._src_args(rT)
+                probe = ops.make_ctbf_desc(g=gptr_ + ca * es, ldg=ctot, yup=rb.srcs[0][0].data_ptr(), ldy=cb, bn_scale=None, bn_shift=None, bn_mean=None,
+                                           bn_rstd=None, bn_c1=None, bn_c2=None, x=saT['x0'], ldx=saT['c0'], w_dgrad=rt.packed[upl.name]['dgrad'].data_ptr(),
+                                           w_npad=rup(rT.c, 32), dx=saT['x0'], lddx=rT.c, dw=rt.gptr(upl.name + '/kernel'), cin=rT.c, cout=cb, n=n,
+                                           h=rT.h, w_=rT.w, dtype=dt)
+                if saT['x1'] is None and saT['c0'] == rT.c == rt.packed[upl.name]['cin'] and lib.satcv_convt_bwd_fused_workspace(C.byref(probe)) > 0:
+                    ctbf = dict(g=gptr_ + ca * es, ldg=ctot, yup=rb.srcs[0][0].data_ptr(), ldy=cb, aff=aff, aoff=ca, ctot=ctot)
+                    sec['dy1'] = None
+            ent = None
+            if (bn not in self.frozen and ta.id not in self.gact and any(cn.op == 'pool' for cn in consumers[ta.id])
+                    and len([cn for cn in consumers[ta.id] if cn.op != 'pool']) == 1 and ta.channels == ca):
+                ent = self.act_sums_for(ta)
+            if ent is not None:
+                sec.update(sk_sums=_fp(ent['buf']), sk_sums_ld=ca)
+                ent['parts'].add('skip')
+            r_, f_, a_ = self.bn_bwd_steps(gptr_, ctot, None, 0, 1, ra.srcs[0][0].data_ptr(), ca, aff, 0, sums, 0, ctot, ctot, hh, ww,
+                                           dskip.data_ptr(), ca, None, rt.gptr(bn + '/gamma'), rt.gptr(bn + '/beta'), frozen=bn in self.frozen,
+                                           second=sec)
+            if ent is not None:
+                a_.label += ' +skipsums'
+            if ctbf is not None:
+                a_.label += ' (skip half)'
+                a_.work = dict(kind='bn_bwd_apply', px=n * hh * ww, c=ca, esize=es)
+                ctbf['coef'] = a_.coef
+            self.bwd += [f_, a_] if (pre is not None or r_ is None) else [r_, f_, a_]
+            self.graw[tb.id] = ctbf if ctbf is not None else du
+        else:
+            ra_, fa_, aa_ = self.bn_bwd_steps(gptr_, ctot, None, 0, 1, ra.srcs[0][0].data_ptr(), ca, aff, 0, sums, 0, ctot, ca, hh, ww,
+                                              dskip.data_ptr(), ca, None, rt.gptr(bn + '/gamma'), rt.gptr(bn + '/beta'), frozen=bn in self.frozen)
+            rb_, fb_, ab_ = self.bn_bwd_steps(gptr_ + ca * es, ctot, None, 0, 1, rb.srcs[0][0].data_ptr(), cb, aff, ca, sums, ca, ctot, cb,
+                                              hh, ww, du.data_ptr(), cb, rt.gptr(upl.name + '/bias') if (tb.node.op == 'convT' and BIAS_NOISE) else None,
+                                              rt.gptr(bn + '/gamma') + 4 * ca, rt.gptr(bn + '/beta') + 4 * ca, frozen=bn in self.frozen)
+            self.bwd += [fa_, fb_, aa_, ab_] if (pre is not None or ra_ is None) else [ra_, rb_, fa_, fb_, aa_, ab_]
+            self.graw[tb.id] = du
+        # the skip is the activated output of an encoder conv_batch_act block
+        self.gact[ta.id] = (dskip, 0, ca)
+        self.dbg['dskip:' + bn] = dskip
+        self.dbg['du:' + bn] = du
+
+    def convT(self, node, cx):
+        rt, n, dt = self.rt, self.n, self.dt
+        tin, tout = node.inputs[0], node.outputs[0]
+        du = self.graw.get(tout.id)
+        if du is None:
+            return
+        lay, r, cout, f = node.layer, cx['r'], cx['cout'], cx['f']
+        pk = rt.packed[lay.name]
+        cinp = r.c
+        gin = self._z(n, r.h, r.w, cinp)
+        if isinstance(du, dict):
+            # fused: BatchNorm-backward apply of the `up` channels + data gradient + weight gradient (csrc/convt_bwd_fused.hip)
+            cb_, sa = du, self._src_args(r)
+            af_, ao_, ct_ = cb_['aff'], cb_['aoff'], cb_['ctot']
+            fz = ops.make_ctbf_desc(g=cb_['g'], ldg=cb_['ldg'], yup=cb_['yup'], ldy=cb_['ldy'], bn_scale=_fp(af_['scale'], ao_), bn_shift=_fp(af_['shift'], ao_),
+                                    bn_mean=_fp(af_['mean'], ao_), bn_rstd=_fp(af_['rstd'], ao_), bn_c1=_fp(cb_['coef'], ao_), bn_c2=_fp(cb_['coef'], ct_ + ao_),
+                                    x=sa['x0'], ldx=sa['c0'], in_scale=sa['in_scale'], in_shift=sa['in_shift'], in_relu=sa['in_relu'],
+                                    w_dgrad=pk['dgrad'].data_ptr(), w_npad=rup(cinp, 32), dx=gin.data_ptr(), lddx=cinp, dw=rt.gptr(lay.name + '/kernel'),
+                                    cin=cinp, cout=cout, n=n, h=r.h, w_=r.w, dtype=dt)
+            sums_below = self.sums_below(fz, tin, sa, cinp)
+            if sums_below is not None:
+                self.fused[tin.id] = sums_below
+            nbc = lib.satcv_convt_bwd_fused_workspace(C.byref(fz))
+            if nbc <= 0:
+                raise RuntimeError('convt_bwd_fused: the probe accepted this shape, the final descriptor did not')
+            wsc = self._z(max(nbc // 4, 1), dtype=torch.float32)
+            fz.workspace, fz.workspace_bytes = wsc.data_ptr(), nbc
+            self.keep.append(fz)
+            cstep = lambda st: check(lib.satcv_convt_bwd_fused(C.byref(fz), st))
+            cstep.label = f"convt_bwd_fused n{n} {r.h}x{r.w} {cinp}<-4x{cout}{' +bnred' if fz.bst_sums else ''}"
+            cstep.work = dict(kind='convt_bwd_fused', px=n * r.h * r.w, cin=cinp, cout=cout, esize=self.es)
+            self.bwd.append(cstep)
+        else:
+            wstep = self.wgrad_step(r, du.data_ptr(), cout, lay, pk['cin'], cout, r.h, r.w, 1, 1, f=f)
+            at = len(self.bwd)
+            self.bwd.append(self.dgrad_step(tin, x0=du.data_ptr(), c0=cout, w=pk['dgrad'].data_ptr(), y=gin.data_ptr(), ldy=cinp, n=n, h=r.h,
+                                            w_=r.w, cout=cinp, cout_pad=rup(cinp, 32), kh=1, kw=1, dil=1, mode_in=1, f=f, dtype=dt))
+            self.place_wgrad(wstep, at)
+        self.set_grad(tin, lay, gin, cinp)

@@ -92,13 +92,7 @@ class _Params:
                 src = self.p(name).data_ptr()
                 jobs.append(PackJob(src, e['fwd'].data_ptr(), 0, kh * kw, cin, cout, e['cin_pad'], ops.rup(cout, 32)))
                 jobs.append(PackJob(src, e['dg'].data_ptr(), 1, kh * kw, cin, cout, ops.rup(cout, 16), ops.rup(cin, 32)))
-            prefix, tot = [], 0
-            for j in jobs:
-                prefix.append(tot)
-                tot += int(lib.satcv_pack_job_items(C.byref(j)))
-            arr = (PackJob * len(jobs))(*jobs)
-            self._pk_tab = dict(jobs=torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(_dev()),
-                                prefix=torch.tensor(prefix, dtype=torch.int64, device=_dev()), n=len(jobs), total=tot)
+            self._pk_tab = ops.job_table(jobs, lib.satcv_pack_job_items, _dev())
         return self._pk_tab
 
     def _repack_all(self, dtype):

@@ -1541,7 +1541,7 @@ class Model:
         plan.step_count += 1                     # fresh dropout masks every step
         plan.run_forward(st)
         self._loss_launch(plan, st)
-        # (single replica: the bulk of the optimizer step may run inside the backward pass, engine.Plan `early` -- an opt-in experiment
+        # (single replica: the bulk of the optimizer step may run inside the backward pass, engine._SlabSums `early` -- an opt-in experiment
         # that exists for plain Adam only: a clipped step needs every gradient first, and the other rules have no `_part` form)
         plan.eo_done = False
         early_ok = sync_grads is None and opt.kind == 'adam' and opt.clipvalue is None and opt.global_clipnorm is None

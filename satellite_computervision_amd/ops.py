@@ -90,6 +90,19 @@ def pack_weights(kernel_f32, cin_pad, dtype, transposed=False, want_dgrad=True, 
     return fwd, dg
 
 
+def job_table(jobs, items_fn, device):
+    """ctypes job structures -> the device table of a batched launch: dict(jobs=the array's bytes, prefix=exclusive prefix sum of the jobs'
+    item counts, n, total).  items_fn is the library's count of one job (satcv_pack_job_items, satcv_reduce_job_items): the counts are
+    padded, so they are asked for per job, never computed here."""
+    prefix, tot = [], 0
+    for j in jobs:
+        prefix.append(tot)
+        tot += int(items_fn(C.byref(j)))
+    arr = (type(jobs[0]) * len(jobs))(*jobs)
+    return dict(jobs=torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device),
+                prefix=torch.tensor(prefix, dtype=torch.int64, device=device), n=len(jobs), total=tot)
+
+
 # --------------------------------------------------------------------------- conv
 def make_conv_desc(*, x0, c0, w, y, ldy, n, h, w_, cout, cout_pad, dtype, x1=None, c1=0, in_scale=None, in_shift=None,
                    in_relu=0, bias=None, stats=None, stats_ld=0, kh=3, kw=3, dil=1, mode_in=0, mode_out=0, f=1,

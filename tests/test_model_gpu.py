@@ -1698,3 +1698,37 @@ def test_launch_counters_are_live_through_the_option_table(mt):
         assert type(before[k]) is int and type(after[k]) is int and 0 <= before[k] <= after[k], (k, before[k], after[k])
     assert after['igemm_thin_launches'] > before['igemm_thin_launches']
     assert {k: v for k, v in after.items() if k not in counters} == {k: v for k, v in before.items() if k not in counters}      # a step leaves every switch as it found it
+
+
+def _plan_cases():
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    if here not in sys.path:
+        sys.path.insert(0, here)
+    import plan_cases
+    return [c for c in plan_cases.CASES if c.name in plan_cases.IN_SUITE]
+
+
+@pytest.mark.parametrize('case', _plan_cases(), ids=lambda c: c.name)
+def test_plan_lowering_reaches_its_forms(mt, case):
+    """the cases of tests/plan_cases.py that reach forms of the backward lowering no other test names: the thin fused launch under the head
+    that forms the head's data gradient itself (+headgrad), the pooled launch of the first block (pooled nodx), a BatchNorm reduce over the
+    part no producer covered ((part)), a data gradient that carries the sums of the layer below (+bnred), the transposed convolution's own
+    weight gradient (convT f2) and, on 128-pixel rows, its fused backward with the skip-half apply pass.  One step: the labels are there and
+    every gradient is finite, the buffer not all zero."""
+    from satellite_computervision_amd import lstm_tools as lt
+    mt.set_compute_dtype(case.dtype)
+    try:
+        m, x, y = case.make(mt, lt)
+        assert np.isfinite(m.train_on_batch(x, y))
+    finally:
+        mt.set_compute_dtype('bfloat16')
+    rt = m.runtime
+    labels = [getattr(s, 'label', '') or '' for s in next(p for p in rt.plans.values() if p.training).bwd]
+    for frag in case.labels:
+        assert any(frag in l for l in labels), frag
+    g = rt.gflat[:rt.n_train]
+    assert bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0
+    for ps in m.param_specs:
+        if ps.kind == 'kernel':
+            assert float(rt.get_grad(ps.name).abs().max()) > 0, ps.name
