@@ -754,6 +754,60 @@ typedef struct satcv_composite_masked_desc {
 } satcv_composite_masked_desc;
 int satcv_median_composite_masked(const satcv_composite_masked_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ Cloud-Optimized GeoTIFF writer: the device half
+ * What numpy_to_raster / arrays_to_cog (utils/raster_tools.py:367-461: rasterio's write, then GDAL's COG driver with COMPRESS=LZW
+ * and nodata = 255) and write_geotiff_prediction(s) (utils/prediction_tools.py:447-536) do to the samples of a map, on a map that is
+ * resident on the device.  The container (IFDs, GeoKeys) is host code in raster_tools.py.  Kinds: 0 u8, 1 u16, 2 f32, 3 i16, 5 i32
+ * (those of satcv_tile_desc).  One descriptor serves the three per-sample entries; each reads the fields named for it.  Refused on
+ * the host before any launch: c > 16, unknown kinds, a map beyond 2^31 pixels, and what each entry lists.
+ *
+ * satcv_raster_convert (rasterio's `astype(dtype)` of :399 / :472 with the `nodata` of :393):
+ *   src (h, w_, ld) of src_kind read at channel offset coff, c bands -> dst contiguous (h, w_, c) of dst_kind
+ *   to f32:                a plain cast; an f32 source is first multiplied by `scale` (one fp32 multiply; 0 = none, f32 sources only)
+ *   f32 -> integer kind:   NaN -> nodata (0 without has_nodata), else rintf (half to even) of the fp32 product, saturated to the kind
+ *   integer -> integer:    saturated
+ * satcv_raster_overview (the overviews GDAL's COG driver adds, :405 / :455; the resampling rules are THIS library's, GDAL's default is cubic):
+ *   src contiguous (h, w_, c) -> dst (ceil(h / 2), ceil(w_ / 2), c), same kind.  Per 2 x 2 block only samples inside the image count; a
+ *   sample equal to nodata (with has_nodata) is invalid, and so is NaN.  resampling:
+ *   0 nearest   src[2 y, 2 x]
+ *   1 average   over the valid samples; none valid -> nodata, NaN for f32 without nodata.  Integers: floor((2 sum + n) / (2 n)) in 64
+ *               bits; f32: the valid samples added in row-major order in fp32, one fp32 division
+ *   2 mode      the most frequent valid value, ties to the smallest; none valid -> nodata.  Integer kinds only
+ * satcv_raster_tiles (TILED=YES, BLOCKSIZE, PREDICTOR=2 of the COG driver):
+ *   src contiguous (h, w_, c) -> dst (nty * ntx, blocksize, blocksize, c), tile-major (tiles row-major), pixel-interleaved, same kind;
+ *   nty = ceil(h / blocksize), ntx = ceil(w_ / blocksize); blocksize a multiple of 16, tile bytes below 2^30.  Samples outside the image
+ *   are nodata (0 without).  predictor != 0 (integer kinds only): every sample but those of the first pixel of a tile row becomes
+ *   itself minus the same band of the pixel to its left, modulo 2^bits, both taken from the padded tile before any subtraction. */
+typedef struct satcv_raster_desc {
+  const void* src; int32_t src_kind;
+  int32_t h, w_, c, ld, coff;
+  void* dst; int32_t dst_kind;
+  float scale;
+  int32_t has_nodata; double nodata;
+  int32_t resampling;
+  int32_t blocksize, predictor;
+} satcv_raster_desc;
+int satcv_raster_convert(const satcv_raster_desc* d, void* stream);
+int satcv_raster_overview(const satcv_raster_desc* d, void* stream);
+int satcv_raster_tiles(const satcv_raster_desc* d, void* stream);
+/* satcv_lzw_tiles (COMPRESS=LZW of :405 / :455): n tiles of tile_bytes each (contiguous, 16-byte aligned, tile_bytes a multiple of 16
+ * below 2^30) -> tile i's stream at dst + i * (2 * tile_bytes + 16), its length in sizes[i]; bytes of a slot past sizes[i] are
+ * unspecified.  The slot is enough for any input: a code is at most 12 bits and consumes at least one byte, plus one Clear per 3836
+ * codes, the opening Clear and EOI.  One wavefront per tile, the dictionary in LDS.
+ * The stream is TIFF 6.0 section 13 LZW, made unique by: MSB-first packing; Clear (256) first, at 9 bits; greedy longest match, first
+ * free code 258; after an entry is added: next free code 4094 -> Clear at the current width and start over at 9 bits, 512 / 1024 / 2048
+ * -> one bit wider (libtiff's "early change"); after the last data code the same counter step once more; then EOI (257), zero-padded
+ * to a byte.  libtiff decodes it; libtiff's own encoder adds ratio-driven Clears, so its bytes differ.
+ * satcv_lzw_encode_host: the same coder on a HOST buffer (n >= 0 bytes below 2^30).  *size receives the length of the stream; when it
+ * exceeds cap the call fails and nothing is written past dst + cap. */
+int satcv_lzw_tiles(const void* src, int32_t n, int64_t tile_bytes, void* dst, int32_t* sizes, void* stream);
+int satcv_lzw_encode_host(const void* src, int64_t n, void* dst, int64_t cap, int64_t* size);
+/* satcv_bytes_compact: the first sizes[i] bytes of slot i (slots + i * slot_bytes) -> dst + offsets[i], i < n; sizes and offsets are
+ * device arrays, the offsets computed by the host from the sizes it read back (every tile of a TIFF starts on an even offset).  A byte
+ * that would land outside [0, dst_bytes) is not written.  The result is the file's tile payload: one device-to-host copy. */
+int satcv_bytes_compact(const void* slots, int64_t slot_bytes, const int32_t* sizes, const int64_t* offsets, int32_t n, void* dst,
+                        int64_t dst_bytes, void* stream);
+
 /* ------------------------------------------------------------------ losses
  * Each writes loss_out[0] += mean loss contribution (caller zeroes) and
  * dlogits = dL/dlogits (through the head activation).

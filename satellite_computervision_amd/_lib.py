@@ -88,6 +88,13 @@ class CompositeMaskedDesc(C.Structure):
     _fields_ = [('base', CompositeDesc), ('clear', c_vp), ('cs', c_i32), ('band_idx', c_i32 * 16)]
 
 
+class RasterDesc(C.Structure):
+    """satcv_raster_desc: one descriptor for satcv_raster_convert / _overview / _tiles"""
+    _fields_ = [('src', c_vp), ('src_kind', c_i32), ('h', c_i32), ('w_', c_i32), ('c', c_i32), ('ld', c_i32), ('coff', c_i32),
+                ('dst', c_vp), ('dst_kind', c_i32), ('scale', c_f32), ('has_nodata', c_i32), ('nodata', C.c_double),
+                ('resampling', c_i32), ('blocksize', c_i32), ('predictor', c_i32)]
+
+
 RECORD_MAX_PLANES = 32     # SATCV_RECORD_MAX_PLANES of include/satcv.h
 RECORD_STAT_SPLITS = 16    # SATCV_RECORD_STAT_SPLITS
 _i32p, _f32p = c_i32 * RECORD_MAX_PLANES, c_f32 * RECORD_MAX_PLANES
@@ -297,6 +304,12 @@ _SIGS = {
     'satcv_median_composite': (C.c_int, [C.POINTER(CompositeDesc), c_vp]),
     'satcv_quality_mask': (C.c_int, [C.POINTER(QualityDesc), c_vp]),
     'satcv_median_composite_masked': (C.c_int, [C.POINTER(CompositeMaskedDesc), c_vp]),
+    'satcv_raster_convert': (C.c_int, [C.POINTER(RasterDesc), c_vp]),
+    'satcv_raster_overview': (C.c_int, [C.POINTER(RasterDesc), c_vp]),
+    'satcv_raster_tiles': (C.c_int, [C.POINTER(RasterDesc), c_vp]),
+    'satcv_lzw_tiles': (C.c_int, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp]),
+    'satcv_lzw_encode_host': (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.POINTER(c_i64)]),
+    'satcv_bytes_compact': (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
     'satcv_record_stats': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_record_to_tuple': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_label_onehot': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),

@@ -1,0 +1,394 @@
+// The device half of the Cloud-Optimized GeoTIFF writer (raster_tools.write_cog): what numpy_to_raster / arrays_to_cog
+// (utils/raster_tools.py:367-461) and write_geotiff_prediction(s) (utils/prediction_tools.py:447-536) leave to rasterio and GDAL's COG
+// driver, on a map that is already resident.
+//   satcv_raster_convert   dtype conversion with nodata (rasterio's astype + `nodata`)                      one thread per sample
+//   satcv_raster_overview  one level of the overview pyramid, nearest / average / mode, nodata-aware          one thread per sample
+//   satcv_raster_tiles     tile-major, pixel-interleaved layout with TIFF predictor 2                         one thread per sample
+//   satcv_lzw_tiles        TIFF LZW of every tile at once (COMPRESS=LZW): ONE WAVEFRONT PER TILE.  The coder (lzw_core.hpp) is sequential,
+//                          so every lane of the wave runs it on the same values -- control flow is wave-uniform by construction -- with
+//                          the dictionary in LDS (32 KB: four tiles per CU).  What the lanes share is the memory traffic: a 1 KB input
+//                          chunk arrives by one 16-byte load per lane, the packed codes leave by one 16-byte store per lane per KB,
+//                          and the table is emptied by all lanes at a Clear.
+//   satcv_bytes_compact    the compressed tiles, each in its slot, gathered to their file offsets: one device-to-host copy of the payload
+//   satcv_lzw_encode_host  the same coder on the CPU (a host function, as satcv_crc32c is)
+// Every kernel is a grid-stride loop over 64-bit indices; descriptors are refused on the host before any launch.
+#include "common.hpp"
+#include "lzw_core.hpp"
+#include <cmath>
+#include <cstring>
+#include <limits>
+
+namespace {
+
+constexpr int RS_BLOCK = 256;
+constexpr int RS_MAX_GRID = 1 << 16;
+constexpr int LZ_CHUNK = 1024;       // bytes per input chunk and per output flush: 64 lanes x 16 bytes
+
+int grid_for(long long items) {
+  long long g = (items + RS_BLOCK - 1) / RS_BLOCK;
+  return (int)(g < 1 ? 1 : g > RS_MAX_GRID ? RS_MAX_GRID : g);
+}
+
+// ---------------------------------------------------------------- kinds
+template <typename F>
+int by_kind(int kind, F&& f) {
+  switch (kind) {
+    case 0: return f(uint8_t{});
+    case 1: return f(uint16_t{});
+    case 2: return f(float{});
+    case 3: return f(int16_t{});
+    default: return f(int32_t{});
+  }
+}
+bool kind_ok(int k) { return k == 0 || k == 1 || k == 2 || k == 3 || k == 5; }
+int kind_bytes(int k) { return k == 0 ? 1 : (k == 1 || k == 3) ? 2 : 4; }
+
+// nodata in the destination kind (integers: saturated, NaN -> 0)
+template <typename T>
+T nodata_as(double v) {
+  if constexpr (std::is_same<T, float>::value) return (float)v;
+  else {
+    if (!(v == v)) return 0;
+    const double lo = (double)std::numeric_limits<T>::min(), hi = (double)std::numeric_limits<T>::max();
+    return (T)(v < lo ? lo : v > hi ? hi : v);
+  }
+}
+
+// ---------------------------------------------------------------- convert
+template <typename S, typename D>
+__device__ __forceinline__ D convert_one(S v, float scale, bool has_nd, D nd) {
+  if constexpr (std::is_same<D, float>::value) {
+    if constexpr (std::is_same<S, float>::value) return scale != 0.f ? v * scale : v;
+    else return (float)v;
+  } else if constexpr (std::is_same<S, float>::value) {
+    const float t = scale != 0.f ? v * scale : v;
+    if (t != t) return has_nd ? nd : (D)0;
+    const float r = rintf(t);                                        // half to even
+    const float lo = (float)std::numeric_limits<D>::min(), hi = (float)std::numeric_limits<D>::max();      // (float)INT32_MAX is 2^31: >= saturates
+    if (r <= lo) return std::numeric_limits<D>::min();
+    if (r >= hi) return std::numeric_limits<D>::max();
+    return (D)r;
+  } else {
+    const long long x = (long long)v, lo = (long long)std::numeric_limits<D>::min(), hi = (long long)std::numeric_limits<D>::max();
+    return (D)(x < lo ? lo : x > hi ? hi : x);
+  }
+}
+
+template <typename S, typename D>
+__global__ __launch_bounds__(RS_BLOCK) void convert_kernel(const S* __restrict__ src, D* __restrict__ dst, long long total, int c, int ld, int coff,
+                                                            float scale, int has_nd, D nd) {
+  for (long long i = (long long)blockIdx.x * RS_BLOCK + threadIdx.x; i < total; i += (long long)gridDim.x * RS_BLOCK) {
+    const long long p = i / c;
+    const int b = (int)(i - p * c);
+    dst[i] = convert_one<S, D>(src[p * ld + coff + b], scale, has_nd != 0, nd);
+  }
+}
+
+// ---------------------------------------------------------------- overview
+template <typename T>
+__device__ __forceinline__ bool sample_valid(T v, bool has_nd, T nd) {
+  if constexpr (std::is_same<T, float>::value) return v == v && !(has_nd && v == nd);
+  else return !(has_nd && v == nd);
+}
+
+template <typename T>
+__global__ __launch_bounds__(RS_BLOCK) void overview_kernel(const T* __restrict__ src, T* __restrict__ dst, int h, int w, int c, int oh, int ow,
+                                                             int resampling, int has_nd, T nd) {
+  const long long total = (long long)oh * ow * c;
+  for (long long i = (long long)blockIdx.x * RS_BLOCK + threadIdx.x; i < total; i += (long long)gridDim.x * RS_BLOCK) {
+    const long long p = i / c;
+    const int b = (int)(i - p * c), oy = (int)(p / ow), ox = (int)(p - (long long)oy * ow);
+    const int y0 = 2 * oy, x0 = 2 * ox;                    // always inside the image
+    if (resampling == 0) {
+      dst[i] = src[((long long)y0 * w + x0) * c + b];
+      continue;
+    }
+    T v[4];
+    int n = 0;                                            // the valid samples of the block, row-major
+    for (int dy = 0; dy < 2; ++dy)
+      for (int dx = 0; dx < 2; ++dx) {
+        const int y = y0 + dy, x = x0 + dx;
+        if (y < h && x < w) {
+          const T s = src[((long long)y * w + x) * c + b];
+          if (sample_valid(s, has_nd != 0, nd)) v[n++] = s;
+        }
+      }
+    T out;
+    if (n == 0) {
+      if constexpr (std::is_same<T, float>::value) out = has_nd ? nd : NAN;
+      else out = nd;                                      // (integers without nodata always have a valid sample)
+    } else if (resampling == 1) {
+      if constexpr (std::is_same<T, float>::value) {
+        float s = v[0];
+        for (int k = 1; k < n; ++k) s = s + v[k];
+        out = s / (float)n;
+      } else {
+        long long s = 0;
+        for (int k = 0; k < n; ++k) s += (long long)v[k];
+        const long long num = 2 * s + n, den = 2 * n;
+        long long q = num / den;
+        if (num % den < 0) --q;                           // floor
+        out = (T)q;
+      }
+    } else {
+      int best = 0;
+      out = v[0];
+      for (int k = 0; k < n; ++k) {
+        int cnt = 0;
+        for (int j = 0; j < n; ++j) cnt += v[j] == v[k];
+        if (cnt > best || (cnt == best && v[k] < out)) { best = cnt; out = v[k]; }
+      }
+    }
+    dst[i] = out;
+  }
+}
+
+// ---------------------------------------------------------------- tiles
+// U: the unsigned integer of the sample's width -- the predictor's arithmetic is modular in it, and a float passes as its bits
+template <typename U>
+__global__ __launch_bounds__(RS_BLOCK) void tiles_kernel(const U* __restrict__ src, U* __restrict__ dst, int h, int w, int c, int bs, int ntx,
+                                                          long long total, int predictor, U fill) {
+  for (long long i = (long long)blockIdx.x * RS_BLOCK + threadIdx.x; i < total; i += (long long)gridDim.x * RS_BLOCK) {
+    long long r = i / c;
+    const int b = (int)(i - r * c);
+    const int px = (int)(r % bs);
+    r /= bs;
+    const int py = (int)(r % bs);
+    const long long tile = r / bs;
+    const int ty = (int)(tile / ntx), tx = (int)(tile - (long long)ty * ntx);
+    const int y = ty * bs + py, x = tx * bs + px;
+    const bool row_in = y < h;
+    const U cur = (row_in && x < w) ? src[((long long)y * w + x) * c + b] : fill;
+    U out = cur;
+    if (predictor && px > 0) {
+      const U left = (row_in && x - 1 < w) ? src[((long long)y * w + (x - 1)) * c + b] : fill;
+      out = (U)(cur - left);
+    }
+    dst[i] = out;
+  }
+}
+
+// ---------------------------------------------------------------- LZW, one wavefront per tile
+struct DevSink {
+  unsigned char* buf;          // LZ_CHUNK bytes of LDS
+  unsigned char* gdst;         // the tile's slot
+  long long flushed, slot_bytes;
+  int pos, lane;
+  __device__ __forceinline__ void flush() {                // every lane of the wave is here: the coder's state is wave-uniform
+    __syncthreads();
+    const long long off = flushed + lane * 16;
+    if (lane * 16 < pos && off + 16 <= slot_bytes) *reinterpret_cast<uint4*>(gdst + off) = *reinterpret_cast<const uint4*>(buf + lane * 16);
+    __syncthreads();
+    flushed += pos;
+    pos = 0;
+  }
+  __device__ __forceinline__ void byte(unsigned b) {
+    buf[pos++] = (unsigned char)b;
+    if (pos == LZ_CHUNK) flush();
+  }
+  __device__ __forceinline__ void clear(uint32_t* table) {
+    __syncthreads();
+    for (int k = lane; k < satcv_lzw::SLOTS; k += 64) table[k] = satcv_lzw::EMPTY;
+    __syncthreads();
+  }
+};
+
+__global__ __launch_bounds__(64) void lzw_tiles_kernel(const unsigned char* __restrict__ src, int n, long long tile_bytes, unsigned char* __restrict__ dst,
+                                                        long long slot_bytes, int* __restrict__ sizes) {
+  __shared__ __attribute__((aligned(16))) uint32_t table[satcv_lzw::SLOTS];
+  __shared__ __attribute__((aligned(16))) unsigned char in[LZ_CHUNK];
+  __shared__ __attribute__((aligned(16))) unsigned char outb[LZ_CHUNK];
+  const int lane = threadIdx.x;
+  for (int tile = blockIdx.x; tile < n; tile += gridDim.x) {
+    const unsigned char* s = src + (long long)tile * tile_bytes;
+    DevSink sink{outb, dst + (long long)tile * slot_bytes, 0, slot_bytes, 0, lane};
+    satcv_lzw::Coder<DevSink> coder;
+    coder.table = table;
+    coder.sink = &sink;
+    coder.start();
+    for (long long base = 0; base < tile_bytes; base += LZ_CHUNK) {
+      __syncthreads();                                     // the previous chunk is consumed
+      const long long off = base + lane * 16;
+      if (off + 16 <= tile_bytes) *reinterpret_cast<uint4*>(in + lane * 16) = *reinterpret_cast<const uint4*>(s + off);      // tile_bytes % 16 == 0
+      __syncthreads();
+      const int m = (int)(tile_bytes - base < LZ_CHUNK ? tile_bytes - base : LZ_CHUNK);      // a multiple of 16
+      for (int k = 0; k < m; k += 16) {                    // one LDS read per 16 input bytes: the probe is the only LDS latency per byte
+        const uint4 q = *reinterpret_cast<const uint4*>(in + k);
+        const unsigned w4[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) coder.feed((w4[j >> 2] >> (8 * (j & 3))) & 0xffu);
+      }
+    }
+    coder.finish();
+    const long long size = sink.flushed + sink.pos;
+    sink.flush();
+    if (lane == 0) sizes[tile] = (int)size;
+    __syncthreads();                                       // the next tile reuses the LDS buffers
+  }
+}
+
+// ---------------------------------------------------------------- compaction
+__global__ __launch_bounds__(RS_BLOCK) void compact_kernel(const unsigned char* __restrict__ slots, long long slot_bytes, const int* __restrict__ sizes,
+                                                            const long long* __restrict__ offsets, int n, long long chunks, unsigned char* __restrict__ dst,
+                                                            long long dst_bytes) {
+  constexpr int PER = 16;                                  // bytes per thread and item
+  const long long items = (long long)n * chunks;
+  for (long long it = blockIdx.x; it < items; it += gridDim.x) {
+    const int tile = (int)(it / chunks);
+    const long long first = (it - (long long)tile * chunks) * (RS_BLOCK * PER);
+    long long size = sizes[tile];
+    size = size < 0 ? 0 : size > slot_bytes ? slot_bytes : size;
+    const long long to = offsets[tile];
+    const unsigned char* s = slots + (long long)tile * slot_bytes;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const long long j = first + (long long)k * RS_BLOCK + threadIdx.x;
+      if (j < size && to >= 0 && to + j < dst_bytes) dst[to + j] = s[j];
+    }
+  }
+}
+
+struct HostSink {
+  unsigned char* dst;
+  long long cap, pos;
+  void byte(unsigned b) {
+    if (pos < cap) dst[pos] = (unsigned char)b;
+    ++pos;
+  }
+  void clear(uint32_t* table) { memset(table, 0xff, sizeof(uint32_t) * satcv_lzw::SLOTS); }
+};
+
+int launched(const char* who) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    satcv_set_error("%s launch: %s", who, hipGetErrorString(e));
+    return SATCV_ERR_HIP;
+  }
+  return SATCV_OK;
+}
+
+// what the three raster entries share; same_kind: overview and tiles keep the kind and read a contiguous raster
+int check_raster(const satcv_raster_desc* d, const char* who, bool same_kind) {
+  SATCV_CHECK(d && d->src && d->dst, "%s: null pointer (descriptor, src or dst)", who);
+  SATCV_CHECK(kind_ok(d->src_kind) && kind_ok(d->dst_kind), "%s: unknown kind %d -> %d (0 u8, 1 u16, 2 f32, 3 i16, 5 i32)", who, d->src_kind, d->dst_kind);
+  SATCV_CHECK(d->h > 0 && d->w_ > 0 && d->c > 0, "%s: sizes must be positive", who);
+  SATCV_CHECK(d->c <= 16, "%s: c = %d bands (at most 16)", who, d->c);
+  SATCV_CHECK(satcv_pixels_ok(1, d->h, d->w_, 1), "%s: map beyond 2^31 pixels", who);
+  SATCV_CHECK(d->ld > 0 && d->coff >= 0 && (long long)d->coff + d->c <= d->ld, "%s: channel range (coff + c <= ld)", who);
+  SATCV_CHECK((uintptr_t)d->src % kind_bytes(d->src_kind) == 0 && (uintptr_t)d->dst % kind_bytes(d->dst_kind) == 0, "%s: misaligned pointer", who);
+  if (same_kind) {
+    SATCV_CHECK(d->src_kind == d->dst_kind, "%s: keeps the kind (src_kind %d, dst_kind %d)", who, d->src_kind, d->dst_kind);
+    SATCV_CHECK(d->ld == d->c && d->coff == 0, "%s: reads a contiguous raster (ld == c, coff == 0)", who);
+  }
+  return SATCV_OK;
+}
+
+}  // namespace
+
+extern "C" int satcv_raster_convert(const satcv_raster_desc* d, void* stream) {
+  const int rc = check_raster(d, "raster_convert", false);
+  if (rc != SATCV_OK) return rc;
+  SATCV_CHECK(d->scale == 0.f || d->src_kind == 2, "raster_convert: scale is for f32 sources");
+  const long long total = (long long)d->h * d->w_ * d->c;
+  const hipStream_t st = (hipStream_t)stream;
+  by_kind(d->src_kind, [&](auto sv) {
+    using S = decltype(sv);
+    return by_kind(d->dst_kind, [&](auto dv) {
+      using D = decltype(dv);
+      hipLaunchKernelGGL((convert_kernel<S, D>), dim3(grid_for(total)), dim3(RS_BLOCK), 0, st, (const S*)d->src, (D*)d->dst, total, d->c, d->ld, d->coff,
+                         d->scale, d->has_nodata, nodata_as<D>(d->nodata));
+      return 0;
+    });
+  });
+  return launched("raster_convert");
+}
+
+extern "C" int satcv_raster_overview(const satcv_raster_desc* d, void* stream) {
+  const int rc = check_raster(d, "raster_overview", true);
+  if (rc != SATCV_OK) return rc;
+  SATCV_CHECK(d->resampling >= 0 && d->resampling <= 2, "raster_overview: resampling %d (0 nearest, 1 average, 2 mode)", d->resampling);
+  SATCV_CHECK(!(d->resampling == 2 && d->src_kind == 2), "raster_overview: mode resampling is for integer kinds");
+  const int oh = (d->h + 1) / 2, ow = (d->w_ + 1) / 2;
+  const long long total = (long long)oh * ow * d->c;
+  const hipStream_t st = (hipStream_t)stream;
+  by_kind(d->src_kind, [&](auto tv) {
+    using T = decltype(tv);
+    hipLaunchKernelGGL((overview_kernel<T>), dim3(grid_for(total)), dim3(RS_BLOCK), 0, st, (const T*)d->src, (T*)d->dst, d->h, d->w_, d->c, oh, ow,
+                       d->resampling, d->has_nodata, nodata_as<T>(d->nodata));
+    return 0;
+  });
+  return launched("raster_overview");
+}
+
+extern "C" int satcv_raster_tiles(const satcv_raster_desc* d, void* stream) {
+  const int rc = check_raster(d, "raster_tiles", true);
+  if (rc != SATCV_OK) return rc;
+  const int bs = d->blocksize, eb = kind_bytes(d->src_kind);
+  SATCV_CHECK(bs > 0 && bs % 16 == 0, "raster_tiles: blocksize %d is not a positive multiple of 16", bs);
+  SATCV_CHECK(bs <= (1 << 15) && (long long)bs * bs * d->c * eb < (1LL << 30), "raster_tiles: blocksize %d gives tiles of 2^30 bytes or more", bs);
+  SATCV_CHECK(!(d->predictor && d->src_kind == 2), "raster_tiles: the predictor is for integer kinds");
+  const int ntx = (d->w_ + bs - 1) / bs, nty = (d->h + bs - 1) / bs;
+  const long long total = (long long)nty * ntx * bs * bs * d->c;
+  const hipStream_t st = (hipStream_t)stream;
+  uint32_t fill = 0;                                       // the bits of nodata in the kind, 0 without
+  if (d->has_nodata)
+    by_kind(d->src_kind, [&](auto tv) {
+      using T = decltype(tv);
+      const T v = nodata_as<T>(d->nodata);
+      memcpy(&fill, &v, sizeof(T));
+      return 0;
+    });
+  const dim3 grid(grid_for(total)), block(RS_BLOCK);
+  if (eb == 1)
+    hipLaunchKernelGGL((tiles_kernel<uint8_t>), grid, block, 0, st, (const uint8_t*)d->src, (uint8_t*)d->dst, d->h, d->w_, d->c, bs, ntx, total, d->predictor, (uint8_t)fill);
+  else if (eb == 2)
+    hipLaunchKernelGGL((tiles_kernel<uint16_t>), grid, block, 0, st, (const uint16_t*)d->src, (uint16_t*)d->dst, d->h, d->w_, d->c, bs, ntx, total, d->predictor, (uint16_t)fill);
+  else
+    hipLaunchKernelGGL((tiles_kernel<uint32_t>), grid, block, 0, st, (const uint32_t*)d->src, (uint32_t*)d->dst, d->h, d->w_, d->c, bs, ntx, total, d->predictor, fill);
+  return launched("raster_tiles");
+}
+
+extern "C" int satcv_lzw_tiles(const void* src, int32_t n, int64_t tile_bytes, void* dst, int32_t* sizes, void* stream) {
+  SATCV_CHECK(src && dst && sizes, "lzw_tiles: null pointer (src, dst or sizes)");
+  SATCV_CHECK(n > 0, "lzw_tiles: n = %d tiles", n);
+  SATCV_CHECK(tile_bytes > 0 && tile_bytes < (1LL << 30), "lzw_tiles: tile_bytes = %lld (1 ... 2^30 - 1)", (long long)tile_bytes);
+  SATCV_CHECK(tile_bytes % 16 == 0, "lzw_tiles: tile_bytes = %lld is not a multiple of 16", (long long)tile_bytes);
+  SATCV_CHECK((uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0, "lzw_tiles: src and dst must be 16-byte aligned");
+  const long long slot = 2 * tile_bytes + 16;
+  const int grid = n < 4096 ? n : 4096;                    // four tiles per CU are resident; the rest is a grid-stride loop
+  hipLaunchKernelGGL(lzw_tiles_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, (const unsigned char*)src, n, (long long)tile_bytes, (unsigned char*)dst, slot, sizes);
+  return launched("lzw_tiles");
+}
+
+extern "C" int satcv_bytes_compact(const void* slots, int64_t slot_bytes, const int32_t* sizes, const int64_t* offsets, int32_t n, void* dst,
+                                   int64_t dst_bytes, void* stream) {
+  SATCV_CHECK(slots && sizes && offsets && dst, "bytes_compact: null pointer (slots, sizes, offsets or dst)");
+  SATCV_CHECK(n > 0, "bytes_compact: n = %d slots", n);
+  SATCV_CHECK(slot_bytes > 0 && slot_bytes <= (1LL << 31) + 16, "bytes_compact: slot_bytes = %lld", (long long)slot_bytes);
+  SATCV_CHECK(dst_bytes > 0, "bytes_compact: dst_bytes = %lld", (long long)dst_bytes);
+  const long long chunks = (slot_bytes + RS_BLOCK * 16 - 1) / (RS_BLOCK * 16);
+  const long long items = (long long)n * chunks;
+  const int grid = (int)(items > RS_MAX_GRID ? RS_MAX_GRID : items);
+  hipLaunchKernelGGL(compact_kernel, dim3(grid), dim3(RS_BLOCK), 0, (hipStream_t)stream, (const unsigned char*)slots, (long long)slot_bytes, sizes,
+                     (const long long*)offsets, n, chunks, (unsigned char*)dst, (long long)dst_bytes);
+  return launched("bytes_compact");
+}
+
+extern "C" int satcv_lzw_encode_host(const void* src, int64_t n, void* dst, int64_t cap, int64_t* size) {
+  SATCV_CHECK(size, "lzw_encode_host: null pointer (size)");
+  *size = 0;
+  SATCV_CHECK((src || n == 0) && (dst || cap == 0), "lzw_encode_host: null pointer (src or dst)");
+  SATCV_CHECK(n >= 0 && n < (1LL << 30) && cap >= 0, "lzw_encode_host: n = %lld bytes (below 2^30), cap = %lld", (long long)n, (long long)cap);
+  uint32_t table[satcv_lzw::SLOTS];
+  HostSink sink{(unsigned char*)dst, cap, 0};
+  satcv_lzw::Coder<HostSink> coder;
+  coder.table = table;
+  coder.sink = &sink;
+  coder.start();
+  const unsigned char* s = (const unsigned char*)src;
+  for (int64_t i = 0; i < n; ++i) coder.feed(s[i]);
+  coder.finish();
+  *size = sink.pos;                                        // the size the stream needs, also when it did not fit
+  SATCV_CHECK(sink.pos <= cap, "lzw_encode_host: the stream needs %lld bytes, cap = %lld", (long long)sink.pos, (long long)cap);
+  return SATCV_OK;
+}

@@ -168,7 +168,8 @@ def median_composite(stack, times=None, offsets=None, fill=None, out=None, chann
 
 
 def predict_change(before, after, m, before_times=None, after_times=None, buff=128, kernel=256, batch_size=16, channel=0,
-                   cover='reference', fill=None, quality=None, band_names=None, bands=None):
+                   cover='reference', fill=None, quality=None, band_names=None, bands=None, out_file=None, transform=None, crs=None,
+                   cog_options=None):
     """`run_local` (utils/pc_tools.py:620-668) from the two time stacks on: `(output, bef_median, aft_median)` -- the change map
     (H, W) float32 and the two median composites (H, W, C) float32 as host arrays (the reference's return without the geotransform).
 
@@ -181,10 +182,23 @@ def predict_change(before, after, m, before_times=None, after_times=None, buff=1
     (maskTOA :288), 'sr' (maskSR :270), 'mask' (mask :257), any rule set `ee_tools.rule_set` takes (these need band_names, the names of
     the planes), or a pair of `ee_tools.ClearMask`s (before, after).  bands: the planes the model sees, see `median_composite`; the
     returned medians are the masked composites of those bands.
+    out_file: also write the change map as a Cloud-Optimized GeoTIFF (`raster_tools.write_cog`, float32 unless cog_options says
+    otherwise) straight from the device map, where the reference hands its array to numpy_to_raster; needs transform (a, b, c, d, e, f)
+    and crs ('EPSG:n' or an int).  cog_options: a dict of further `write_cog` arguments (dtype, scale, nodata, compress, ...).  The
+    return value is unchanged.
     The composites stay on the device from the composite kernel to the stitch; the three returned arrays are the only copies back."""
     import torch
     from . import prediction_tools as pt
     from .prediction_tools import _device_empty
+    if out_file is not None:
+        from . import raster_tools as rt
+        if transform is None or crs is None:
+            raise ValueError('out_file needs transform and crs')
+        rt.parse_crs(crs)
+        if len(tuple(transform)) != 6:
+            raise ValueError(f'transform is six numbers (a, b, c, d, e, f), got {len(tuple(transform))}')
+    elif transform is not None or crs is not None or cog_options:
+        raise ValueError('transform, crs and cog_options describe out_file, which is not given')
     if getattr(before, 'ndim', 0) != 4 or getattr(after, 'ndim', 0) != 4 or tuple(before.shape[1:]) != tuple(after.shape[1:]):
         raise ValueError(f'before and after must be (T, C, H, W) stacks of equal C, H, W, got {tuple(before.shape)} and {tuple(after.shape)}')
     cs, H, W = (int(v) for v in before.shape[1:])
@@ -219,5 +233,10 @@ def predict_change(before, after, m, before_times=None, after_times=None, buff=1
     bef_median, aft_median = medians
     if two_inputs:
         scene = (norms[1], norms[0])
-    output = pt.predict_scene(scene, m, kernel=kernel, buff=buff, batch_size=batch_size, channel=channel, cover=cover)
+    if out_file is None:
+        output = pt.predict_scene(scene, m, kernel=kernel, buff=buff, batch_size=batch_size, channel=channel, cover=cover)
+    else:
+        dev_map = pt.predict_scene(scene, m, kernel=kernel, buff=buff, batch_size=batch_size, channel=channel, cover=cover, device=True)
+        rt.write_cog(dev_map, out_file, transform, crs, **dict(cog_options or {}))
+        output = dev_map.cpu().numpy()
     return output, bef_median.cpu().numpy(), aft_median.cpu().numpy()

@@ -334,14 +334,22 @@ class _Maps:
         self.out = _device_empty((H, W, self.nc), torch.float32, 'the prediction map', 0.0)
         self.cls = _device_empty((H, W, 1), torch.uint8, 'the class map', 255) if want_classes else None
 
-    def host(self, channel):
-        """the one copy back: the (H, W) map of an int channel or (H, W, n_classes), with a class map the pair (map, (H, W) uint8)"""
-        probs = (self.out if channel is None else self.out[..., 0]).cpu().numpy()
-        return probs if self.cls is None else (probs, self.cls[..., 0].cpu().numpy())
+    def host(self, channel, device=False):
+        """the one copy back: the (H, W) map of an int channel or (H, W, n_classes), with a class map the pair (map, (H, W) uint8).
+        device=True: no copy, the same shapes as views of the CUDA tensors held here (what raster_tools.write_cog reads in place)"""
+        probs = self.out if channel is None else self.out[..., 0]
+        cls = None if self.cls is None else self.cls[..., 0]
+        if not device:
+            probs, cls = probs.cpu().numpy(), (None if cls is None else cls.cpu().numpy())
+        return probs if cls is None else (probs, cls)
 
 
-def _empty_result(H, W, channel, ncls, classes):
+def _empty_result(H, W, channel, ncls, classes, device=False):
     """what a predictor returns for a scene too small for one reference chip: nothing is predicted"""
+    if device:
+        import torch
+        probs = _device_empty((H, W) if channel is not None else (H, W, ncls), torch.float32, 'the prediction map', 0.0)
+        return (probs, _device_empty((H, W), torch.uint8, 'the class map', 255)) if classes else probs
     probs = np.zeros((H, W) if channel is not None else (H, W, ncls), np.float32)
     return (probs, np.full((H, W), 255, np.uint8)) if classes else probs
 
@@ -400,7 +408,7 @@ def _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, channel, want_cl
     return _stitch_batches(idx, origins, batch_size, kernel, off, maps, gather, forward)
 
 
-def predict_chips_device(arr, chip_indices, template, m, kernel=256, buff=128, batch_size=16, channel=0, rescale=None):
+def predict_chips_device(arr, chip_indices, template, m, kernel=256, buff=128, batch_size=16, channel=0, rescale=None, device=False):
     """`predict_chips` with the scene and the prediction map resident on the device: same signature, same result.
 
     The scene(s) go to the device once in their own dtype (uint8 / uint16 / int16 / float32; `rescale` divides an integer scene in
@@ -414,20 +422,25 @@ def predict_chips_device(arr, chip_indices, template, m, kernel=256, buff=128, b
     * centres that overlap (legal in both) are summed in float32 on the device, in list order, before they meet the template, where
       `predict_chips` adds each in the template's dtype.
     `arr` may be the two-date pair (arr_a, arr_b), as for `predict_chips`.  A scene that is already resident -- a contiguous float32 CUDA
-    tensor (H, W, C), e.g. from `pc_tools.median_composite` -- is read in place.  An empty index list returns `template` untouched."""
+    tensor (H, W, C), e.g. from `pc_tools.median_composite` -- is read in place.  An empty index list returns `template` untouched.
+    device=True: nothing is copied back and `template` is neither read nor changed (it may be None): the return value is the (H, W)
+    float32 CUDA map itself, the values `template` would receive, zero where no chip lands."""
     scenes, _ = _scenes(arr)
     _check_geometry(kernel, buff, batch_size)
     idx = [(int(y), int(x)) for y, x in chip_indices]
     if not idx:
-        return template
+        return _empty_result(scenes[0].shape[0], scenes[0].shape[1], 0, 1, False, True) if device else template
     if scenes[0].ndim != 3:
         raise ValueError(f'expected an (H, W, C) scene, got shape {scenes[0].shape}')
     _check_windows(idx, scenes[0].shape[0], scenes[0].shape[1], kernel, buff // 2)
-    template += _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, int(channel), False, rescale).host(int(channel))
+    maps = _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, int(channel), False, rescale)
+    if device:
+        return maps.host(int(channel), True)
+    template += maps.host(int(channel))
     return template
 
 
-def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover='reference', classes=False, rescale=None):
+def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover='reference', classes=False, rescale=None, device=False):
     """Prediction map of a whole (H, W, C) scene (or two-date pair of scenes), stitched on the device; returns new arrays.
 
     cover='reference': the chips of `generate_chip_indices` -- the buff // 2 border and a last chip ending on the image edge stay
@@ -437,7 +450,9 @@ def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover=
     once.  Needs H, W >= kernel + buff (one reflection then suffices), else ValueError.
     channel: int -> (H, W) float32; None -> (H, W, n_classes).  classes=True returns (map, class map (H, W) uint8) from the model's
     second output (ValueError for a single-output model).  The returned arrays are the only device-to-host traffic.  A scene may be a
-    contiguous float32 CUDA tensor (H, W, C), read in place."""
+    contiguous float32 CUDA tensor (H, W, C), read in place.
+    device=True: nothing is copied back; the same shapes come as CUDA tensors (float32 map, uint8 class map with 255 where nothing is
+    predicted -- the nodata of `raster_tools.write_cog`, which reads them where they lie)."""
     scenes, _ = _scenes(arr)
     _check_geometry(kernel, buff, batch_size)
     if scenes[0].ndim != 3:
@@ -447,9 +462,9 @@ def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover=
     if classes and len(getattr(m, 'outputs', ())) < 2:
         raise ValueError('classes=True needs a model with a class output next to its probabilities')
     if not idx:
-        return _empty_result(H, W, channel, m.outputs[0].channels, classes)
+        return _empty_result(H, W, channel, m.outputs[0].channels, classes, device)
     channel = None if channel is None else int(channel)
-    return _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, channel, classes, rescale).host(channel)
+    return _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, channel, classes, rescale).host(channel, device)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -458,7 +473,7 @@ def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover=
 # (predict_on_device(..., shape=...)) and satcv_scene_scatter stitches the centres.  DESIGN.md, "Scene prediction for the time-series
 # models".
 def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=0, cover='reference', classes=False, maxval=10000,
-                         harmonics=None, plan=None):
+                         harmonics=None, plan=None, device=False):
     """Prediction map of a (T, C, H, W) time stack -- the layout of the LSTMDataGenerator files and of `pc_tools.median_composite`'s
     input -- by a ConvLSTM2D time-series model (get_lstm_model, get_lstm_autoencoder), stitched on the device; returns new arrays.
 
@@ -477,7 +492,7 @@ def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=
     batches run through its preallocated, graph-replayed forward; a short last batch fills a prefix of the plan's input, the stale rest
     is computed and ignored.
     The returned arrays are the only device-to-host traffic; hybrid and hierarchical models (two inputs at two resolutions) go through
-    `predict_hybrid_scene`."""
+    `predict_hybrid_scene`.  device=True: as for `predict_scene`, the results stay on the device."""
     from .lstm_tools import LSTMAutoencoder
     _check_geometry(kernel, buff, batch_size)
     _, H, W = _check_stack(stack, m)
@@ -495,13 +510,13 @@ def predict_series_scene(stack, m, kernel=256, buff=128, batch_size=16, channel=
     if classes and (is_ae or not getattr(m, 'class_output', True)):
         raise ValueError("classes=True needs a model with a class output: an LSTMModel with activation='softmax'")
     if not idx:
-        return _empty_result(H, W, channel, m.n_classes, classes)
+        return _empty_result(H, W, channel, m.n_classes, classes, device)
     channel = None if channel is None else int(channel)
     _channel_range(channel, m.n_classes)
     side = kernel + 2 * (buff // 2)
     want = (min(batch_size, len(idx)), m.n_time, side, side)
     plan = _resolve_plan(plan, m, want, lambda: m.inference_plan(want), 'SeriesInferPlan', 'shape')
-    return _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, classes, maxval, harmonics, plan).host(channel)
+    return _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, classes, maxval, harmonics, plan).host(channel, device)
 
 
 def _stitch_series(stack, idx, m, kernel, buff, batch_size, channel, want_classes, maxval, harmonics, plan=None):
@@ -598,7 +613,7 @@ def _hybrid_head(m, output):
 
 
 def predict_hybrid_scene(scene, stack, m, kernel=256, buff=128, batch_size=16, channel=0, cover='reference', classes=False, rescale=None,
-                         maxval=10000, output=None, plan=None):
+                         maxval=10000, output=None, plan=None, device=False):
     """Prediction map of a fine (H, W, C) scene together with a coarse (T, c, h, w) time stack by a two-resolution model
     (get_hybrid_model, get_hierarchical_model), stitched on the device; returns new arrays.
 
@@ -614,7 +629,8 @@ def predict_hybrid_scene(scene, stack, m, kernel=256, buff=128, batch_size=16, c
     HybridInferPlan of this model and these sizes is used as given (HybridModel only: NotImplementedError for a hierarchical model, whose
     ACNN trunk lives on the tape).
     Per batch the model stops before its last dense layer; satcv_dense_scene_fwd computes that layer on the chip centres and stores
-    them into the map.  The returned arrays are the only device-to-host traffic."""
+    them into the map.  The returned arrays are the only device-to-host traffic.  device=True: as for `predict_scene`, the results stay
+    on the device."""
     import torch
     from .lstm_tools import HierarchicalModel
     head, multiple = _hybrid_head(m, output)
@@ -635,7 +651,7 @@ def predict_hybrid_scene(scene, stack, m, kernel=256, buff=128, batch_size=16, c
     if plan is not None and plan is not False and isinstance(m, HierarchicalModel):
         raise NotImplementedError('plan: HybridInferPlan covers HybridModel; the ACNN trunk of a HierarchicalModel lives on the tape')
     if not len(hi):
-        return _empty_result(H, W, channel, ncls, classes)
+        return _empty_result(H, W, channel, ncls, classes, device)
     want = (min(int(batch_size), len(hi)), geo['side'], geo['side_lo'])
 
     def build():
@@ -645,7 +661,7 @@ def predict_hybrid_scene(scene, stack, m, kernel=256, buff=128, batch_size=16, c
             raise MemoryError(f'a HybridInferPlan for (batch, side, side_lo) = {want} does not fit in device memory; lower batch_size') from e
     plan = _resolve_plan(plan, m, want, build, 'HybridInferPlan', '(batch, side, side_lo) =')
     return _stitch_hybrid(scene, stack, hi, lo, geo, m, head, output, int(kernel), int(batch_size), channel, bool(classes), rescale, maxval,
-                          plan).host(channel)
+                          plan).host(channel, device)
 
 
 def _stitch_hybrid(scene, stack, hi, lo, geo, m, head, output, kernel, batch_size, channel, want_classes, rescale, maxval, plan):
@@ -695,17 +711,12 @@ def _stitch_hybrid(scene, stack, hi, lo, geo, m, head, output, kernel, batch_siz
     return _stitch_batches(hi, org_hi, batch_size, kernel, off, maps, gather, forward)
 
 
-def callback_predictions(imageDataset, model, mixer, kernel_shape=[256, 256], kernel_buffer=[128, 128]):
-    """utils/prediction_tools.py:245-291 without its prints: predict mixer['totalPatches'] patches, keep the probability of class 1 and
-    assemble the cropped patches into a mosaic of mixer['patchesPerRow'] patches per row; returns the (rows, columns) float32 mosaic.
-
-    The crop and the placement are those of `_patch_grid` (as coded in the reference: each axis starts at its own half buffer and stops
-    at its kernel size plus the OTHER axis' half buffer; patch i lands at mosaic row i // patchesPerRow, column i % patchesPerRow; a
-    trailing partial row is dropped).  imageDataset: an (N, h, w, c) array or an iterable of batches.  The patches are cropped and
-    placed on the device by the scatter kernel; the mosaic is the only copy back."""
+def _device_mosaic(imageDataset, model, patches, cols, channel, grid_of):
+    """The batch loop of `callback_predictions`: predict `patches` patches and place the kept window of channel `channel` of each into a
+    device-resident (rows, columns, 1) float32 mosaic, which is returned.  grid_of(patch_hw) -> (crop, origins, mosaic_hw) as
+    `_patch_grid` returns them.  The patches are cropped and placed on the device by the scatter kernel."""
     import torch
     from .model_tools import _as_batches
-    patches, cols = int(mixer['totalPatches']), int(mixer['patchesPerRow'])
     multi = len(getattr(model, 'inputs', ())) > 1
     batches, _ = _as_batches(imageDataset, None, 16)
     grid = origins = mosaic = None
@@ -718,16 +729,79 @@ def callback_predictions(imageDataset, model, mixer, kernel_shape=[256, 256], ke
         if probs.dtype != torch.float32 or not probs.is_contiguous():
             probs = probs.to(torch.float32).contiguous()
         if grid is None:
-            if probs.shape[-1] < 2:
-                raise ValueError('callback_predictions writes the probability of class 1: the model has a single output channel')
-            grid, place, hw = _patch_grid(patches, cols, probs.shape[1:3], kernel_shape, kernel_buffer)
+            if probs.shape[-1] <= channel:
+                raise ValueError(f'the mosaic holds output channel {channel}: the model has {probs.shape[-1]} output channel(s)')
+            grid, place, hw = grid_of(probs.shape[1:3])
             origins = _origin_table(place)
-            mosaic = _device_empty(hw + (1,), torch.float32, 'the mosaic', 0.0)
+            mosaic = _device_empty(tuple(hw) + (1,), torch.float32, 'the mosaic', 0.0)
         n = min(probs.shape[0], len(place) - filled)
-        _scatter(probs, 0, n, grid, origins, len(place), filled, mosaic, 0, 1, 1, False)
+        _scatter(probs, 0, n, grid, origins, len(place), filled, mosaic, 0, channel, 1, False)
         filled += n
         if filled >= len(place):
             break
     if grid is None or filled < len(place):
         raise ValueError(f'the dataset ended after {filled} patches, mixer announces {patches}')
+    return mosaic
+
+
+def callback_predictions(imageDataset, model, mixer, kernel_shape=[256, 256], kernel_buffer=[128, 128]):
+    """utils/prediction_tools.py:245-291 without its prints: predict mixer['totalPatches'] patches, keep the probability of class 1 and
+    assemble the cropped patches into a mosaic of mixer['patchesPerRow'] patches per row; returns the (rows, columns) float32 mosaic.
+
+    The crop and the placement are those of `_patch_grid` (as coded in the reference: each axis starts at its own half buffer and stops
+    at its kernel size plus the OTHER axis' half buffer; patch i lands at mosaic row i // patchesPerRow, column i % patchesPerRow; a
+    trailing partial row is dropped).  imageDataset: an (N, h, w, c) array or an iterable of batches.  The patches are cropped and
+    placed on the device by the scatter kernel; the mosaic is the only copy back."""
+    patches, cols = int(mixer['totalPatches']), int(mixer['patchesPerRow'])
+    mosaic = _device_mosaic(imageDataset, model, patches, cols, 1, lambda hw: _patch_grid(patches, cols, hw, kernel_shape, kernel_buffer))
     return mosaic[..., 0].cpu().numpy()
+
+
+def _mixer_georeference(jsonFile):
+    """(mixer dict, transform (a, b, c, d, e, f), crs) of an Earth-Engine mixer file: projection.affine.doubleMatrix and projection.crs"""
+    import json
+    with open(jsonFile) as file:
+        mixer = json.load(file)
+    transform = tuple(float(v) for v in mixer['projection']['affine']['doubleMatrix'][0:6])
+    return mixer, transform, mixer['projection']['crs']
+
+
+def _plain_blocksize(H, W):
+    return min(512, -(-max(int(H), int(W)) // 16) * 16)
+
+
+def write_geotiff_prediction(image, jsonFile, aoi):
+    """utils/prediction_tools.py:447-472: write `image` -- (H, W) or (H, W, C), a host array or a CUDA tensor -- as f'{aoi}.tif' with the
+    georeference of the Earth-Engine mixer file `jsonFile`: uncompressed, no overviews, no nodata tag, in the image's own dtype (float64
+    becomes float32), as rasterio's defaults give it there.  The file is tiled where the reference's is written in strips; readers do
+    not care.  Returns the path."""
+    from . import raster_tools as rt
+    _, transform, crs = _mixer_georeference(jsonFile)
+    H, W = image.shape[:2]
+    return rt.write_cog(image, f'{aoi}.tif', transform, crs, nodata=None, compress=None, overviews=0, blocksize=_plain_blocksize(H, W))
+
+
+def write_geotiff_predictions(imageDataset, model, jsonFile, outImgBase, outImgPath, kernel_buffer=[128, 128]):
+    """utils/prediction_tools.py:475-536 without its prints: predict the mixer's totalPatches patches, keep output channel 0 of each
+    without its buffer (rows y_buffer : y_buffer + patchDimensions[0], columns x_buffer : x_buffer + patchDimensions[1], :520), place patch
+    i at row i // patchesPerRow, column i % patchesPerRow of a float32 mosaic, and write it as join(outImgPath, f'{outImgBase}.tif') with
+    the mixer's georeference -- uncompressed and without overviews, as `write_geotiff_prediction`.  The mosaic is assembled on the
+    device by the scatter kernel of `callback_predictions` and written from there; returns the path.
+    (Where the reference calls `model.predict` once per patch, the patches run in batches.)"""
+    from os.path import join
+    from . import raster_tools as rt
+    mixer, transform, crs = _mixer_georeference(jsonFile)
+    cols, patches = int(mixer['patchesPerRow']), int(mixer['totalPatches'])
+    rows = int(patches / cols)
+    kh, kw = (int(v) for v in mixer['patchDimensions'][:2])
+    x_buffer, y_buffer = int(kernel_buffer[0] / 2), int(kernel_buffer[1] / 2)
+    if cols < 1 or rows < 1:
+        raise ValueError(f'totalPatches={patches} does not fill one mosaic row of patchesPerRow={cols}')
+
+    def grid_of(patch_hw):
+        if y_buffer + kh > patch_hw[0] or x_buffer + kw > patch_hw[1]:
+            raise ValueError(f'a {patch_hw[0]} x {patch_hw[1]} patch does not hold patchDimensions {kh} x {kw} behind buffers {y_buffer}, {x_buffer}')
+        return (y_buffer, x_buffer, kh, kw), [((i // cols) * kh, (i % cols) * kw) for i in range(rows * cols)], (rows * kh, cols * kw)
+    mosaic = _device_mosaic(imageDataset, model, rows * cols, cols, 0, grid_of)
+    out_image_file = join(outImgPath, f'{outImgBase}.tif')
+    return rt.write_cog(mosaic, out_image_file, transform, crs, nodata=None, compress=None, overviews=0, blocksize=_plain_blocksize(rows * kh, cols * kw))
