@@ -808,6 +808,50 @@ int satcv_lzw_encode_host(const void* src, int64_t n, void* dst, int64_t cap, in
 int satcv_bytes_compact(const void* slots, int64_t slot_bytes, const int32_t* sizes, const int64_t* offsets, int32_t n, void* dst,
                         int64_t dst_bytes, void* stream);
 
+/* ------------------------------------------------------------------ GeoTIFF / COG reader: the device half
+ * What rasterio's `open().read(window=)` and rioxarray's `open_rasterio` (utils/pc_tools.py:131-186, 328-386) do to the blocks of a
+ * file, with the result resident on the device: the mirror image of the writer above.  The container is parsed on the host
+ * (raster_tools.read_info), the compressed blocks go up in one copy.
+ *
+ * satcv_lzw_decode_tiles: n compressed slices payload[offsets[i], offsets[i] + sizes[i]) (offsets and sizes are device arrays; a slice
+ * may start at any byte and is clipped to [0, payload_bytes)) -> block i at dst + i * dst_stride, at most block_bytes of it, the count
+ * in lengths[i] (lengths may be NULL), and status[i]:
+ *   0 ok          EOI was read, or block_bytes bytes are out (a stream need not end with EOI)
+ *   1 truncated   the slice ended inside a code, or before either of the above
+ *   2 bad code    a code above the next free one, or a non-literal first code after a Clear
+ *   3 overlong    a code whose string would pass block_bytes
+ * Bytes of a block past lengths[i] are not written, bytes outside a slice are not read.  Accepted: every TIFF 6.0 section 13 stream
+ * libtiff accepts -- MSB-first codes; widths 9 -> 10 once the next free code is 511, then 1023, 2047 ("early change"); a Clear
+ * anywhere; no Clear at the start; no EOI; a full table (no more entries, the width stays 12).  Not the LSB-first "old-style" variant.
+ * One wavefront per block; no loop bound depends on the data.  dst_stride >= block_bytes; a 16-byte aligned slot is written 16 bytes
+ * per lane.
+ * satcv_lzw_decode_host: the same decoder on HOST buffers: n bytes of stream -> at most cap bytes at dst, the count in *size, the
+ * status above in *status.  The return value is SATCV_OK whenever the arguments were usable, whatever the stream held. */
+int satcv_lzw_decode_tiles(const void* payload, int64_t payload_bytes, const int64_t* offsets, const int32_t* sizes, int32_t n, int64_t block_bytes,
+                           void* dst, int64_t dst_stride, int32_t* status, int32_t* lengths, void* stream);
+int satcv_lzw_decode_host(const void* src, int64_t n, void* dst, int64_t cap, int64_t* size, int32_t* status);
+/* satcv_raster_untile, the inverse of satcv_raster_tiles: decoded blocks -> the window (row0, col0, h, w_) of the image, resident.
+ *   src         decoded block j (j < nblocks) at src + j * src_stride: (bh, bw, spp) samples for planar 1, (bh, bw) for planar 2; a strip
+ *               is a block of the image's width and RowsPerStrip rows
+ *   blocks      device array: blocks[j] is block j's index in the file's block list -- row-major with `across` blocks per row, and for
+ *               planar 2 band after band, per_plane blocks each.  Only the blocks the window touches need to be there
+ *   predictor   2 (integer kinds only): a running sum along every block row, per band, modulo 2^bits, from the block's first pixel on
+ *               -- also when the window starts to its right.  One wavefront per block row; without a predictor one thread per sample
+ *   dst         layout 0: (h, w_, ld), sample of band b at channel coff + band_map[b]; layout 1: (ld, h, w_), plane coff + band_map[b].
+ *               band_map[b] = -1 drops band b.  Samples outside the window are dropped, those of edge blocks outside the image with them
+ * Refused on the host before any launch: unknown kinds, spp > 16, a planar configuration other than 1 or 2, a predictor other than 0 or
+ * 2 or on f32, blocks of 2^30 bytes and more, a window beyond 2^31 pixels, channels outside ld, misaligned pointers. */
+typedef struct satcv_untile_desc {
+  const void* src; int64_t src_stride;
+  const int32_t* blocks; int32_t nblocks;
+  int32_t bh, bw, across, per_plane;
+  int32_t spp, planar, kind, predictor;
+  int32_t row0, col0, h, w_;
+  void* dst; int32_t layout, ld, coff;
+  int32_t band_map[16];
+} satcv_untile_desc;
+int satcv_raster_untile(const satcv_untile_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ losses
  * Each writes loss_out[0] += mean loss contribution (caller zeroes) and
  * dlogits = dL/dlogits (through the head activation).

@@ -95,6 +95,13 @@ class RasterDesc(C.Structure):
                 ('resampling', c_i32), ('blocksize', c_i32), ('predictor', c_i32)]
 
 
+class UntileDesc(C.Structure):
+    """satcv_untile_desc: decoded blocks -> a window of a resident raster (satcv_raster_untile)"""
+    _fields_ = [('src', c_vp), ('src_stride', c_i64), ('blocks', c_vp), ('nblocks', c_i32), ('bh', c_i32), ('bw', c_i32), ('across', c_i32),
+                ('per_plane', c_i32), ('spp', c_i32), ('planar', c_i32), ('kind', c_i32), ('predictor', c_i32), ('row0', c_i32), ('col0', c_i32),
+                ('h', c_i32), ('w_', c_i32), ('dst', c_vp), ('layout', c_i32), ('ld', c_i32), ('coff', c_i32), ('band_map', c_i32 * 16)]
+
+
 RECORD_MAX_PLANES = 32     # SATCV_RECORD_MAX_PLANES of include/satcv.h
 RECORD_STAT_SPLITS = 16    # SATCV_RECORD_STAT_SPLITS
 _i32p, _f32p = c_i32 * RECORD_MAX_PLANES, c_f32 * RECORD_MAX_PLANES
@@ -310,6 +317,9 @@ _SIGS = {
     'satcv_lzw_tiles': (C.c_int, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp]),
     'satcv_lzw_encode_host': (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.POINTER(c_i64)]),
     'satcv_bytes_compact': (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    'satcv_lzw_decode_tiles': (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    'satcv_lzw_decode_host': (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.POINTER(c_i64), C.POINTER(c_i32)]),
+    'satcv_raster_untile': (C.c_int, [C.POINTER(UntileDesc), c_vp]),
     'satcv_record_stats': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_record_to_tuple': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_label_onehot': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),

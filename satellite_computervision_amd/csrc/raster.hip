@@ -11,6 +11,15 @@
 //                          and the table is emptied by all lanes at a Clear.
 //   satcv_bytes_compact    the compressed tiles, each in its slot, gathered to their file offsets: one device-to-host copy of the payload
 //   satcv_lzw_encode_host  the same coder on the CPU (a host function, as satcv_crc32c is)
+// and the device half of the reader (raster_tools.read_cog), the mirror image:
+//   satcv_lzw_decode_tiles TIFF LZW of every block at once, ONE WAVEFRONT PER BLOCK, the decoder of lzw_core.hpp with wave-uniform control
+//                          flow.  The dictionary is (position in the output, length) per code (24 KB of LDS); a code is a copy of `len`
+//                          bytes from an earlier output position, done by the 64 lanes together.  The last 16 KB of output live in an LDS
+//                          ring that leaves in 1 KB pieces, one 16-byte store per lane; a copy whose source has left the ring reads it
+//                          back from global memory, where it was stored at least one flush -- one __syncthreads() -- ago.  DESIGN.md,
+//                          "Reading GeoTIFFs", has the LDS budget and the memory-ordering argument.
+//   satcv_lzw_decode_host  the same decoder on the CPU
+//   satcv_raster_untile    decoded blocks -> a window of a resident raster, predictor 2 undone by one wavefront per block row
 // Every kernel is a grid-stride loop over 64-bit indices; descriptors are refused on the host before any launch.
 #include "common.hpp"
 #include "lzw_core.hpp"
@@ -227,6 +236,181 @@ __global__ __launch_bounds__(64) void lzw_tiles_kernel(const unsigned char* __re
   }
 }
 
+// ---------------------------------------------------------------- LZW decode, one wavefront per block
+constexpr int LZ_RING = 16384;       // bytes of output kept in LDS; a string is at most 4096 - 257 bytes, a flush lags by less than LZ_CHUNK
+
+// the compressed slice starts anywhere: chunk c holds the bytes of the 16-byte-aligned window [c * LZ_CHUNK, (c + 1) * LZ_CHUNK) counted
+// from the slice start rounded down to 16; a 16-byte group that lies wholly inside the slice comes by one load per lane, the head and
+// the tail byte by byte, so nothing outside the slice is read
+struct DevSource {
+  unsigned char* in;           // LZ_CHUNK bytes of LDS
+  const unsigned char* g;      // the slice
+  long long size;
+  int shift, lane;             // g - shift is 16-byte aligned
+  long long chunk, word_at;    // what `in` and `word` hold (-1: nothing)
+  uint32_t word;
+  __device__ __forceinline__ void load(long long c) {      // every lane of the wave is here
+    __syncthreads();
+    const long long first = c * LZ_CHUNK + lane * 16 - shift;      // slice index of this lane's group
+    if (first >= 0 && first + 16 <= size) *reinterpret_cast<uint4*>(in + lane * 16) = *reinterpret_cast<const uint4*>(g + first);
+    else
+      for (int k = 0; k < 16; ++k)
+        if (first + k >= 0 && first + k < size) in[lane * 16 + k] = g[first + k];
+    __syncthreads();
+    chunk = c;
+  }
+  __device__ __forceinline__ unsigned byte(long long i) {
+    const long long v = i + shift;
+    if ((v >> 10) != chunk) load(v >> 10);
+    if ((v >> 2) != word_at) {
+      word = *reinterpret_cast<const uint32_t*>(in + (v & (LZ_CHUNK - 4)));
+      word_at = v >> 2;
+    }
+    return (word >> (8 * (int)(v & 3))) & 0xffu;
+  }
+};
+
+struct DevDecSink {
+  unsigned char* ring;         // LZ_RING bytes of LDS: output byte p lives at ring[p % LZ_RING] until p + LZ_RING bytes are out
+  unsigned char* gdst;         // the block's slot (read back by `copy`: not __restrict__)
+  long long flushed;           // bytes of the block in global memory, a multiple of LZ_CHUNK; every flush ended with a barrier
+  int lane;
+  bool wide;                   // gdst is 16-byte aligned
+  __device__ __forceinline__ void flush() {
+    const long long at = flushed + lane * 16;
+    if (wide) *reinterpret_cast<uint4*>(gdst + at) = *reinterpret_cast<const uint4*>(ring + (at & (LZ_RING - 1)));
+    else
+      for (int k = 0; k < 16; ++k) gdst[at + k] = ring[(at + k) & (LZ_RING - 1)];
+    flushed += LZ_CHUNK;
+    __syncthreads();           // workgroup-scope fence: these stores are visible to the wave's later loads
+  }
+  // the bytes up to `end` are in the ring: make them visible to the next code's reads, then let full KBs leave
+  __device__ __forceinline__ void wrote(long long end) {
+    __syncthreads();
+    for (int r = 0; r < satcv_lzw::TABLE / LZ_CHUNK + 1; ++r)
+      if (flushed + LZ_CHUNK <= end) flush();
+  }
+  __device__ __forceinline__ void literal(long long at, unsigned b) {
+    ring[at & (LZ_RING - 1)] = (unsigned char)b;
+    wrote(at + 1);
+  }
+  // The source [from, from + len) was written by earlier codes.  It is still in the ring when from + LZ_RING >= at + len (this code's own
+  // bytes then overwrite nothing of it); otherwise from + len < at + 2 len - LZ_RING <= at - 8192 < flushed: it is read from the slot.
+  __device__ __forceinline__ void copy(long long from, int len, long long at, bool wrap) {
+    const bool in_ring = from + LZ_RING >= at + len;
+    for (int r = 0; r < satcv_lzw::TABLE; r += 64) {
+      const int j = r + lane;
+      if (j < len) {
+        const long long q = from + ((wrap && j == len - 1) ? 0 : j);
+        ring[(at + j) & (LZ_RING - 1)] = in_ring ? ring[q & (LZ_RING - 1)] : gdst[q];
+      }
+      if (r + 64 >= len) break;                            // (len is wave-uniform)
+    }
+    wrote(at + len);
+  }
+  __device__ __forceinline__ void finish(long long n) {    // the tail below one KB, byte by byte
+    for (long long j = flushed + lane; j < n; j += 64) gdst[j] = ring[j & (LZ_RING - 1)];
+    __syncthreads();
+  }
+};
+
+__global__ __launch_bounds__(64) void lzw_decode_kernel(const unsigned char* __restrict__ payload, long long payload_bytes, const long long* __restrict__ offsets,
+                                                         const int* __restrict__ sizes, int n, long long block_bytes, long long dst_stride, unsigned char* dst,
+                                                         int* __restrict__ status, int* __restrict__ lengths) {
+  __shared__ __attribute__((aligned(16))) uint32_t pos[satcv_lzw::TABLE];
+  __shared__ __attribute__((aligned(16))) uint16_t len[satcv_lzw::TABLE];
+  __shared__ __attribute__((aligned(16))) unsigned char ring[LZ_RING];
+  __shared__ __attribute__((aligned(16))) unsigned char in[LZ_CHUNK];
+  const int lane = threadIdx.x;
+  for (int blk = blockIdx.x; blk < n; blk += gridDim.x) {
+    long long off = offsets[blk], size = sizes[blk];
+    if (off < 0 || off > payload_bytes || size < 0) { off = 0; size = 0; }      // a slice is clipped to the payload: it then ends as truncated
+    if (size > payload_bytes - off) size = payload_bytes - off;
+    unsigned char* g = dst + (long long)blk * dst_stride;
+    DevSource source{in, payload + off, size, (int)((uintptr_t)(payload + off) & 15), lane, -1, -1, 0u};
+    DevDecSink sink{ring, g, 0, lane, ((uintptr_t)g & 15) == 0};
+    satcv_lzw::Decoder<DevSource, DevDecSink> dec{pos, len, &source, &sink};
+    long long produced = 0;
+    const int st = dec.run(size, block_bytes, &produced);
+    sink.finish(produced);
+    if (lane == 0) {
+      status[blk] = st;
+      if (lengths) lengths[blk] = (int)produced;
+    }
+    __syncthreads();                                       // the next block reuses the LDS buffers
+  }
+}
+
+// ---------------------------------------------------------------- untile
+struct UntileAt {
+  bool ok;
+  long long to;
+};
+// where sample (py, px, band) of decoded block j goes: the window test, the band map, the destination layout
+__device__ __forceinline__ UntileAt untile_at(const satcv_untile_desc& d, int t, int py, int px, int b) {
+  UntileAt r{false, 0};
+  if (t < 0) return r;
+  int plane = 0;
+  if (d.planar == 2) { plane = t / d.per_plane; t -= plane * d.per_plane; }
+  const int by = t / d.across, bx = t - by * d.across;
+  const long long y = (long long)by * d.bh + py - d.row0, x = (long long)bx * d.bw + px - d.col0;
+  const int band = d.planar == 2 ? plane : b;
+  if (y < 0 || y >= d.h || x < 0 || x >= d.w_ || band >= d.spp) return r;
+  const int m = d.band_map[band];
+  if (m < 0) return r;
+  r.ok = true;
+  r.to = d.layout == 0 ? (y * d.w_ + x) * d.ld + d.coff + m : ((long long)(d.coff + m) * d.h + y) * d.w_ + x;
+  return r;
+}
+
+template <typename U>
+__global__ __launch_bounds__(RS_BLOCK) void untile_kernel(satcv_untile_desc d, int cb, long long total) {
+  const unsigned char* src = (const unsigned char*)d.src;
+  U* dst = (U*)d.dst;
+  for (long long i = (long long)blockIdx.x * RS_BLOCK + threadIdx.x; i < total; i += (long long)gridDim.x * RS_BLOCK) {
+    long long r = i / cb;
+    const int b = (int)(i - r * cb);
+    const int px = (int)(r % d.bw);
+    r /= d.bw;
+    const int py = (int)(r % d.bh);
+    const long long j = r / d.bh;
+    const UntileAt a = untile_at(d, d.blocks[j], py, px, b);
+    if (a.ok) dst[a.to] = reinterpret_cast<const U*>(src + j * d.src_stride)[((long long)py * d.bw + px) * cb + b];
+  }
+}
+
+// predictor 2: one wavefront per block row; per band a 64-lane inclusive scan with a carry between rounds, from the block's first pixel on
+template <typename U>
+__global__ __launch_bounds__(RS_BLOCK) void untile_scan_kernel(satcv_untile_desc d, int cb, long long rows) {
+  const unsigned char* src = (const unsigned char*)d.src;
+  U* dst = (U*)d.dst;
+  const int lane = threadIdx.x & 63, waves = RS_BLOCK / 64;
+  for (long long it = (long long)blockIdx.x * waves + (threadIdx.x >> 6); it < rows; it += (long long)gridDim.x * waves) {
+    const long long j = it / d.bh;
+    const int py = (int)(it - j * d.bh);
+    const int t = d.blocks[j];
+    const U* row = reinterpret_cast<const U*>(src + j * d.src_stride) + (long long)py * d.bw * cb;
+    for (int b = 0; b < cb; ++b) {
+      uint32_t carry = 0;
+      for (int px0 = 0; px0 < d.bw; px0 += 64) {
+        const int px = px0 + lane;
+        uint32_t v = px < d.bw ? (uint32_t)row[(long long)px * cb + b] : 0u;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+          const uint32_t up = __shfl_up(v, s, 64);
+          if (lane >= s) v += up;
+        }
+        v += carry;
+        carry = __shfl(v, 63, 64);
+        if (px < d.bw) {
+          const UntileAt a = untile_at(d, t, py, px, b);
+          if (a.ok) dst[a.to] = (U)v;
+        }
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- compaction
 __global__ __launch_bounds__(RS_BLOCK) void compact_kernel(const unsigned char* __restrict__ slots, long long slot_bytes, const int* __restrict__ sizes,
                                                             const long long* __restrict__ offsets, int n, long long chunks, unsigned char* __restrict__ dst,
@@ -256,6 +440,18 @@ struct HostSink {
     ++pos;
   }
   void clear(uint32_t* table) { memset(table, 0xff, sizeof(uint32_t) * satcv_lzw::SLOTS); }
+};
+
+struct HostSource {
+  const unsigned char* src;
+  unsigned byte(long long i) const { return src[i]; }
+};
+struct HostDecSink {
+  unsigned char* dst;
+  void literal(long long at, unsigned b) { dst[at] = (unsigned char)b; }
+  void copy(long long from, int len, long long at, bool wrap) {
+    for (int j = 0; j < len; ++j) dst[at + j] = dst[from + ((wrap && j == len - 1) ? 0 : j)];
+  }
 };
 
 int launched(const char* who) {
@@ -391,4 +587,81 @@ extern "C" int satcv_lzw_encode_host(const void* src, int64_t n, void* dst, int6
   *size = sink.pos;                                        // the size the stream needs, also when it did not fit
   SATCV_CHECK(sink.pos <= cap, "lzw_encode_host: the stream needs %lld bytes, cap = %lld", (long long)sink.pos, (long long)cap);
   return SATCV_OK;
+}
+
+extern "C" int satcv_lzw_decode_tiles(const void* payload, int64_t payload_bytes, const int64_t* offsets, const int32_t* sizes, int32_t n, int64_t block_bytes,
+                                      void* dst, int64_t dst_stride, int32_t* status, int32_t* lengths, void* stream) {
+  SATCV_CHECK(payload && offsets && sizes && dst && status, "lzw_decode_tiles: null pointer (payload, offsets, sizes, dst or status)");
+  SATCV_CHECK(n > 0, "lzw_decode_tiles: n = %d blocks", n);
+  SATCV_CHECK(payload_bytes > 0, "lzw_decode_tiles: payload_bytes = %lld", (long long)payload_bytes);
+  SATCV_CHECK(block_bytes > 0 && block_bytes < (1LL << 30), "lzw_decode_tiles: block_bytes = %lld (1 ... 2^30 - 1)", (long long)block_bytes);
+  SATCV_CHECK(dst_stride >= block_bytes && dst_stride < (1LL << 31), "lzw_decode_tiles: dst_stride = %lld is below block_bytes = %lld (or 2^31 and more)",
+              (long long)dst_stride, (long long)block_bytes);
+  SATCV_CHECK((uintptr_t)offsets % 8 == 0 && (uintptr_t)sizes % 4 == 0 && (uintptr_t)status % 4 == 0 && (uintptr_t)lengths % 4 == 0,
+              "lzw_decode_tiles: misaligned pointer (offsets, sizes, status or lengths)");
+  const int grid = n < 4096 ? n : 4096;                    // three blocks per CU are resident (41 KB of LDS each); the rest is a grid-stride loop
+  hipLaunchKernelGGL(lzw_decode_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, (const unsigned char*)payload, (long long)payload_bytes,
+                     (const long long*)offsets, sizes, n, (long long)block_bytes, (long long)dst_stride, (unsigned char*)dst, status, lengths);
+  return launched("lzw_decode_tiles");
+}
+
+extern "C" int satcv_lzw_decode_host(const void* src, int64_t n, void* dst, int64_t cap, int64_t* size, int32_t* status) {
+  SATCV_CHECK(size && status, "lzw_decode_host: null pointer (size or status)");
+  *size = 0;
+  *status = satcv_lzw::DEC_TRUNCATED;
+  SATCV_CHECK((src || n == 0) && (dst || cap == 0), "lzw_decode_host: null pointer (src or dst)");
+  SATCV_CHECK(n >= 0 && n < (1LL << 31) && cap >= 0 && cap < (1LL << 30), "lzw_decode_host: n = %lld bytes (below 2^31), cap = %lld (below 2^30)", (long long)n,
+              (long long)cap);
+  uint32_t pos[satcv_lzw::TABLE];
+  uint16_t len[satcv_lzw::TABLE];
+  HostSource source{(const unsigned char*)src};
+  HostDecSink sink{(unsigned char*)dst};
+  satcv_lzw::Decoder<HostSource, HostDecSink> dec{pos, len, &source, &sink};
+  long long produced = 0;
+  *status = dec.run(n, cap, &produced);
+  *size = produced;
+  return SATCV_OK;
+}
+
+extern "C" int satcv_raster_untile(const satcv_untile_desc* d, void* stream) {
+  SATCV_CHECK(d && d->src && d->dst && d->blocks, "raster_untile: null pointer (descriptor, src, dst or blocks)");
+  SATCV_CHECK(kind_ok(d->kind), "raster_untile: unknown kind %d (0 u8, 1 u16, 2 f32, 3 i16, 5 i32)", d->kind);
+  SATCV_CHECK(d->nblocks > 0 && d->bh > 0 && d->bw > 0 && d->across > 0 && d->h > 0 && d->w_ > 0, "raster_untile: sizes must be positive");
+  SATCV_CHECK(d->spp > 0 && d->spp <= 16, "raster_untile: spp = %d bands (1 ... 16)", d->spp);
+  SATCV_CHECK(d->planar == 1 || (d->planar == 2 && d->per_plane > 0), "raster_untile: planar = %d (1 pixel-interleaved, 2 one block sequence per band with per_plane > 0)", d->planar);
+  SATCV_CHECK(d->predictor == 0 || d->predictor == 2, "raster_untile: predictor %d (0 or 2)", d->predictor);
+  SATCV_CHECK(!(d->predictor && d->kind == 2), "raster_untile: the predictor is for integer kinds");
+  SATCV_CHECK(d->layout == 0 || d->layout == 1, "raster_untile: layout %d (0 (h, w, c), 1 (c, h, w))", d->layout);
+  SATCV_CHECK(d->row0 >= 0 && d->col0 >= 0, "raster_untile: the window starts at (%d, %d)", d->row0, d->col0);
+  SATCV_CHECK(satcv_pixels_ok(1, d->h, d->w_, 1), "raster_untile: window beyond 2^31 pixels");
+  const int eb = kind_bytes(d->kind), cb = d->planar == 1 ? d->spp : 1;
+  const long long block_bytes = (long long)d->bh * d->bw * cb * eb;
+  SATCV_CHECK(d->bh <= (1 << 20) && d->bw <= (1 << 20) && block_bytes < (1LL << 30), "raster_untile: blocks of %d x %d give 2^30 bytes or more", d->bh, d->bw);
+  SATCV_CHECK(d->src_stride >= block_bytes && d->src_stride % eb == 0, "raster_untile: src_stride = %lld (at least the block's %lld bytes, a multiple of the sample's)",
+              (long long)d->src_stride, block_bytes);
+  SATCV_CHECK((uintptr_t)d->src % eb == 0 && (uintptr_t)d->dst % eb == 0 && (uintptr_t)d->blocks % 4 == 0, "raster_untile: misaligned pointer");
+  SATCV_CHECK(d->ld > 0 && d->coff >= 0 && d->coff < d->ld, "raster_untile: channel range (0 <= coff < ld)");
+  int used = 0;
+  for (int b = 0; b < d->spp; ++b) {
+    const int m = d->band_map[b];
+    SATCV_CHECK(m >= -1 && (long long)d->coff + m < d->ld, "raster_untile: band_map[%d] = %d (-1: dropped, else coff + band_map < ld)", b, m);
+    used += m >= 0;
+  }
+  SATCV_CHECK(used > 0, "raster_untile: band_map keeps no band");
+  const hipStream_t st = (hipStream_t)stream;
+  if (d->predictor) {
+    const long long rows = (long long)d->nblocks * d->bh;
+    const long long g = (rows + RS_BLOCK / 64 - 1) / (RS_BLOCK / 64);
+    const dim3 grid((unsigned)(g > RS_MAX_GRID ? RS_MAX_GRID : g)), block(RS_BLOCK);
+    if (eb == 1) hipLaunchKernelGGL((untile_scan_kernel<uint8_t>), grid, block, 0, st, *d, cb, rows);
+    else if (eb == 2) hipLaunchKernelGGL((untile_scan_kernel<uint16_t>), grid, block, 0, st, *d, cb, rows);
+    else hipLaunchKernelGGL((untile_scan_kernel<uint32_t>), grid, block, 0, st, *d, cb, rows);
+  } else {
+    const long long total = (long long)d->nblocks * d->bh * d->bw * cb;
+    const dim3 grid(grid_for(total)), block(RS_BLOCK);
+    if (eb == 1) hipLaunchKernelGGL((untile_kernel<uint8_t>), grid, block, 0, st, *d, cb, total);
+    else if (eb == 2) hipLaunchKernelGGL((untile_kernel<uint16_t>), grid, block, 0, st, *d, cb, total);
+    else hipLaunchKernelGGL((untile_kernel<uint32_t>), grid, block, 0, st, *d, cb, total);
+  }
+  return launched("raster_untile");
 }

@@ -467,6 +467,35 @@ def predict_scene(arr, m, kernel=256, buff=128, batch_size=16, channel=0, cover=
     return _stitch_on_device(scenes, idx, m, kernel, buff, batch_size, channel, classes, rescale).host(channel, device)
 
 
+def predict_raster(in_file, m, out_file, window=None, cog_options=None, **predict_scene_kwargs):
+    """File to file: `raster_tools.read_cog` -> `predict_scene(..., device=True)` -> `raster_tools.write_cog`, the pixels never on the host
+    uncompressed; returns what `predict_scene` returns (CUDA tensors).
+
+    in_file: a GeoTIFF / COG `read_cog` reads; window: (row0, col0, h, w) of it, None: all.  The scene is predicted in float32: an integer
+    file is cast on the device (satcv_raster_convert, exact for 8- and 16-bit samples).  out_file: the prediction map (the first result of
+    `predict_scene`) as a Cloud-Optimized GeoTIFF that carries the source's transform -- of the window -- and CRS; cog_options: a dict of
+    further `write_cog` arguments (dtype, scale, nodata, compress, ...).  predict_scene_kwargs: kernel, buff, batch_size, channel, cover,
+    classes, rescale.  ValueError when the file carries no transform or no EPSG code."""
+    import ctypes as C
+    import torch
+    from . import ops, raster_tools as rt
+    from ._lib import check, lib
+    if 'device' in predict_scene_kwargs:
+        raise ValueError('predict_raster keeps the scene and the map on the device: device is not an argument')
+    r = rt.read_cog(in_file, window=window, layout='hwc', device=True)
+    if r.transform is None or r.crs is None:
+        raise ValueError(f'{in_file} carries no transform or no EPSG code: the output cannot be georeferenced')
+    scene = r.array
+    if r.dtype != 'float32':
+        H, W, C_ = (int(v) for v in scene.shape)
+        f32 = _device_empty((H, W, C_), torch.float32, 'the float32 scene')
+        check(lib.satcv_raster_convert(C.byref(rt._desc(scene.data_ptr(), rt.DTYPES[r.dtype][1], H, W, C_, C_, 0, f32, 2)), ops.stream_ptr()))
+        scene = f32
+    res = predict_scene(scene, m, device=True, **predict_scene_kwargs)
+    rt.write_cog(res[0] if isinstance(res, tuple) else res, out_file, r.transform, r.crs, **dict(cog_options or {}))
+    return res
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # Scene prediction for the ConvLSTM2D time-series models (lstm_tools.LSTMModel / LSTMAutoencoder): the (T, C, H, W) stack goes to the
 # device once, satcv_series_gather cuts, normalises and ingests a chip batch in one launch, the model reads the result in place

@@ -1,5 +1,7 @@
 """The writers of the reference's utils/raster_tools.py (:367-461 `numpy_to_raster`, `arrays_to_cog`) without rasterio and GDAL: a map
 that lies on the device is written as a Cloud-Optimized GeoTIFF -- tiled, with overviews, COMPRESS=LZW, nodata = 255 -- from there.
+The second half of the file is the way back (`read_info`, `read_cog`, `read_stack`): what the reference asks of rasterio's
+`open().read(window=)` and rioxarray's `open_rasterio` (utils/pc_tools.py:131-186, 328-386).
 
     map (host array or CUDA tensor) -> satcv_raster_convert (dtype, nodata) -> satcv_raster_overview (the pyramid, level by level)
       -> satcv_raster_tiles (tile-major layout, predictor 2) -> satcv_lzw_tiles (every tile of every level in one launch)
@@ -8,7 +10,7 @@ that lies on the device is written as a Cloud-Optimized GeoTIFF -- tiled, with o
 The container is this file's host code: little-endian classic TIFF, every IFD and every out-of-line value before the first tile byte,
 tile data from the smallest overview to the full resolution (the order GDAL's COG driver writes, without its ghost header).  The
 overview resampling rules are defined here (include/satcv.h, satcv_raster_overview), they are not GDAL's: GDAL's COG default is cubic.
-Out of scope: reading GeoTIFFs, BigTIFF, the float predictor 3, `arrays_to_cog`'s window-by-window assembly from .npy files (its body
+Out of scope: BigTIFF, the float predictor 3, `arrays_to_cog`'s window-by-window assembly from .npy files (its body
 writes to an undefined `src`), cloud destinations, and the chip and window helpers of utils/raster_tools.py.
 """
 import struct
@@ -287,7 +289,7 @@ def _resident(obj, ld, coff):
     return t, t.data_ptr(), ld, coff
 
 
-_stage_hook = None       # tools/cog_probe.py sets a callable: it receives a stage's name once the stage's launches are issued
+_stage_hook = None       # tools/cog_probe.py and tools/cog_read_probe.py set a callable: it receives a stage's name once the stage's launches are issued
 
 
 def _mark(stage):
@@ -449,3 +451,482 @@ def numpy_to_raster(arr, mixer, out_file, dtype):
     if int(mixer['cols']) != shape[1] or int(mixer['rows']) != shape[0]:
         raise ValueError(f"mixer announces {mixer['rows']} rows x {mixer['cols']} cols, the array is {shape[0]} x {shape[1]}")
     return write_cog(arr, out_file, tuple(mixer['transform'][0:6]), mixer['crs'], dtype=dtype, nodata=255, compress='lzw')
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The reader: GeoTIFF / COG -> resident raster.
+#
+#     container parsed on the host (read_info) -> the blocks the window touches, read into ONE pinned buffer behind their offsets, sizes
+#       and indices -> one host-to-device copy -> satcv_lzw_decode_tiles (one wavefront per block) -> satcv_raster_untile (predictor 2,
+#       window, band subset, destination layout) -> a device tensor in the file's own kind
+#
+# Deflate blocks are inflated on the host (zlib, at most 16 threads) and go up raw; uncompressed blocks go up as they are; decode='host'
+# does the same for LZW with satcv_lzw_decode_host.  Read: little-endian classic TIFF, tiles or strips, planar configuration 1 or 2,
+# 8 / 16 / 32-bit samples of one kind, predictor 1 or 2.  Refused by name: big-endian files, BigTIFF, JPEG and every other compression,
+# the floating-point predictor, other sample widths, bands of differing kinds, more than 16 bands, blocks that point past the file.
+_TIFF_TYPES = {1: 'B', 2: 'c', 3: 'H', 4: 'I', 5: 'II', 6: 'b', 7: 'B', 8: 'h', 9: 'i', 10: 'ii', 11: 'f', 12: 'd', 16: 'Q'}
+_COMPRESSION_NAMES = {1: None, 5: 'lzw', 8: 'deflate', 32946: 'deflate'}
+_FOREIGN_COMPRESSION = {2: 'CCITT RLE', 3: 'CCITT fax 3', 4: 'CCITT fax 4', 6: 'old-style JPEG', 7: 'JPEG', 32773: 'PackBits', 34712: 'JPEG 2000',
+                        34887: 'LERC', 34925: 'LZMA', 50000: 'ZSTD', 50001: 'WebP', 50002: 'JPEG XL'}
+_KIND_OF_FORMAT = {(8, 1): 'uint8', (16, 1): 'uint16', (16, 2): 'int16', (32, 2): 'int32', (32, 3): 'float32'}
+STATUS_NAMES = {0: 'ok', 1: 'truncated input', 2: 'bad code', 3: 'overlong'}       # satcv_lzw_decode_tiles
+
+
+class LevelInfo:
+    """One IFD of a file, as `read_info` returns it: shape (h, w), bands, dtype (name), block_shape (bh, bw), tiled, compression (None,
+    'lzw' or 'deflate'), predictor (bool: TIFF predictor 2), planar (1 or 2), nodata (float or None), transform (six numbers in Affine
+    order, or None), epsg (int or None), crs ('EPSG:n' or None), overview (NewSubfileType bit 0), offsets / counts (int64 arrays of the
+    block list) and index (the IFD's place in the file)."""
+    __slots__ = ('index', 'shape', 'bands', 'dtype', 'block_shape', 'tiled', 'compression', 'predictor', 'planar', 'nodata', 'transform', 'epsg',
+                 'overview', 'offsets', 'counts')
+
+    @property
+    def crs(self):
+        return None if self.epsg is None else f'EPSG:{self.epsg}'
+
+    def __repr__(self):
+        return 'LevelInfo(' + ', '.join(f'{k}={getattr(self, k)!r}' for k in self.__slots__[:-2]) + ')'
+
+
+class Raster:
+    """What `read_cog` returns: array (a CUDA tensor, or a NumPy array with device=False), transform (Affine order, of the window and
+    level that were read), crs ('EPSG:n' or None), nodata, dtype (name of the file's kind)."""
+    __slots__ = ('array', 'transform', 'crs', 'nodata', 'dtype')
+
+    def __init__(self, array, transform, crs, nodata, dtype):
+        self.array, self.transform, self.crs, self.nodata, self.dtype = array, transform, crs, nodata, dtype
+
+
+def _read_at(f, at, n, size, what):
+    if at < 0 or at + n > size:
+        raise ValueError(f'{what} at offset {at} ({n} bytes) points past the end of the file ({size} bytes)')
+    f.seek(at)
+    return f.read(n)
+
+
+def _parse_ifd(f, pos, size, index):
+    n = struct.unpack('<H', _read_at(f, pos, 2, size, f'IFD {index}'))[0]
+    raw = _read_at(f, pos + 2, 12 * n + 4, size, f'IFD {index}')
+    tags = {}
+    for i in range(n):
+        tag, typ, count, val = struct.unpack_from('<HHI4s', raw, 12 * i)
+        if typ not in _TIFF_TYPES:
+            continue
+        nbytes = struct.calcsize('<' + _TIFF_TYPES[typ]) * count
+        if nbytes > 4:
+            val = _read_at(f, struct.unpack('<I', val)[0], nbytes, size, f'the value of tag {tag} of IFD {index}')
+        val = val[:nbytes]
+        if typ == 2:
+            tags[tag] = val
+        elif typ in (4, 16) and count > 64:
+            tags[tag] = np.frombuffer(val, '<u4' if typ == 4 else '<u8').astype(np.int64)
+        else:
+            v = struct.unpack('<%d%s' % (count * len(_TIFF_TYPES[typ]), _TIFF_TYPES[typ][0]), val)
+            tags[tag] = tuple(a / b if b else float('nan') for a, b in zip(v[::2], v[1::2])) if typ in (5, 10) else v
+    return tags, struct.unpack_from('<I', raw, 12 * n)[0]
+
+
+def _geo(tags):
+    """(transform or None, epsg or None) of an IFD's GeoTIFF tags"""
+    keys = {}
+    gk = tags.get(34735)
+    if gk is not None and len(gk) >= 4:
+        for i in range(int(gk[3])):
+            k = gk[4 + 4 * i:8 + 4 * i]
+            if len(k) == 4 and k[1] == 0:
+                keys[int(k[0])] = int(k[3])
+    epsg = keys.get(3072, keys.get(2048))
+    if epsg is not None and not 1 <= epsg < 32767:
+        epsg = None                                           # 32767: user-defined, there is no EPSG database here
+    transform = None
+    if 34264 in tags and len(tags[34264]) == 16:
+        m = tags[34264]
+        transform = (m[0], m[1], m[3], m[4], m[5], m[7])
+    elif 33550 in tags and 33922 in tags and len(tags[33922]) >= 6:
+        (sx, sy), (i, j, _, x, y) = tags[33550][:2], tags[33922][:5]
+        transform = (sx, 0.0, x - i * sx, 0.0, -sy, y + j * sy)
+    if transform is not None and keys.get(1025) == 2:         # RasterPixelIsPoint: the tiepoint is a pixel centre
+        a, b, c, d, e, f_ = transform
+        transform = (a, b, c - 0.5 * (a + b), d, e, f_ - 0.5 * (d + e))
+    return (tuple(float(v) for v in transform) if transform is not None else None), epsg
+
+
+def _level_info(tags, index, size):
+    def one(tag, default=None):
+        v = tags.get(tag)
+        return default if v is None or len(v) == 0 else int(v[0])
+    who = f'IFD {index}'
+    info = LevelInfo()
+    info.index = index
+    w, h = one(256), one(257)
+    if not w or not h:
+        raise ValueError(f'{who} has no ImageWidth / ImageLength')
+    info.shape = (h, w)
+    info.bands = spp = one(277, 1)
+    if spp > 16:
+        raise ValueError(f'{who} has {spp} bands: more than 16 bands are not read')
+    comp = one(259, 1)
+    if comp not in _COMPRESSION_NAMES:
+        name = _FOREIGN_COMPRESSION.get(comp, 'unknown')
+        raise ValueError(f'{who} is compressed with {name} (Compression = {comp}): only none (1), LZW (5) and deflate (8, 32946) are read'
+                         + ('; JPEG blocks are out of scope' if 'JPEG' in name else ''))
+    info.compression = _COMPRESSION_NAMES[comp]
+    bits = tuple(int(v) for v in tags.get(258, (1,)))
+    fmts = tuple(int(v) for v in tags.get(339, (1,) * len(bits)))
+    if len(set(bits)) > 1 or len(set(fmts)) > 1:
+        raise ValueError(f'{who} has bands of differing kinds (BitsPerSample {bits}, SampleFormat {fmts}): one kind per file is read')
+    if bits[0] not in (8, 16, 32):
+        raise ValueError(f'{who} has {bits[0]} bits per sample: 8, 16 and 32 are read')
+    if (bits[0], fmts[0]) not in _KIND_OF_FORMAT:
+        raise ValueError(f'{who} has {bits[0]}-bit samples of SampleFormat {fmts[0]}: uint8, uint16, int16, int32 and float32 are read')
+    info.dtype = _KIND_OF_FORMAT[(bits[0], fmts[0])]
+    pred = one(317, 1)
+    if pred == 3:
+        raise ValueError(f'{who} uses predictor 3 (floating-point), which is not read; predictor 1 and 2 are')
+    if pred not in (1, 2) or (pred == 2 and info.dtype == 'float32'):
+        raise ValueError(f'{who} uses predictor {pred} on {info.dtype} samples: 1 (none) and 2 (integer kinds) are read')
+    info.predictor = pred == 2
+    info.planar = one(284, 1)
+    if info.planar not in (1, 2):
+        raise ValueError(f'{who} has PlanarConfiguration {info.planar}')
+    info.tiled = 322 in tags
+    if info.tiled:
+        bw, bh = one(322), one(323)
+        offs, cnts = tags.get(324), tags.get(325)
+    else:
+        bw, bh = w, min(one(278, h) or h, h)
+        offs, cnts = tags.get(273), tags.get(279)
+    if not bw or not bh or offs is None or cnts is None:
+        raise ValueError(f'{who} has no complete block list (tile or strip shape, offsets and byte counts)')
+    info.block_shape = (bh, bw)
+    nblocks = -(-h // bh) * -(-w // bw) * (spp if info.planar == 2 else 1)
+    info.offsets, info.counts = np.asarray(offs, np.int64).reshape(-1), np.asarray(cnts, np.int64).reshape(-1)
+    if info.offsets.size != nblocks or info.counts.size != nblocks:
+        raise ValueError(f'{who} needs {nblocks} blocks, its lists have {info.offsets.size} offsets and {info.counts.size} byte counts')
+    bad = np.nonzero((info.offsets + info.counts > size) | (info.counts < 0))[0]
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f'{who}: block {i} at offset {int(info.offsets[i])} with {int(info.counts[i])} bytes points past the end of the file ({size} bytes)')
+    if bh * bw * (spp if info.planar == 1 else 1) * (bits[0] // 8) >= 1 << 30:
+        raise ValueError(f'{who} has blocks of {bh} x {bw}: blocks stay below 2^30 bytes')
+    nd = tags.get(42113)
+    info.nodata = None
+    if nd is not None:
+        try:
+            info.nodata = float(bytes(nd).split(b'\0')[0].decode('ascii').strip())
+        except ValueError:
+            pass
+    info.transform, info.epsg = _geo(tags)
+    info.overview = bool(one(254, 0) & 1)
+    return info
+
+
+def read_info(path):
+    """[LevelInfo] of every IFD of a GeoTIFF, in file order (a COG: the full resolution, then its overviews).  Only the container is
+    read.  ValueError, naming what the file has, for: a big-endian (MM) file, BigTIFF, a compression other than none / LZW / deflate,
+    predictor 3, bits per sample other than 8 / 16 / 32, bands of differing kinds, more than 16 bands, and block offsets or byte counts
+    that point past the end of the file."""
+    import os
+    size = os.path.getsize(path)
+    with open(path, 'rb') as f:
+        head = f.read(8)
+        if len(head) < 8 or head[:2] not in (b'II', b'MM'):
+            raise ValueError(f'{path} is not a TIFF file')
+        if head[:2] == b'MM':
+            raise ValueError(f'{path} is a big-endian (MM) TIFF: only little-endian (II) files are read')
+        version = struct.unpack('<H', head[2:4])[0]
+        if version == 43:
+            raise ValueError(f'{path} is a BigTIFF (version 43): only classic TIFF (version 42) is read')
+        if version != 42:
+            raise ValueError(f'{path} has TIFF version {version}, expected 42')
+        pos = struct.unpack('<I', head[4:8])[0]
+        infos, seen = [], set()
+        while pos:
+            if pos in seen:
+                raise ValueError(f'{path}: the IFD chain loops at offset {pos}')
+            seen.add(pos)
+            tags, pos = _parse_ifd(f, pos, size, len(infos))
+            infos.append(_level_info(tags, len(infos), size))
+    if not infos:
+        raise ValueError(f'{path} has no image')
+    return infos
+
+
+def _levels(infos):
+    """the image and its overview chain: IFD 0, then every IFD marked as an overview"""
+    return [infos[0]] + [i for i in infos[1:] if i.overview]
+
+
+def _window_transform(base, full_hw, level_hw, row0, col0):
+    if base is None:
+        return None
+    a, b, c, d, e, f = base
+    sx, sy = full_hw[1] / level_hw[1], full_hw[0] / level_hw[0]
+    a, b, d, e = a * sx, b * sy, d * sx, e * sy
+    return (a, b, c + col0 * a + row0 * b, d, e, f + col0 * d + row0 * e)
+
+
+def _plan_read(info, window, bands):
+    """-> (row0, col0, h, w), band list, file indices of the blocks the window touches (row-major; planar 2: band after band)"""
+    H, W = info.shape
+    if window is None:
+        window = (0, 0, H, W)
+    if len(window) != 4 or any(isinstance(v, bool) or int(v) != v for v in window):
+        raise ValueError(f'window is four integers (row0, col0, h, w), got {window!r}')
+    row0, col0, h, w = (int(v) for v in window)
+    if row0 < 0 or col0 < 0 or h < 1 or w < 1 or row0 + h > H or col0 + w > W:
+        raise ValueError(f'window {(row0, col0, h, w)} lies outside the image of {H} x {W}')
+    if bands is None:
+        bands = list(range(info.bands))
+    bands = [int(b) for b in bands]
+    if not bands or len(set(bands)) != len(bands) or min(bands) < 0 or max(bands) >= info.bands:
+        raise ValueError(f'bands must be distinct indices below {info.bands}, got {bands}')
+    bh, bw = info.block_shape
+    across, down = -(-W // bw), -(-H // bh)
+    plane = [by * across + bx for by in range(row0 // bh, (row0 + h - 1) // bh + 1) for bx in range(col0 // bw, (col0 + w - 1) // bw + 1)]
+    blocks = plane if info.planar == 1 else [b * across * down + t for b in sorted(bands) for t in plane]
+    return (row0, col0, h, w), bands, blocks
+
+
+def _stream_hint(stream):
+    first = (int.from_bytes(bytes(stream[:2]), 'big') >> 7) if len(stream) >= 2 else 256
+    return '' if first == 256 else ("; the stream does not open with a Clear code (its first 9 bits, MSB-first, are %d): this may be the LSB-first "
+                                    "'old-style' LZW, which is not supported" % first)
+
+
+def lzw_decode(stream, cap):
+    """TIFF LZW of a bytes-like object decoded on the CPU (satcv_lzw_decode_host): -> (status, bytes), at most `cap` bytes"""
+    import ctypes as C
+    from ._lib import check, lib
+    stream = bytes(stream)
+    dst = C.create_string_buffer(max(int(cap), 1))
+    size, status = C.c_int64(), C.c_int32()
+    check(lib.satcv_lzw_decode_host(stream, len(stream), dst, int(cap), C.byref(size), C.byref(status)))
+    return status.value, dst.raw[:size.value]
+
+
+def _expected_bytes(info, blocks):
+    """per block the bytes it must decode to: a full block, but only the rows inside the image for the last strip"""
+    H, W = info.shape
+    bh, bw = info.block_shape
+    eb = np.dtype(DTYPES[info.dtype][0]).itemsize
+    cb = info.bands if info.planar == 1 else 1
+    if info.tiled:
+        return [bh * bw * cb * eb] * len(blocks)
+    down = -(-H // bh)
+    return [min(bh, H - (t % down) * bh) * bw * cb * eb for t in blocks]
+
+
+def _refuse_block(t, status, stream):
+    raise ValueError(f'block {t} does not decode: status {status} ({STATUS_NAMES.get(status, "?")})' + _stream_hint(stream))
+
+
+def _decode_host(info, blocks, slices, into, stride):
+    """the blocks decoded on the host into `into` (a uint8 array), block j at j * stride; at most 16 threads"""
+    import ctypes as C
+    import os
+    from ._lib import check, lib
+    want = _expected_bytes(info, blocks)
+    block_bytes = info.block_shape[0] * info.block_shape[1] * (info.bands if info.planar == 1 else 1) * np.dtype(DTYPES[info.dtype][0]).itemsize
+
+    def one(j):
+        raw, dst = slices[j], into[j * stride:j * stride + stride]
+        if info.compression is None:
+            got = bytes(raw)
+        elif info.compression == 'deflate':
+            try:
+                got = zlib.decompress(raw)
+            except zlib.error as e:
+                raise ValueError(f'block {blocks[j]} does not inflate: {e}') from e
+        else:
+            size, status = C.c_int64(), C.c_int32()
+            check(lib.satcv_lzw_decode_host(bytes(raw), len(raw), dst.ctypes.data, block_bytes, C.byref(size), C.byref(status)))
+            if status.value or size.value < want[j]:
+                _refuse_block(blocks[j], status.value if status.value else 1, raw)
+            return
+        if len(got) < want[j]:
+            raise ValueError(f'block {blocks[j]} holds {len(got)} bytes, {want[j]} are needed')
+        dst[:min(len(got), stride)] = np.frombuffer(got, np.uint8)[:stride]
+    with ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1))) as ex:
+        list(ex.map(one, range(len(blocks))))
+
+
+def _untile_host(info, blocks, raw, stride, window, bands, layout):
+    """NumPy counterpart of satcv_raster_untile for device=False"""
+    H, W = info.shape
+    bh, bw = info.block_shape
+    dt = np.dtype(DTYPES[info.dtype][0])
+    across, down = -(-W // bw), -(-H // bh)
+    cb = info.bands if info.planar == 1 else 1
+    row0, col0, h, w = window
+    out = np.zeros((h, w, len(bands)), dt)
+    for j, t in enumerate(blocks):
+        plane, t2 = (t // (across * down), t % (across * down)) if info.planar == 2 else (0, t)
+        by, bx = t2 // across, t2 % across
+        blk = raw[j * stride:j * stride + bh * bw * cb * dt.itemsize].view(dt).reshape(bh, bw, cb)
+        if info.predictor:
+            blk = np.cumsum(blk.view('u%d' % dt.itemsize), axis=1, dtype=np.uint64).astype('u%d' % dt.itemsize).view(dt)
+        y0, x0 = max(by * bh, row0), max(bx * bw, col0)
+        y1, x1 = min(by * bh + bh, row0 + h), min(bx * bw + bw, col0 + w)
+        part = blk[y0 - by * bh:y1 - by * bh, x0 - bx * bw:x1 - bx * bw]
+        for k, b in enumerate(bands):
+            if info.planar == 1:
+                out[y0 - row0:y1 - row0, x0 - col0:x1 - col0, k] = part[..., b]
+            elif b == plane:
+                out[y0 - row0:y1 - row0, x0 - col0:x1 - col0, k] = part[..., 0]
+    return out if layout == 'hwc' else np.ascontiguousarray(out.transpose(2, 0, 1))
+
+
+def _torch_dtype(name):
+    import torch
+    if name == 'uint16':
+        return torch.uint16 if hasattr(torch, 'uint16') else torch.int16      # (bytes only, where this torch has no uint16)
+    return getattr(torch, name)
+
+
+def default_decode(info):
+    """where `read_cog(decode=None)` decodes LZW blocks: the choice tools/cog_read_probe.py measured per input class ("Reading
+    GeoTIFFs")"""
+    return 'host'
+
+
+def read_cog(path, window=None, level=0, bands=None, layout='hwc', device=True, decode=None, out=None):
+    """Read a GeoTIFF / COG onto the device: -> `Raster` (array, transform, crs, nodata, dtype).
+
+    window: (row0, col0, h, w) in pixels of the level that is read, None: all of it; only the blocks it touches are read from the file.
+    level: 0 the image, k its k-th overview (the IFDs marked as overviews, in file order).  bands: indices of the bands to keep, in the
+    order given; None: all.  layout: 'hwc' -> (h, w, C), 'chw' -> (C, h, w).  The array is in the file's own kind (uint8, uint16,
+    int16, int32, float32): a CUDA tensor, or a NumPy array with device=False.  The transform is that of the window at that level.
+    decode: where LZW blocks are decoded -- 'device' (satcv_lzw_decode_tiles: the compressed bytes go up, one wavefront decodes a block),
+    'host' (satcv_lzw_decode_host in at most 16 threads, the raw blocks go up), None: `default_decode`.  Deflate blocks are always
+    inflated on the host (zlib), uncompressed blocks go up as they are.  Either way the blocks travel in one pinned buffer and one
+    copy, and one satcv_raster_untile launch undoes predictor 2 and scatters them into the window.
+    out: a contiguous CUDA tensor of the result's shape and kind to write into (a slot of a stack), returned as `.array`.
+    ValueError: what `read_info` refuses, a window outside the image, and a block that does not decode (its index and status)."""
+    import ctypes as C
+    if layout not in ('hwc', 'chw'):
+        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
+    if decode not in (None, 'host', 'device'):
+        raise ValueError(f"decode must be 'host', 'device' or None, got {decode!r}")
+    infos = read_info(path)
+    levels = _levels(infos)
+    if isinstance(level, bool) or int(level) != level or not 0 <= level < len(levels):
+        raise ValueError(f'level {level!r}: the file has levels 0 ... {len(levels) - 1}')
+    info = levels[int(level)]
+    window, bands, blocks = _plan_read(info, window, bands)
+    row0, col0, h, w = window
+    if info.compression != 'lzw':
+        decode = 'host'
+    elif decode is None:
+        decode = default_decode(info) if device else 'host'
+    if decode == 'device' and not device:
+        raise ValueError("decode='device' leaves the raster on the device: it needs device=True")
+    if out is not None and not device:
+        raise ValueError('out is a CUDA tensor: it needs device=True')
+    dt = np.dtype(DTYPES[info.dtype][0])
+    bh, bw = info.block_shape
+    cb = info.bands if info.planar == 1 else 1
+    block_bytes = bh * bw * cb * dt.itemsize
+    stride = (block_bytes + 15) // 16 * 16
+    n = len(blocks)
+    transform = _window_transform(levels[0].transform, levels[0].shape, info.shape, row0, col0)
+    result = lambda arr: Raster(arr, transform, levels[0].crs, info.nodata if info.nodata is not None else levels[0].nodata, info.dtype)
+    offs, cnts = info.offsets[blocks], info.counts[blocks]
+    if not device:
+        with open(path, 'rb') as f:
+            slices = []
+            for o, c in zip(offs, cnts):
+                f.seek(int(o))
+                slices.append(f.read(int(c)))
+        raw = np.zeros(n * stride, np.uint8)
+        _decode_host(info, blocks, slices, raw, stride)
+        return result(_untile_host(info, blocks, raw, stride, window, bands, layout))
+    import torch
+    from . import ops
+    from ._lib import UntileDesc, check, lib
+    from .prediction_tools import _device_empty
+    shape = (h, w, len(bands)) if layout == 'hwc' else (len(bands), h, w)
+    td = _torch_dtype(info.dtype)
+    if out is None:
+        out = _device_empty(shape, td, 'the raster')
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and tuple(out.shape) == shape and out.element_size() == dt.itemsize
+              and out.dtype.is_floating_point == (dt.kind == 'f')):
+        raise ValueError(f'out must be a contiguous CUDA tensor of shape {shape} and kind {info.dtype}')
+    # one pinned buffer: offsets (int64), sizes (int32) and block indices (int32) of the n blocks, then the payload
+    head = 16 * n
+    payload = int(cnts.sum()) if decode == 'device' else n * stride
+    pinned = torch.empty(head + max(payload, 16), dtype=torch.uint8, pin_memory=True)
+    buf = pinned.numpy()
+    rel = np.concatenate([[0], np.cumsum(cnts)[:-1]]).astype(np.int64) if decode == 'device' else np.arange(n, dtype=np.int64) * stride
+    buf[:8 * n].view(np.int64)[:] = rel
+    buf[8 * n:12 * n].view(np.int32)[:] = cnts if decode == 'device' else block_bytes
+    buf[12 * n:16 * n].view(np.int32)[:] = blocks
+    with open(path, 'rb') as f:
+        if decode == 'device':
+            for o, c, r in zip(offs, cnts, rel):
+                f.seek(int(o))
+                f.readinto(memoryview(buf[head + int(r):head + int(r) + int(c)]))
+        else:
+            slices = []
+            for o, c in zip(offs, cnts):
+                f.seek(int(o))
+                slices.append(f.read(int(c)))
+    if decode != 'device':
+        buf[head:head + payload] = 0
+        _decode_host(info, blocks, slices, buf[head:head + payload], stride)
+    _mark('read')
+    dev = pinned.to('cuda', non_blocking=True)                 # the one host-to-device copy
+    _mark('upload')
+    st = ops.stream_ptr()
+    base = dev.data_ptr()
+    if decode == 'device':
+        decoded = _device_empty((n * stride,), torch.uint8, 'the decoded blocks')
+        flags = _device_empty((2 * n,), torch.int32, 'the block statuses')
+        check(lib.satcv_lzw_decode_tiles(base + head, payload, base, base + 8 * n, n, block_bytes, decoded.data_ptr(), stride, flags.data_ptr(),
+                                         flags.data_ptr() + 4 * n, st))
+        src = decoded.data_ptr()
+    else:
+        src = base + head
+    _mark('decode')
+    d = UntileDesc(src=src, src_stride=stride, blocks=base + 12 * n, nblocks=n, bh=bh, bw=bw, across=-(-info.shape[1] // bw),
+                   per_plane=-(-info.shape[1] // bw) * -(-info.shape[0] // bh), spp=info.bands, planar=info.planar, kind=DTYPES[info.dtype][1],
+                   predictor=2 if info.predictor else 0, row0=row0, col0=col0, h=h, w_=w, dst=out.data_ptr(), layout=0 if layout == 'hwc' else 1,
+                   ld=len(bands), coff=0)
+    for b in range(16):
+        d.band_map[b] = bands.index(b) if b in bands else -1
+    check(lib.satcv_raster_untile(C.byref(d), st))
+    _mark('untile')
+    if decode == 'device':
+        got = flags.cpu().numpy()                              # the one host synchronisation: statuses and decoded lengths
+        want = np.asarray(_expected_bytes(info, blocks))
+        bad = np.nonzero((got[:n] != 0) | (got[n:] < want))[0]
+        if bad.size:
+            j = int(bad[0])
+            r, c = int(rel[j]), int(cnts[j])
+            _refuse_block(blocks[j], int(got[j]) if got[j] else 1, buf[head + r:head + r + c])
+    else:
+        torch.cuda.current_stream().synchronize()              # the pinned buffer is released only after the copy
+    _mark('status')
+    return result(out)
+
+
+def read_stack(paths, window=None, bands=None):
+    """The files of a time series as one resident stack: -> (stack, transform, crs, nodata), stack a (T, C, H, W) CUDA tensor in the
+    files' kind -- what `pc_tools.median_composite`, `ee_tools.mask` and `pc_tools.predict_change` take.  Every file is decoded straight
+    into its slot (`read_cog(..., layout='chw', out=stack[t])`).  The files must agree on shape, kind, transform and CRS: ValueError
+    names the first that differs."""
+    from .prediction_tools import _device_empty
+    paths = list(paths)
+    if not paths:
+        raise ValueError('read_stack needs at least one file')
+    first = read_info(paths[0])[0]
+    for p in paths[1:]:
+        i = read_info(p)[0]
+        for what in ('shape', 'bands', 'dtype', 'transform', 'epsg'):
+            if getattr(i, what) != getattr(first, what):
+                raise ValueError(f'{p} differs from {paths[0]} in {what}: {getattr(i, what)!r} against {getattr(first, what)!r}')
+    (row0, col0, h, w), bands, _ = _plan_read(first, window, bands)
+    stack = _device_empty((len(paths), len(bands), h, w), _torch_dtype(first.dtype), 'the time stack')
+    for t, p in enumerate(paths):
+        r = read_cog(p, (row0, col0, h, w), 0, bands, 'chw', True, None, stack[t])
+    return stack, r.transform, r.crs, r.nodata
