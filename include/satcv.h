@@ -852,6 +852,63 @@ typedef struct satcv_untile_desc {
 } satcv_untile_desc;
 int satcv_raster_untile(const satcv_untile_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ Raster alignment: resampling between two grids of one CRS
+ * What stackstac.stack(resolution=), gdal.BuildVRT / rioxarray's merge_arrays and reproject_match do to the samples before any code of
+ * the reference runs (utils/pc_tools.py:152-186, 251-282, 368-431): a resident raster is resampled onto another north-up or south-up
+ * grid of the SAME coordinate system (scale and shift per axis; no rotation, no reprojection).  The grid arithmetic is host code in
+ * raster_tools.py.  The rules below are THIS library's (GDAL's and stackstac's are not restated): tests/warp_oracle.py says them again
+ * in float64 NumPy.
+ *
+ * Rasters: src is a window of the source grid, (sh, sw, src_ld) for src_layout 0 or (src_ld, sh, sw) for 1; src[0, 0] is pixel
+ * (src_row0, src_col0) of the source grid.  dst likewise with (dh, dw, dst_ld), dst[0, 0] being pixel (dst_row0, dst_col0) of the
+ * destination grid.  Bands src_coff .. src_coff + c - 1 go to dst_coff .. dst_coff + c - 1; no other channel of dst is written.  Kinds
+ * as in the writer section (0 u8, 1 u16, 2 f32, 3 i16, 5 i32); dst_kind is src_kind or 2.
+ * Coordinates: pixel k of a grid covers [k, k + 1).  Destination pixel (i, j) = (dst_row0 + local row, dst_col0 + local column) has the
+ * source-grid coordinates u = su * (j + 0.5) + ou, v = sv * (i + 0.5) + ov, in float64 with the product and the sum rounded
+ * separately (the kernel is compiled with floating-point contraction off: a fused multiply-add moves floor(u) on real grids).  From
+ * two Affine transforms: su = a_d / a_s, ou = (c_d - c_s) / a_s, sv = e_d / e_s, ov = (f_d - f_s) / e_s; su or sv < 0 is a grid of
+ * the opposite orientation.  The window origin is subtracted from floor(...) only, so a warp of a window equals the warp of the whole
+ * raster bit for bit wherever the window holds the taps.
+ * Validity: a source sample is valid when it lies inside the sh x sw window, is not NaN and (with has_src_nodata) differs from
+ * src_nodata (compared as float64).
+ * resampling (all arithmetic in float64; taps are added rows outer, columns inner):
+ *   0 nearest    the sample at (floor(v), floor(u)); invalid when that sample is
+ *   1 bilinear   x0 = floor(u - 0.5), t = u - 0.5 - x0, taps x0, x0 + 1 with the weights 1 - t, t; the same in v; a tap's weight is
+ *                the product of its two.  The tap nearest picks (the pixel that contains the point) must be valid, otherwise the
+ *                result is invalid.  Then: sum of weight * sample over the valid taps, divided by the sum of their weights -- a convex
+ *                combination: nothing bleeds into a hole, nothing is amplified
+ *   2 cubic      Catmull-Rom (a = -0.5): taps x0 - 1 .. x0 + 2 with the weights -t^3/2 + t^2 - t/2, 3t^3/2 - 5t^2/2 + 1,
+ *                -3t^3/2 + 2t^2 + t/2, t^3/2 - t^2/2, evaluated as written from t, t * t and t * t * t; the sum of the 16
+ *                products, not renormalised.  Only when all 16 taps are valid; otherwise the sample takes rule 1.  (A partial stencil
+ *                is not renormalised: with the negative lobes alone beside the containing tap the weight sum falls to 0.035.)
+ *   3 average    the footprint of the destination pixel is [min, max] of su * j + ou and su * (j + 1) + ou, likewise in v; a source
+ *                pixel's weight is the area of its overlap with it (product of the overlaps per axis); sum of weight * sample over
+ *                the valid samples of positive weight, divided by their weight sum; no such sample: invalid.  ceil(|s|) + 1 taps
+ *                per axis, whatever the data.  |su| or |sv| above 64 is refused: read an overview instead
+ * Result: f32 -- the float64 value rounded once; integer kinds -- rint (half to even), saturated to the kind.  An invalid result
+ * leaves dst untouched with keep; otherwise it is dst_nodata (in the kind, as the writer's nodata), and without has_dst_nodata NaN
+ * for f32 and 0 for integers.
+ * One thread per destination pixel and all its bands, neighbouring lanes on neighbouring columns; bands travel in groups of 4 or 2
+ * by one load and one store where c, ld, coff and the address allow.
+ * Refused on the host before any launch: null or misaligned pointers, unknown kinds, layouts or methods, dst_kind neither src_kind
+ * nor f32, c > 16, channels outside ld, a zero or non-finite scale or a non-finite offset, non-positive sizes, rasters beyond 2^31
+ * pixels, src and dst overlapping. */
+typedef struct satcv_warp_desc {
+  const void* src; int32_t src_kind, src_layout;
+  int32_t sh, sw, src_ld, src_coff;
+  int32_t src_row0, src_col0;
+  void* dst; int32_t dst_kind, dst_layout;
+  int32_t dh, dw, dst_ld, dst_coff;
+  int32_t dst_row0, dst_col0;
+  int32_t c;
+  double su, ou, sv, ov;
+  int32_t resampling;
+  int32_t has_src_nodata; double src_nodata;
+  int32_t has_dst_nodata; double dst_nodata;
+  int32_t keep;
+} satcv_warp_desc;
+int satcv_raster_warp(const satcv_warp_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ losses
  * Each writes loss_out[0] += mean loss contribution (caller zeroes) and
  * dlogits = dL/dlogits (through the head activation).

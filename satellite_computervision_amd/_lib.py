@@ -102,6 +102,15 @@ class UntileDesc(C.Structure):
                 ('h', c_i32), ('w_', c_i32), ('dst', c_vp), ('layout', c_i32), ('ld', c_i32), ('coff', c_i32), ('band_map', c_i32 * 16)]
 
 
+class WarpDesc(C.Structure):
+    """satcv_warp_desc: a resident raster resampled onto another grid of the same CRS (satcv_raster_warp)"""
+    _fields_ = [('src', c_vp), ('src_kind', c_i32), ('src_layout', c_i32), ('sh', c_i32), ('sw', c_i32), ('src_ld', c_i32), ('src_coff', c_i32),
+                ('src_row0', c_i32), ('src_col0', c_i32), ('dst', c_vp), ('dst_kind', c_i32), ('dst_layout', c_i32), ('dh', c_i32), ('dw', c_i32),
+                ('dst_ld', c_i32), ('dst_coff', c_i32), ('dst_row0', c_i32), ('dst_col0', c_i32), ('c', c_i32), ('su', C.c_double), ('ou', C.c_double),
+                ('sv', C.c_double), ('ov', C.c_double), ('resampling', c_i32), ('has_src_nodata', c_i32), ('src_nodata', C.c_double),
+                ('has_dst_nodata', c_i32), ('dst_nodata', C.c_double), ('keep', c_i32)]
+
+
 RECORD_MAX_PLANES = 32     # SATCV_RECORD_MAX_PLANES of include/satcv.h
 RECORD_STAT_SPLITS = 16    # SATCV_RECORD_STAT_SPLITS
 _i32p, _f32p = c_i32 * RECORD_MAX_PLANES, c_f32 * RECORD_MAX_PLANES
@@ -320,6 +329,7 @@ _SIGS = {
     'satcv_lzw_decode_tiles': (C.c_int, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     'satcv_lzw_decode_host': (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.POINTER(c_i64), C.POINTER(c_i32)]),
     'satcv_raster_untile': (C.c_int, [C.POINTER(UntileDesc), c_vp]),
+    'satcv_raster_warp': (C.c_int, [C.POINTER(WarpDesc), c_vp]),
     'satcv_record_stats': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_record_to_tuple': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_label_onehot': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),

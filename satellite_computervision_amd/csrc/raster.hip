@@ -23,9 +23,9 @@
 // Every kernel is a grid-stride loop over 64-bit indices; descriptors are refused on the host before any launch.
 #include "common.hpp"
 #include "lzw_core.hpp"
+#include "raster_kinds.hpp"
 #include <cmath>
 #include <cstring>
-#include <limits>
 
 namespace {
 
@@ -36,31 +36,6 @@ constexpr int LZ_CHUNK = 1024;       // bytes per input chunk and per output flu
 int grid_for(long long items) {
   long long g = (items + RS_BLOCK - 1) / RS_BLOCK;
   return (int)(g < 1 ? 1 : g > RS_MAX_GRID ? RS_MAX_GRID : g);
-}
-
-// ---------------------------------------------------------------- kinds
-template <typename F>
-int by_kind(int kind, F&& f) {
-  switch (kind) {
-    case 0: return f(uint8_t{});
-    case 1: return f(uint16_t{});
-    case 2: return f(float{});
-    case 3: return f(int16_t{});
-    default: return f(int32_t{});
-  }
-}
-bool kind_ok(int k) { return k == 0 || k == 1 || k == 2 || k == 3 || k == 5; }
-int kind_bytes(int k) { return k == 0 ? 1 : (k == 1 || k == 3) ? 2 : 4; }
-
-// nodata in the destination kind (integers: saturated, NaN -> 0)
-template <typename T>
-T nodata_as(double v) {
-  if constexpr (std::is_same<T, float>::value) return (float)v;
-  else {
-    if (!(v == v)) return 0;
-    const double lo = (double)std::numeric_limits<T>::min(), hi = (double)std::numeric_limits<T>::max();
-    return (T)(v < lo ? lo : v > hi ? hi : v);
-  }
 }
 
 // ---------------------------------------------------------------- convert
@@ -94,12 +69,6 @@ __global__ __launch_bounds__(RS_BLOCK) void convert_kernel(const S* __restrict__
 }
 
 // ---------------------------------------------------------------- overview
-template <typename T>
-__device__ __forceinline__ bool sample_valid(T v, bool has_nd, T nd) {
-  if constexpr (std::is_same<T, float>::value) return v == v && !(has_nd && v == nd);
-  else return !(has_nd && v == nd);
-}
-
 template <typename T>
 __global__ __launch_bounds__(RS_BLOCK) void overview_kernel(const T* __restrict__ src, T* __restrict__ dst, int h, int w, int c, int oh, int ow,
                                                              int resampling, int has_nd, T nd) {
@@ -453,15 +422,6 @@ struct HostDecSink {
     for (int j = 0; j < len; ++j) dst[at + j] = dst[from + ((wrap && j == len - 1) ? 0 : j)];
   }
 };
-
-int launched(const char* who) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    satcv_set_error("%s launch: %s", who, hipGetErrorString(e));
-    return SATCV_ERR_HIP;
-  }
-  return SATCV_OK;
-}
 
 // what the three raster entries share; same_kind: overview and tiles keep the kind and read a contiguous raster
 int check_raster(const satcv_raster_desc* d, const char* who, bool same_kind) {

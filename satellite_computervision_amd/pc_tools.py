@@ -5,8 +5,9 @@
       -> normalize_dataArray over bands (:90-107) -> [before bands, after bands] (:650) -> chips -> model -> stitched map
 
 The first four arrows are ONE kernel (satcv_median_composite, csrc/composite.hip) on a stack that is uploaded once; its output is the
-(H, W, C) float32 scene the device-resident prediction loop of prediction_tools reads in place.  Acquisition (STAC search, stackstac,
-rioxarray), reprojection and clipping stay with the caller.
+(H, W, C) float32 scene the device-resident prediction loop of prediction_tools reads in place.  Acquisition (STAC search, rioxarray),
+reprojection between coordinate systems and clipping stay with the caller; files of one CRS on differing grids are aligned by
+`predict_change_files` (raster_tools.read_aligned_stack, what stackstac.stack(resolution=) does for the reference).
 
 The composites the reference's models were trained on were masked per acquisition first (utils/ee_tools.py: basicQA :159, maskTOA
 :288, maskSR :270, mask :257).  `median_composite(clear=...)` / `predict_change(quality=...)` take those masks from `ee_tools` as bit-planes
@@ -240,3 +241,33 @@ def predict_change(before, after, m, before_times=None, after_times=None, buff=1
         rt.write_cog(dev_map, out_file, transform, crs, **dict(cog_options or {}))
         output = dev_map.cpu().numpy()
     return output, bef_median.cpu().numpy(), aft_median.cpu().numpy()
+
+
+def predict_change_files(before_items, after_items, m, grid=None, resolution=None, out_file=None, file_bands=None, resampling='nearest',
+                         **predict_change_kwargs):
+    """`predict_change` from files that need not share a pixel grid: both periods are read as aligned stacks on ONE grid
+    (`raster_tools.read_aligned_stack` -- what the reference gets from stackstac.stack(epsg=, resolution=)) and handed to
+    `predict_change` with that grid's georeference; returns what `predict_change` returns.
+
+    before_items, after_items: per acquisition a path or a list of paths mosaicked into one acquisition; one CRS throughout.  grid: the
+    common `raster_tools.Grid`; None: `union_grid` of every file of both periods at `resolution` (None: the finest).  file_bands: the
+    bands read from every file (None: all); resampling: as for `raster_tools.warp`.  out_file: the change map as a Cloud-Optimized
+    GeoTIFF with the grid's transform and CRS.  predict_change_kwargs: every other argument of `predict_change` (times, kernel, buff,
+    quality, bands, fill, cog_options, ...); transform and crs come from the grid."""
+    import os
+    from . import raster_tools as rt
+    for k in ('transform', 'crs'):
+        if k in predict_change_kwargs:
+            raise ValueError(f'{k} comes from the common grid: it is not an argument of predict_change_files')
+    if grid is None:
+        flat = [p for it in list(before_items) + list(after_items) for p in ([it] if isinstance(it, (str, os.PathLike)) else it)]
+        grid = rt.union_grid(flat, resolution=resolution)
+    elif resolution is not None:
+        raise ValueError('resolution describes the grid that is built when none is given')
+    before = rt.read_aligned_stack(before_items, grid, bands=file_bands, resampling=resampling)
+    after = rt.read_aligned_stack(after_items, grid, bands=file_bands, resampling=resampling)
+    if out_file is not None:
+        if grid.crs is None and before[2] is None:
+            raise ValueError('the files carry no EPSG code: out_file cannot be georeferenced')
+        predict_change_kwargs.update(out_file=out_file, transform=grid.transform, crs=grid.crs or before[2])
+    return predict_change(before[0], after[0], m, **predict_change_kwargs)

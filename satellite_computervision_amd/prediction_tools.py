@@ -693,6 +693,72 @@ def predict_hybrid_scene(scene, stack, m, kernel=256, buff=128, batch_size=16, c
                           plan).host(channel, device)
 
 
+def _model_ratio(m):
+    """the resolution ratio r a two-resolution model was built for: the side of its fine input over the side of its coarse input"""
+    hi_dim = getattr(m, 'unet_dim', None) or getattr(m, 'acnn_dim', None)
+    if hi_dim is None or not hasattr(m, 'lstm_dim'):
+        raise ValueError(f'predict_hybrid_raster covers HybridModel and HierarchicalModel, got {type(m).__name__}')
+    side, side_lo = int(hi_dim[0]), int(m.lstm_dim[1])
+    if side_lo < 1 or side % side_lo:
+        raise ValueError(f'the fine input side {side} of the model is not a multiple of its coarse input side {side_lo}')
+    return side // side_lo
+
+
+def predict_hybrid_raster(scene_file, stack_items, m, out_file, window=None, resampling='nearest', cog_options=None, **kwargs):
+    """File to file for the two-resolution models: a fine scene file and the files of a coarse time series that need not share its
+    grid -> `predict_hybrid_scene(..., device=True)` -> a Cloud-Optimized GeoTIFF; returns what `predict_hybrid_scene` returns (CUDA
+    tensors).
+
+    scene_file: a GeoTIFF / COG; window: (row0, col0, h, w) of it, None: all.  The fine grid is that of the file (of the window).  The
+    coarse grid has the same bounds with pixels r times larger, r being the ratio the model was built for (fine input side / coarse
+    input side); stack_items (per acquisition a path or a list of paths, as for `raster_tools.read_aligned_stack`) are resampled onto it
+    with `resampling`.  A fine extent that is not a multiple of r is a ValueError: cut the window, or trim the scene as
+    `pc_tools.trim_array` does.  out_file carries the scene file's transform -- of the window -- and CRS; cog_options: further `write_cog`
+    arguments.  kwargs: the other arguments of `predict_hybrid_scene` (kernel, buff, batch_size, channel, cover, classes, rescale,
+    maxval, output, plan)."""
+    import torch
+    from . import raster_tools as rt
+    if 'device' in kwargs:
+        raise ValueError('predict_hybrid_raster keeps the scene, the stack and the map on the device: device is not an argument')
+    r = _model_ratio(m)
+    info = rt.read_info(scene_file)[0]
+    if info.transform is None or info.crs is None:
+        raise ValueError(f'{scene_file} carries no transform or no EPSG code: the output cannot be georeferenced')
+    (row0, col0, h, w), _, _ = rt._plan_read(info, window, None)
+    if h % r or w % r:
+        raise ValueError(f'the fine extent {h} x {w} is not a multiple of the resolution ratio r = {r}: choose a window that is, or trim the scene '
+                         f'(pc_tools.trim_array(arr, {r}))')
+    fine = rt.Grid(rt._window_transform(info.transform, info.shape, info.shape, row0, col0), (h, w), info.crs)
+    a, _, c, _, e, f = fine.transform
+    coarse = rt.Grid((a * r, 0.0, c, 0.0, e * r, f), (h // r, w // r), info.crs)
+    scene = rt.read_cog(scene_file, window=(row0, col0, h, w), layout='hwc', device=True)
+    stack = rt.read_aligned_stack(stack_items, coarse, resampling=resampling)[0]
+    fine_scene = scene.array if scene.dtype == 'float32' else _as_float32(scene.array, scene.dtype)
+    if stack.dtype not in (torch.int16, torch.float32):       # (the series gather reads int16 and float32)
+        stack = _as_float32(stack, rt.read_info(_first_path(stack_items))[0].dtype)
+    res = predict_hybrid_scene(fine_scene, stack, m, device=True, **kwargs)
+    rt.write_cog(res[0] if isinstance(res, tuple) else res, out_file, fine.transform, fine.crs, **dict(cog_options or {}))
+    return res
+
+
+def _first_path(items):
+    import os
+    first = list(items)[0]
+    return first if isinstance(first, (str, os.PathLike)) else list(first)[0]
+
+
+def _as_float32(t, dtype):
+    """an integer raster or stack on the device cast to float32 there (satcv_raster_convert, exact for 8- and 16-bit samples)"""
+    import ctypes as C
+    import torch
+    from . import ops, raster_tools as rt
+    from ._lib import check, lib
+    f32 = _device_empty(tuple(t.shape), torch.float32, 'the float32 copy')
+    rows, cols = t.numel() // int(t.shape[-1]), int(t.shape[-1])
+    check(lib.satcv_raster_convert(C.byref(rt._desc(t.data_ptr(), rt.DTYPES[dtype][1], rows, cols, 1, 1, 0, f32, 2)), ops.stream_ptr()))
+    return f32
+
+
 def _stitch_hybrid(scene, stack, hi, lo, geo, m, head, output, kernel, batch_size, channel, want_classes, rescale, maxval, plan):
     """predict_hybrid_scene on the device: -> _Maps"""
     import ctypes as C

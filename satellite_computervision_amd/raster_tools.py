@@ -1,7 +1,8 @@
 """The writers of the reference's utils/raster_tools.py (:367-461 `numpy_to_raster`, `arrays_to_cog`) without rasterio and GDAL: a map
 that lies on the device is written as a Cloud-Optimized GeoTIFF -- tiled, with overviews, COMPRESS=LZW, nodata = 255 -- from there.
 The second half of the file is the way back (`read_info`, `read_cog`, `read_stack`): what the reference asks of rasterio's
-`open().read(window=)` and rioxarray's `open_rasterio` (utils/pc_tools.py:131-186, 328-386).
+`open().read(window=)` and rioxarray's `open_rasterio` (utils/pc_tools.py:131-186, 328-386).  The last part aligns rasters of one CRS that do not share
+a pixel grid (`union_grid`, `warp`, `read_warped`, `read_mosaic`, `read_aligned_stack`): stackstac's, BuildVRT's and reproject_match's part.
 
     map (host array or CUDA tensor) -> satcv_raster_convert (dtype, nodata) -> satcv_raster_overview (the pyramid, level by level)
       -> satcv_raster_tiles (tile-major layout, predictor 2) -> satcv_lzw_tiles (every tile of every level in one launch)
@@ -231,15 +232,22 @@ def _deflate_all(tiles):
 
 
 # ----------------------------------------------------------------------------------------------------------------- the device side
+def _tensor_kinds():
+    """torch dtype -> kind of satcv_raster_desc (float64 is converted to float32 before a kernel reads it)"""
+    import torch
+    kinds = {torch.uint8: 0, torch.float32: 2, torch.float64: 2, torch.int16: 3, torch.int32: 5}
+    if hasattr(torch, 'uint16'):
+        kinds[torch.uint16] = 1
+    return kinds
+
+
 def _inspect(arr):
     """What a map is, without touching the device: (obj, kind, H, W, C, ld, coff).  obj is the CUDA tensor to read where it lies, or the
     host array to upload.  ValueError for anything `write_cog` does not take."""
     import torch
     if isinstance(arr, torch.Tensor) and arr.is_cuda:
         t = arr
-        kinds = {torch.uint8: 0, torch.float32: 2, torch.float64: 2, torch.int16: 3, torch.int32: 5}
-        if hasattr(torch, 'uint16'):
-            kinds[torch.uint16] = 1
+        kinds = _tensor_kinds()
         if t.dtype not in kinds:
             raise ValueError(f'a map is uint8, uint16, int16, int32, float32 or float64, got {t.dtype}')
         if t.dim() not in (2, 3) or 0 in t.shape:
@@ -930,3 +938,410 @@ def read_stack(paths, window=None, bands=None):
     for t, p in enumerate(paths):
         r = read_cog(p, (row0, col0, h, w), 0, bands, 'chw', True, None, stack[t])
     return stack, r.transform, r.crs, r.nodata
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Alignment: rasters of one CRS brought onto one pixel grid, on the device.
+#
+#     grids on the host (Grid, union_grid, warp_window) -> the window of the file the grid needs (read_cog) -> satcv_raster_warp
+#       (nearest / bilinear / cubic / average, nodata-aware, into a new raster, a slot of a stack or a channel range of a scene)
+#
+# What the reference takes from stackstac.stack(epsg=, resolution=), gdal.BuildVRT / rioxarray's merge_arrays and reproject_match
+# (utils/pc_tools.py:152-186, 251-282, 368-431).  The resampling rules are this library's own (include/satcv.h, "Raster alignment").
+# Refused by name: rotated or sheared transforms, two different EPSG codes (there is no reprojection), a raster without a transform.
+WARP_RESAMPLING = {'nearest': 0, 'bilinear': 1, 'cubic': 2, 'average': 3}
+_WARP_MARGIN = {'nearest': 0, 'bilinear': 1, 'cubic': 2}
+MAX_AVERAGE_SCALE = 64
+
+
+def _check_transform(transform, what):
+    if transform is None:
+        raise ValueError(f'{what} has no transform: it cannot be placed on a grid')
+    t = tuple(float(v) for v in transform)
+    if len(t) != 6:
+        raise ValueError(f'transform is six numbers (a, b, c, d, e, f), got {len(t)} for {what}')
+    if t[1] != 0 or t[3] != 0:
+        raise ValueError(f'{what} has a rotated or sheared transform (b = {t[1]}, d = {t[3]}): only scale and shift are resampled')
+    if not (np.isfinite(t).all() and t[0] != 0 and t[4] != 0):
+        raise ValueError(f'{what} has a transform with a zero or non-finite pixel size: {t}')
+    return t
+
+
+def _epsg_of(crs):
+    return None if crs is None else parse_crs(crs)[0]
+
+
+def _common_epsg(codes, what='the sources'):
+    """the one EPSG code of `codes` (None entries say nothing): ValueError for two different ones"""
+    known = sorted({c for c in codes if c is not None})
+    if len(known) > 1:
+        raise ValueError(f'{what} are in EPSG:{known[0]} and EPSG:{known[1]}: reprojection between coordinate systems is not done')
+    return known[0] if known else None
+
+
+class Grid(tuple):
+    """A pixel grid: transform (six numbers in Affine order, b == d == 0), shape (H, W), crs ('EPSG:n' or None).  An immutable value;
+    `bounds` is (left, bottom, right, top), `resolution` (|a|, |e|)."""
+    __slots__ = ()
+
+    def __new__(cls, transform, shape, crs=None):
+        t = _check_transform(transform, 'a grid')
+        if len(tuple(shape)) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 1 for v in shape):
+            raise ValueError(f'a grid has a shape (H, W) of positive integers, got {shape!r}')
+        epsg = _epsg_of(crs)
+        return tuple.__new__(cls, (t, (int(shape[0]), int(shape[1])), None if epsg is None else f'EPSG:{epsg}'))
+
+    transform = property(lambda self: self[0])
+    shape = property(lambda self: self[1])
+    crs = property(lambda self: self[2])
+
+    @property
+    def epsg(self):
+        return _epsg_of(self[2])
+
+    @property
+    def resolution(self):
+        return abs(self[0][0]), abs(self[0][4])
+
+    @property
+    def bounds(self):
+        a, _, c, _, e, f = self[0]
+        H, W = self[1]
+        xs, ys = (c, c + W * a), (f, f + H * e)
+        return min(xs), min(ys), max(xs), max(ys)
+
+    def __repr__(self):
+        return f'Grid(transform={self[0]!r}, shape={self[1]!r}, crs={self[2]!r})'
+
+
+def _as_grid(source):
+    """a path, a LevelInfo or a Grid as a Grid"""
+    if isinstance(source, Grid):
+        return source
+    if isinstance(source, LevelInfo):
+        _check_transform(source.transform, f'IFD {source.index}')
+        return Grid(source.transform, source.shape, source.crs)
+    info = read_info(source)[0]
+    _check_transform(info.transform, str(source))
+    return Grid(info.transform, info.shape, info.crs)
+
+
+def union_grid(sources, resolution=None, bounds=None, crs=None):
+    """The north-up grid that holds every source: -> Grid.  sources: paths, `LevelInfo`s or `Grid`s.  resolution: a number or (x, y);
+    None: the finest among the sources, per axis.  bounds: (left, bottom, right, top); None: the union of the sources' bounds.  The
+    bounds are snapped outward to multiples of the resolution (stackstac's snap_bounds), so grids made from overlapping sets of files
+    share their pixel edges.  ValueError for rotated sources, sources without a transform, and two different EPSG codes."""
+    grids = [_as_grid(s) for s in sources]
+    epsg = _common_epsg([g.epsg for g in grids] + [_epsg_of(crs)])
+    if resolution is None:
+        if not grids:
+            raise ValueError('union_grid needs sources or a resolution')
+        rx, ry = min(g.resolution[0] for g in grids), min(g.resolution[1] for g in grids)
+    else:
+        rx, ry = (float(resolution),) * 2 if np.ndim(resolution) == 0 else (float(v) for v in resolution)
+    if not (np.isfinite([rx, ry]).all() and rx > 0 and ry > 0):
+        raise ValueError(f'resolution must be positive, got {resolution!r}')
+    if bounds is None:
+        if not grids:
+            raise ValueError('union_grid needs sources or bounds')
+        b = [g.bounds for g in grids]
+        bounds = min(v[0] for v in b), min(v[1] for v in b), max(v[2] for v in b), max(v[3] for v in b)
+    left, bottom, right, top = (float(v) for v in bounds)
+    if not (np.isfinite([left, bottom, right, top]).all() and left < right and bottom < top):
+        raise ValueError(f'bounds are (left, bottom, right, top) with left < right and bottom < top, got {bounds!r}')
+    left, right = np.floor(left / rx) * rx, np.ceil(right / rx) * rx
+    bottom, top = np.floor(bottom / ry) * ry, np.ceil(top / ry) * ry
+    return Grid((rx, 0.0, float(left), 0.0, -ry, float(top)), (int(round((top - bottom) / ry)), int(round((right - left) / rx))),
+                None if epsg is None else f'EPSG:{epsg}')
+
+
+def warp_coefficients(src_transform, dst_transform):
+    """(su, ou, sv, ov) of satcv_raster_warp: destination pixel coordinates (j + 0.5, i + 0.5) -> source pixel coordinates
+    u = su * (j + 0.5) + ou, v = sv * (i + 0.5) + ov"""
+    a_s, _, c_s, _, e_s, f_s = _check_transform(src_transform, 'the source')
+    a_d, _, c_d, _, e_d, f_d = _check_transform(dst_transform, 'the destination grid')
+    return a_d / a_s, (c_d - c_s) / a_s, e_d / e_s, (f_d - f_s) / e_s
+
+
+def _check_method(resampling, su, sv):
+    if resampling not in WARP_RESAMPLING:
+        raise ValueError(f'resampling must be one of {sorted(WARP_RESAMPLING)}, got {resampling!r}')
+    if resampling == 'average' and max(abs(su), abs(sv)) > MAX_AVERAGE_SCALE:
+        raise ValueError(f"resampling='average' over a footprint of {abs(sv):.4g} x {abs(su):.4g} source pixels (at most {MAX_AVERAGE_SCALE} per axis): "
+                         "read an overview of the source instead (level='auto')")
+
+
+def warp_window(src_transform, src_shape, grid, resampling='nearest'):
+    """The window (row0, col0, h, w) of a source raster that `grid` needs under `resampling`, or None when the grid misses the raster:
+    the pixels under the grid's sample points and 0 (nearest), 1 (bilinear) or 2 (cubic) more on every side, for 'average' the pixels
+    the grid's footprint touches; clipped to the raster."""
+    su, ou, sv, ov = warp_coefficients(src_transform, grid.transform)
+    _check_method(resampling, su, sv)
+    out = []
+    for s, o, n_dst, n_src in ((sv, ov, grid.shape[0], src_shape[0]), (su, ou, grid.shape[1], src_shape[1])):
+        if resampling == 'average':
+            ends = (s * 0.0 + o, s * float(n_dst) + o)
+            lo, hi = int(np.floor(min(ends))), int(np.ceil(max(ends))) - 1
+        else:
+            ends = (s * 0.5 + o, s * (n_dst - 0.5) + o)
+            m = _WARP_MARGIN[resampling]
+            lo, hi = int(np.floor(min(ends))) - m, int(np.floor(max(ends))) + m
+        lo, hi = max(lo, 0), min(hi, int(n_src) - 1)
+        if lo > hi:
+            return None
+        out.append((lo, hi - lo + 1))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def auto_level(level_transforms, grid):
+    """level='auto' of `read_warped`: the index of the coarsest level whose pixels are no larger than the grid's on either axis (level 0
+    when none is); level_transforms: the transform of every level, the image first"""
+    rx, ry = grid.resolution
+    best, size = 0, -1.0
+    for k, t in enumerate(level_transforms):
+        px, py = abs(t[0]), abs(t[4])
+        if px <= rx * (1 + 1e-9) and py <= ry * (1 + 1e-9) and px * py > size:
+            best, size = k, px * py
+    return best
+
+
+def _fill(t, dtype, value):
+    """every sample of the CUDA tensor `t` (a view too) becomes `value` of kind `dtype` (uint16 may be stored as int16)"""
+    import torch
+    if dtype == 'float32':
+        t.fill_(float(value))
+    else:
+        nt = np.dtype(DTYPES[dtype][0])
+        store = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[nt.itemsize]
+        t.view(store).fill_(int(np.array(value, nt).view({1: np.uint8, 2: np.int16, 4: np.int32}[nt.itemsize])))
+    return t
+
+
+def _invalid_value(dtype, nodata):
+    return nodata if nodata is not None else (float('nan') if dtype == 'float32' else 0)
+
+
+def _chw_or_hwc(layout):
+    if layout not in ('hwc', 'chw'):
+        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
+    return 0 if layout == 'hwc' else 1
+
+
+def _warp_source(src, src_layout, src_dtype):
+    """a resident source as (pointer of band 0 of pixel 0 of the ld-wide raster, kind name, h, w, c, ld, coff, two-dimensional)"""
+    import torch
+    if not (isinstance(src, torch.Tensor) and src.is_cuda):
+        raise ValueError('warp takes a resident raster: a CUDA tensor')
+    if src.dtype == torch.float64:
+        raise ValueError('a resident raster is uint8, uint16, int16, int32 or float32, got torch.float64')
+    if _chw_or_hwc(src_layout) == 0:
+        t, kind, h, w, c, ld, coff = _inspect(src)
+        ptr = t.data_ptr() - coff * t.element_size()
+    else:
+        if src.dim() not in (2, 3) or 0 in src.shape or not src.is_contiguous():
+            raise ValueError(f"a 'chw' source is a contiguous, non-empty (C, H, W) or (H, W) CUDA tensor, got shape {tuple(src.shape)}")
+        if src.dtype not in _tensor_kinds():
+            raise ValueError(f'a resident raster is uint8, uint16, int16, int32 or float32, got {src.dtype}')
+        kind = _tensor_kinds()[src.dtype]
+        c, h, w = ((1,) + tuple(src.shape))[-3:]
+        ld, coff, ptr = c, 0, src.data_ptr()
+        if c > 16:
+            raise ValueError(f'{c} bands: a raster has at most 16')
+    name = _NAME_OF_KIND[kind]
+    if src_dtype is not None:
+        if src_dtype not in DTYPES or np.dtype(DTYPES[src_dtype][0]).itemsize != src.element_size() or (src_dtype == 'float32') != (name == 'float32'):
+            raise ValueError(f'src_dtype {src_dtype!r} does not describe a tensor of {src.dtype}')
+        name = src_dtype
+    return ptr, name, int(h), int(w), int(c), int(ld), int(coff), src.dim() == 2
+
+
+def warp(src, src_transform, grid, resampling='nearest', src_nodata=None, nodata=None, dtype=None, src_layout='hwc', layout='hwc', out=None,
+         channel_offset=0, keep=False, src_origin=(0, 0), src_dtype=None):
+    """A resident raster resampled onto `grid` (same CRS), on the device: -> CUDA tensor of grid.shape.
+
+    src: a CUDA tensor -- (H, W) or (H, W, C) for src_layout 'hwc' (contiguous, or a channel slice of a contiguous (H, W, ld) tensor),
+    (H, W) or a contiguous (C, H, W) for 'chw'; C <= 16; uint8, uint16, int16, int32 or float32 (src_dtype='uint16' names the kind of
+    an int16 tensor that stores uint16 bytes).  src_transform: the Affine transform of the grid `src` is a window of; src_origin:
+    (row, col) of src[0, 0] on that grid -- a window warped with its origin equals the whole raster warped, bit for bit.
+    grid: the destination `Grid`.  resampling: 'nearest', 'bilinear', 'cubic' (Catmull-Rom) or 'average' (area-weighted; at most 64
+    source pixels per destination pixel and axis) -- the rules of satcv_raster_warp in include/satcv.h, which are this library's own.
+    src_nodata: samples equal to it are invalid, as NaN is.  nodata: what an invalid result becomes; None: src_nodata, and without
+    that NaN (float32) or 0.  dtype: None keeps the source's kind, 'float32' converts.  keep=True leaves the destination untouched where
+    the result is invalid (the mosaic rule: later sources lie on top only where they have data).
+    out: the tensor to write into, contiguous: (H, W, ld) for layout 'hwc', (ld, H, W) for 'chw' (a slot stack[t] of a (T, C, H, W)
+    stack), or (H, W) -- bands go to channels channel_offset .. channel_offset + C - 1, no other channel is touched; returned as given.
+    Without `out` the result is a new (H, W, C) / (C, H, W) tensor ((H, W) for a two-dimensional source).
+    ValueError: rotated transforms, an unknown method, 'average' beyond 64 pixels, shapes or kinds that do not fit; MemoryError names a
+    destination that does not fit in device memory."""
+    import ctypes as C
+    import torch
+    from . import ops
+    from ._lib import WarpDesc, check, lib
+    from .prediction_tools import _device_empty
+    if not isinstance(grid, Grid):
+        raise ValueError(f'grid must be a Grid, got {type(grid).__name__}')
+    su, ou, sv, ov = warp_coefficients(src_transform, grid.transform)
+    _check_method(resampling, su, sv)
+    ptr, name, sh, sw, c, sld, scoff, flat = _warp_source(src, src_layout, src_dtype)
+    dname = name if dtype is None else dtype
+    if dname not in (name, 'float32'):
+        raise ValueError(f'dtype must be None, {name!r} (the source) or \'float32\', got {dtype!r}')
+    dl = _chw_or_hwc(layout)
+    H, W = grid.shape
+    if out is None:
+        shape = (H, W) if flat else ((H, W, c) if dl == 0 else (c, H, W))
+        out = _device_empty(shape, _torch_dtype(dname), 'the warped raster')
+        dld, dcoff = c, 0
+    else:
+        nt = np.dtype(DTYPES[dname][0])
+        want = '(H, W, ld)' if dl == 0 else '(ld, H, W)'
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dim() in (2, 3)):
+            raise ValueError(f'out must be a contiguous CUDA tensor of shape {want} or (H, W)')
+        hw = tuple(out.shape) if out.dim() == 2 else (tuple(out.shape[:2]) if dl == 0 else tuple(out.shape[1:]))
+        dld = 1 if out.dim() == 2 else int(out.shape[2] if dl == 0 else out.shape[0])
+        if hw != (H, W):
+            raise ValueError(f'out is {hw[0]} x {hw[1]}, the grid {H} x {W}')
+        if dtype is None and out.dtype == torch.float32:
+            dname, nt = 'float32', np.dtype(np.float32)
+        if out.element_size() != nt.itemsize or out.dtype.is_floating_point != (nt.kind == 'f') or out.dtype == torch.float64:
+            raise ValueError(f'out is {out.dtype}, the result {dname}')
+        dcoff = int(channel_offset)
+        if dcoff < 0 or dcoff + c > dld:
+            raise ValueError(f'channels {dcoff} ... {dcoff + c - 1} do not fit the {dld} of out')
+    if nodata is None:
+        nodata = src_nodata
+    d = WarpDesc(src=ptr, src_kind=DTYPES[name][1], src_layout=_chw_or_hwc(src_layout), sh=sh, sw=sw, src_ld=sld, src_coff=scoff,
+                 src_row0=int(src_origin[0]), src_col0=int(src_origin[1]), dst=out.data_ptr(), dst_kind=DTYPES[dname][1], dst_layout=dl, dh=H, dw=W,
+                 dst_ld=dld, dst_coff=dcoff, dst_row0=0, dst_col0=0, c=c, su=su, ou=ou, sv=sv, ov=ov, resampling=WARP_RESAMPLING[resampling],
+                 has_src_nodata=int(src_nodata is not None), src_nodata=float(src_nodata if src_nodata is not None else 0.0),
+                 has_dst_nodata=int(nodata is not None), dst_nodata=float(nodata if nodata is not None else 0.0), keep=int(bool(keep)))
+    check(lib.satcv_raster_warp(C.byref(d), ops.stream_ptr()))
+    _mark('warp')
+    return out
+
+
+def _file_levels(path, grid):
+    """the levels of a file that can be placed on `grid`: -> (levels, their transforms); ValueError for a file without a transform, a
+    rotated one, or one in another CRS"""
+    levels = _levels(read_info(path))
+    base = levels[0]
+    _check_transform(base.transform, str(path))
+    _common_epsg([base.epsg, grid.epsg], f'{path} and the grid')
+    return levels, [_window_transform(base.transform, base.shape, lv.shape, 0, 0) for lv in levels]
+
+
+def read_warped(path, grid, bands=None, resampling='nearest', level=0, layout='hwc', out=None, keep=False, nodata=None, dtype=None,
+                channel_offset=0, decode=None):
+    """A GeoTIFF / COG read onto `grid`: -> `Raster` on the grid (array, the grid's transform and CRS, nodata, dtype).
+
+    Only the window of the file that the grid needs is read (`warp_window`: the samples under the grid and 0 / 1 / 2 more for nearest /
+    bilinear / cubic, the footprint for average), then `warp` resamples it with the window's origin, so the result equals the whole
+    file warped.  A grid that misses the file reads nothing: the result is all nodata (untouched with keep).
+    bands, decode: as for `read_cog`.  level: 0 the image (the default: results do not depend on how the overviews were made), k its
+    k-th overview, 'auto' the coarsest level whose pixels are no larger than the grid's on either axis (`auto_level`).
+    resampling, layout, out, channel_offset, keep, dtype: as for `warp`.  nodata: what invalid results become; None: the file's nodata,
+    without one NaN (float32) or 0.  ValueError: a file without a transform, a rotated one, one in another EPSG code than the grid's
+    ("reprojection between coordinate systems is not done"), and what `read_cog` and `warp` refuse."""
+    from .prediction_tools import _device_empty
+    if not isinstance(grid, Grid):
+        raise ValueError(f'grid must be a Grid, got {type(grid).__name__}')
+    levels, transforms = _file_levels(path, grid)
+    if level == 'auto':
+        level = auto_level(transforms, grid)
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 0 <= level < len(levels):
+        raise ValueError(f"level {level!r}: the file has levels 0 ... {len(levels) - 1} (or 'auto')")
+    info, lt = levels[int(level)], transforms[int(level)]
+    src_nodata = info.nodata if info.nodata is not None else levels[0].nodata
+    if nodata is None:
+        nodata = src_nodata
+    dname = info.dtype if dtype is None else dtype
+    crs = grid.crs if grid.crs is not None else levels[0].crs
+    window = warp_window(lt, info.shape, grid, resampling)
+    if window is None:
+        _, nb, _ = _plan_read(info, None, bands)
+        c = len(nb)
+        if out is None:
+            H, W = grid.shape
+            out = _device_empty((H, W, c) if _chw_or_hwc(layout) == 0 else (c, H, W), _torch_dtype(dname), 'the warped raster')
+            _fill(out, dname, _invalid_value(dname, nodata))
+        elif not keep:
+            if out.dtype.is_floating_point:
+                dname = 'float32'
+            part = out if out.dim() == 2 else (out[..., channel_offset:channel_offset + c] if layout == 'hwc' else out[channel_offset:channel_offset + c])
+            _fill(part, dname, _invalid_value(dname, nodata))
+        return Raster(out, grid.transform, crs, nodata, dname)
+    r = read_cog(path, window, int(level), bands, 'hwc', True, decode)
+    arr = warp(r.array, lt, grid, resampling, src_nodata, nodata, dtype, 'hwc', layout, out, channel_offset, keep, window[:2], info.dtype)
+    return Raster(arr, grid.transform, crs, nodata, 'float32' if arr.dtype.is_floating_point else info.dtype)
+
+
+def _same_kind(paths, bands):
+    """(dtype, number of bands read, nodata) the files share; ValueError names the first that differs in kind or band count"""
+    first = read_info(paths[0])[0]
+    n = len(_plan_read(first, None, bands)[1])
+    for p in paths[1:]:
+        i = read_info(p)[0]
+        if i.dtype != first.dtype or (bands is None and i.bands != first.bands):
+            raise ValueError(f'{p} differs from {paths[0]} in kind or bands: {i.dtype} x {i.bands} against {first.dtype} x {first.bands}')
+    return first.dtype, n, first.nodata
+
+
+def read_mosaic(paths, grid=None, bands=None, resampling='nearest', level=0, layout='hwc', first=False, nodata=None, dtype=None, out=None,
+                channel_offset=0, decode=None):
+    """Files of one CRS mosaicked onto one grid: -> `Raster`.  grid: None is `union_grid(paths)`.  The destination is filled with
+    nodata, then every file is read onto it with keep=True, in order: a later file lies on top wherever it has valid data
+    (gdal.BuildVRT's order); first=True goes through the files in reverse, so the first file wins (rioxarray's merge_arrays).
+    nodata: None is the first file's, without one NaN (float32) or 0.  The other arguments as for `read_warped`."""
+    from .prediction_tools import _device_empty
+    paths = list(paths)
+    if not paths:
+        raise ValueError('read_mosaic needs at least one file')
+    if grid is None:
+        grid = union_grid(paths)
+    for p in paths:
+        _file_levels(p, grid)                                  # every refusal before anything is allocated
+    name, c, file_nodata = _same_kind(paths, bands)
+    if nodata is None:
+        nodata = file_nodata
+    dname = name if dtype is None else dtype
+    H, W = grid.shape
+    if out is None:
+        out = _device_empty((H, W, c) if _chw_or_hwc(layout) == 0 else (c, H, W), _torch_dtype(dname), 'the mosaic')
+        part = out
+    else:
+        part = out if out.dim() == 2 else (out[..., channel_offset:channel_offset + c] if layout == 'hwc' else out[channel_offset:channel_offset + c])
+        if out.dtype.is_floating_point:
+            dname = 'float32'
+    _fill(part, dname, _invalid_value(dname, nodata))
+    for p in (reversed(paths) if first else paths):
+        r = read_warped(p, grid, bands, resampling, level, layout, out, True, nodata, dtype, channel_offset, decode)
+    return Raster(out, grid.transform, r.crs, nodata, dname)
+
+
+def read_aligned_stack(items, grid=None, resolution=None, bands=None, resampling='nearest', level=0):
+    """The acquisitions of a time series on ONE grid as a resident stack: -> (stack, transform, crs, nodata), the contract of
+    `read_stack` -- stack a (T, C, H, W) CUDA tensor in the files' kind -- for files that need not share a grid: other footprints,
+    other resolutions (the 20 m bands beside the 10 m ones), one CRS.  items: per acquisition a path, or a list of paths mosaicked
+    into the slot (`read_mosaic`).  grid: None is `union_grid` of every file at `resolution` (None: the finest).  Every file is
+    resampled straight into its slot.  With files that already share the grid, nearest gives `read_stack`'s result bit for bit."""
+    import os
+    from .prediction_tools import _device_empty
+    items = [[it] if isinstance(it, (str, os.PathLike)) else list(it) for it in items]
+    flat = [p for it in items for p in it]
+    if not flat or any(not it for it in items):
+        raise ValueError('read_aligned_stack needs at least one file per acquisition')
+    if grid is None:
+        grid = union_grid(flat, resolution=resolution)
+    elif resolution is not None:
+        raise ValueError('resolution describes the grid that is built when none is given')
+    for p in flat:
+        _file_levels(p, grid)
+    name, c, nodata = _same_kind(flat, bands)
+    H, W = grid.shape
+    stack = _device_empty((len(items), c, H, W), _torch_dtype(name), 'the time stack')
+    for t, it in enumerate(items):
+        if len(it) == 1:
+            r = read_warped(it[0], grid, bands, resampling, level, 'chw', stack[t], False, nodata)
+        else:
+            r = read_mosaic(it, grid, bands, resampling, level, 'chw', False, nodata, None, stack[t])
+    return stack, grid.transform, r.crs, nodata
