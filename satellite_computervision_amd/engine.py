@@ -261,7 +261,7 @@ class Runtime:
             self.adam_m = torch.zeros_like(self.pflat)
             self.adam_v = torch.zeros_like(self.pflat)
 
-    # ---- what model_tools.apply_optimizer asks of the owner of the flat buffers
+    # ---- what training.apply_optimizer asks of the owner of the flat buffers
     def opt_buffers(self):
         return self.pflat, self.gflat, self.adam_state, self.lr_mul
 

@@ -23,6 +23,7 @@ import torch
 
 from . import ops, switches
 from . import model_tools as mt
+from .training import MeanIoU, resolve_optimizer, resolve_loss, reset_slots_on_recompile, apply_optimizer, metric_from_confusion, fit_loop
 from ._lib import lib, check, F32, BF16, LstmGatesDesc, DenseDesc
 
 RECURRENT_ACTIVATION = switches.read('lstm_recurrent_activation')
@@ -123,7 +124,7 @@ class _Params:
                 mul[off:off + int(np.prod(shape))] = 0
         self.lr_mul = torch.from_numpy(mul).to(_dev())
 
-    # ---- what model_tools.apply_optimizer asks of the owner of the flat buffers (as engine.Runtime)
+    # ---- what training.apply_optimizer asks of the owner of the flat buffers (as engine.Runtime)
     @property
     def adam_state(self):
         return self.state
@@ -566,7 +567,7 @@ def _dev_f32(a):
 
 
 class _SeqModelBase:
-    """compile / fit / predict / train_on_batch plumbing shared by the LSTM-family models (the optimizer step through model_tools.apply_optimizer)"""
+    """compile / fit / predict / train_on_batch plumbing shared by the LSTM-family models (the Keras training surface -- losses, optimizers, callbacks, the epoch loop -- is training.py)"""
 
     def _finish(self):
         self.P.build()
@@ -606,16 +607,13 @@ class _SeqModelBase:
             raise TypeError(f'{type(self).__name__}.compile: unsupported arguments {sorted(kw)}')
         if loss_weights is not None:
             raise NotImplementedError(f'{type(self).__name__}.compile: loss_weights (the outputs\' losses are added with weight 1, the Keras default)')
-        prev, new_opt = self.optimizer, mt.resolve_optimizer(optimizer)
-        spec = loss(mt._LossArg('y_true'), mt._LossArg('y_pred')) if callable(loss) else loss
-        if not isinstance(spec, mt.LossSpec):
-            raise ValueError('loss must be one of the model_tools loss functions (or a lambda wrapping one)')
-        self._loss = spec
+        prev, new_opt = self.optimizer, resolve_optimizer(optimizer)
+        self._loss = resolve_loss(loss)
         ms = []
         for m_ in (metrics or []):
             if isinstance(m_, str) and m_ in ('accuracy', 'acc', 'categorical_accuracy'):
                 ms.append(('accuracy', None))
-            elif isinstance(m_, mt.MeanIoU):
+            elif isinstance(m_, MeanIoU):
                 ms.append((m_.name, m_.num_classes))
             else:
                 raise ValueError(f'{type(self).__name__}.compile: metric {m_!r} is not supported (accuracy, model_tools.MeanIoU)')
@@ -628,19 +626,9 @@ class _SeqModelBase:
         self.__dict__.pop('_loss_w_dev', None)
         self._drop_graphs()
         self.optimizer = new_opt
-        mt.reset_slots_on_recompile(self.P, prev, new_opt)
+        reset_slots_on_recompile(self.P, prev, new_opt)
         self.optimizer._rt = self.P              # (`optimizer.learning_rate = ...` lands in the device state buffer at once)
         self.P.state[0:1].fill_(self.optimizer._lr)
-
-    @staticmethod
-    def _metric_value(kind, ncls, conf):
-        conf = conf.astype(np.float64)
-        if kind == 'accuracy':
-            return float(np.trace(conf) / max(conf.sum(), 1))
-        tp = np.diag(conf)
-        denom = conf.sum(0) + conf.sum(1) - tp
-        valid = denom > 0
-        return float((tp[valid] / denom[valid]).mean()) if valid.any() else 0.0
 
     def _loss_grad(self, out, y_true, activation):
         """fused device loss on the model output: returns (loss tensor, dL/dlogits for softmax / sigmoid heads, dL/dout for linear ones)"""
@@ -700,7 +688,7 @@ class _SeqModelBase:
         P, opt = self.P, self.optimizer
         if set_lr:
             P.state[0:1].fill_(opt._lr)
-        mt.apply_optimizer(opt, P)               # (clip if asked, then the step of whichever optimizer was compiled)
+        apply_optimizer(opt, P)                  # (clip if asked, then the step of whichever optimizer was compiled)
         P.bump()
 
     def get_weights_dict(self):
@@ -819,7 +807,7 @@ class _SeqModelBase:
             cnt += k
         vals = list(tot / max(cnt, 1))
         for oi in range(nout):
-            vals += [self._metric_value(kind, nc, confs[oi][mi]) for mi, (kind, nc) in enumerate(self._metrics)]
+            vals += [metric_from_confusion(kind, confs[oi][mi]) for mi, (kind, _) in enumerate(self._metrics)]
         if return_dict:
             return dict(zip(self.metrics_names, vals))
         return vals if len(vals) > 1 else vals[0]
@@ -835,44 +823,23 @@ class _SeqModelBase:
             raise NotImplementedError(f'{type(self).__name__}.fit(shuffle=True): shuffle inside the generator (on_epoch_end), as the reference does')
         if self._loss is None:
             raise RuntimeError('compile() the model before fit')
-        hist = mt.History()
-        callbacks = list(callbacks or [])
-        for cb in callbacks:
-            cb.model = self
-        self.stop_training = False
-        mt.run_callbacks(callbacks, 'on_train_begin')
-        for epoch in range(initial_epoch, epochs):
-            mt.run_callbacks(callbacks, 'on_epoch_begin', epoch)
+
+        def train_epoch(epoch):
             tot, cnt = 0.0, 0
             for i, (xb, yb) in enumerate(self._batches_of(x, y, batch_size, sample_weight)):
                 if steps_per_epoch is not None and i >= steps_per_epoch:
                     break
                 k = (xb[0] if isinstance(xb, (list, tuple)) else xb).shape[0]
                 tot, cnt = tot + self.train_on_batch(xb, yb) * k, cnt + k
-            logs = {'loss': tot / max(cnt, 1)}
-            if validation_data is not None:
-                if isinstance(validation_data, tuple) and len(validation_data) in (2, 3) and not hasattr(validation_data[0], '__next__'):
-                    v = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size, steps=validation_steps,
-                                      sample_weight=validation_data[2] if len(validation_data) == 3 else None, return_dict=True)
-                else:
-                    v = self.evaluate(validation_data, steps=validation_steps, return_dict=True)
-                logs.update({'val_' + k_: v_ for k_, v_ in v.items()})
-            for k_, v_ in logs.items():
-                hist.history[k_].append(v_)
-            hist.epoch.append(epoch)
-            if verbose:
-                print(f'Epoch {epoch + 1}/{epochs} - ' + ' - '.join(f'{k_}: {v_:.4f}' for k_, v_ in logs.items()))
-            before = set(logs)
-            for cb in callbacks:
-                if hasattr(cb, 'on_epoch_end'):
-                    cb.on_epoch_end(epoch, logs)
-            mt.record_callback_logs(hist, logs, before)
-            if hasattr(x, 'on_epoch_end'):
-                x.on_epoch_end()
-            if self.stop_training:
-                break
-        mt.run_callbacks(callbacks, 'on_train_end')
-        return hist
+            return {'loss': tot / max(cnt, 1)}
+
+        def validate():
+            if isinstance(validation_data, tuple) and len(validation_data) in (2, 3) and not hasattr(validation_data[0], '__next__'):
+                return self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size, steps=validation_steps,
+                                     sample_weight=validation_data[2] if len(validation_data) == 3 else None, return_dict=True)
+            return self.evaluate(validation_data, steps=validation_steps, return_dict=True)
+
+        return fit_loop(self, x, epochs, initial_epoch, callbacks, verbose, train_epoch, validate if validation_data is not None else None, show_time=False)
 
 
 class LSTMModel(_SeqModelBase):
@@ -977,12 +944,12 @@ class HybridModel(_SeqModelBase):
 
     def compile(self, optimizer='adam', loss=None, metrics=None, **kw):
         prev = self.optimizer
-        if mt.resolve_optimizer(optimizer).global_clipnorm is not None:
+        if resolve_optimizer(optimizer).global_clipnorm is not None:
             raise NotImplementedError('HybridModel.compile: global_clipnorm (the norm would span the two parameter buffers of the U-Net branch and '
                                       'of the ConvLSTM tape, which are clipped separately); clipvalue is element-wise and is supported')
         super().compile(optimizer, loss, metrics)
         self.unet.optimizer = self.optimizer
-        mt.reset_slots_on_recompile(self.unet.runtime, prev, self.optimizer)
+        reset_slots_on_recompile(self.unet.runtime, prev, self.optimizer)
         self.unet.runtime.adam_state[0:1].fill_(self.optimizer._lr)
 
     def _unet_branch(self, xu, training):
@@ -1091,7 +1058,7 @@ class HybridModel(_SeqModelBase):
         plan.run_backward(ops.stream_ptr())
         opt = self.optimizer
         rt.adam_state[0:1].fill_(opt._lr)
-        mt.apply_optimizer(opt, rt)
+        apply_optimizer(opt, rt)
         rt.repack()
         self.unet._weights_version = getattr(self.unet, '_weights_version', 0) + 1
         self._adam()

@@ -19,7 +19,6 @@ Surface mirrored here
 import ctypes as C
 import json
 import os
-import time
 from collections import defaultdict
 from fractions import Fraction
 
@@ -29,6 +28,12 @@ import torch
 from . import engine as E
 from . import ops, switches
 from ._lib import lib, check, F32, BF16
+# the Keras training surface (losses, optimizers, metrics, callbacks, the epoch loop) lives in training.py, shared with lstm_tools; its
+# names stay reachable here, under the reference's module name
+from .training import (LossSpec, _LossArg, weighted_categorical_crossentropy, weighted_bce, gen_dice, iou_loss, mse_4d,       # noqa: F401
+                       Adam, SGD, RMSprop, resolve_optimizer, reset_slots_on_recompile, apply_optimizer, MeanIoU, History,
+                       ModelCheckpoint, LearningRateScheduler, ReduceLROnPlateau, EarlyStopping, TensorBoard, run_callbacks,
+                       record_callback_logs, resolve_loss, metric_from_confusion, fit_loop)
 
 # ------------------------------------------------------------------------- globals
 _DEFAULT_DTYPE = 'bfloat16'
@@ -515,20 +520,7 @@ def get_acnn_model2(nclasses, nchannels, nfilters=16, depth=16):
     return m
 
 
-# ---------------------------------------------------------------------------- losses
-class LossSpec:
-    def __init__(self, kind, weights=None, eps=1e-6):
-        self.kind, self.eps = kind, float(eps)
-        self.weights = None if weights is None else np.asarray(weights, np.float32).reshape(-1)
-
-
-class _LossArg:
-    """placeholder handed to a user loss function so that it can describe itself"""
-
-    def __init__(self, what):
-        self.what = what
-
-
+# ----------------------------------------------------------------------------- Model
 def _resident_f32(x, like):
     """True when a caller's batch tensor can be read in place of the plan's staging tensor: float32, contiguous, same shape and device."""
     return (x.dtype == torch.float32 and x.is_contiguous() and x.device == like.device and tuple(x.shape) == tuple(like.shape)
@@ -540,411 +532,6 @@ def _y_ptr(plan):
     return y.data_ptr() if y is not None else plan.y_true.data_ptr()
 
 
-def _eager_loss(kind, y_true, y_pred, weights, activation='softmax', eps=1e-6):
-    dev = torch.device('cuda')
-    p = torch.as_tensor(np.asarray(y_pred, np.float32)).to(dev).contiguous()
-    t = torch.as_tensor(np.asarray(y_true, np.float32)).to(dev).contiguous()
-    w = None if weights is None else torch.as_tensor(np.asarray(weights, np.float32).reshape(-1)).to(dev)
-    loss, _ = ops.loss_fwd_bwd(kind, p, t, w, activation, eps=eps)
-    return float(loss.item())
-
-
-def weighted_categorical_crossentropy(target, output, weights, axis=-1):
-    """utils/model_tools.py:25-40 (reduced to its mean, as Keras does for a loss function)."""
-    if isinstance(output, _LossArg):
-        return LossSpec('weighted_categorical_crossentropy', weights)
-    return _eager_loss('weighted_categorical_crossentropy', target, output, weights)
-
-
-def weighted_bce(y_true, y_pred, pos_weight, logits=False):
-    """utils/model_tools.py:96-112 (probability form; logits=True is not on the fused path)."""
-    if logits:
-        raise NotImplementedError('weighted_bce(logits=True): the model heads output probabilities')
-    if isinstance(y_pred, _LossArg):
-        return LossSpec('weighted_bce', [pos_weight])
-    return _eager_loss('weighted_bce', y_true, y_pred, [pos_weight])
-
-
-def gen_dice(y_true, y_pred, eps=1e-6, global_weights=None):
-    """utils/model_tools.py:42-94: generalised Dice over (b, h*w, classes), mean over the batch.
-    With global_weights=None the per-image class weights are 1/count^2 (eps where a class is absent) --
-    the documented intent; the reference's own reduction axis (:80) does not broadcast."""
-    if isinstance(y_pred, _LossArg):
-        return LossSpec('gen_dice', global_weights if global_weights else None, eps)
-    return _eager_loss('gen_dice', y_true, y_pred, global_weights if global_weights else None, eps=eps)
-
-
-def iou_loss(true, pred):
-    """utils/model_tools.py:131-140: 1 - sum(t*p) / sum(t + (1-t)*p) over the whole batch."""
-    if isinstance(pred, _LossArg):
-        return LossSpec('iou_loss')
-    return _eager_loss('iou_loss', true, pred, None)
-
-
-def mse_4d(y_true, y_pred, eps=1e-6):
-    """utils/model_tools.py:142-166: mean squared error over the finite elements."""
-    if isinstance(y_pred, _LossArg):
-        return LossSpec('mse_4d')
-    return _eager_loss('mse_4d', y_true, y_pred, None)
-
-
-# ------------------------------------------------------------- optimizers / metrics
-class _LR:
-    def __init__(self, opt):
-        self._opt = opt
-
-    def numpy(self):
-        return np.float32(self._opt._lr)
-
-    def assign(self, v):
-        self._opt._set_lr(float(v))
-
-    def __float__(self):
-        return float(self._opt._lr)
-
-
-class _Optimizer:
-    """what the Keras optimizers share: the `learning_rate` / `lr` property whose value lands in the device state buffer, and the
-    base-class gradient clipping arguments `clipvalue` / `global_clipnorm` (at most one; the per-variable `clipnorm` is refused)."""
-    kind = None
-    slot_names = ()
-
-    def _init_base(self, learning_rate, kwargs, strict=True):
-        kwargs = dict(kwargs)
-        if kwargs.pop('clipnorm', None) is not None:
-            raise ValueError(f'{type(self).__name__}(clipnorm=...): per-variable norm clipping is not implemented; global_clipnorm= clips by the '
-                             'norm of the whole gradient')
-        self.clipvalue, self.global_clipnorm = kwargs.pop('clipvalue', None), kwargs.pop('global_clipnorm', None)
-        if self.clipvalue is not None and self.global_clipnorm is not None:
-            raise ValueError(f'{type(self).__name__}: at most one of clipvalue and global_clipnorm may be set')
-        for name in ('clipvalue', 'global_clipnorm'):
-            c = getattr(self, name)
-            if c is not None and not float(c) > 0:
-                raise ValueError(f'{type(self).__name__}({name}={c!r}): must be positive')
-        self._lr = float(kwargs.pop('lr', learning_rate))
-        if strict and kwargs:
-            raise TypeError(f'{type(self).__name__}: unsupported arguments {sorted(kwargs)}')
-        self._rt = None
-
-    def _set_lr(self, v):
-        self._lr = v
-        if self._rt is not None:
-            self._rt.adam_state[0:1].fill_(v)
-
-    @property
-    def learning_rate(self):
-        return _LR(self)
-
-    @learning_rate.setter
-    def learning_rate(self, v):
-        self._set_lr(float(v))
-
-    lr = learning_rate
-
-
-class Adam(_Optimizer):
-    """tf.keras.optimizers.Adam: epsilon 1e-7 outside the bias correction."""
-    kind = 'adam'
-    slot_names = ('m', 'v')
-
-    def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, **kwargs):
-        self._init_base(learning_rate, kwargs, strict=False)
-        self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
-
-
-class SGD(_Optimizer):
-    """tf.keras.optimizers.SGD: v = momentum v - lr g, p += v (nesterov: p += momentum v - lr g); no slot without momentum."""
-    kind = 'sgd'
-
-    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, **kwargs):
-        self._init_base(learning_rate, kwargs)
-        if not 0.0 <= float(momentum) <= 1.0:
-            raise ValueError('`momentum` must be between [0, 1].')
-        self.momentum, self.nesterov = float(momentum), bool(nesterov) and float(momentum) > 0     # (Keras: nesterov without momentum is plain SGD)
-        self.slot_names = ('v',) if self.momentum > 0 else ()
-
-
-class RMSprop(_Optimizer):
-    """tf.keras.optimizers.RMSprop: epsilon inside the root (ApplyRMSProp / ApplyCenteredRMSProp); `mg` only when centered, `mom`
-    only with momentum."""
-    kind = 'rmsprop'
-
-    def __init__(self, learning_rate=1e-3, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, **kwargs):
-        self._init_base(learning_rate, kwargs)
-        if not 0.0 <= float(momentum) <= 1.0:
-            raise ValueError('`momentum` must be between [0, 1].')
-        self.rho, self.momentum, self.epsilon, self.centered = float(rho), float(momentum), float(epsilon), bool(centered)
-        self.slot_names = ('ms',) + (('mg',) if self.centered else ()) + (('mom',) if self.momentum > 0 else ())
-
-
-_OPTIMIZERS = {'adam': Adam, 'sgd': SGD, 'rmsprop': RMSprop}
-
-
-def resolve_optimizer(optimizer):
-    """the `optimizer=` of compile(): 'adam' / 'sgd' / 'rmsprop' or an instance of Adam, SGD, RMSprop; anything else is refused"""
-    if isinstance(optimizer, str):
-        if optimizer.lower() not in _OPTIMIZERS:
-            raise ValueError(f'unknown optimizer {optimizer!r}: one of {sorted(_OPTIMIZERS)}')
-        return _OPTIMIZERS[optimizer.lower()]()
-    if isinstance(optimizer, (Adam, SGD, RMSprop)):
-        return optimizer
-    raise TypeError(f'compile(optimizer={type(optimizer).__name__}): supported are model_tools.Adam, model_tools.SGD, model_tools.RMSprop '
-                    "or the strings 'adam', 'sgd', 'rmsprop'")
-
-
-def reset_slots_on_recompile(owner, prev, new):
-    """Keras builds fresh slots for a newly compiled optimizer.  Here the moments of an Adam model have always survived a re-compile with
-    another Adam; any other change of optimizer starts from zero slots and step 0."""
-    if prev is not None and prev is not new and (prev.kind != new.kind or new.kind != 'adam'):
-        owner.reset_opt_slots()
-
-
-def apply_optimizer(opt, owner, st=None):
-    """The one step dispatch of every training path (U-Net engine, ConvLSTM tape, hybrid, data parallel -- whose all-reduce has run by
-    now): clip the flat gradient if the optimizer asks for it, then launch its update.  `owner` holds the flat buffers and the slots
-    (engine.Runtime or lstm_tools._Params).  A missing kernel is an error: there is no eager fallback."""
-    p, g, state, lr_mul = owner.opt_buffers()
-    st = ops.stream_ptr() if st is None else st
-    if opt.clipvalue is not None:
-        check(lib.satcv_grad_clip(g.data_ptr(), g.numel(), ops.CLIP_VALUE, float(opt.clipvalue), state.data_ptr(), None, st))
-    elif opt.global_clipnorm is not None:
-        check(lib.satcv_grad_clip(g.data_ptr(), g.numel(), ops.CLIP_GLOBAL_NORM, float(opt.global_clipnorm), state.data_ptr(),
-                                  owner.clip_workspace().data_ptr(), st))
-    lm = lr_mul.data_ptr() if lr_mul is not None else None
-    sl = owner.opt_slots(opt)
-    if opt.kind == 'adam':
-        check(lib.satcv_adam_step(p.data_ptr(), g.data_ptr(), sl['m'].data_ptr(), sl['v'].data_ptr(), p.numel(), opt.beta_1, opt.beta_2, opt.epsilon,
-                                  state.data_ptr(), lm, st))
-    elif opt.kind == 'sgd':
-        check(lib.satcv_sgd_step(p.data_ptr(), g.data_ptr(), sl['v'].data_ptr() if 'v' in sl else None, p.numel(), opt.momentum, int(opt.nesterov),
-                                 state.data_ptr(), lm, st))
-    elif opt.kind == 'rmsprop':
-        check(lib.satcv_rmsprop_step(p.data_ptr(), g.data_ptr(), sl['ms'].data_ptr(), sl['mg'].data_ptr() if 'mg' in sl else None,
-                                     sl['mom'].data_ptr() if 'mom' in sl else None, p.numel(), opt.rho, opt.momentum, opt.epsilon, state.data_ptr(), lm, st))
-    else:
-        raise TypeError(f'no update kernel for optimizer {type(opt).__name__}')
-
-
-class MeanIoU:
-    """tf.keras.metrics.MeanIoU(num_classes): mean over classes of TP/(TP+FP+FN), on class ids."""
-
-    def __init__(self, num_classes, name='mean_io_u'):
-        self.num_classes, self.name = num_classes, name
-
-
-class History:
-    def __init__(self):
-        self.history = defaultdict(list)
-        self.epoch = []
-
-
-class ModelCheckpoint:
-    """tf.keras.callbacks.ModelCheckpoint (nb:1228-1235); `.best` is mutable as retrain_model needs (:1168)."""
-
-    def __init__(self, filepath, monitor='val_loss', verbose=0, save_best_only=False, save_weights_only=False, mode='auto', **kw):
-        self.filepath, self.monitor, self.verbose = filepath, monitor, verbose
-        self.save_best_only, self.save_weights_only = save_best_only, save_weights_only
-        if mode == 'auto':
-            mode = 'max' if ('acc' in monitor or 'io_u' in monitor or 'iou' in monitor) else 'min'
-        self.mode = mode
-        self.best = -np.inf if mode == 'max' else np.inf
-        self.model = None
-
-    def on_epoch_end(self, epoch, logs):
-        cur = logs.get(self.monitor)
-        path = self.filepath.format(epoch=epoch + 1, **logs)
-        if self.save_best_only:
-            if cur is None:
-                return
-            better = cur > self.best if self.mode == 'max' else cur < self.best
-            if not better:
-                return
-            self.best = cur
-        (self.model.save_weights if self.save_weights_only else self.model.save)(path)
-
-
-def _auto_mode(mode, monitor):
-    if mode not in ('auto', 'min', 'max'):
-        raise ValueError(f"mode {mode!r}: one of 'auto', 'min', 'max'")
-    if mode == 'auto':
-        mode = 'max' if 'acc' in monitor else 'min'
-    return mode
-
-
-class LearningRateScheduler:
-    """tf.keras.callbacks.LearningRateScheduler: at the start of every epoch the rate becomes schedule(epoch, lr) (or schedule(epoch)
-    for a one-argument schedule), through `optimizer.learning_rate`; `lr` is added to the epoch logs."""
-
-    def __init__(self, schedule, verbose=0):
-        self.schedule, self.verbose = schedule, verbose
-        self.model = None
-
-    def on_epoch_begin(self, epoch, logs=None):
-        opt = self.model.optimizer
-        lr = float(opt.learning_rate)
-        try:
-            lr = self.schedule(epoch, lr)
-        except TypeError:               # (old one-argument form, as Keras still accepts)
-            lr = self.schedule(epoch)
-        if not isinstance(lr, (float, np.float32, np.float64)):
-            raise ValueError(f'The output of the "schedule" function should be float. Got: {lr}')
-        opt.learning_rate = float(lr)
-        if self.verbose:
-            print(f'Epoch {epoch + 1}: LearningRateScheduler setting learning rate to {float(lr)}.')
-
-    def on_epoch_end(self, epoch, logs):
-        logs['lr'] = float(self.model.optimizer.learning_rate)
-
-
-class ReduceLROnPlateau:
-    """tf.keras.callbacks.ReduceLROnPlateau: after `patience` epochs without an improvement of `monitor` by more than `min_delta` the rate
-    is multiplied by `factor` (not below `min_lr`), then `cooldown` epochs pass before the count starts again.  The rate goes through
-    `optimizer.learning_rate`; `lr` (the rate the epoch ran with) is added to the epoch logs."""
-
-    def __init__(self, monitor='val_loss', factor=0.1, patience=10, verbose=0, mode='auto', min_delta=1e-4, cooldown=0, min_lr=0, **kw):
-        if kw:
-            raise TypeError(f'ReduceLROnPlateau: unsupported arguments {sorted(kw)}')
-        if factor >= 1.0:
-            raise ValueError('ReduceLROnPlateau does not support a factor >= 1.0.')
-        self.monitor, self.factor, self.patience, self.verbose = monitor, factor, patience, verbose
-        self.min_delta, self.cooldown, self.min_lr = min_delta, cooldown, min_lr
-        self.mode = _auto_mode(mode, monitor)
-        self.model = None
-        self._reset()
-
-    def _reset(self):
-        self.best = -np.inf if self.mode == 'max' else np.inf
-        self.cooldown_counter, self.wait = 0, 0
-
-    def _better(self, cur):
-        return cur > self.best + self.min_delta if self.mode == 'max' else cur < self.best - self.min_delta
-
-    def on_train_begin(self, logs=None):
-        self._reset()
-
-    def on_epoch_end(self, epoch, logs):
-        opt = self.model.optimizer
-        logs['lr'] = float(opt.learning_rate)
-        cur = logs.get(self.monitor)
-        if cur is None:
-            import warnings
-            warnings.warn(f'ReduceLROnPlateau: metric `{self.monitor}` is not available (have {sorted(logs)})')
-            return
-        if self.cooldown_counter > 0:
-            self.cooldown_counter -= 1
-            self.wait = 0
-        if self._better(cur):
-            self.best, self.wait = cur, 0
-        elif self.cooldown_counter <= 0:
-            self.wait += 1
-            if self.wait >= self.patience:
-                old = float(opt.learning_rate)
-                if old > float(self.min_lr):
-                    opt.learning_rate = max(old * self.factor, float(self.min_lr))
-                    if self.verbose:
-                        print(f'Epoch {epoch + 1}: ReduceLROnPlateau reducing learning rate to {float(opt.learning_rate)}.')
-                    self.cooldown_counter, self.wait = self.cooldown, 0
-
-
-def _snapshot_weights(model):
-    snap = {'': model.get_weights_dict()}
-    for tag, bm in getattr(model, '_branch_models', dict)().items():
-        snap[tag] = bm.get_weights_dict()
-    return snap
-
-
-def _restore_weights(model, snap):
-    model.set_weights_dict(snap[''])
-    for tag, bm in getattr(model, '_branch_models', dict)().items():
-        bm.set_weights_dict(snap[tag])
-
-
-class EarlyStopping:
-    """tf.keras.callbacks.EarlyStopping: sets `model.stop_training` after `patience` epochs in which `monitor` has not improved on its
-    best value by more than `min_delta`; restore_best_weights puts the best epoch's variables (moving statistics included) back."""
-
-    def __init__(self, monitor='val_loss', min_delta=0, patience=0, verbose=0, mode='auto', restore_best_weights=False, **kw):
-        if kw:
-            raise TypeError(f'EarlyStopping: unsupported arguments {sorted(kw)}')
-        self.monitor, self.min_delta, self.patience, self.verbose = monitor, abs(min_delta), patience, verbose
-        self.mode = _auto_mode(mode, monitor)
-        self.restore_best_weights = restore_best_weights
-        self.model = None
-        self.on_train_begin()
-
-    def on_train_begin(self, logs=None):
-        self.wait, self.stopped_epoch, self.best_epoch = 0, 0, 0
-        self.best = -np.inf if self.mode == 'max' else np.inf
-        self.best_weights = None
-
-    def _better(self, cur):
-        return cur - self.min_delta > self.best if self.mode == 'max' else cur + self.min_delta < self.best
-
-    def on_epoch_end(self, epoch, logs):
-        cur = logs.get(self.monitor)
-        if cur is None:
-            import warnings
-            warnings.warn(f'EarlyStopping: metric `{self.monitor}` is not available (have {sorted(logs)})')
-            return
-        if self._better(cur):
-            self.best, self.best_epoch, self.wait = cur, epoch, 0
-            if self.restore_best_weights:
-                self.best_weights = _snapshot_weights(self.model)
-            return
-        self.wait += 1
-        if self.wait >= self.patience:
-            self.stopped_epoch = epoch
-            self.model.stop_training = True
-            if self.restore_best_weights and self.best_weights is not None:
-                _restore_weights(self.model, self.best_weights)
-            if self.verbose:
-                print(f'Epoch {epoch + 1}: early stopping')
-
-
-def run_callbacks(callbacks, hook, *args):
-    """call `hook` on every callback that has it (the callbacks of this module define only the hooks they use)"""
-    for cb in callbacks:
-        fn = getattr(cb, hook, None)
-        if fn is not None:
-            fn(*args)
-
-
-def record_callback_logs(hist, logs, before):
-    """entries the callbacks added to the epoch logs (`lr`) join the history, as in Keras, where History runs last"""
-    for k, v in logs.items():
-        if k not in before:
-            hist.history[k].append(v)
-
-
-class TensorBoard:
-    """tf.keras.callbacks.TensorBoard(log_dir): epoch scalars as real TensorBoard event files -- `<log_dir>/train` and
-    `<log_dir>/validation`, tags `epoch_<name>` like Keras (notebooks/UNET_G4G_2019_solar.ipynb:1255) -- written without
-    TensorFlow (tfrecord_io.EventFileWriter), plus one JSON line per epoch in `<log_dir>/scalars.jsonl`."""
-
-    def __init__(self, log_dir='logs', **kw):
-        self.log_dir = log_dir
-        self.model = None
-        self._writers = {}
-
-    def _writer(self, which):
-        from . import tfrecord_io
-        if which not in self._writers:
-            self._writers[which] = tfrecord_io.EventFileWriter(os.path.join(self.log_dir, which))
-        return self._writers[which]
-
-    def on_epoch_end(self, epoch, logs):
-        os.makedirs(self.log_dir, exist_ok=True)
-        with open(os.path.join(self.log_dir, 'scalars.jsonl'), 'a') as f:
-            f.write(json.dumps(dict(epoch=epoch, **{k: float(v) for k, v in logs.items()})) + '\n')
-        train = {f'epoch_{k}': float(v) for k, v in logs.items() if not k.startswith('val_')}
-        val = {f'epoch_{k[4:]}': float(v) for k, v in logs.items() if k.startswith('val_')}
-        if train:
-            self._writer('train').scalars(epoch, train)
-        if val:
-            self._writer('validation').scalars(epoch, val)
-
-
-# ----------------------------------------------------------------------------- Model
 def _as_batches(x, y, batch_size, order=None):
     """ndarray pair / Sequence / iterable of (x, y) -> generator of batches (possibly endless).  order: optional permutation of the
     samples of array inputs (Keras' fit(shuffle=True) draws a new one every epoch)."""
@@ -1249,15 +836,7 @@ class Model:
             loss = next(iter(loss.values()))
         if isinstance(metrics, dict):        # {'output name': [metrics]} -> flat list
             metrics = [mm for v in metrics.values() for mm in (v if isinstance(v, (list, tuple)) else [v])]
-        if callable(loss):
-            spec = loss(_LossArg('y_true'), _LossArg('y_pred'))
-        elif isinstance(loss, LossSpec):
-            spec = loss
-        else:
-            raise ValueError('loss must be one of the model_tools loss functions (or a lambda wrapping one)')
-        if not isinstance(spec, LossSpec):
-            raise ValueError('loss function did not resolve to a fused device loss')
-        self._loss = spec
+        self._loss = resolve_loss(loss)
         self._metrics = list(metrics or [])
         names = ['loss']
         for mt in self._metrics:
@@ -1558,25 +1137,13 @@ class Model:
         else:
             apply_optimizer(opt, rt, st)         # all-reduce (above), then clip if asked, then the optimizer's step
             rt.repack()
+        plan.early_opt = None                    # (other callers run this plan's backward pass -- HybridModel.train_on_batch -- with their own full step)
         self._weights_version = getattr(self, '_weights_version', 0) + 1
         return plan
 
     def train_on_batch(self, x, y):
         plan = self.train_step_device(x, y, getattr(self, '_sync_grads', None))
         return float(plan.loss_buf.item())
-
-    def _metric_values(self, conf, loss):
-        vals = [loss]
-        conf = conf.astype(np.float64)
-        for mt in self._metrics:
-            if isinstance(mt, str):
-                vals.append(float(np.trace(conf) / max(conf.sum(), 1)))
-            else:
-                tp = np.diag(conf)
-                denom = conf.sum(0) + conf.sum(1) - tp
-                valid = denom > 0
-                vals.append(float((tp[valid] / denom[valid]).mean()) if valid.any() else 0.0)
-        return vals
 
     def _run_epoch(self, batches, steps, train):
         rt = self.runtime
@@ -1614,7 +1181,7 @@ class Model:
             cnt += plan.n
         loss = float(loss_sum.item()) / max(cnt, 1)
         c = conf.cpu().numpy() if conf is not None else np.zeros((1, 1))
-        return self._metric_values(c, loss)
+        return [loss] + [metric_from_confusion('accuracy' if isinstance(mt, str) else 'mean_iou', c) for mt in self._metrics]      # (any string counts as accuracy)
 
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, callbacks=None, validation_data=None, steps_per_epoch=None,
             validation_steps=None, initial_epoch=0, shuffle=True, **kw):
@@ -1627,16 +1194,10 @@ class Model:
             if y is not None and len(y) != len(x):
                 raise ValueError(f'x and y hold different numbers of samples: {len(x)} vs {len(y)}')
         self._apply_trainable()
-        hist = History()
-        callbacks = list(callbacks or [])
-        for cb in callbacks:
-            cb.model = self
-        self.stop_training = False
-        run_callbacks(callbacks, 'on_train_begin')
         it = None
-        for epoch in range(initial_epoch, epochs):
-            t0 = time.time()
-            run_callbacks(callbacks, 'on_epoch_begin', epoch)
+
+        def train_epoch(epoch):
+            nonlocal it
             if it is None or steps_per_epoch is None:
                 order = None
                 if shuffle and (isinstance(x, (np.ndarray, torch.Tensor)) or (isinstance(x, (list, tuple)) and y is not None)):
@@ -1647,31 +1208,16 @@ class Model:
                     else:
                         order = _SHUFFLE_RNG.permutation(nsamp)
                 it, _ = _as_batches(x, y, batch_size, order)
-            vals = self._run_epoch(it, steps_per_epoch, True)
-            logs = dict(zip(self.metrics_names, vals))
-            if validation_data is not None:
-                if isinstance(validation_data, tuple) and len(validation_data) == 2 and isinstance(validation_data[0], (np.ndarray, torch.Tensor)):
-                    vit, _ = _as_batches(validation_data[0], validation_data[1], batch_size)
-                else:
-                    vit, _ = _as_batches(validation_data, None, batch_size)
-                vvals = self._run_epoch(vit, validation_steps, False)
-                logs.update({'val_' + k: v for k, v in zip(self.metrics_names, vvals)})
-            for k, v in logs.items():
-                hist.history[k].append(v)
-            hist.epoch.append(epoch)
-            if verbose:
-                print(f'Epoch {epoch + 1}/{epochs} - {time.time() - t0:.1f}s - ' + ' - '.join(f'{k}: {v:.4f}' for k, v in logs.items()))
-            before = set(logs)
-            for cb in callbacks:
-                if hasattr(cb, 'on_epoch_end'):
-                    cb.on_epoch_end(epoch, logs)
-            record_callback_logs(hist, logs, before)
-            if hasattr(x, 'on_epoch_end'):
-                x.on_epoch_end()
-            if self.stop_training:
-                break
-        run_callbacks(callbacks, 'on_train_end')
-        return hist
+            return dict(zip(self.metrics_names, self._run_epoch(it, steps_per_epoch, True)))
+
+        def validate():
+            if isinstance(validation_data, tuple) and len(validation_data) == 2 and isinstance(validation_data[0], (np.ndarray, torch.Tensor)):
+                vit, _ = _as_batches(validation_data[0], validation_data[1], batch_size)
+            else:
+                vit, _ = _as_batches(validation_data, None, batch_size)
+            return dict(zip(self.metrics_names, self._run_epoch(vit, validation_steps, False)))
+
+        return fit_loop(self, x, epochs, initial_epoch, callbacks, verbose, train_epoch, validate if validation_data is not None else None, show_time=True)
 
     def evaluate(self, x=None, y=None, batch_size=None, verbose=0, steps=None, **kw):
         """Model.evaluate -> list aligned with metrics_names (utils/model_tools.py:1164-1168)."""

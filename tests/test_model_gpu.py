@@ -1006,6 +1006,24 @@ def test_round6_scheduling_switches_leave_the_numbers_alone(mt, monkeypatch):
     np.testing.assert_allclose(l2, l0, rtol=2e-2)
 
 
+def test_early_optimizer_step_is_cleared_after_the_training_step(mt, monkeypatch):
+    """Model.train_step_device arms plan.early_opt for its own backward pass only: once the step is done the plan carries none, so another caller
+    of plan.run_backward (HybridModel.train_on_batch, which runs its own full step afterwards) cannot run the early partial Adam as well."""
+    from satellite_computervision_amd import engine as E
+    monkeypatch.setattr(E, 'EARLY_OPT', True)
+    rng = np.random.default_rng(12)
+    x = rng.random((2, 64, 64, 4)).astype(np.float32)
+    y = np.eye(2, dtype=np.float32)[(rng.random((2, 64, 64)) < 0.3).astype(np.int64)]
+    mt.reset_uids(); mt.set_seed(21)
+    m = mt.get_unet_model(2, 4)
+    m.compute_dtype = 'bfloat16'
+    m.compile(optimizer=mt.Adam(1e-3), loss=lambda t, p: mt.weighted_categorical_crossentropy(t, p, [1.0, 5.0]))
+    plan = m.train_step_device(x, y)
+    torch.cuda.synchronize()
+    assert plan.eo_done                          # (the early step did run inside this step's backward pass)
+    assert plan.early_opt is None
+
+
 @pytest.mark.parametrize('channels', [4, 13])
 def test_timed_configuration_bf16_batch64_training_step_properties(mt, channels):
     """The configuration bench.py times (BASELINE configs[1]; configs[3] with 13 bands): ONE bf16 training step of get_unet_model(2, C) at
