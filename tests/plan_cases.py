@@ -7,8 +7,16 @@ A case is Case(name, make, dtype, training, env, early_opt, labels):
   env            SATCV_* variables set while the model and its plan are built (model and plan rows of switches.py)
   early_opt      engine.EARLY_OPT for the case (the tests' way of switching it: tests/test_model_gpu.py)
   labels         label fragments the backward step list of the case must contain
-IMPORT_VARIANTS are import rows: they need a process of their own and apply to the five-level bf16 case."""
-from collections import namedtuple
+IMPORT_VARIANTS are import rows: they need a process of their own and apply to the five-level bf16 case.
+
+FOLDED_CASES reach every arm of the folded inference lowering (fp8_infer._FoldedLowering) in the same way, for the same tool and for
+tests/test_fp8_gpu.py::test_folded_lowering_reaches_its_forms.  A case is FoldedCase(name, make, store, plan_kw, arms):
+  make(mt, lt)  -> (model, x): the model carries BatchNorm statistics, gamma, beta and biases drawn from a fixed seed (a freshly
+                 initialised model would hide an error in the folding); x a batch, a pair of batches for the Siamese graph
+  store          'bf16' | 'fp8' (fp8: the scales come from fp8_infer.calibrate on x)
+  plan_kw        hybrid / first_bf16 / pair of fp8_infer.Fp8Plan
+  arms           what the case is there to reach (documentation; folded_forms() says what a recorded run did reach)"""
+from collections import Counter, namedtuple
 
 import numpy as np
 
@@ -133,3 +141,115 @@ IMPORT_VARIANTS = {'wgrad_late': {'SATCV_WGRAD_LATE': '1'}, 'ctbf=0': {'SATCV_CT
 IN_SUITE = (FIVE, 'unet3_wide')
 SUFFIXES = ('+bnred', '+poolsums', '+skipsums', '(skip half)', '(part)', 'pooled', 'pooled nodx', '+headgrad', 'convt_bwd_fused',
             'wgrad_reduce_batched', 'early optimizer step', 'convT f2')
+
+
+# ------------------------------------------------------------------ folded inference (fp8_infer.Fp8Plan)
+FoldedCase = namedtuple('FoldedCase', 'name make store plan_kw arms')
+
+
+def _trained_look(m, seed):
+    """non-trivial moving statistics, gamma, beta and biases (kernels as initialised) through set_weights_dict"""
+    rng = np.random.default_rng(seed)
+    w = m.get_weights_dict()
+    for k in w:
+        if k.endswith('moving_mean') or k.endswith('/bias') or k.endswith('/beta'):
+            w[k] = (0.2 * rng.standard_normal(w[k].shape)).astype(np.float32)
+        elif k.endswith('moving_var') or k.endswith('/gamma'):
+            w[k] = (0.5 + rng.random(w[k].shape)).astype(np.float32)
+    m.set_weights_dict(w)
+    return m
+
+
+def _f_unet(n, h, w, **kw):
+    def make(mt, lt):
+        mt.reset_uids(); mt.set_seed(6)
+        m = mt.get_unet_model(2, 4, filters=[32, 64, 128], factors=[2, 2, 2], **kw)
+        return _trained_look(m, 3), np.random.default_rng(31).random((n, h, w, 4)).astype(np.float32)
+    return make
+
+
+def _f_hybrid_branch(mt, lt):
+    mt.reset_uids(); mt.set_seed(4)
+    m = lt.get_hybrid_model((48, 48, 4), (3, 8, 8, 6), 3, filters=[32, 64], factors=[3, 2])
+    return _trained_look(m.unet, 5), np.random.default_rng(32).random((2, 48, 48, 4)).astype(np.float32)
+
+
+def _f_siamese(mt, lt):
+    mt.reset_uids(); mt.set_seed(4)
+    m = _trained_look(mt.make_siamese_unet(4, [32, 64], [2, 2], class_thresh=0.4), 17)
+    rng = np.random.default_rng(33)
+    return m, [rng.random((3, 64, 64, 4)).astype(np.float32) for _ in range(2)]
+
+
+def _f_two_date_extras(mt, lt):
+    """A two-date graph from the package's own blocks with what make_siamese_unet lacks: a shared level that is no skip and whose
+    max-pool cannot fuse (factor 3: no kernel tile holds whole 3 x 3 windows), SpatialDropout2D on the two-date part, and an ASPP on
+    8 x 8 maps (dilation 12 reads only padding off the centre tap).  The head works at a third of the input resolution."""
+    from satellite_computervision_amd import engine as E
+    mt.reset_uids(); mt.set_seed(11)
+    ia, ib = mt.Input((None, None, 4)), mt.Input((None, None, 4))
+    stem, enc, aspp = mt.encoder_block(32, pool_size=(3, 3), name='stem'), mt.encoder_block(64, name='encoder_0'), mt.DilatedSpatialPyramidPooling(128)
+    pooled, skips = [], []
+    for x in (ia, ib):
+        p, _ = stem(x)
+        p, e = enc(mt._dropout(p, 0.25, True))
+        pooled.append(aspp(p)); skips.append(e)
+
+    def cat(a, b):
+        return E.Node('concat', [b, a]).out(a.channels + b.channels, a.down)
+    dec = mt.decoder_block(cat(*pooled), cat(*skips), 64)
+    probs = mt._Head(1, 'sigmoid', None, 'probs')(dec)
+    m = _trained_look(mt.Model(inputs=[ia, ib], outputs=[probs, mt._classes(probs, 'classes', thresh=0.5)]), 19)
+    rng = np.random.default_rng(34)
+    return m, [rng.random((2, 48, 48, 4)).astype(np.float32) for _ in range(2)]
+
+
+def _f_siamese32(mt, lt):
+    m, _ = _f_siamese(mt, lt)
+    rng = np.random.default_rng(35)
+    return m, [rng.random((2, 32, 32, 4)).astype(np.float32) for _ in range(2)]
+
+
+_ALL8 = dict(hybrid=False)
+FOLDED_CASES = [
+    FoldedCase('unet3 bf16', _f_unet(2, 64, 64), 'bf16', {}, 'input (bf16 bands), cba with fused pool, two-source cba, convT to its own tensor, head, classes'),
+    FoldedCase('unet3 fp8 hybrid', _f_unet(2, 64, 64), 'fp8', {}, 'pooled map quantised at the boundary, convT input de-quantised, block-scaled deep layers'),
+    FoldedCase('unet3 fp8', _f_unet(2, 64, 64), 'fp8', _ALL8, 'cba behind bf16 bands (conv + requant), thin fp8 layers, two-source fp8 read'),
+    FoldedCase('unet3 fp8 scaled-ingest', _f_unet(2, 64, 64), 'fp8', dict(hybrid=False, first_bf16=False), 'input (scaled e4m3 ingest)'),
+    FoldedCase('unet3 fp8 first-bf16', _f_unet(2, 64, 64), 'fp8', dict(hybrid=False, first_bf16=True), 'the same plan as "unet3 fp8", first_bf16 given'),
+    FoldedCase('unet3 24x40 fp8', _f_unet(3, 24, 40), 'fp8', _ALL8, 'separate max-pool (fp8), materialised concatenation (skip half re-quantised)'),
+    FoldedCase('hybrid-branch bf16', _f_hybrid_branch, 'bf16', {}, 'separate max-pool (factor 3, bf16), linear head without a classes node'),
+    FoldedCase('hybrid-branch fp8', _f_hybrid_branch, 'fp8', {}, 'separate max-pool whose pooled map is quantised at the boundary'),
+    FoldedCase('unet3 dropout bf16', _f_unet(2, 64, 64, dropout=0.25), 'bf16', {}, 'dropout (identity)'),
+    FoldedCase('unet3 dropout fp8', _f_unet(2, 64, 64, dropout=0.25), 'fp8', {}, 'dropout behind a boundary tensor'),
+    FoldedCase('siamese bf16 paired', _f_siamese, 'bf16', dict(pair=True), 'two-date input / cba / pool / concat, pair store, ASPP slot tensor, pair concatenation'),
+    FoldedCase('siamese bf16 unpaired', _f_siamese, 'bf16', dict(pair=False), 'one launch per date into the concatenation'),
+    FoldedCase('siamese fp8 paired', _f_siamese, 'fp8', dict(pair=True), 'pair store in e4m3, group scales, dilated plain-e4m3 packing'),
+    FoldedCase('siamese fp8 unpaired', _f_siamese, 'fp8', dict(pair=False), 'one launch per date in e4m3'),
+    FoldedCase('siamese 32x32 fp8 paired', _f_siamese32, 'fp8', dict(pair=True), 'centre-tap cut of the dilation-12 branch on 8 x 8 maps, in e4m3'),
+    FoldedCase('two-date extras bf16', _f_two_date_extras, 'bf16', dict(pair=True), 'two-date dropout, two-date separate max-pool (2n images), centre-tap cut'),
+]
+FOLDED_IN_SUITE = ('siamese bf16 paired', 'siamese bf16 unpaired', 'unet3 fp8 hybrid', 'hybrid-branch bf16')
+
+
+def folded_forms(calls):
+    """Counter of the forms the recorded calls of one Fp8Plan.run_forward took (calls: tools/plan_manifest.py's Recorder)"""
+    from satellite_computervision_amd._lib import BF16, FP8
+    code = {BF16: 'bf16', FP8: 'fp8'}
+    forms = Counter()
+    for name, _, structs, scalars in calls:
+        if name == 'satcv_conv2d_igemm':
+            d = structs[0]
+            forms['convT' if d['mode_out'] == 1 else 'conv'] += 1
+            forms['conv, pair store over 2n images'] += bool(d['pair_n'] and d['n'] == 2 * d['pair_n'])
+            forms['conv, fused pool'] += bool(d['pool_f'])
+            forms['conv, two sources'] += bool(d['c1'])
+            forms['conv, raw output'] += not d['out_relu']
+        elif name == 'satcv_maxpool':
+            forms['separate maxpool'] += 1
+        elif name == 'satcv_affine_requant':
+            ld_src, relu, ld_dst, npix, c, dt_in, dt_out = scalars
+            forms[f'requant {code[dt_in]} -> {code[dt_out]}' + (', BN + ReLU' if relu else '') + (' into a concatenation' if ld_dst != c else '')] += 1
+        else:
+            forms[name[len('satcv_'):]] += 1
+    return +forms

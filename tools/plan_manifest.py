@@ -4,11 +4,12 @@ that must not change a launch) on the same library:
     SATCV_LIB=<libsatcv.so> PYTHONPATH=<checkout A> python tools/plan_manifest.py --out a.json
     SATCV_LIB=<libsatcv.so> PYTHONPATH=<checkout B> python tools/plan_manifest.py --out b.json
     python tools/plan_manifest.py --compare a.json b.json [--baseline a2.json]
+With --folded the same for plan_cases.FOLDED_CASES, the folded inference plans of fp8_infer.Fp8Plan (a change of its lowering).
 
 For every case of tests/plan_cases.py (always the list beside THIS file; the package is the first one on the path):
   steps   (phase, label or null, work or null) of every step of plan.fwd and plan.bwd
   calls   one step under a recording wrapper around every lib.satcv_* entry point: (name, stream: main | side | third, the non-pointer
-          fields of every ctypes structure argument)
+          fields of every ctypes structure argument, the non-pointer scalar arguments)
   hashes  training: three steps from a fixed seed, sha256 of pflat / gflat / sflat, of the first step's gflat and of the packed images,
           and the three losses; inference: sha256 of every output
 The import rows of the switch table (plan_cases.IMPORT_VARIANTS) run in a process each.  --compare holds steps, calls and hashes to
@@ -66,7 +67,8 @@ class Recorder:
             last = args[-1] if args else None
             handle = last.value if isinstance(last, C.c_void_p) else last
             structs = [_fields(a._obj) for a in args if hasattr(a, '_obj') and isinstance(a._obj, C.Structure)]
-            self.calls.append([name, self.streams.get(handle, 'main') if handle else 'main', structs])
+            scalars = [a for a, t in zip(args, fn.argtypes or ()) if t not in (C.c_void_p, C.c_char_p) and not issubclass(t, C._Pointer)]
+            self.calls.append([name, self.streams.get(handle, 'main') if handle else 'main', structs, scalars])
             return fn(*args)
         return call
 
@@ -122,6 +124,37 @@ def run_case(case):
                 del os.environ[k]
             else:
                 os.environ[k] = v
+
+
+def run_folded(case, made=None):
+    """one Fp8Plan of a FoldedCase (made: what case.make returned, if the caller holds it): the calls of one run_forward (calibration and
+    plan construction are not recorded) and its outputs"""
+    import torch
+    from satellite_computervision_amd import fp8_infer as fi, lstm_tools as lt, model_tools as mt, ops
+    from satellite_computervision_amd._lib import lib
+    m, x = made or case.make(mt, lt)
+    n, h, w = (x[0] if isinstance(x, list) else x).shape[:3]
+    q = fi.calibrate(m, x) if case.store == 'fp8' else None
+    plan = fi.Fp8Plan(m, n, h, w, q, store=fi.FP8 if case.store == 'fp8' else fi.BF16, **case.plan_kw)
+    m._stage_x(plan, x)
+    rec = Recorder(lib)
+    try:
+        plan.run_forward(ops.stream_ptr())
+        torch.cuda.synchronize()
+    finally:
+        rec.restore()
+    return dict(steps=[], calls=rec.calls, hashes={f'output{i}': _sha(plan.outputs[t.id]) for i, t in enumerate(m.outputs)}, losses=[])
+
+
+def child_folded(out, only):
+    import satellite_computervision_amd
+    print('package:', os.path.dirname(satellite_computervision_amd.__file__), flush=True)
+    pc = _cases()
+    res = {}
+    for c in [c for c in pc.FOLDED_CASES if not only or c.name in only]:
+        res[c.name] = run_folded(c)
+        print(f"{c.name}: {len(res[c.name]['calls'])} calls, reaches {dict(pc.folded_forms(res[c.name]['calls']))}", flush=True)
+    json.dump(res, open(out, 'w'), indent=0, sort_keys=True)
 
 
 def child(variant, out, only):
@@ -198,9 +231,12 @@ if __name__ == '__main__':
     ap.add_argument('--compare', nargs=2, metavar=('A', 'B'))
     ap.add_argument('--baseline', nargs='+', help='further runs of checkout A')
     ap.add_argument('--cases', type=lambda v: v.split(','), help='only these cases (comma-separated names)')
+    ap.add_argument('--folded', action='store_true', help='the folded inference cases (plan_cases.FOLDED_CASES), in this process')
     a = ap.parse_args()
     if a.compare:
         sys.exit(compare(a.compare[0], a.compare[1], a.baseline))
+    if a.folded:
+        sys.exit(child_folded(a.out, a.cases))
     if a.child is not None:
         child(a.child, a.out, a.cases)
     else:
