@@ -909,6 +909,45 @@ typedef struct satcv_warp_desc {
 } satcv_warp_desc;
 int satcv_raster_warp(const satcv_warp_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ Reprojection between coordinate systems
+ * What the reference leaves to PROJ behind gdal.Warp (utils/pc_tools.py:152-186, the two-UTM-zone NAIP case), stackstac.stack(epsg=)
+ * (get_s2_stac / get_s1_stac / get_hag_stac) and rasterio's transform_bounds (utils/prediction_tools.py:560-600).  The projection rules
+ * -- Krueger's n^6 series for the transverse Mercator, the spherical Mercator, longitude wrapping, the domain, no datum shift between
+ * WGS84 and NAD83 -- are written in csrc/crs_core.hpp, the one source of the host loop and of the kernels; tests/crs_oracle.py says
+ * them again in float64 NumPy.  csrc/reproject.hip is compiled with floating-point contraction off.
+ *
+ * satcv_crs: kind 0 geographic (x = longitude, y = latitude, degrees: the GeoTIFF axis order), 1 transverse Mercator, 2 spherical (web)
+ * Mercator; a, inv_f the ellipsoid; lon0 the central meridian in degrees (0 for kinds 0 and 2); k0 the scale on it; fe, fn the false
+ * easting and northing in metres.  The host table of EPSG codes is satellite_computervision_amd/crs.py.
+ *
+ * satcv_crs_transform: n points (x[k], y[k]) of `from` -> (xo[k], yo[k]) of `to`: crs_inverse(from), then crs_forward(to).  A point
+ * outside either domain gets NaN and ok[k] = 0 (ok may be NULL).  on_device = 0: host pointers, the loop runs on the CPU (bounds and
+ * windows of the Python host code); 1: device pointers, one thread per point.  xo / yo may be x / y.
+ *
+ * satcv_reproject_map: the destination grid (dst_crs; dst_a, dst_c, dst_e, dst_f of its Affine transform) and the source (src_crs; with
+ * has_src_transform its src_a, src_c, src_e, src_f; without, "source CRS units": u, v are the coordinates themselves, e.g. the
+ * longitude / latitude field of a UTM scene).  The chain of destination pixel (i, j), GLOBAL indices (so a strip equals the whole):
+ *     X = dst_a * (j + 0.5) + dst_c,  Y = dst_e * (i + 0.5) + dst_f;  (lon, lat) = crs_inverse(dst_crs, X, Y);
+ *     (Xs, Ys) = crs_forward(src_crs, lon, lat);  u = (Xs - src_c) / src_a,  v = (Ys - src_f) / src_e
+ * each product, sum and quotient rounded on its own.  A pixel whose chain is not ok has u = v = NaN.
+ * satcv_grid_coords: u and v (dh x dw float64 planes on the device) of the window (row0, col0, dh, dw) of the destination grid.
+ * satcv_raster_reproject: satcv_raster_warp with u, v from the chain -- through the same inline device function as satcv_grid_coords,
+ * so the two kernels' coordinates agree bit for bit -- in place of su * (j + 0.5) + ou; d->su / ou / sv / ov are ignored, every other
+ * field and rule of the descriptor is unchanged (kinds, layouts, ld / coff, src_row0 / src_col0, dst_row0 / dst_col0, nodata, keep,
+ * band packs; 0 nearest, 1 bilinear, 2 cubic).  A pixel whose chain is not ok is invalid.  Method 3 (average) is refused: the footprint
+ * of a pixel is no axis-parallel rectangle any more.
+ * Refused on the host before any launch: what satcv_raster_warp refuses except its scale checks, a null map, an unknown CRS kind,
+ * non-positive a or inv_f, non-finite parameters, zero or non-finite transform scales, non-finite origins, method 3. */
+typedef struct satcv_crs { int32_t kind; double a, inv_f, lon0, k0, fe, fn; } satcv_crs;
+typedef struct satcv_reproject_map {
+  satcv_crs dst_crs; double dst_a, dst_c, dst_e, dst_f;
+  satcv_crs src_crs; int32_t has_src_transform; double src_a, src_c, src_e, src_f;
+} satcv_reproject_map;
+int satcv_crs_transform(const satcv_crs* from, const satcv_crs* to, const double* x, const double* y, double* xo, double* yo, uint8_t* ok,
+                        int64_t n, int32_t on_device, void* stream);
+int satcv_grid_coords(const satcv_reproject_map* m, int32_t dh, int32_t dw, int32_t row0, int32_t col0, double* u, double* v, void* stream);
+int satcv_raster_reproject(const satcv_warp_desc* d, const satcv_reproject_map* m, void* stream);
+
 /* ------------------------------------------------------------------ losses
  * Each writes loss_out[0] += mean loss contribution (caller zeroes) and
  * dlogits = dL/dlogits (through the head activation).

@@ -111,6 +111,17 @@ class WarpDesc(C.Structure):
                 ('has_dst_nodata', c_i32), ('dst_nodata', C.c_double), ('keep', c_i32)]
 
 
+class Crs(C.Structure):
+    """satcv_crs: kind 0 geographic, 1 transverse Mercator, 2 spherical Mercator; ellipsoid, central meridian, scale, false origin"""
+    _fields_ = [('kind', c_i32), ('a', C.c_double), ('inv_f', C.c_double), ('lon0', C.c_double), ('k0', C.c_double), ('fe', C.c_double), ('fn', C.c_double)]
+
+
+class ReprojectMap(C.Structure):
+    """satcv_reproject_map: destination CRS and transform (a, c, e, f), source CRS and, with has_src_transform, its transform"""
+    _fields_ = [('dst_crs', Crs), ('dst_a', C.c_double), ('dst_c', C.c_double), ('dst_e', C.c_double), ('dst_f', C.c_double), ('src_crs', Crs),
+                ('has_src_transform', c_i32), ('src_a', C.c_double), ('src_c', C.c_double), ('src_e', C.c_double), ('src_f', C.c_double)]
+
+
 RECORD_MAX_PLANES = 32     # SATCV_RECORD_MAX_PLANES of include/satcv.h
 RECORD_STAT_SPLITS = 16    # SATCV_RECORD_STAT_SPLITS
 _i32p, _f32p = c_i32 * RECORD_MAX_PLANES, c_f32 * RECORD_MAX_PLANES
@@ -330,6 +341,9 @@ _SIGS = {
     'satcv_lzw_decode_host': (C.c_int, [c_vp, c_i64, c_vp, c_i64, C.POINTER(c_i64), C.POINTER(c_i32)]),
     'satcv_raster_untile': (C.c_int, [C.POINTER(UntileDesc), c_vp]),
     'satcv_raster_warp': (C.c_int, [C.POINTER(WarpDesc), c_vp]),
+    'satcv_crs_transform': (C.c_int, [C.POINTER(Crs), C.POINTER(Crs), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
+    'satcv_grid_coords': (C.c_int, [C.POINTER(ReprojectMap), c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'satcv_raster_reproject': (C.c_int, [C.POINTER(WarpDesc), C.POINTER(ReprojectMap), c_vp]),
     'satcv_record_stats': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_record_to_tuple': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_label_onehot': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),

@@ -244,7 +244,7 @@ def predict_change(before, after, m, before_times=None, after_times=None, buff=1
 
 
 def predict_change_files(before_items, after_items, m, grid=None, resolution=None, out_file=None, file_bands=None, resampling='nearest',
-                         **predict_change_kwargs):
+                         reproject=False, **predict_change_kwargs):
     """`predict_change` from files that need not share a pixel grid: both periods are read as aligned stacks on ONE grid
     (`raster_tools.read_aligned_stack` -- what the reference gets from stackstac.stack(epsg=, resolution=)) and handed to
     `predict_change` with that grid's georeference; returns what `predict_change` returns.
@@ -253,7 +253,9 @@ def predict_change_files(before_items, after_items, m, grid=None, resolution=Non
     common `raster_tools.Grid`; None: `union_grid` of every file of both periods at `resolution` (None: the finest).  file_bands: the
     bands read from every file (None: all); resampling: as for `raster_tools.warp`.  out_file: the change map as a Cloud-Optimized
     GeoTIFF with the grid's transform and CRS.  predict_change_kwargs: every other argument of `predict_change` (times, kernel, buff,
-    quality, bands, fill, cog_options, ...); transform and crs come from the grid."""
+    quality, bands, fill, cog_options, ...); transform and crs come from the grid.
+    reproject=True: the files may be in several EPSG codes (a series that straddles a UTM zone boundary): they are reprojected onto the
+    grid (`raster_tools.read_warped(reproject=True)`); the grid built here is in the code of the first file."""
     import os
     from . import raster_tools as rt
     for k in ('transform', 'crs'):
@@ -261,11 +263,11 @@ def predict_change_files(before_items, after_items, m, grid=None, resolution=Non
             raise ValueError(f'{k} comes from the common grid: it is not an argument of predict_change_files')
     if grid is None:
         flat = [p for it in list(before_items) + list(after_items) for p in ([it] if isinstance(it, (str, os.PathLike)) else it)]
-        grid = rt.union_grid(flat, resolution=resolution)
+        grid = rt.union_grid(flat, resolution=resolution, reproject=reproject)
     elif resolution is not None:
         raise ValueError('resolution describes the grid that is built when none is given')
-    before = rt.read_aligned_stack(before_items, grid, bands=file_bands, resampling=resampling)
-    after = rt.read_aligned_stack(after_items, grid, bands=file_bands, resampling=resampling)
+    before = rt.read_aligned_stack(before_items, grid, bands=file_bands, resampling=resampling, reproject=reproject)
+    after = rt.read_aligned_stack(after_items, grid, bands=file_bands, resampling=resampling, reproject=reproject)
     if out_file is not None:
         if grid.crs is None and before[2] is None:
             raise ValueError('the files carry no EPSG code: out_file cannot be georeferenced')

@@ -704,7 +704,7 @@ def _model_ratio(m):
     return side // side_lo
 
 
-def predict_hybrid_raster(scene_file, stack_items, m, out_file, window=None, resampling='nearest', cog_options=None, **kwargs):
+def predict_hybrid_raster(scene_file, stack_items, m, out_file, window=None, resampling='nearest', cog_options=None, reproject=False, **kwargs):
     """File to file for the two-resolution models: a fine scene file and the files of a coarse time series that need not share its
     grid -> `predict_hybrid_scene(..., device=True)` -> a Cloud-Optimized GeoTIFF; returns what `predict_hybrid_scene` returns (CUDA
     tensors).
@@ -715,7 +715,8 @@ def predict_hybrid_raster(scene_file, stack_items, m, out_file, window=None, res
     with `resampling`.  A fine extent that is not a multiple of r is a ValueError: cut the window, or trim the scene as
     `pc_tools.trim_array` does.  out_file carries the scene file's transform -- of the window -- and CRS; cog_options: further `write_cog`
     arguments.  kwargs: the other arguments of `predict_hybrid_scene` (kernel, buff, batch_size, channel, cover, classes, rescale,
-    maxval, output, plan)."""
+    maxval, output, plan).  reproject=True: the series may be in another EPSG code than the scene (a 10 m Sentinel series in 326xx beside
+    a NAIP scene in 269xx): it is reprojected onto the coarse grid (`raster_tools.read_warped(reproject=True)`)."""
     import torch
     from . import raster_tools as rt
     if 'device' in kwargs:
@@ -732,13 +733,40 @@ def predict_hybrid_raster(scene_file, stack_items, m, out_file, window=None, res
     a, _, c, _, e, f = fine.transform
     coarse = rt.Grid((a * r, 0.0, c, 0.0, e * r, f), (h // r, w // r), info.crs)
     scene = rt.read_cog(scene_file, window=(row0, col0, h, w), layout='hwc', device=True)
-    stack = rt.read_aligned_stack(stack_items, coarse, resampling=resampling)[0]
+    stack = rt.read_aligned_stack(stack_items, coarse, resampling=resampling, reproject=reproject)[0]
     fine_scene = scene.array if scene.dtype == 'float32' else _as_float32(scene.array, scene.dtype)
     if stack.dtype not in (torch.int16, torch.float32):       # (the series gather reads int16 and float32)
         stack = _as_float32(stack, rt.read_info(_first_path(stack_items))[0].dtype)
     res = predict_hybrid_scene(fine_scene, stack, m, device=True, **kwargs)
     rt.write_cog(res[0] if isinstance(res, tuple) else res, out_file, fine.transform, fine.crs, **dict(cog_options or {}))
     return res
+
+
+def get_img_bounds(img, jsonFile, dst_crs=None):
+    """utils/prediction_tools.py:560-600: the corner coordinates of an image, for a map viewer.  img: a two-dimensional array, placed by
+    the mixer's transform, or the path of a GeoTIFF, whose own bounds are taken (`raster_tools.read_info`).  jsonFile: the mixer JSON
+    of the export ('projection': 'affine': 'doubleMatrix' and 'crs').  dst_crs: the bounds are taken to it with
+    `raster_tools.transform_bounds(..., densify_pts=21)` as the reference does with rasterio's (no datum shift between WGS84 and NAD83).
+    -> [[lat_min, lon_min], [lat_max, lon_max]], i.e. [[bottom, left], [top, right]]."""
+    import json
+    import os
+    from . import raster_tools as rt
+    with open(jsonFile) as f:
+        mixer = json.load(f)
+    src_crs = mixer['projection']['crs']
+    if isinstance(img, (str, os.PathLike)):
+        info = rt.read_info(img)[0]
+        if info.transform is None:
+            raise ValueError(f'{img} carries no transform')
+        left, bottom, right, top = rt.Grid(info.transform, info.shape).bounds
+    else:
+        shape = tuple(getattr(img, 'shape', ()))
+        if len(shape) != 2:
+            raise ValueError(f'expected an (H, W) array or the path of a GeoTIFF, got shape {shape}')
+        left, bottom, right, top = rt.Grid(tuple(mixer['projection']['affine']['doubleMatrix'][:6]), shape).bounds
+    if dst_crs:
+        left, bottom, right, top = rt.transform_bounds(src_crs, dst_crs, left, bottom, right, top, densify_pts=21)
+    return [[bottom, left], [top, right]]
 
 
 def _first_path(items):

@@ -2,7 +2,9 @@
 that lies on the device is written as a Cloud-Optimized GeoTIFF -- tiled, with overviews, COMPRESS=LZW, nodata = 255 -- from there.
 The second half of the file is the way back (`read_info`, `read_cog`, `read_stack`): what the reference asks of rasterio's
 `open().read(window=)` and rioxarray's `open_rasterio` (utils/pc_tools.py:131-186, 328-386).  The last part aligns rasters of one CRS that do not share
-a pixel grid (`union_grid`, `warp`, `read_warped`, `read_mosaic`, `read_aligned_stack`): stackstac's, BuildVRT's and reproject_match's part.
+a pixel grid (`union_grid`, `warp`, `read_warped`, `read_mosaic`, `read_aligned_stack`): stackstac's, BuildVRT's and reproject_match's part; the
+end of the file takes points, bounds and rasters between coordinate systems (`transform_points`, `transform_bounds`, `reproject_grid`,
+`pixel_coords`, `reproject`, and `reproject=True` of the readers): PROJ's part behind gdal.Warp and stackstac.stack(epsg=).
 
     map (host array or CUDA tensor) -> satcv_raster_convert (dtype, nodata) -> satcv_raster_overview (the pyramid, level by level)
       -> satcv_raster_tiles (tile-major layout, predictor 2) -> satcv_lzw_tiles (every tile of every level in one launch)
@@ -948,7 +950,7 @@ def read_stack(paths, window=None, bands=None):
 #
 # What the reference takes from stackstac.stack(epsg=, resolution=), gdal.BuildVRT / rioxarray's merge_arrays and reproject_match
 # (utils/pc_tools.py:152-186, 251-282, 368-431).  The resampling rules are this library's own (include/satcv.h, "Raster alignment").
-# Refused by name: rotated or sheared transforms, two different EPSG codes (there is no reprojection), a raster without a transform.
+# Refused by name: rotated or sheared transforms, two different EPSG codes (unless reproject=True: the last section), a raster without a transform.
 WARP_RESAMPLING = {'nearest': 0, 'bilinear': 1, 'cubic': 2, 'average': 3}
 _WARP_MARGIN = {'nearest': 0, 'bilinear': 1, 'cubic': 2}
 MAX_AVERAGE_SCALE = 64
@@ -1026,13 +1028,21 @@ def _as_grid(source):
     return Grid(info.transform, info.shape, info.crs)
 
 
-def union_grid(sources, resolution=None, bounds=None, crs=None):
+def union_grid(sources, resolution=None, bounds=None, crs=None, reproject=False):
     """The north-up grid that holds every source: -> Grid.  sources: paths, `LevelInfo`s or `Grid`s.  resolution: a number or (x, y);
     None: the finest among the sources, per axis.  bounds: (left, bottom, right, top); None: the union of the sources' bounds.  The
     bounds are snapped outward to multiples of the resolution (stackstac's snap_bounds), so grids made from overlapping sets of files
-    share their pixel edges.  ValueError for rotated sources, sources without a transform, and two different EPSG codes."""
+    share their pixel edges.  ValueError for rotated sources, sources without a transform, and two different EPSG codes.
+    reproject=True takes sources of several EPSG codes (`crs.crs_params` names the supported ones): the grid is in `crs`, without one in
+    the code of the first source that has one; a source of another code enters with `transform_bounds` of its bounds and with its pixel
+    size measured in the target CRS at its centre (`measured_pixel_size`)."""
     grids = [_as_grid(s) for s in sources]
-    epsg = _common_epsg([g.epsg for g in grids] + [_epsg_of(crs)])
+    if reproject:
+        known = [g.epsg for g in grids if g.epsg is not None]
+        epsg = _epsg_of(crs) if crs is not None else (known[0] if known else None)
+        grids = [g if g.epsg in (None, epsg) else _foreign_extent(g, epsg) for g in grids]
+    else:
+        epsg = _common_epsg([g.epsg for g in grids] + [_epsg_of(crs)])
     if resolution is None:
         if not grids:
             raise ValueError('union_grid needs sources or a resolution')
@@ -1093,13 +1103,18 @@ def warp_window(src_transform, src_shape, grid, resampling='nearest'):
     return out[0][0], out[1][0], out[0][1], out[1][1]
 
 
-def auto_level(level_transforms, grid):
+def auto_level(level_transforms, grid, src_crs=None):
     """level='auto' of `read_warped`: the index of the coarsest level whose pixels are no larger than the grid's on either axis (level 0
-    when none is); level_transforms: the transform of every level, the image first"""
+    when none is); level_transforms: the transform of every level, the image first.  src_crs: the files' CRS when it is not the grid's --
+    a level's pixel size is then measured in the grid's CRS at the grid's centre (`measured_pixel_size`)."""
     rx, ry = grid.resolution
     best, size = 0, -1.0
+    foreign = src_crs is not None and grid.epsg is not None and _epsg_of(src_crs) != grid.epsg
+    if foreign:
+        a, _, c, _, e, f = grid.transform
+        centre = (c + 0.5 * grid.shape[1] * a, f + 0.5 * grid.shape[0] * e)
     for k, t in enumerate(level_transforms):
-        px, py = abs(t[0]), abs(t[4])
+        px, py = measured_pixel_size(t, src_crs, grid.crs, centre) if foreign else (abs(t[0]), abs(t[4]))
         if px <= rx * (1 + 1e-9) and py <= ry * (1 + 1e-9) and px * py > size:
             best, size = k, px * py
     return best
@@ -1173,15 +1188,22 @@ def warp(src, src_transform, grid, resampling='nearest', src_nodata=None, nodata
     Without `out` the result is a new (H, W, C) / (C, H, W) tensor ((H, W) for a two-dimensional source).
     ValueError: rotated transforms, an unknown method, 'average' beyond 64 pixels, shapes or kinds that do not fit; MemoryError names a
     destination that does not fit in device memory."""
+    if not isinstance(grid, Grid):
+        raise ValueError(f'grid must be a Grid, got {type(grid).__name__}')
+    su, ou, sv, ov = warp_coefficients(src_transform, grid.transform)
+    _check_method(resampling, su, sv)
+    return _resample(src, (su, ou, sv, ov), None, grid, resampling, src_nodata, nodata, dtype, src_layout, layout, out, channel_offset, keep, src_origin, src_dtype)
+
+
+def _resample(src, coeff, rmap, grid, resampling, src_nodata, nodata, dtype, src_layout, layout, out, channel_offset, keep, src_origin, src_dtype):
+    """the launch `warp` and `reproject` share: the descriptor of satcv_raster_warp, with the coefficients `coeff` (rmap None) or with a
+    `ReprojectMap` for satcv_raster_reproject"""
     import ctypes as C
     import torch
     from . import ops
     from ._lib import WarpDesc, check, lib
     from .prediction_tools import _device_empty
-    if not isinstance(grid, Grid):
-        raise ValueError(f'grid must be a Grid, got {type(grid).__name__}')
-    su, ou, sv, ov = warp_coefficients(src_transform, grid.transform)
-    _check_method(resampling, su, sv)
+    su, ou, sv, ov = coeff
     ptr, name, sh, sw, c, sld, scoff, flat = _warp_source(src, src_layout, src_dtype)
     dname = name if dtype is None else dtype
     if dname not in (name, 'float32'):
@@ -1215,23 +1237,32 @@ def warp(src, src_transform, grid, resampling='nearest', src_nodata=None, nodata
                  dst_ld=dld, dst_coff=dcoff, dst_row0=0, dst_col0=0, c=c, su=su, ou=ou, sv=sv, ov=ov, resampling=WARP_RESAMPLING[resampling],
                  has_src_nodata=int(src_nodata is not None), src_nodata=float(src_nodata if src_nodata is not None else 0.0),
                  has_dst_nodata=int(nodata is not None), dst_nodata=float(nodata if nodata is not None else 0.0), keep=int(bool(keep)))
-    check(lib.satcv_raster_warp(C.byref(d), ops.stream_ptr()))
-    _mark('warp')
+    if rmap is None:
+        check(lib.satcv_raster_warp(C.byref(d), ops.stream_ptr()))
+        _mark('warp')
+    else:
+        check(lib.satcv_raster_reproject(C.byref(d), C.byref(rmap), ops.stream_ptr()))
+        _mark('reproject')
     return out
 
 
-def _file_levels(path, grid):
+def _file_levels(path, grid, reproject=False):
     """the levels of a file that can be placed on `grid`: -> (levels, their transforms); ValueError for a file without a transform, a
-    rotated one, or one in another CRS"""
+    rotated one, or one in another CRS (with reproject: in a CRS `crs.crs_params` does not know)"""
     levels = _levels(read_info(path))
     base = levels[0]
     _check_transform(base.transform, str(path))
-    _common_epsg([base.epsg, grid.epsg], f'{path} and the grid')
+    if reproject and None not in (base.epsg, grid.epsg) and base.epsg != grid.epsg:
+        from .crs import crs_params
+        for code in (base.epsg, grid.epsg):                    # (a ValueError that names the supported set)
+            crs_params(code)
+    else:
+        _common_epsg([base.epsg, grid.epsg], f'{path} and the grid')
     return levels, [_window_transform(base.transform, base.shape, lv.shape, 0, 0) for lv in levels]
 
 
 def read_warped(path, grid, bands=None, resampling='nearest', level=0, layout='hwc', out=None, keep=False, nodata=None, dtype=None,
-                channel_offset=0, decode=None):
+                channel_offset=0, decode=None, reproject=False):
     """A GeoTIFF / COG read onto `grid`: -> `Raster` on the grid (array, the grid's transform and CRS, nodata, dtype).
 
     Only the window of the file that the grid needs is read (`warp_window`: the samples under the grid and 0 / 1 / 2 more for nearest /
@@ -1241,13 +1272,20 @@ def read_warped(path, grid, bands=None, resampling='nearest', level=0, layout='h
     k-th overview, 'auto' the coarsest level whose pixels are no larger than the grid's on either axis (`auto_level`).
     resampling, layout, out, channel_offset, keep, dtype: as for `warp`.  nodata: what invalid results become; None: the file's nodata,
     without one NaN (float32) or 0.  ValueError: a file without a transform, a rotated one, one in another EPSG code than the grid's
-    ("reprojection between coordinate systems is not done"), and what `read_cog` and `warp` refuse."""
+    ("reprojection between coordinate systems is not done"), and what `read_cog` and `warp` refuse.
+    reproject=True reads a file of another EPSG code instead of refusing it: the window is `reproject_window`'s (the source pixels
+    under the grid's boundary, the method's margin and one pixel more), the resampling `reproject`'s -- the same rules with the pixel's
+    coordinates taken through both projections; 'average' is a ValueError there, and level='auto' measures the file's pixels in the
+    grid's CRS at the grid's centre."""
     from .prediction_tools import _device_empty
     if not isinstance(grid, Grid):
         raise ValueError(f'grid must be a Grid, got {type(grid).__name__}')
-    levels, transforms = _file_levels(path, grid)
+    levels, transforms = _file_levels(path, grid, reproject)
+    foreign = reproject and None not in (levels[0].epsg, grid.epsg) and levels[0].epsg != grid.epsg
+    if foreign:
+        _check_reproject_method(resampling)
     if level == 'auto':
-        level = auto_level(transforms, grid)
+        level = auto_level(transforms, grid, levels[0].crs if foreign else None)
     if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 0 <= level < len(levels):
         raise ValueError(f"level {level!r}: the file has levels 0 ... {len(levels) - 1} (or 'auto')")
     info, lt = levels[int(level)], transforms[int(level)]
@@ -1256,7 +1294,7 @@ def read_warped(path, grid, bands=None, resampling='nearest', level=0, layout='h
         nodata = src_nodata
     dname = info.dtype if dtype is None else dtype
     crs = grid.crs if grid.crs is not None else levels[0].crs
-    window = warp_window(lt, info.shape, grid, resampling)
+    window = reproject_window(lt, info.shape, levels[0].crs, grid, resampling) if foreign else warp_window(lt, info.shape, grid, resampling)
     if window is None:
         _, nb, _ = _plan_read(info, None, bands)
         c = len(nb)
@@ -1271,7 +1309,10 @@ def read_warped(path, grid, bands=None, resampling='nearest', level=0, layout='h
             _fill(part, dname, _invalid_value(dname, nodata))
         return Raster(out, grid.transform, crs, nodata, dname)
     r = read_cog(path, window, int(level), bands, 'hwc', True, decode)
-    arr = warp(r.array, lt, grid, resampling, src_nodata, nodata, dtype, 'hwc', layout, out, channel_offset, keep, window[:2], info.dtype)
+    if foreign:
+        arr = _reproject_raster(r.array, lt, levels[0].crs, grid, resampling, src_nodata, nodata, dtype, 'hwc', layout, out, channel_offset, keep, window[:2], info.dtype)
+    else:
+        arr = warp(r.array, lt, grid, resampling, src_nodata, nodata, dtype, 'hwc', layout, out, channel_offset, keep, window[:2], info.dtype)
     return Raster(arr, grid.transform, crs, nodata, 'float32' if arr.dtype.is_floating_point else info.dtype)
 
 
@@ -1287,19 +1328,20 @@ def _same_kind(paths, bands):
 
 
 def read_mosaic(paths, grid=None, bands=None, resampling='nearest', level=0, layout='hwc', first=False, nodata=None, dtype=None, out=None,
-                channel_offset=0, decode=None):
+                channel_offset=0, decode=None, reproject=False):
     """Files of one CRS mosaicked onto one grid: -> `Raster`.  grid: None is `union_grid(paths)`.  The destination is filled with
     nodata, then every file is read onto it with keep=True, in order: a later file lies on top wherever it has valid data
     (gdal.BuildVRT's order); first=True goes through the files in reverse, so the first file wins (rioxarray's merge_arrays).
-    nodata: None is the first file's, without one NaN (float32) or 0.  The other arguments as for `read_warped`."""
+    nodata: None is the first file's, without one NaN (float32) or 0.  The other arguments as for `read_warped`; with reproject=True the
+    files may be in several EPSG codes (the two-UTM-zone case), grid=None is then `union_grid(paths, reproject=True)`."""
     from .prediction_tools import _device_empty
     paths = list(paths)
     if not paths:
         raise ValueError('read_mosaic needs at least one file')
     if grid is None:
-        grid = union_grid(paths)
+        grid = union_grid(paths, reproject=reproject)
     for p in paths:
-        _file_levels(p, grid)                                  # every refusal before anything is allocated
+        _file_levels(p, grid, reproject)                       # every refusal before anything is allocated
     name, c, file_nodata = _same_kind(paths, bands)
     if nodata is None:
         nodata = file_nodata
@@ -1314,16 +1356,17 @@ def read_mosaic(paths, grid=None, bands=None, resampling='nearest', level=0, lay
             dname = 'float32'
     _fill(part, dname, _invalid_value(dname, nodata))
     for p in (reversed(paths) if first else paths):
-        r = read_warped(p, grid, bands, resampling, level, layout, out, True, nodata, dtype, channel_offset, decode)
+        r = read_warped(p, grid, bands, resampling, level, layout, out, True, nodata, dtype, channel_offset, decode, reproject)
     return Raster(out, grid.transform, r.crs, nodata, dname)
 
 
-def read_aligned_stack(items, grid=None, resolution=None, bands=None, resampling='nearest', level=0):
+def read_aligned_stack(items, grid=None, resolution=None, bands=None, resampling='nearest', level=0, reproject=False):
     """The acquisitions of a time series on ONE grid as a resident stack: -> (stack, transform, crs, nodata), the contract of
     `read_stack` -- stack a (T, C, H, W) CUDA tensor in the files' kind -- for files that need not share a grid: other footprints,
     other resolutions (the 20 m bands beside the 10 m ones), one CRS.  items: per acquisition a path, or a list of paths mosaicked
     into the slot (`read_mosaic`).  grid: None is `union_grid` of every file at `resolution` (None: the finest).  Every file is
-    resampled straight into its slot.  With files that already share the grid, nearest gives `read_stack`'s result bit for bit."""
+    resampled straight into its slot.  With files that already share the grid, nearest gives `read_stack`'s result bit for bit.
+    reproject=True: the files may be in several EPSG codes (`read_warped`); the grid built here is `union_grid(..., reproject=True)`."""
     import os
     from .prediction_tools import _device_empty
     items = [[it] if isinstance(it, (str, os.PathLike)) else list(it) for it in items]
@@ -1331,17 +1374,211 @@ def read_aligned_stack(items, grid=None, resolution=None, bands=None, resampling
     if not flat or any(not it for it in items):
         raise ValueError('read_aligned_stack needs at least one file per acquisition')
     if grid is None:
-        grid = union_grid(flat, resolution=resolution)
+        grid = union_grid(flat, resolution=resolution, reproject=reproject)
     elif resolution is not None:
         raise ValueError('resolution describes the grid that is built when none is given')
     for p in flat:
-        _file_levels(p, grid)
+        _file_levels(p, grid, reproject)
     name, c, nodata = _same_kind(flat, bands)
     H, W = grid.shape
     stack = _device_empty((len(items), c, H, W), _torch_dtype(name), 'the time stack')
     for t, it in enumerate(items):
         if len(it) == 1:
-            r = read_warped(it[0], grid, bands, resampling, level, 'chw', stack[t], False, nodata)
+            r = read_warped(it[0], grid, bands, resampling, level, 'chw', stack[t], False, nodata, reproject=reproject)
         else:
-            r = read_mosaic(it, grid, bands, resampling, level, 'chw', False, nodata, None, stack[t])
+            r = read_mosaic(it, grid, bands, resampling, level, 'chw', False, nodata, None, stack[t], reproject=reproject)
     return stack, grid.transform, r.crs, nodata
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Reprojection: rasters of several coordinate systems brought onto one grid, on the device.
+#
+#     EPSG table on the host (crs.py) -> points through satcv_crs_transform (bounds, windows, pixel sizes: the CPU loop of the same
+#       csrc/crs_core.hpp the kernels use) -> satcv_raster_reproject (the warp's rules, u and v through both projections per pixel)
+#
+# What the reference takes from gdal.Warp (utils/pc_tools.py:152-186: NAIP tiles in two UTM zones), stackstac.stack(epsg=) and
+# rasterio's transform_bounds (utils/prediction_tools.py:560-600).  The projection rules are csrc/crs_core.hpp's; WGS84 and NAD83
+# coordinates are taken as the same point (no datum shift, at most 1-2 m).  Every default of the functions above is unchanged:
+# reprojection is opt-in (reproject=True) or goes through the names below.
+def _check_reproject_method(resampling):
+    if resampling not in WARP_RESAMPLING:
+        raise ValueError(f'resampling must be one of {sorted(WARP_RESAMPLING)}, got {resampling!r}')
+    if resampling == 'average':
+        raise ValueError("resampling='average' between two coordinate systems is not done (a pixel's footprint is no axis-parallel rectangle): "
+                         "read an overview with level='auto' and resample it with 'bilinear'")
+
+
+def transform_points(xs, ys, src_crs, dst_crs, device=False):
+    """Points of `src_crs` in `dst_crs`: -> (xs, ys) of the same shape, float64.  Geographic coordinates are x = longitude, y = latitude
+    in degrees.  A point outside a projection's domain (csrc/crs_core.hpp: |lat| > 90, more than 30 degrees off a UTM zone's central
+    meridian, beyond the square world of EPSG:3857, not finite) comes back as NaN.  device=False: array-likes in, NumPy arrays out, the
+    loop runs on the CPU; device=True: CUDA float64 tensors in and out, one thread per point.  No datum shift between WGS84 and NAD83
+    (at most 1-2 m).  ValueError for a code `crs.crs_params` does not know."""
+    import ctypes as C
+    from ._lib import check, lib
+    from .crs import crs_struct
+    a, b = crs_struct(src_crs), crs_struct(dst_crs)
+    if device:
+        import torch
+        from . import ops
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 for t in (xs, ys)) or xs.shape != ys.shape:
+            raise ValueError('device=True takes two CUDA float64 tensors of one shape')
+        xs, ys = xs.contiguous(), ys.contiguous()
+        xo, yo = torch.empty_like(xs), torch.empty_like(ys)
+        check(lib.satcv_crs_transform(C.byref(a), C.byref(b), xs.data_ptr(), ys.data_ptr(), xo.data_ptr(), yo.data_ptr(), None, xs.numel(), 1, ops.stream_ptr()))
+        return xo, yo
+    xs, ys = np.ascontiguousarray(xs, np.float64), np.ascontiguousarray(ys, np.float64)
+    if xs.shape != ys.shape:
+        raise ValueError(f'xs and ys differ in shape: {xs.shape} against {ys.shape}')
+    xo, yo = np.empty_like(xs), np.empty_like(ys)
+    check(lib.satcv_crs_transform(C.byref(a), C.byref(b), xs.ctypes.data, ys.ctypes.data, xo.ctypes.data, yo.ctypes.data, None, xs.size, 0, None))
+    return xo, yo
+
+
+def transform_bounds(src_crs, dst_crs, left, bottom, right, top, densify_pts=21):
+    """rasterio's `transform_bounds`: the box (left, bottom, right, top) of `dst_crs` that holds the box of `src_crs`.  Every edge gets
+    `densify_pts` points between its corners (an edge that is straight in one projection bulges in another), all are transformed, and
+    the result is the minimum and maximum over the points inside the projections' domains.  ValueError when none is."""
+    if isinstance(densify_pts, bool) or int(densify_pts) != densify_pts or densify_pts < 0:
+        raise ValueError(f'densify_pts must be an integer >= 0, got {densify_pts!r}')
+    t = np.linspace(0.0, 1.0, int(densify_pts) + 2)
+    ex, ey = left + (right - left) * t, bottom + (top - bottom) * t
+    xs = np.concatenate([ex, ex, np.full_like(t, left), np.full_like(t, right)])
+    ys = np.concatenate([np.full_like(t, bottom), np.full_like(t, top), ey, ey])
+    xo, yo = transform_points(xs, ys, src_crs, dst_crs)
+    ok = ~np.isnan(xo)
+    if not ok.any():
+        raise ValueError(f'no point of the bounds {(left, bottom, right, top)} of {src_crs} lies inside the domain of {dst_crs}')
+    return float(xo[ok].min()), float(yo[ok].min()), float(xo[ok].max()), float(yo[ok].max())
+
+
+def measured_pixel_size(src_transform, src_crs, dst_crs, centre):
+    """(px, py): the size of a pixel of `src_transform` (of `src_crs`) in units of `dst_crs`, at the point `centre` = (x, y) of
+    `dst_crs`: the point is taken to `src_crs`, it and its two one-pixel neighbours (one column on, one row on) are taken back, and the
+    two distances are the sizes.  ValueError when one of the three lies outside a projection's domain."""
+    a, _, _, _, e, _ = _check_transform(src_transform, 'the source')
+    cx, cy = transform_points([centre[0]], [centre[1]], dst_crs, src_crs)
+    xs, ys = transform_points([cx[0], cx[0] + a, cx[0]], [cy[0], cy[0], cy[0] + e], src_crs, dst_crs)
+    if np.isnan(xs).any():
+        raise ValueError(f'the point {tuple(centre)} of {dst_crs} and its neighbours do not lie inside the domain of {src_crs}')
+    return float(np.hypot(xs[1] - xs[0], ys[1] - ys[0])), float(np.hypot(xs[2] - xs[0], ys[2] - ys[0]))
+
+
+class _Extent:
+    """bounds and resolution of a source in another CRS (what `union_grid` needs of a Grid)"""
+    __slots__ = ('bounds', 'resolution', 'epsg')
+
+    def __init__(self, bounds, resolution, epsg):
+        self.bounds, self.resolution, self.epsg = bounds, resolution, epsg
+
+
+def _foreign_extent(g, epsg):
+    dst = f'EPSG:{epsg}'
+    bounds = transform_bounds(g.crs, dst, *g.bounds)
+    a, _, c, _, e, f = g.transform
+    cx, cy = transform_points([c + 0.5 * g.shape[1] * a], [f + 0.5 * g.shape[0] * e], g.crs, dst)
+    if np.isnan(cx[0]):
+        raise ValueError(f'the centre of a source in {g.crs} lies outside the domain of {dst}')
+    return _Extent(bounds, measured_pixel_size(g.transform, g.crs, dst, (cx[0], cy[0])), epsg)
+
+
+def reproject_grid(source, dst_crs, resolution=None, bounds=None):
+    """A north-up grid of `dst_crs` that holds `source` (a path, a `LevelInfo` or a `Grid` with a CRS): -> Grid.  bounds: None is
+    `transform_bounds` of the source's bounds.  resolution: a number or (x, y); None keeps the number of pixels along the diagonal --
+    the length of the destination bounds' diagonal over sqrt(H^2 + W^2), square pixels.  The bounds are snapped outward to multiples of
+    the resolution, as `union_grid` does.  This rule is the library's own (it is the one GDAL documents for its suggested warp output,
+    but GDAL's `calculate_default_transform` was not run against it)."""
+    g = _as_grid(source)
+    if g.crs is None:
+        raise ValueError('the source carries no EPSG code: it cannot be reprojected')
+    if bounds is None:
+        bounds = transform_bounds(g.crs, dst_crs, *g.bounds)
+    if resolution is None:
+        left, bottom, right, top = (float(v) for v in bounds)
+        resolution = float(np.hypot(right - left, top - bottom) / np.hypot(g.shape[0], g.shape[1]))
+    return union_grid([], resolution=resolution, bounds=bounds, crs=dst_crs)
+
+
+def _reproject_map(grid, src_crs, src_transform):
+    from ._lib import ReprojectMap
+    from .crs import crs_struct
+    if grid.crs is None or src_crs is None:
+        raise ValueError('reprojection needs the EPSG codes of the grid and of the source')
+    a_d, _, c_d, _, e_d, f_d = grid.transform
+    m = ReprojectMap(dst_crs=crs_struct(grid.crs), dst_a=a_d, dst_c=c_d, dst_e=e_d, dst_f=f_d, src_crs=crs_struct(src_crs), has_src_transform=0)
+    if src_transform is not None:
+        a_s, _, c_s, _, e_s, f_s = _check_transform(src_transform, 'the source')
+        m.has_src_transform, m.src_a, m.src_c, m.src_e, m.src_f = 1, a_s, c_s, e_s, f_s
+    return m
+
+
+def pixel_coords(grid, crs=None, transform=None):
+    """Per pixel of `grid` the coordinates of its centre in another system: -> a (2, H, W) float64 CUDA tensor (satcv_grid_coords).
+    crs: the other CRS (None: the grid's own); with crs=4326 the result is the longitude [0] and latitude [1] of every pixel.
+    transform: an Affine transform in that CRS -- the result is then in its pixel coordinates, column u [0] and row v [1], the very
+    numbers `reproject` samples at; None: CRS units.  NaN where a pixel lies outside a projection's domain."""
+    import ctypes as C
+    import torch
+    from . import ops
+    from ._lib import check, lib
+    from .prediction_tools import _device_empty
+    if not isinstance(grid, Grid):
+        raise ValueError(f'grid must be a Grid, got {type(grid).__name__}')
+    m = _reproject_map(grid, grid.crs if crs is None else crs, transform)
+    H, W = grid.shape
+    out = _device_empty((2, H, W), torch.float64, 'the coordinate field')
+    check(lib.satcv_grid_coords(C.byref(m), H, W, 0, 0, out[0].data_ptr(), out[1].data_ptr(), ops.stream_ptr()))
+    return out
+
+
+def reproject(src, src_transform, src_crs, grid, resampling='nearest', src_nodata=None, nodata=None, dtype=None, src_layout='hwc', layout='hwc',
+              out=None, channel_offset=0, keep=False, src_origin=(0, 0), src_dtype=None):
+    """A resident raster of `src_crs` resampled onto `grid` of another CRS, on the device: -> CUDA tensor of grid.shape.  Every argument
+    but src_crs is `warp`'s, and so are the rules: per destination pixel the centre's coordinates go through the grid's projection
+    back to longitude / latitude and through the source's projection forward (csrc/crs_core.hpp; no datum shift between WGS84 and
+    NAD83, at most 1-2 m), then 'nearest', 'bilinear' or 'cubic' sample as `warp` does; a pixel outside a projection's domain is
+    invalid.  With equal EPSG codes (or a missing one) this IS `warp`.  'average' across two codes is a ValueError: read an overview
+    (level='auto') and use 'bilinear'."""
+    if not isinstance(grid, Grid):
+        raise ValueError(f'grid must be a Grid, got {type(grid).__name__}')
+    if src_crs is None or grid.crs is None or _epsg_of(src_crs) == grid.epsg:
+        return warp(src, src_transform, grid, resampling, src_nodata, nodata, dtype, src_layout, layout, out, channel_offset, keep, src_origin, src_dtype)
+    _check_reproject_method(resampling)
+    m = _reproject_map(grid, src_crs, src_transform)
+    return _resample(src, (0.0, 0.0, 0.0, 0.0), m, grid, resampling, src_nodata, nodata, dtype, src_layout, layout, out, channel_offset, keep, src_origin, src_dtype)
+
+
+_reproject_raster = reproject      # (the readers have a keyword of that name)
+
+
+def reproject_window(src_transform, src_shape, src_crs, grid, resampling='nearest'):
+    """`warp_window` across two coordinate systems: the window (row0, col0, h, w) of a source raster of `src_crs` that `grid` needs, or
+    None when the grid misses the raster.  The centres of ALL boundary pixels of the grid are transformed (the map between two
+    projections is a homeomorphism: the extremes of u and v over the grid lie on its boundary); the window runs from floor(min) to
+    floor(max), widened by the method's margin (0 / 1 / 2) and by one pixel more -- the host's and the device's libm may differ in the
+    last bits -- and clipped to the raster.  When some boundary pixel lies outside a projection's domain the extremes are unknown: the
+    window is the whole raster; when every one does: None."""
+    _check_reproject_method(resampling)
+    if not isinstance(grid, Grid):
+        raise ValueError(f'grid must be a Grid, got {type(grid).__name__}')
+    a_s, _, c_s, _, e_s, f_s = _check_transform(src_transform, 'the source')
+    a_d, _, c_d, _, e_d, f_d = grid.transform
+    H, W = grid.shape
+    jj = np.concatenate([np.arange(W), np.arange(W), np.zeros(H), np.full(H, W - 1)]).astype(np.float64)
+    ii = np.concatenate([np.zeros(W), np.full(W, H - 1), np.arange(H), np.arange(H)]).astype(np.float64)
+    xs, ys = transform_points(a_d * (jj + 0.5) + c_d, e_d * (ii + 0.5) + f_d, grid.crs, src_crs)
+    ok = ~np.isnan(xs)
+    if not ok.any():
+        return None
+    if not ok.all():
+        return 0, 0, int(src_shape[0]), int(src_shape[1])
+    u, v = (xs - c_s) / a_s, (ys - f_s) / e_s
+    m = _WARP_MARGIN[resampling] + 1
+    out = []
+    for w_, n_src in ((v, src_shape[0]), (u, src_shape[1])):
+        lo, hi = int(np.floor(w_.min())) - m, int(np.floor(w_.max())) + m
+        lo, hi = max(lo, 0), min(hi, int(n_src) - 1)
+        if lo > hi:
+            return None
+        out.append((lo, hi - lo + 1))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
