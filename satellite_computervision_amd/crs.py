@@ -11,7 +11,7 @@ and NAIP scenes in UTM zones, longitude / latitude, the web Mercator of its map 
 Datum: WGS84 and NAD83 coordinates are taken as the same point -- no datum shift is applied (at most 1-2 m; PROJ's default "ballpark"
 transformation for these pairs).  Only the ellipsoid differs: WGS84 for 4326 / 326xx / 327xx / 3857, GRS80 for 4269 / 269xx.
 """
-from .raster_tools import parse_crs
+from .tiff_container import parse_crs
 
 GEOGRAPHIC, TRANSVERSE_MERCATOR, SPHERICAL_MERCATOR = 0, 1, 2
 WGS84 = (6378137.0, 298.257223563)

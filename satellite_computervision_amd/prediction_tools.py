@@ -476,21 +476,13 @@ def predict_raster(in_file, m, out_file, window=None, cog_options=None, **predic
     `predict_scene`) as a Cloud-Optimized GeoTIFF that carries the source's transform -- of the window -- and CRS; cog_options: a dict of
     further `write_cog` arguments (dtype, scale, nodata, compress, ...).  predict_scene_kwargs: kernel, buff, batch_size, channel, cover,
     classes, rescale.  ValueError when the file carries no transform or no EPSG code."""
-    import ctypes as C
-    import torch
-    from . import ops, raster_tools as rt
-    from ._lib import check, lib
+    from . import raster_tools as rt
     if 'device' in predict_scene_kwargs:
         raise ValueError('predict_raster keeps the scene and the map on the device: device is not an argument')
     r = rt.read_cog(in_file, window=window, layout='hwc', device=True)
     if r.transform is None or r.crs is None:
         raise ValueError(f'{in_file} carries no transform or no EPSG code: the output cannot be georeferenced')
-    scene = r.array
-    if r.dtype != 'float32':
-        H, W, C_ = (int(v) for v in scene.shape)
-        f32 = _device_empty((H, W, C_), torch.float32, 'the float32 scene')
-        check(lib.satcv_raster_convert(C.byref(rt._desc(scene.data_ptr(), rt.DTYPES[r.dtype][1], H, W, C_, C_, 0, f32, 2)), ops.stream_ptr()))
-        scene = f32
+    scene = r.array if r.dtype == 'float32' else rt.to_float32(r.array, r.dtype, what='the float32 scene', as_raster=True)
     res = predict_scene(scene, m, device=True, **predict_scene_kwargs)
     rt.write_cog(res[0] if isinstance(res, tuple) else res, out_file, r.transform, r.crs, **dict(cog_options or {}))
     return res
@@ -725,18 +717,18 @@ def predict_hybrid_raster(scene_file, stack_items, m, out_file, window=None, res
     info = rt.read_info(scene_file)[0]
     if info.transform is None or info.crs is None:
         raise ValueError(f'{scene_file} carries no transform or no EPSG code: the output cannot be georeferenced')
-    (row0, col0, h, w), _, _ = rt._plan_read(info, window, None)
+    (row0, col0, h, w), transform = rt.level_window(info, window)
     if h % r or w % r:
         raise ValueError(f'the fine extent {h} x {w} is not a multiple of the resolution ratio r = {r}: choose a window that is, or trim the scene '
                          f'(pc_tools.trim_array(arr, {r}))')
-    fine = rt.Grid(rt._window_transform(info.transform, info.shape, info.shape, row0, col0), (h, w), info.crs)
+    fine = rt.Grid(transform, (h, w), info.crs)
     a, _, c, _, e, f = fine.transform
     coarse = rt.Grid((a * r, 0.0, c, 0.0, e * r, f), (h // r, w // r), info.crs)
     scene = rt.read_cog(scene_file, window=(row0, col0, h, w), layout='hwc', device=True)
     stack = rt.read_aligned_stack(stack_items, coarse, resampling=resampling, reproject=reproject)[0]
-    fine_scene = scene.array if scene.dtype == 'float32' else _as_float32(scene.array, scene.dtype)
+    fine_scene = scene.array if scene.dtype == 'float32' else rt.to_float32(scene.array, scene.dtype)
     if stack.dtype not in (torch.int16, torch.float32):       # (the series gather reads int16 and float32)
-        stack = _as_float32(stack, rt.read_info(_first_path(stack_items))[0].dtype)
+        stack = rt.to_float32(stack, rt.read_info(_first_path(stack_items))[0].dtype)
     res = predict_hybrid_scene(fine_scene, stack, m, device=True, **kwargs)
     rt.write_cog(res[0] if isinstance(res, tuple) else res, out_file, fine.transform, fine.crs, **dict(cog_options or {}))
     return res
@@ -765,7 +757,7 @@ def get_img_bounds(img, jsonFile, dst_crs=None):
             raise ValueError(f'expected an (H, W) array or the path of a GeoTIFF, got shape {shape}')
         left, bottom, right, top = rt.Grid(tuple(mixer['projection']['affine']['doubleMatrix'][:6]), shape).bounds
     if dst_crs:
-        left, bottom, right, top = rt.transform_bounds(src_crs, dst_crs, left, bottom, right, top, densify_pts=21)
+        left, bottom, right, top = rt.transform_bounds(src_crs, dst_crs, left=left, bottom=bottom, right=right, top=top, densify_pts=21)
     return [[bottom, left], [top, right]]
 
 
@@ -773,18 +765,6 @@ def _first_path(items):
     import os
     first = list(items)[0]
     return first if isinstance(first, (str, os.PathLike)) else list(first)[0]
-
-
-def _as_float32(t, dtype):
-    """an integer raster or stack on the device cast to float32 there (satcv_raster_convert, exact for 8- and 16-bit samples)"""
-    import ctypes as C
-    import torch
-    from . import ops, raster_tools as rt
-    from ._lib import check, lib
-    f32 = _device_empty(tuple(t.shape), torch.float32, 'the float32 copy')
-    rows, cols = t.numel() // int(t.shape[-1]), int(t.shape[-1])
-    check(lib.satcv_raster_convert(C.byref(rt._desc(t.data_ptr(), rt.DTYPES[dtype][1], rows, cols, 1, 1, 0, f32, 2)), ops.stream_ptr()))
-    return f32
 
 
 def _stitch_hybrid(scene, stack, hi, lo, geo, m, head, output, kernel, batch_size, channel, want_classes, rescale, maxval, plan):

@@ -351,6 +351,28 @@ def test_new_value_errors_and_unchanged_refusals(tmp_path):
         rt.reproject(np.zeros((4, 4), np.uint8), north, 32618, g)
 
 
+def test_the_order_of_refusals_where_two_coincide(tmp_path):
+    """`reproject` refuses the method before it names a code it cannot reproject; `read_warped(reproject=True)` names the code first,
+    then the method, then the level; with one CRS the level comes before the method"""
+    rt = _rt()
+    north = (10, 0, 500000, 0, -10, 4400160)
+    a, b = _tiny_file(tmp_path / 'a.tif', north, 32617), _tiny_file(tmp_path / 'b.tif', north, 32618)
+    odd = _tiny_file(tmp_path / 'odd.tif', north, 2154)
+    g = rt.Grid(north, (16, 16), 32617)
+    for method, what in (('lanczos', 'resampling must be one of'), ('average', "level='auto'"), ('nearest', '32601-32660')):
+        with pytest.raises(ValueError, match=what):
+            rt.reproject(None, north, 2154, g, method)
+    for path, method, what in ((odd, 'lanczos', '32601-32660'), (b, 'lanczos', 'resampling must be one of'), (b, 'average', "level='auto'"),
+                               (b, 'nearest', 'the file has levels'), (a, 'lanczos', 'the file has levels')):
+        with pytest.raises(ValueError, match=what):
+            rt.read_warped(path, g, resampling=method, level=7, reproject=True)
+    # with one CRS a transform that cannot be resampled is refused before the method
+    for call in (lambda: rt.warp(None, (10, 1, 0, 0, -10, 0), g, 'lanczos'), lambda: rt.warp_window((10, 1, 0, 0, -10, 0), (16, 16), g, 'lanczos'),
+                 lambda: rt.reproject(None, (10, 1, 0, 0, -10, 0), 32617, g, 'lanczos')):
+        with pytest.raises(ValueError, match='rotated or sheared'):
+            call()
+
+
 # ------------------------------------------------------------------------------------------------------------ C ABI
 def _fields(hdr, name):
     m = re.search(r'typedef struct %s \{(.*?)\} %s;' % (name, name), hdr, re.S)

@@ -432,3 +432,20 @@ def test_write_geotiff_predictions_from_a_mixer(env, tmp_path):
     assert pt.write_geotiff_prediction(image, jf, str(tmp_path / 'aoi')) == str(tmp_path / 'aoi') + '.tif'
     _, ifds, levels = _read(TO, str(tmp_path / 'aoi.tif'))
     assert len(ifds) == 1 and levels[0].dtype == np.int16 and np.array_equal(levels[0], image) and TO.tag(ifds[0], 322) == (96,)
+
+
+def test_to_float32_is_exact(env):
+    """raster_tools.to_float32 (satcv_raster_convert on a raster or a stack of any rank) equals the NumPy cast: every integer kind with its
+    extremes, int32 within +-2^24, which float32 holds exactly"""
+    rt = env['rt']
+    rng = np.random.default_rng(5)
+    for dtype in (np.uint8, np.uint16, np.int16, np.int32):
+        lo, hi = max(np.iinfo(dtype).min, -2 ** 24), min(np.iinfo(dtype).max, 2 ** 24)
+        for shape in ((5, 7, 3), (2, 3, 5, 7)):
+            a = rng.integers(lo, hi, shape, dtype=np.int64, endpoint=True).astype(dtype)
+            a.flat[:4] = [lo, hi, 0, lo + 1]
+            got = rt.to_float32(_dev(a), np.dtype(dtype).name)
+            assert got.dtype == torch.float32 and tuple(got.shape) == shape
+            assert np.array_equal(got.cpu().numpy(), a.astype(np.float32))
+            if len(shape) == 3:                                # (the same tensor described to the kernel as an (H, W, C) raster)
+                assert torch.equal(rt.to_float32(_dev(a), np.dtype(dtype).name, as_raster=True), got)

@@ -414,3 +414,19 @@ def test_new_entries_keep_the_older_signatures():
     assert list(inspect.signature(rt.read_stack).parameters) == ['paths', 'window', 'bands']
     assert list(inspect.signature(pt.predict_raster).parameters)[:4] == ['in_file', 'm', 'out_file', 'window']
     assert list(inspect.signature(rt.write_cog).parameters)[:4] == ['arr', 'out_file', 'transform', 'crs']
+
+
+def test_the_container_module_needs_neither_torch_nor_the_library():
+    """`import satellite_computervision_amd.tiff_container` in a fresh interpreter loads neither torch nor the ctypes binding.  The
+    package's own __init__ loads the library on purpose (there is no CPU fallback), so the child registers a bare namespace for the
+    package first: what is held is that the module itself, and whatever it imports, needs neither."""
+    code = ("import sys, types\n"
+            f"pkg = types.ModuleType('satellite_computervision_amd'); pkg.__path__ = [{os.path.join(ROOT, 'satellite_computervision_amd')!r}]\n"
+            "sys.modules['satellite_computervision_amd'] = pkg\n"
+            "import satellite_computervision_amd.tiff_container as tc\n"
+            "assert callable(tc.read_info) and callable(tc.build_container) and tc.LevelInfo.block_bytes\n"
+            "bad = [m for m in sys.modules if m == 'torch' or m.startswith('torch.') or m.startswith('satellite_computervision_amd.') and m != tc.__name__]\n"
+            "assert not bad, bad\n")
+    import sys
+    done = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=120)
+    assert done.returncode == 0, done.stderr

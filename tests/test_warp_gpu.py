@@ -428,3 +428,37 @@ def test_predict_change_files_equals_predict_change_on_aligned_stacks(env, tmp_p
         assert np.array_equal(g, w_, equal_nan=True)
     back = rt.read_cog(out_file)
     assert back.transform == grid.transform and back.crs == 'EPSG:32633' and np.array_equal(back.array.cpu().numpy()[..., 0], want[0])
+
+
+def test_each_file_is_parsed_once(env, tmp_path, monkeypatch):
+    """Within one call of read_aligned_stack, read_mosaic, read_warped and read_stack the container of every file is parsed exactly once
+    (`read_info`, counted where raster_tools looks it up), and the result is, bit for bit, what the uncounted call returns.  Three
+    48 x 40 two-band uint16 files with overlapping footprints: a and b on one 10 m grid, c at 20 m; a2 is a copy of a; d lies in the
+    neighbouring UTM zone."""
+    import shutil
+    rt = env['rt']
+    x, y = rt.transform_points([-78.0], [40.0], 4326, 32617)
+    x0, y0 = round(float(x[0]) / 20) * 20.0, round(float(y[0]) / 20) * 20.0
+    xd, yd = rt.transform_points([x0 + 150.0], [y0 - 90.0], 32617, 32618)
+    placed = {'a': ((10.0, 0.0, x0, 0.0, -10.0, y0), 32617), 'b': ((10.0, 0.0, x0 + 200.0, 0.0, -10.0, y0 - 100.0), 32617),
+              'c': ((20.0, 0.0, x0 - 100.0, 0.0, -20.0, y0 + 60.0), 32617),
+              'd': ((10.0, 0.0, round(float(xd[0])), 0.0, -10.0, round(float(yd[0]))), 32618)}
+    p = {k: rt.write_cog(source('uint16', 2, 48, 40, seed=i), str(tmp_path / f'{k}.tif'), t, code, nodata=7, blocksize=16)
+         for i, (k, (t, code)) in enumerate(placed.items())}
+    p['a2'] = shutil.copy(p['a'], str(tmp_path / 'a2.tif'))
+    grid = rt.Grid((10.0, 0.0, x0 + 50.0, 0.0, -10.0, y0 - 30.0), (33, 29), 32617)
+    cases = {'aligned stack': (lambda: rt.read_aligned_stack([p['a'], [p['b'], p['c']]])[0], 'abc'),
+             'mosaic': (lambda: rt.read_mosaic([p['a'], p['b'], p['c']]).array, 'abc'),
+             'warped': (lambda: rt.read_warped(p['a'], grid).array, 'a'),
+             'stack': (lambda: rt.read_stack([p['a'], p['a2']])[0], ['a', 'a2']),
+             'two-zone mosaic': (lambda: rt.read_mosaic([p['a'], p['b'], p['d']], reproject=True).array, 'abd')}
+    want = {name: call() for name, (call, _) in cases.items()}
+    parsed = []
+    read_info = rt.read_info
+    monkeypatch.setattr(rt, 'read_info', lambda path: (parsed.append(str(path)), read_info(path))[1])
+    for name, (call, files) in cases.items():
+        parsed.clear()
+        got = call()
+        assert sorted(parsed) == sorted(p[k] for k in files), (name, parsed)
+        assert _same(got, want[name]), name
+    assert (_host(want['two-zone mosaic'], np.uint16) != 7).all(axis=2).any() and want['aligned stack'].shape[:2] == (2, 2)
