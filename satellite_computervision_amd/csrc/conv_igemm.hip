@@ -396,7 +396,9 @@ static int igemm_dispatch(IgemmArgs& a, int dtype, hipStream_t st, bool dry, Ige
   if (note && note->info) { *note->info = satcv_conv_plan_info{}; note->info->dtype = dtype; }
   if (a.kh == 3 && a.kw == 3 && a.stride == 1 && a.dil >= a.h && a.dil >= a.w_) {
     // every off-centre tap of this dilated conv reads only zero padding: it IS the 1x1 conv of its centre tap
-    const size_t esz = dtype == SATCV_BF16 ? 2 : 4;
+    // (a tap image is (cin / 8) x cout_pad items of 8 elements; the scaled e4m3 image's 16-element granules, (cin / 16) x cout_pad x 16, are the
+    //  same bytes: satcv_pack_weights.  Element size per storage type: e4m3 is ONE byte)
+    const size_t esz = dtype == SATCV_F32 ? 4 : (dtype == SATCV_BF16 ? 2 : 1);
     a.w = reinterpret_cast<const unsigned char*>(a.w) + (size_t)4 * ((a.c0 + a.c1) / 8) * a.cout_pad * 8 * esz;
     a.kh = a.kw = 1; a.dil = 1;
     if (note && note->info) note->info->centre_tap = 1;

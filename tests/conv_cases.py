@@ -13,7 +13,9 @@ satcv_conv2d_igemm serves Conv2D forward, its data gradient, Conv2DTranspose for
 
 ALL_KEYS is written out by hand from the `if` chains of fast_tw / igemm_fast_launch, igemm_m16_launch, igemm_m16p_launch, igemm_ws_launch,
 igemm_tr_launch, the two convt_thin launchers and the generic launch_tw, for bf16 and fp32 storage and, as far as the chain names them, the
-two e4m3 storage types (reached on the CPU only: their values stay with tests/test_fp8_gpu.py).  CASES is the table, every entry with the key it is meant to reach.  The CPU test asks the library's plan query
+two e4m3 storage types SATCV_FP8 and SATCV_FP8X (value cases like the rest: every reachable e4m3 key runs on the GPU, bit-exactly, with the once-rounded,
+saturating reference of tests/test_conv_plan_gpu.py; where bf16 would fall to the generic kernel, which e4m3 does not have, the table records the
+refusal in REFUSALS).  CASES is the table, every entry with the key it is meant to reach.  The CPU test asks the library's plan query
 (satcv_conv2d_igemm_plan_info: the launch path's own decision chain, nothing launched) that every case lands on its key and that the
 union of the reached keys is ALL_KEYS minus UNREACHABLE; the GPU test runs the cases against a float64 oracle and, on integer data,
 bit-exactly.
@@ -141,6 +143,15 @@ def describe(name, n, h, w, c0, cout, key, *, c1=0, k=3, dil=1, stride=1, mode='
 def case(name, *args, **kw):
     assert not any(c['name'] == name for c in CASES), name
     CASES.append(describe(name, *args, **kw))
+
+
+REFUSALS = []          # e4m3 descriptors the dispatcher answers with SATCV_ERR_UNSUPPORTED (bf16 / fp32 would run the generic kernel): nothing is launched
+REFUSAL_MESSAGE = "outside the pipelined kernel's limits"
+
+
+def refusal(name, n, h, w, c0, cout, dtype, **kw):
+    assert dtype in (FP8, FP8X) and not any(c['name'] == name for c in CASES + REFUSALS), name
+    REFUSALS.append(describe(name, n, h, w, c0, cout, (dtype,), **kw))
 
 
 def planned(n, h, w, c0, cout, dtype, ncu=0, **kw):
@@ -279,8 +290,9 @@ def fast_cases(form, dt, c0, cout, *, dyn=0, tag='', tws=TWS, kinds='wrm', k=Non
     form's register staging (fast_cfg: rl * cl * KC / EL > AI * NTHREADS) the table names the form the shape falls to:
       * 3x3 on the 4-row x 32-pixel tile, two 2-row images: 2 x (2 + 2) x 34 pixels x 2 items = 544 > 512 -> the GENERIC kernel of
         conv_igemm.hip (no pipelined form serves 2-row maps of 64 / 128 output columns at tile width 32; out_scale / pool / pair / fused sums
-        are refused there: test_conv_plan_cpu.py::test_two_row_maps_have_no_pipelined_3x3_form);
-      * the dilated-halo form with two images per tile -> the tap loop."""
+        are refused there: test_conv_plan_cpu.py::test_two_row_maps_have_no_pipelined_3x3_form).  The e4m3 types have no generic kernel
+        (and the scaled form's four 16-channel items per pixel overflow the same way, 1088 > 1024): the shape is REFUSED, and recorded so;
+      * the dilated-halo form with two images per tile -> the tap loop; the scaled e4m3 form has no tap loop: REFUSED."""
     wm, wn, mt, nt, ks, taps = FAST[form][:6]
     for tw in tws:
         for kind, (n, h, w) in shapes(32 * wm * mt, tw).items():
@@ -288,11 +300,17 @@ def fast_cases(form, dt, c0, cout, *, dyn=0, tag='', tws=TWS, kinds='wrm', k=Non
                 continue
             key = fast_key(dt, tw, form, dyn)
             if kind == 'm' and taps == 9 and FAST[form][7] == 0:
-                if dyn and not (form == 't32-9' and tw < 32):
-                    key = fast_key(dt, tw, 'tl16-32' if cout % 64 else 'tl16-64')
+                # (the 256-pixel tile holds two dilated images below width 32 -- the scaled form, whose 1920 items of four per pixel meet a budget
+                #  of 7 x 256 at width 16, at width 8 only)
+                if dyn and not (form == 't32-9' and tw < (16 if dt == FP8X else 32)):
+                    key = fast_key(dt, tw, 'tl16-32' if cout % 64 else 'tl16-64') if dt != FP8X else None
                 elif not dyn and tw == 32 and wm * mt == 4:
-                    key = generic_key(dt, tw, 'g128' if cout % 128 == 0 else 'g64')
-            case(f'{form}{tag}-{dt}-tw{tw}-{kind}', n, h, w, c0, cout, key, k=k or (3 if taps == 9 else 1), **kw)
+                    key = generic_key(dt, tw, 'g128' if cout % 128 == 0 else 'g64') if dt in (F32, BF16) else None
+            name = f'{form}{tag}-{dt}-tw{tw}-{kind}'
+            if key is None:
+                refusal(name, n, h, w, c0, cout, dt, k=k or (3 if taps == 9 else 1), **kw)
+            else:
+                case(name, n, h, w, c0, cout, key, k=k or (3 if taps == 9 else 1), **kw)
 
 
 for dt in (F32, BF16):
@@ -472,31 +490,84 @@ case('padded-cin-m16', 2, 20, 44, 64, 128, (BF16, 'm16', 16, 0, 0), cin=40, bias
 case('padded-cin-m16p', 2, 8, 64, 64, 128, (BF16, 'm16p', 128, 0), cin=40, bias=True, stats=True, affine=True, opts={'m16p': 2})
 case('padded-cin-sk', 3, 8, 8, 256, 128, fast_key(BF16, 8, 'sk-t128-9'), cin=200, bias=True, stats=True, opts={'splitk': 1})
 
-# ---- the e4m3 storage types: keys only (gpu=False; their values are tests/test_fp8_gpu.py's)
-_k = dict(gpu=False)
-fast_cases('t128-9', FP8, 48, 128, kinds='w', **_k)
-fast_cases('t64-9', FP8, 48, 64, kinds='r', **_k)
-fast_cases('t32-9', FP8, 48, 32, kinds='w', **_k)
-fast_cases('t128-9', FP8, 48, 128, dyn=1, tag='-dyn', dil=2, tws=(8, 16), kinds='w', **_k)
-fast_cases('t64-9', FP8, 48, 64, dyn=1, tag='-dyn', dil=2, tws=(8, 16), kinds='r', **_k)
-fast_cases('t32-9', FP8, 48, 32, dyn=1, tag='-dyn', dil=2, kinds='w', **_k)
-fast_cases('tl16-64', FP8, 48, 64, dil=6, k=3, kinds='r', **_k)
-fast_cases('tl16-32', FP8, 48, 32, dil=6, k=3, kinds='w', **_k)
-fast_cases('tl128', FP8, 32, 128, dil=6, k=3, kinds='r', **_k)
-fast_cases('tl64', FP8, 32, 64, dil=6, k=3, kinds='w', **_k)
-fast_cases('c128', FP8, 32, 128, kinds='r', out_scale=True, bias=True, out_relu=True, **_k)
-fast_cases('c64', FP8, 32, 64, kinds='w', **_k)
-fast_cases('c32', FP8, 32, 32, kinds='m', **_k)
-fast_cases('t128-1', FP8, 48, 128, kinds='w', **_k)
-fast_cases('t64-1', FP8, 48, 64, kinds='r', **_k)
-fast_cases('t32-1', FP8, 48, 32, kinds='w', **_k)
+# ---- the e4m3 storage types, SATCV_FP8 and the block-scaled SATCV_FP8X: value cases like the rest.  Every launch carries the output multiplier, as
+# every launch of the folded plan does (fp8_infer.py); the GPU test scales it so that nothing saturates, and runs two cases that saturate on purpose
+# (E4M3_SATURATING).  Channel counts: 48 and 32 for FP8 (16- and 32-channel chunks; off the thin-layer kernel's 32 / 64 where the map is whole tiles),
+# 64 for FP8X.  No stats, fused sums, accumulate, stride or space-to-depth: no lowering produces them in e4m3.
+_e = dict(out_scale=True, bias=True, out_relu=True)
+
+
+def e4m3_cases(form, dt, c0, cout, rot, *, tws=TWS, **kw):
+    """one shape kind per tile width, rotated by rot: the three widths of a form together see the whole-tile, the ragged and the
+    several-images-per-tile shape"""
+    for i, tw in enumerate(TWS):
+        if tw in tws:
+            fast_cases(form, dt, c0, cout, tws=(tw,), kinds='wrm'[(i + rot) % 3], **dict(_e, **kw))
+
+
+# 3x3 halo tiles.  The 128- and 64-column forms keep 'm' off tile width 32, where it is refused (fast_cases); the refusal is recorded beside them
+e4m3_cases('t128-9', FP8, 48, 128, 1)
+e4m3_cases('t64-9', FP8, 48, 64, 2)
+e4m3_cases('t32-9', FP8, 48, 32, 0)
+fast_cases('t128-9', FP8, 48, 128, tws=(32,), kinds='m', **_e)
+fast_cases('t64-9', FP8, 48, 64, tws=(32,), kinds='m', **_e)
+# the dilated-halo kernel exists at two widths for the 128- / 64-column forms: every kind at every width ('m' falls to the tap loop but for
+# the 256-pixel tile below width 32)
+fast_cases('t128-9', FP8, 48, 128, dyn=1, tag='-dyn', dil=2, tws=(8, 16), **_e)
+fast_cases('t64-9', FP8, 48, 64, dyn=1, tag='-dyn', dil=2, tws=(8, 16), **_e)
+fast_cases('t32-9', FP8, 48, 32, dyn=1, tag='-dyn', dil=2, **_e)
+# tap loop: dilation 6, at every tile width
+e4m3_cases('tl16-64', FP8, 48, 64, 1, dil=6, k=3)
+e4m3_cases('tl16-32', FP8, 48, 32, 2, dil=6, k=3)
+e4m3_cases('tl128', FP8, 32, 128, 0, dil=6, k=3)
+e4m3_cases('tl64', FP8, 32, 64, 1, dil=6, k=3)
+# 1x1: 32-channel chunks, and the 16-channel-chunk forms t*-1
+e4m3_cases('c128', FP8, 32, 128, 2)
+e4m3_cases('c64', FP8, 32, 64, 0)
+e4m3_cases('c32', FP8, 32, 32, 1)
+e4m3_cases('t128-1', FP8, 48, 128, 2)
+e4m3_cases('t64-1', FP8, 48, 64, 0)
+e4m3_cases('t32-1', FP8, 48, 32, 1)
+# the scaled form: 64-channel chunks, 16-byte items; a dilated launch has the dilated-halo kernel alone (no tap loop: refused where it does not fit)
+e4m3_cases('t64-9', FP8X, 64, 64, 1)
+e4m3_cases('t32-9', FP8X, 64, 32, 0)
+fast_cases('t64-9', FP8X, 64, 64, tws=(32,), kinds='m', **_e)
+e4m3_cases('t64-1', FP8X, 64, 64, 2)
+e4m3_cases('t32-1', FP8X, 64, 32, 1)
+fast_cases('t64-9', FP8X, 64, 64, dyn=1, tag='-dyn', dil=2, tws=(8, 16), **_e)
+fast_cases('t32-9', FP8X, 64, 32, dyn=1, tag='-dyn', dil=2, **_e)
+refusal('fp8x-dilation-6-has-no-tap-loop', 2, 9, 20, 64, 64, FP8X, dil=6, **_e)
+# thin-layer kernel (whole 8 x 32 tiles, 32 / 64 input channels), with the launch counter moving by one; pair store and dual source + loader affine
+# as tests/test_fp8_gpu.py::test_fp8_thin_layer_kernel_bit_exact has them
 for (ci, nt, wps, wn, dil) in WS_FP8:
-    case(f'fp8-ws-{ci}-{32 * nt * wn}', 2, 8, 64, ci, 32 * nt * wn, (FP8, 'ws', ci, nt, wps, wn, dil), out_scale=True, bias=True, out_relu=True, pool_f=2, **_k)
-case('fp8-ws-ragged-neighbour', 2, 5, 60, 64, 64, fast_key(FP8, 32, 't64-9'), out_scale=True, bias=True, out_relu=True, **_k)
-for _f in FP8X_FORMS:
-    fast_cases(_f, FP8X, 64, 64 if '64' in _f else 32, kinds='wr', out_scale=True, bias=True, out_relu=True, **_k)
-fast_cases('t64-9', FP8X, 64, 64, dyn=1, tag='-dyn', dil=2, tws=(8, 16), kinds='w', out_scale=True, **_k)
-fast_cases('t32-9', FP8X, 64, 32, dyn=1, tag='-dyn', dil=2, kinds='w', out_scale=True, **_k)
+    case(f'fp8-ws-{ci}-{32 * nt * wn}', 2, 8, 64, ci, 32 * nt * wn, (FP8, 'ws', ci, nt, wps, wn, dil), pool_f=2, **_e)
+case('fp8-ws-64-64-pair', 2, 8, 32, 64, 64, (FP8, 'ws', 64, 1, 1, 2, 1), pair=True, **_e)
+case('fp8-ws-64-32-dual-affine', 3, 8, 32, 32, 32, (FP8, 'ws', 64, 1, 2, 1, 1), c1=32, affine=True, **_e)
+case('fp8-ws-ragged-neighbour', 2, 5, 60, 64, 64, fast_key(FP8, 32, 't64-9'), **_e)
+# what the folded plan emits for e4m3 tensors, on the general epilogue at ragged shapes
+_k9 = fast_key(FP8, 32, 't64-9')
+case('feat-fp8-pool2', 2, 10, 60, 48, 64, _k9, pool_f=2, **_e)
+case('feat-fp8-pair', 4, 5, 60, 48, 64, _k9, pair=True, **_e)
+case('feat-fp8-pair-several-images-per-tile', 6, 4, 16, 48, 64, fast_key(FP8, 16, 't64-9'), pair=True, out_scale=True, bias=True)
+case('feat-fp8-convt-f2-r', 2, 11, 44, 32, 32, fast_key(FP8, 16, 'c128'), k=1, mode='convt', f=2, ldy=48, **_e)        # (a channel slice: 32 of 48 stored)
+case('feat-fp8-no-relu', 2, 5, 60, 48, 64, _k9, out_scale=True, bias=True)
+case('feat-fp8-ragged-cout', 2, 5, 60, 48, 48, fast_key(FP8, 32, 't32-9'), **_e)                  # (48 of cout_pad = 64 columns, two 32-column tiles)
+case('feat-fp8-centre-tap', 3, 8, 8, 32, 64, fast_key(FP8, 8, 'c64'), dil=8, centre_tap=True, **_e)
+case('feat-fp8-dilation-one-below-centre-tap', 3, 8, 8, 32, 64, fast_key(FP8, 8, 'tl64'), dil=7, **_e)
+_k9 = fast_key(FP8X, 32, 't64-9')
+case('feat-fp8x-pool2', 2, 10, 60, 64, 64, _k9, pool_f=2, **_e)
+case('feat-fp8x-pair', 4, 5, 60, 64, 64, _k9, pair=True, **_e)
+case('feat-fp8x-convt-f2', 2, 11, 44, 64, 32, fast_key(FP8X, 16, 't64-1'), k=1, mode='convt', f=2, ldy=48, **_e)
+case('feat-fp8x-centre-tap', 3, 8, 8, 64, 64, fast_key(FP8X, 8, 't64-1'), dil=8, centre_tap=True, **_e)
+# what the C API accepts for e4m3 and no lowering uses
+_k9 = fast_key(FP8, 32, 't64-9')
+case('feat-fp8-dual', 2, 5, 60, 32, 64, _k9, c1=16, **_e)
+case('feat-fp8-dual-affine', 2, 5, 60, 32, 64, _k9, c1=16, affine=True, **_e)
+case('feat-fp8-padded-cin', 2, 5, 60, 16, 64, _k9, cin=4, **_e)
+# the two cases the GPU test drives into saturation on purpose (one plain, one scaled; no ReLU: both signs must stop at 448)
+E4M3_SATURATING = ('feat-fp8-no-relu-saturating', 'feat-fp8x-saturating')
+case('feat-fp8-no-relu-saturating', 2, 5, 60, 48, 64, _k9, out_scale=True, bias=True)
+case('feat-fp8x-saturating', 2, 5, 60, 64, 64, fast_key(FP8X, 32, 't64-9'), out_scale=True, bias=True)
 
 # ---- startup-only options: each set is the environment of ONE fresh child process that runs the set's cases
 STARTUP_SETS = []

@@ -6,7 +6,9 @@ igemm_dispatch of csrc/conv_igemm.hip --, nothing launched, no device touched; t
   * every kernel family sees every feature it accepts (ACCEPTS), and the pairs the chain forbids are refused or fall where REFUSED says;
   * lds_bytes <= 160 KB everywhere;
   * query and satcv_conv2d_igemm_pipelined agree on pipelined versus generic for the bf16 cases with a plain store;
-  * the key and workgroup count of every launch of bench.py's workload, from a hand-built descriptor, are the pinned ones.
+  * the key and workgroup count of every launch of bench.py's workload, from a hand-built descriptor, are the pinned ones;
+  * the e4m3 storage types: every reachable key has a value case, the shapes bf16 hands to the generic kernel are refused (REFUSALS), and the
+    conditions the bit-exact e4m3 runs rest on -- multiplier bound, sensitivity, saturated share -- hold on the float64 reference.
 """
 import ctypes as C
 import json
@@ -40,6 +42,18 @@ ACCEPTS = {
     'tr': {'bias', 'stats', 'dual', 'affine', 'out_relu', 'out_scale', 'pool2', 'padded_cin'},
     'convt_thin': {'bias', 'stats', 'affine', 'out_relu', 'out_scale', 'd2s2'},
     'convt_thin_dgrad': {'stats', 'bst1', 's2d2'},
+}
+
+
+# the e4m3 storage types: what the table SHOWS each family (every feature the folded fp8 plan emits, and the three the C API accepts beside
+# them: a dual source on a tiled form, with the loader affine, and a padded Cin).  Statistics, fused sums, accumulate, stride and
+# space-to-depth are accepted by the tiled forms too, but no lowering produces them in e4m3 and no case runs them.
+_E = {'bias', 'out_relu', 'out_scale'}
+SHOWN_E4M3 = {
+    (W.FP8, 'fast'): _E | {'pool2', 'pair', 'd2s2', 'dilated', 'centre_tap', 'dual', 'affine', 'padded_cin'},      # (feat-fp8-ragged-cout: 48 of cout_pad = 64
+                                                                                                                     #  columns, whole 16-byte vectors -- not the feature 'ragged_cout', cout % 16 != 0)
+    (W.FP8X, 'fast'): _E | {'pool2', 'pair', 'd2s2', 'dilated', 'centre_tap'},
+    (W.FP8, 'ws'): _E | {'pool2', 'pair', 'dual', 'affine'},
 }
 
 
@@ -91,12 +105,16 @@ def test_reached_keys_are_all_keys_minus_unreachable(reached):
 
 def test_every_family_sees_every_feature_it_accepts(reached):
     fam = {name: f for name, _, f, _ in reached}
-    seen = {}
+    seen, seen8 = {}, {}
     for c in all_cases():
-        seen.setdefault(fam[c['name']], set()).update(W.features(c))
+        if c['dtype'] in (W.FP8, W.FP8X):
+            seen8.setdefault((c['dtype'], fam[c['name']]), set()).update(W.features(c))
+        else:
+            seen.setdefault(fam[c['name']], set()).update(W.features(c))
     for f, acc in ACCEPTS.items():
         assert acc <= seen[f], f'{f}: no case with {sorted(acc - seen[f])}'
         assert seen[f] <= acc, f'{f} served {sorted(seen[f] - acc)}, which ACCEPTS says it refuses'
+    assert seen8 == SHOWN_E4M3, {k: sorted(v ^ SHOWN_E4M3.get(k, set())) for k, v in seen8.items()}
 
 
 def test_lds_fits(reached):
@@ -207,3 +225,50 @@ def test_cu_count_moves_the_persistent_kernels_only():
     c = W.BY_NAME['tr-32-32']
     with W.options(c['opts']):
         assert [W.plan_info(W.make_desc(c), n)['workgroups'] for n in (2, 256)] == [2, 4]
+
+
+# ------------------------------------------------------------------------------------------------ the e4m3 storage types
+def e4m3_cases():
+    return [c for c in all_cases() if c['dtype'] in (W.FP8, W.FP8X)]
+
+
+def test_every_reachable_e4m3_key_has_a_value_case():
+    """no e4m3 entry is keys-only: every case runs for values on the GPU, and together they reach every e4m3 key of ALL_KEYS but the
+    unreachable ones"""
+    cases = e4m3_cases()
+    assert len(cases) > 100 and all(c['gpu'] for c in cases), [c['name'] for c in cases if not c['gpu']]
+    want = {k for k in W.ALL_KEYS - set(W.UNREACHABLE) if k[0] in (W.FP8, W.FP8X)}
+    assert {c['key'] for c in cases} == want
+    # every tiled form sees the whole-tile, the ragged and the several-images-per-tile shape over its tile widths (a shape that is refused, or
+    # falls to another form, is in the table under the form's name all the same)
+    names = {c['name'] for c in cases} | {c['name'] for c in W.REFUSALS}
+    for dt, forms in ((W.FP8, [f for f in W.FAST if f not in W.BF16_ONLY]), (W.FP8X, W.FP8X_FORMS)):
+        for f in forms:
+            kinds = {n.rsplit('-', 1)[1] for n in names if n.startswith(f'{f}-{dt}-tw')}
+            assert kinds == set('wrm'), (f, dt, kinds)
+
+
+def test_e4m3_shapes_beyond_the_pipelined_kernels_are_refused():
+    """the e4m3 types have no generic kernel (and the scaled form no tap loop): where bf16 falls to one, the dispatcher answers
+    SATCV_ERR_UNSUPPORTED with its message, and nothing is launched.  The same shape in bf16 is served."""
+    from satellite_computervision_amd import _lib
+    assert len(W.REFUSALS) == 8
+    for c in W.REFUSALS:
+        info = _lib.ConvPlanInfo()
+        rc = _lib.lib.satcv_conv2d_igemm_plan_info(C.byref(W.make_desc(c)), W.NCU, C.byref(info))
+        assert rc == -3 and W.REFUSAL_MESSAGE in _lib.lib.satcv_last_error().decode(), (c['name'], rc, _lib.lib.satcv_last_error())        # SATCV_ERR_UNSUPPORTED
+        b = dict(c, dtype=W.BF16, out_scale=False)
+        assert W.plan_info(W.make_desc(b))['family'] in ('generic', 'fast'), c['name']
+
+
+def test_e4m3_reference_conditions():
+    """what the bit-exact e4m3 runs rest on, asserted on the float64 reference alone (test_conv_plan_gpu.lattice_case; no device): the
+    multiplier's bound (nothing saturates, every fp32 operation exact), the sensitivity condition -- one zeroed input channel at one tap changes at
+    least 5 % of the stored reference -- and, for the two saturating cases, a saturated share between 2 % and 30 %."""
+    import test_conv_plan_gpu as T
+    for c in e4m3_cases():
+        d, ref, L, notes = T.lattice_case(c, T.case_seed(c) + 1, 'fast')
+        raw = ref['raw'] * L['unit']
+        assert abs(raw).max() <= L['ymax'] and (raw == raw.round()).all(), c['name']
+        assert (abs(ref['raw']).max() > T.E4M3_MAX) == (c['name'] in W.E4M3_SATURATING), c['name']
+        assert (abs(ref['y']) <= T.E4M3_MAX).all() and any(n.startswith('sens') for n in notes)

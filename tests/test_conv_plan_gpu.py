@@ -20,6 +20,20 @@ Per case
     input runs first); stored input channels beyond the real cin carry non-zero lattice values, as do their scale / shift entries (padded-cin
     cases); stored channels beyond cout must come back untouched, and y has a sentinel image row before and after it;
   * two runs are torch.equal.
+
+The e4m3 storage types (SATCV_FP8, and the block-scaled SATCV_FP8X with its 16-byte items and K = 64 fragments) run the same checks; x, y and pool_y
+are float8_e4m3fn and the dtype code comes from the case.  What differs, and why:
+  * rounding once to e4m3 is clamp to +-448, then float64 -> float32 -> float8_e4m3fn: the hardware conversion saturates, torch's gives NaN above 464;
+  * lattice: x and w are integers of [-4, 4], exact in e4m3; every case has the output multiplier s m_c, m_c from {1, 2, -1, 0.5} and s the largest
+    power of two with 2 s K amax aw + 4 <= 448 (lattice()): no element saturates and every fp32 operation of the epilogue is exact, so the stored
+    bytes must decode to the float64 reference rounded once -- tolerance zero, derived.  Two cases (conv_cases.E4M3_SATURATING) raise s until 2 - 30 %
+    of the reference exceeds 448: the kernel must store +-448 there;
+  * three mantissa bits hide small errors, so each lattice case first shows, on the reference alone, that zeroing ONE input channel at ONE tap changes
+    at least 5 % of the stored elements (lattice_case(); tests/test_conv_plan_cpu.py asserts the same without a device);
+  * Gaussian data: products of e4m3 values are exact in fp32 and the fp32 sum, multiplier and bias err far below half an e4m3 step, so every element
+    must lie within ONE e4m3 step of the once-rounded reference (the neighbour near a tie) and none is NaN; the share of elements that are not
+    bit-identical goes into the record line, as a record;
+  * the sentinel rows hold a fixed byte and are compared as uint8 (777 is no e4m3 value).
 """
 import ctypes as C
 import json
@@ -58,13 +72,42 @@ def case_options(request):
         yield request.param
 
 
+E4M3 = torch.float8_e4m3fn
+E4M3_MAX = 448.0
+SENTINEL_BYTE = 0x5A        # 777 is no e4m3 value: the sentinel rows of an e4m3 buffer hold this byte and are compared as uint8
+
+
 def tdtype(c):
-    return torch.bfloat16 if c['dtype'] == W.BF16 else torch.float32
+    """the torch type of x, y and pool_y (both e4m3 storage types are float8_e4m3fn: the dtype CODE comes from the case, dcode())"""
+    return {W.BF16: torch.bfloat16, W.F32: torch.float32, W.FP8: E4M3, W.FP8X: E4M3}[c['dtype']]
+
+
+def dcode(ops, c):
+    return {W.F32: ops.F32, W.BF16: ops.BF16, W.FP8: ops.FP8, W.FP8X: ops.FP8X}[c['dtype']]
+
+
+def is8(c):
+    return c['dtype'] in (W.FP8, W.FP8X)
 
 
 def rne(a, td):
-    """float64 array rounded once to the storage type, round to nearest even"""
-    return torch.tensor(a, dtype=torch.float64).to(torch.float32).to(td).to(torch.float64).numpy()
+    """float64 array rounded once to the storage type, round to nearest even.  e4m3: the hardware conversion SATURATES at +-448 (common.hpp),
+    torch's gives NaN above 464 -- clamped first"""
+    t = torch.tensor(a, dtype=torch.float64)
+    if td == E4M3:
+        t = t.clamp(-E4M3_MAX, E4M3_MAX)
+    return t.to(torch.float32).to(td).to(torch.float32).to(torch.float64).numpy()
+
+
+def host64(t):
+    """device tensor -> float64 array (e4m3 goes through float32: exact)"""
+    return t.float().double().cpu().numpy()
+
+
+def spacing8(v):
+    """distance between neighbouring e4m3 values at |v|: 2^(floor(log2 |v|) - 3), the subnormal step 2^-9 at least"""
+    e = np.floor(np.log2(np.maximum(np.abs(v), 2.0 ** -20)))
+    return np.maximum(2.0 ** (e - 3), 2.0 ** -9)
 
 
 def geometry(c):
@@ -84,6 +127,21 @@ def lattice(c):
     amax: largest |activation| in units; the accumulator bound K amax aw must stay below 2^24 (asserted); ymax bounds |y| in units (multiplier
     at most 2, bias at most 4, base at most 4).  The largest amplitudes for which the statistics' sum is exact too are taken."""
     _, _, _, kk, npix = geometry(c)
+    if is8(c):
+        # e4m3: x and w are integers of [-4, 4] (exact in e4m3, and so is every staged loader value, at most 11 in steps of 1/2).  The
+        # multiplier is s m_c with m_c from {1, 2, -1, 0.5} and s the largest power of two with 2 s K amax aw + 4 <= 448: no element
+        # saturates, and every fp32 operation of the epilogue is exact (all values are integers below 2^24 in units of s / 4, or s / 8
+        # with the affine's halves)
+        assert c['out_scale'] and not (c['stats'] or c['accumulate'] or c['bst'])
+        ax = aw = 4
+        amax = (2 * ax + 3) if c['affine'] else ax
+        bound = kk * amax * aw
+        s = 2.0 ** np.floor(np.log2((E4M3_MAX - 4) / (2 * bound)))
+        assert 2 * s * bound + 4 <= E4M3_MAX < 4 * s * bound + 4, (c['name'], s)
+        unit = (2 if c['affine'] else 1) * 2 / s
+        acc, ymax = bound * (2 if c['affine'] else 1), (2 * s * bound + 4) * unit
+        assert acc < 2 ** 24 and ymax < 2 ** 24, (c['name'], acc, ymax)
+        return dict(ax=ax, aw=aw, unit=unit, ymax=ymax, s=s, sum_exact=False, sq_exact=False, bst_exact=False)
     unit = (2 if c['affine'] else 1) * (2 if c['out_scale'] else 1)
     for ax, aw in ((4, 4), (2, 2), (2, 1), (1, 1)):
         amax = (2 * ax + 3) if c['affine'] else ax
@@ -113,6 +171,8 @@ def make_data(c, rng, lat):
         d['v'] = ri(-4, 4, ys + (co,))
         d['bsc'], d['bsh'] = rng.choice([1.0, 2.0, -1.0, 0.5], co), ri(-3, 3, co)
         d['bmu'], d['brs'] = ri(-4, 4, co), rng.choice([0.5, 1.0, 2.0], co)
+        if is8(c):
+            d['osc'] = d['osc'] * L['s']
     else:
         r = lambda s, k=1.0: torch.tensor(rng.standard_normal(s) * k, dtype=torch.float32).to(td).to(torch.float64).numpy()
         f32 = lambda a: a.astype(np.float32).astype(np.float64)
@@ -182,6 +242,52 @@ def reference(c, d, family):
     return out
 
 
+def probe_tap(c):
+    """the tap whose weights the sensitivity condition zeroes: the last one, in raster order, that reads real data at a quarter of the output
+    pixels or more.  An undilated kernel's last tap always does; a strongly dilated kernel's reads mostly padding (dilation 6 on a 16 x 8 map: 15 %
+    of the pixels; the centre-tap cases: none), and the centre tap always qualifies"""
+    k, dil, h, w = c['k'], c['dil'], c['h'], c['w']
+    for t in range(k * k - 1, -1, -1):
+        i, j = divmod(t, k)
+        if 4 * max(h - abs(i - k // 2) * dil, 0) * max(w - abs(j - k // 2) * dil, 0) >= h * w:
+            return i, j
+
+
+def lattice_case(c, seed, fam):
+    """(data, reference, lattice(), notes) of the bit-exact run of a case.  For the e4m3 types, asserted here on the reference alone
+      * sensitivity: three mantissa bits hide small errors, so zeroing the weights of the last real input channel at probe_tap() (a transposed
+        conv: at every tap, each of which writes its own quarter of the output) must change at least 5 % of the stored reference elements;
+      * the cases of conv_cases.E4M3_SATURATING: the multiplier is raised by the smallest power of two for which at least 2 % of the
+        reference elements exceed 448 before the clamp; the share must lie between 2 % and 30 %."""
+    L = lattice(c)
+    d = make_data(c, np.random.default_rng(seed), True)
+    notes = []
+    if is8(c) and c['name'] in W.E4M3_SATURATING:
+        osc, p = d['osc'], 1
+        while True:
+            p *= 2
+            assert p <= 64, c['name']
+            d['osc'] = osc * p
+            share = float((np.abs(reference(c, d, fam)['raw']) > E4M3_MAX).mean())
+            if share >= 0.02:
+                break
+        assert 0.02 <= share <= 0.30, (c['name'], p, share)
+        L['ymax'] *= p
+        notes.append(f'saturated {100 * share:.1f}%')
+    ref = reference(c, d, fam)
+    if is8(c):
+        kern = d['kern'].copy()
+        if c['mode'] == 'convt':
+            kern[:, :, :, -1] = 0
+        else:
+            i, j = probe_tap(c)
+            kern[i, j, c['cin'] - 1, :] = 0
+        share = float((reference(c, dict(d, kern=kern), fam)['y'] != ref['y']).mean())
+        assert share >= 0.05, f"{c['name']}: zeroing one input channel at one tap changes {100 * share:.1f} % of the stored reference"
+        notes.append(f'sens {100 * share:.1f}%')
+    return d, ref, L, notes
+
+
 def counters():
     from satellite_computervision_amd._lib import lib, check
     v, o = C.c_int32(), {}
@@ -195,7 +301,7 @@ def run(ops, c, d):
     """one satcv_conv2d_igemm of the case; returns dict(y, stats, pool, plan) of device tensors and the plan"""
     from satellite_computervision_amd._lib import lib, check
     td, dev = tdtype(c), torch.device('cuda')
-    code = ops.DTYPE_CODE[td]
+    code = dcode(ops, c)            # (ops.DTYPE_CODE cannot tell the two e4m3 types apart)
     up = lambda a: torch.tensor(a, dtype=torch.float32).to(td).to(dev).contiguous()
     f32 = lambda a: torch.tensor(a, dtype=torch.float32, device=dev).contiguous()
     _, _, ys, _, _ = geometry(c)
@@ -212,8 +318,14 @@ def run(ops, c, d):
     # y with one sentinel image row before and after; pair store: (pair_n, h, w, ldy)
     ny = ys[0] // 2 if c['pair'] else ys[0]
     rows = ny * ys[1]
-    ybuf = torch.full((rows + 2, ys[2], ldy), float('nan'), dtype=td, device=dev)
-    ybuf[0], ybuf[-1] = SENTINEL, SENTINEL
+    nans = lambda shape: torch.full(shape, float('nan'), dtype=torch.float32, device=dev).to(td)
+    ybuf = nans((rows + 2, ys[2], ldy))
+    if td == E4M3:
+        ybuf.view(torch.uint8)[0], ybuf.view(torch.uint8)[-1] = SENTINEL_BYTE, SENTINEL_BYTE
+        sentinels_intact = lambda: bool((ybuf.view(torch.uint8)[0] == SENTINEL_BYTE).all()) and bool((ybuf.view(torch.uint8)[-1] == SENTINEL_BYTE).all())
+    else:
+        ybuf[0], ybuf[-1] = SENTINEL, SENTINEL
+        sentinels_intact = lambda: bool((ybuf[0] == SENTINEL).all()) and bool((ybuf[-1] == SENTINEL).all())
     if c['accumulate']:
         ybuf[1:-1, :, :co] = up(d['base']).reshape(rows, ys[2], co)
     y = ybuf[1:-1]
@@ -229,7 +341,7 @@ def run(ops, c, d):
         p['stats'] = stats.data_ptr()
     pool = None
     if c['pool_f']:
-        pool = torch.full((ys[0], ys[1] // c['pool_f'], ys[2] // c['pool_f'], co), float('nan'), dtype=td, device=dev)
+        pool = nans((ys[0], ys[1] // c['pool_f'], ys[2] // c['pool_f'], co))
         p['pool_y'] = pool.data_ptr()
     if c['bst']:
         half = co // c['bst']
@@ -267,13 +379,13 @@ def run(ops, c, d):
     fam = got['family']
     want = dict(igemm_thin_launches=int(fam in ('ws', 'tr')), thin_roles_launches=int(fam == 'tr'), m16p_launches=int(fam == 'm16p'))
     assert {k: after[k] - before[k] for k in want} == want, (c['name'], fam, before, after)
-    assert bool((ybuf[0] == SENTINEL).all()) and bool((ybuf[-1] == SENTINEL).all()), f"{c['name']}: a sentinel row around y was overwritten"
+    assert sentinels_intact(), f"{c['name']}: a sentinel row around y was overwritten"
     return dict(y=y.reshape((ny,) + ys[1:] + (ldy,)), stats=stats, pool=pool, plan=got, keep=keep)
 
 
 def stored(c, r):
     """float64 (n, ho, wo, cout) of what the launch stored, the pair store undone; asserts that channels beyond cout were left alone"""
-    y = r['y'].double().cpu().numpy()
+    y = host64(r['y'])
     co, ldy = c['cout'], c['ldy']
     if c['pair']:
         assert np.isnan(y[..., co:ldy // 2]).all() and np.isnan(y[..., ldy // 2 + co:]).all(), f"{c['name']}: the pair store wrote outside its channels"
@@ -282,10 +394,15 @@ def stored(c, r):
     return y[..., :co]
 
 
+def case_seed(c):
+    """seed of a case's Gaussian data; the lattice data takes the next one"""
+    return sum(ord(ch) * (i + 1) for i, ch in enumerate(c['name'])) % 2**31
+
+
 def check_case(ops, c):
     """every check of one case; returns the record line of profiles/conv_plan_parity.txt"""
     td = tdtype(c)
-    seed = sum(ord(ch) * (i + 1) for i, ch in enumerate(c['name'])) % 2**31
+    seed = case_seed(c)
     npix = geometry(c)[4]
     # ---- Gaussian parity
     d = make_data(c, np.random.default_rng(seed), False)
@@ -294,7 +411,15 @@ def check_case(ops, c):
     ref = reference(c, d, fam)
     got = stored(c, r)
     assert not np.isnan(got).any(), f"{c['name']}: {int(np.isnan(got).sum())} output elements were never written"
-    err, tol = close(got, ref['y'], td, f"conv {c['name']}", k=2.0 if (c['affine'] or c['stride'] > 1) else 1.0)
+    if is8(c):
+        # e4m3 inputs: every product is exact in fp32, and the fp32 sum, multiplier and bias add errors far below half an e4m3 step -- the stored
+        # value is the once-rounded reference or, near a tie, its neighbour.  The share of not bit-identical elements is a record, not a threshold
+        off = np.abs(got - ref['y']) > spacing8(ref['y'])
+        assert not off.any(), f"{c['name']}: {int(off.sum())} of {got.size} elements are more than one e4m3 step from the once-rounded reference, max |diff| {np.abs(got - ref['y']).max()}"
+        gauss = f"gauss one step, {100 * float((got != ref['y']).mean()):.2f}% not identical"
+    else:
+        err, tol = close(got, ref['y'], td, f"conv {c['name']}", k=2.0 if (c['affine'] or c['stride'] > 1) else 1.0)
+        gauss = f'gauss {err:.2e} < {tol:.1e}'
     if c['stats']:
         s = r['stats'].sum(0).double().cpu().numpy()[:, :c['cout']]
         if c['bst']:            # sums of the STORED gradient (the rule of test_16x16x32_tile_fused_bn_backward_sums)
@@ -307,16 +432,16 @@ def check_case(ops, c):
             np.testing.assert_allclose(s[0], got.sum((0, 1, 2)), rtol=2e-4, atol=2e-3 * np.sqrt(npix), err_msg=f"sum {c['name']}")
             np.testing.assert_allclose(s[1], (got ** 2).sum((0, 1, 2)), rtol=2e-4, err_msg=f"sum of squares {c['name']}")
     if c['pool_f']:
-        assert np.array_equal(r['pool'].double().cpu().numpy(), K.maxpool(got, c['pool_f'])), f"{c['name']}: pooled output is not the max of the stored one"
-    # ---- integer lattice, bit-exact
-    L = lattice(c)
-    d = make_data(c, np.random.default_rng(seed + 1), True)
-    ref = reference(c, d, fam)
+        assert np.array_equal(host64(r['pool']), K.maxpool(got, c['pool_f'])), f"{c['name']}: pooled output is not the max of the stored one"
+    # ---- integer lattice, bit-exact (e4m3: with the sensitivity and saturation conditions of lattice_case)
+    d, ref, L, notes = lattice_case(c, seed + 1, fam)
     assert np.abs(ref['raw']).max() * L['unit'] <= L['ymax'] and np.array_equal(ref['raw'] * L['unit'], np.rint(ref['raw'] * L['unit']))      # on the lattice
     r = run(ops, c, d)
     got = stored(c, r)
     nbad = int((got != ref['y']).sum())
-    notes = []
+    if is8(c):
+        over = np.abs(ref['raw']) > E4M3_MAX
+        assert over.any() == (c['name'] in W.E4M3_SATURATING), c['name']
     if c['stats']:
         s = r['stats'].sum(0).double().cpu().numpy()[:, :c['cout']]
         exact1 = L['bst_exact'] if c['bst'] else L['sum_exact']
@@ -332,10 +457,12 @@ def check_case(ops, c):
                 np.testing.assert_allclose(s[1], ref['s2'], rtol=2e-4, atol=2e-4 * np.abs(ref['s2']).max() + 1e-30)
         notes.append(f"sums {'exact' if exact1 else 'tol'}/{'exact' if exact2 else 'tol'}")
     if c['pool_f'] and nbad == 0:
-        assert np.array_equal(r['pool'].double().cpu().numpy(), ref['pool']), f"{c['name']}: pooled output differs"
-    line = (f"CONV-PARITY {c['name']:46s} {'/'.join(str(v) for v in c['key']):44s} wg {r['plan']['workgroups']:5d} gauss {err:.2e} < {tol:.1e}  "
+        assert np.array_equal(host64(r['pool']), ref['pool']), f"{c['name']}: pooled output differs"
+    line = (f"CONV-PARITY {c['name']:46s} {'/'.join(str(v) for v in c['key']):44s} wg {r['plan']['workgroups']:5d} {gauss}  "
             f"lattice {'exact' if nbad == 0 else 'NOT EXACT (%d of %d)' % (nbad, got.size)}{' ' + ' '.join(notes) if notes else ''}")
     print(line)
+    if is8(c):
+        assert np.array_equal(got[over], np.sign(ref['raw'][over]) * E4M3_MAX), f"{c['name']}: elements beyond 448 were not stored as +-448"
     assert nbad == 0, f"{c['name']}: {nbad} of {got.size} elements differ from the exact reference, max |diff| {np.nanmax(np.abs(got - ref['y']))}"
     r2 = run(ops, c, d)
     assert torch.equal(torch.nan_to_num(r['y'].float(), nan=-1.0), torch.nan_to_num(r2['y'].float(), nan=-1.0)), f"{c['name']}: two lattice runs differ"
