@@ -70,16 +70,9 @@ class ParamSpec:
 # no effect on any output.  Here the gradient is the exact 0 (the bias stays at its value) unless the summed-noise form is asked for;
 # the atomics it needs are also the one remaining source of run-to-run differences in a training step.
 BIAS_NOISE = switches.read('bn_bias_noise')
-# default: a layer's weight gradient (second stream) is enqueued BEFORE its data gradient -- it starts beside its own layer's data gradient and
-# the side stream finishes earlier; WGRAD_LATE enqueues it behind the data gradient
-WGRAD_LATE = switches.read('wgrad_late')
 CTBF = switches.read('ctbf')
 CTBF_COUTS = switches.read('ctbf_couts')
 FUSE_RESIDUAL = switches.read('fuse_residual')
-# EARLY_OPT (tests run both): the parameters whose gradients are final early in the backward pass are 99.5 % of them once the fourth encoder
-# block is done; the weight-gradient stream is busy to the last microsecond of the backward pass, so work moved onto it only lengthens it
-EARLY_OPT = switches.read('early_opt')
-EARLY_OPT_FRAC = 0.05
 FUSE_DGRAD_ALL = switches.read('fuse_dgrad_bn_bwd') == 2      # (Model.fuse_dgrad_bn_bwd is the same row != 0)
 
 
@@ -183,7 +176,7 @@ class Runtime:
                     fwd=torch.zeros(ef, dtype=self.tdtype, device=self.dev),
                     dgrad=torch.zeros(ed, dtype=self.tdtype, device=self.dev),
                     k=(ks[0], ks[1]), cin=cin, cout=cout, cin_pad=cin_pad, transposed=tr)
-        self._ptabs = {}
+        self._ptab = None
         self.repack()
         self.plans = {}
 
@@ -224,14 +217,11 @@ class Runtime:
             else:
                 self.zero_gamma.discard(bn)
 
-    def _pack_table(self, lo=0, hi=None):
-        """device table of the pack jobs (forward + data-gradient image) of every layer whose kernel starts in [lo, hi) of the flat parameter
-        buffer, for satcv_pack_weights_batched; None when no layer does"""
+    def _pack_table(self):
+        """device table of the pack jobs (forward + data-gradient image) of every layer, for satcv_pack_weights_batched"""
         from ._lib import PackJob
         jobs = []
         for lname, pk in self.packed.items():
-            if not (lo <= self.offsets[lname + '/kernel'] < (self.n_train if hi is None else hi)):
-                continue
             taps, cin, cout, cp = pk['k'][0] * pk['k'][1], pk['cin'], pk['cout'], pk['cin_pad']
             src = self.pptr(lname + '/kernel')
             if not pk['transposed']:
@@ -240,21 +230,16 @@ class Runtime:
             else:
                 jobs.append(PackJob(src, pk['fwd'].data_ptr(), 2, taps, cin, cout, cp, rup(taps * cout, 32)))
                 jobs.append(PackJob(src, pk['dgrad'].data_ptr(), 3, taps, cin, cout, rup(taps * cout, 16), rup(cin, 32)))
-        return ops.job_table(jobs, lib.satcv_pack_job_items, self.dev) if jobs else None
+        return ops.job_table(jobs, lib.satcv_pack_job_items, self.dev)
 
-    def repack(self, lo=0, hi=None, stream=None):
-        """fp32 Keras-layout kernels -> MFMA operand images (after every weight update), one launch for all layers (or for the layers whose
-        kernels start in [lo, hi) of the flat buffer: the early part of a split optimizer step, engine.Plan)."""
+    def repack(self):
+        """fp32 Keras-layout kernels -> MFMA operand images (after every weight update), one launch for all layers"""
         if not self.packed:
             return
-        key = (lo, hi)
-        if key not in self._ptabs:
-            self._ptabs[key] = self._pack_table(lo, hi)
-        t = self._ptabs[key]
-        if t is None:
-            return
-        check(lib.satcv_pack_weights_batched(t['jobs'].data_ptr(), t['prefix'].data_ptr(), t['n'], t['total'], self.dtype,
-                                             ops.stream_ptr() if stream is None else stream))
+        if self._ptab is None:
+            self._ptab = self._pack_table()
+        t = self._ptab
+        check(lib.satcv_pack_weights_batched(t['jobs'].data_ptr(), t['prefix'].data_ptr(), t['n'], t['total'], self.dtype, ops.stream_ptr()))
 
     def ensure_adam(self):
         if self.adam_m is None:
@@ -310,15 +295,13 @@ class Plan:
         self.frozen = set(frozen)
         self.raw_bn = set(raw_bn)             # BatchNorms (zero gamma) whose backward sums no activation-based producer may form
         self.tile_policy = 2 if (training and _M16_DEFAULT == 1) else 0      # satcv_conv_desc.tile_policy of this plan's convolution launches
-        self.eo_lo, self.early_opt, self.eo_done = None, None, False          # split optimizer step (see _SlabSums.layer_done: `early`)
         self.fwd, self.bwd = [], []
         self.keep = []                        # ctypes descriptors / tensors kept alive
         self.dropouts = []                    # dropout masks (regenerated every training step)
         self.x_inputs = []                    # fp32 staging tensor of every model input
         self.x_by_tid = {}
         self.x_src = {}                       # tensor id -> device pointer of a caller's batch read in place (Model._stage_x), else the staging tensor
-        _sp = switches.read('side_priority')
-        self.side = (torch.cuda.Stream(priority=_sp) if _sp is not None else torch.cuda.Stream()) if (training and rt.model.wgrad_side_stream) else None
+        self.side = torch.cuda.Stream() if (training and rt.model.wgrad_side_stream) else None
         self.step_count = 0
         self.outputs = {}
         self.sync_bn = bool(training and getattr(rt.model, 'sync_bn', False) and parallel.active())
@@ -840,147 +823,6 @@ class _ForwardLowering:
         self.outputs[node.outputs[0].id] = hctx['classes']
 
 
-class _SlabSums:
-    """Where the slab sums of the weight-gradient and fused launches run, and the early optimizer step: the three opt-in schedulers
-    (switches.py: defer_reduce, reduce_stream, early_opt; DESIGN.md section 6 holds their measurements).  With all three off every launch
-    sums its slabs itself from the shared workspace and this object emits nothing.
-      defer: deferred, batched slab sums (satcv_reduce_slabs_batched; otherwise one sum launch behind every weight-gradient launch): a
-        deferring launch keeps a workspace of its own; the sums run in groups, one launch per ~16 MiB of finished gradients (the bucket
-        size of the gradient exchange, whose checkpoints move to the group boundaries)
-      red3: the slab sum of a side-stream weight gradient on a THIRD stream, behind an event of its launch; with a workspace of its own
-        per layer the next weight gradient does not have to wait for the sum of the previous one"""
-
-    def __init__(self, plan):
-        self.plan = plan
-        self.defer = switches.read('defer_reduce') != 0
-        self.red3 = (not self.defer) and plan.side is not None and switches.read('reduce_stream')
-        plan.rstream = torch.cuda.Stream() if self.red3 else None
-        plan._last_red_ev = None
-        self.pending = []                   # (descriptor, 'w' | 'f', gradient bytes) of launches whose sum has not been scheduled yet
-        self.groups = []                    # {'items': [(desc, kind)], 'tab': device job table, filled once the workspaces are assigned}
-
-    def own_workspace(self, d, kind, nb, grad_bytes, eligible):
-        """a weight-gradient ('w') or fused ('f') descriptor was made: True when it keeps a workspace of `nb` bytes of its own and its
-        slab sum is scheduled here, False when it sums its slabs itself from the workspace all such launches share"""
-        if not eligible or not (self.defer or (self.red3 and kind == 'w')):
-            return False
-        d.defer_reduce = 1
-        d._own_ws = nb
-        if self.defer:
-            self.pending.append((d, kind, grad_bytes))
-        else:
-            self.groups.append({'items': [(d, kind)], 'tab': None})       # (a one-job table, built with the others once the workspaces are assigned)
-        return True
-
-    def behind_wgrad(self, run, d):
-        """the side-stream step of weight-gradient launch d; red3: followed by its slab sum on the third stream"""
-        if not (self.red3 and d.defer_reduce):
-            return run
-        p, grp = self.plan, self.groups[-1]
-        evw, evr = torch.cuda.Event(), torch.cuda.Event()
-
-        def run3(st):
-            run(st)
-            t = grp['tab']
-            evw.record(p.side)
-            p.rstream.wait_event(evw)
-            check(lib.satcv_reduce_slabs_batched(t['jobs'].data_ptr(), t['prefix'].data_ptr(), t['n'], t['total'], C.c_void_p(p.rstream.cuda_stream)))
-            evr.record(p.rstream)
-            p._last_red_ev = evr
-        return run3
-
-    def _flush(self, force=False):
-        """schedule the batched slab sum of the launches recorded so far (on the weight-gradient stream, behind an event of the main
-        stream: the fused thin-layer launches write their slabs there).  Returns False while a group is still being collected."""
-        p = self.plan
-        if not self.pending:
-            return True
-        if not force and sum(b for _, _, b in self.pending) < (16 << 20):
-            return False
-        grp = {'items': [(d, kind) for d, kind, _ in self.pending], 'tab': None}
-        self.pending.clear()
-        self.groups.append(grp)
-        ev = torch.cuda.Event() if p.side is not None else None
-
-        def flush(st, grp=grp, ev=ev):
-            t = grp['tab']
-            if p.side is not None:
-                ev.record(torch.cuda.current_stream())
-                p.side.wait_event(ev)
-                st = C.c_void_p(p.side.cuda_stream)
-            check(lib.satcv_reduce_slabs_batched(t['jobs'].data_ptr(), t['prefix'].data_ptr(), t['n'], t['total'], st))
-        flush.label = f"wgrad_reduce_batched {len(grp['items'])} layers"
-        p.bwd.append(flush)
-        return True
-
-    def layer_done(self, lo, more):
-        """a layer's gradients are complete; `more`: other layers are still pending.  False while the gradients above `lo` are not final
-        (their slabs are not summed yet)."""
-        if not self._flush(force=not more):
-            return False
-        p, rt = self.plan, self.plan.rt
-        # ---- round 6: the optimizer step of the parameters in [lo, n) beside the REST of the backward pass.  When what is still pending is a
-        # few per cent of the parameters (the three thin encoder blocks of get_unet_model hold 0.5 %), everything above `lo` is final: Adam
-        # and the operand repack of that range run on the weight-gradient stream -- idle from here on: the thin layers' weight gradients
-        # are part of the fused launches of the main stream -- while the main stream finishes the encoder's backward pass; the step's tail
-        # then only updates [0, lo).  Single replica only (a gradient exchange must see every gradient first): Model.train_step_device
-        # sets plan.early_opt per step.
-        if EARLY_OPT and p.side is not None and p.eo_lo is None and more and 0 < lo <= EARLY_OPT_FRAC * rt.n_train and lo % 4 == 0:
-            p.eo_lo = lo
-            evo = torch.cuda.Event()
-
-            def early(st, lo=lo, evo=evo):
-                eo = p.early_opt
-                if eo is None:
-                    return
-                evo.record(torch.cuda.current_stream())
-                p.side.wait_event(evo)
-                if p._last_red_ev is not None:
-                    p.side.wait_event(p._last_red_ev)
-                sp = C.c_void_p(p.side.cuda_stream)
-                n = rt.n_train - lo
-                check(lib.satcv_adam_step_part(_fp(rt.pflat, lo), _fp(rt.gflat, lo), _fp(rt.adam_m, lo), _fp(rt.adam_v, lo), n, eo['beta_1'], eo['beta_2'],
-                                               eo['epsilon'], rt.adam_state.data_ptr(), _fp(rt.lr_mul, lo) if rt.lr_mul is not None else None, 0, sp))
-                rt.repack(lo, None, stream=sp)
-                p.eo_done = True
-            early.label = f'early optimizer step [{lo}, {rt.n_train}) on the side stream'
-            p.bwd.append(early)
-        return True
-
-    def assign(self):
-        """all descriptors exist: the last group, one arena for the workspaces the launches keep for themselves, one job table per group"""
-        self._flush(force=True)
-        if not self.groups:
-            return
-        from ._lib import ReduceJob
-        p = self.plan
-        own = [d for g in self.groups for d, _ in g['items']]
-        arena = p._z(max(sum((d._own_ws + 255) // 256 * 256 for d in own) // 4, 1), dtype=torch.float32)
-        off = 0
-        for d in own:
-            d.workspace, d.workspace_bytes = arena.data_ptr() + off, d._own_ws
-            off += (d._own_ws + 255) // 256 * 256
-        for g in self.groups:
-            jobs = []
-            for d, kind in g['items']:
-                jobs.append(ReduceJob())
-                check((lib.satcv_conv2d_wgrad_reduce_job if kind == 'w' else lib.satcv_conv2d_bwd_fused_reduce_job)(C.byref(d), C.byref(jobs[-1])))
-            g['tab'] = ops.job_table(jobs, lib.satcv_reduce_job_items, p.rt.dev)
-
-    def behind_join(self, join):
-        """the step that lets the main stream wait for the weight-gradient stream; red3: and for the third stream"""
-        p = self.plan
-        if p.rstream is None:
-            return join
-        evj2 = torch.cuda.Event()
-
-        def join3(st):
-            join(st)
-            evj2.record(p.rstream)
-            torch.cuda.current_stream().wait_event(evj2)
-        return join3
-
-
 # one visit of a conv -> BatchNorm block by the backward lowering: its gradients (da activated, dp pooled, graws of raw consumers), the sums
 # buffer (pre: already filled by the producer of da) and whether its weight gradient accumulates
 _CbaVisit = namedtuple('_CbaVisit', 'node cx da dp da_ptr graws pre sums accum')
@@ -1011,7 +853,6 @@ class _BackwardLowering:
         self.seen_layers = set()            # layers applied more than once (shared weights): later visits accumulate their gradients
         self.ws_need, self.wdescs = 0, []   # the workspace the weight-gradient launches (side stream) share: bytes, descriptors
         self.fused_ws_need, self.fdescs = 0, []     # the fused thin-layer backward launches run on the MAIN stream: a workspace of their own
-        self.sums = _SlabSums(plan)
         # loss -> dlogits is written by Model.train step into this buffer
         h = plan.head
         self.dlogits = plan.dlogits = self._z(self.n * h['r'].h * h['r'].w, h['ncls'], dtype=torch.float32)
@@ -1050,21 +891,18 @@ class _BackwardLowering:
         if self.ws_need:
             ws = self._z(max(self.ws_need // 4, 1), dtype=torch.float32)
             for d in self.wdescs:
-                if not d.defer_reduce:
-                    d.workspace, d.workspace_bytes = ws.data_ptr(), self.ws_need
+                d.workspace, d.workspace_bytes = ws.data_ptr(), self.ws_need
         if self.fused_ws_need:
             wsf = self._z(max(self.fused_ws_need // 4, 1), dtype=torch.float32)
             for d in self.fdescs:
-                if not d.defer_reduce:
-                    d.workspace, d.workspace_bytes = wsf.data_ptr(), self.fused_ws_need
-        self.sums.assign()
+                d.workspace, d.workspace_bytes = wsf.data_ptr(), self.fused_ws_need
         if self.side is not None:
             side, evj = self.side, torch.cuda.Event()
 
             def join(st):          # the optimizer (main stream) must see every weight gradient
                 evj.record(side)
                 torch.cuda.current_stream().wait_event(evj)
-            self.bwd.append(self.sums.behind_join(join))
+            self.bwd.append(join)
 
     # -- helpers
     def bn_bwd_steps(self, da, ldda, dp, lddp, f, yraw, ldy, aff, aoff, sums, sums_off, sums_ld, c, hh, ww, dy, lddy, dbias,
@@ -1242,10 +1080,7 @@ class _BackwardLowering:
         nb = lib.satcv_conv2d_wgrad_workspace(C.byref(d))
         if nb < 0:
             raise RuntimeError(lib.satcv_last_error().decode())
-        nvalid = (f * f if f else 1) * cout
-        if not self.sums.own_workspace(d, 'w', nb, 4 * k * k * cin_real * nvalid,
-                                       not accum and lay.name not in self.shared_layers and nvalid % 4 == 0 and not (k == 3 and dil > 1)):
-            self.ws_need = max(self.ws_need, nb)
+        self.ws_need = max(self.ws_need, nb)
         self.wdescs.append(d)
         self.keep.append(d)
         if self.side is None:
@@ -1260,14 +1095,9 @@ class _BackwardLowering:
                 ev.record(torch.cuda.current_stream())
                 side.wait_event(ev)
                 check(lib.satcv_conv2d_wgrad(C.byref(d), sptr))
-            run = self.sums.behind_wgrad(run, d)
         run.label = f"wgrad k{k} d{dil} n{n} {hh}x{ww} {sa['c0']}+{sa['c1']}->{cout}{' convT f%d' % f if f else ''}"
         run.work = dict(kind='wgrad', taps=(f * f if f else k * k), px=n * hh * ww, cin=cin_real, cout=cout, esize=self.es)
         return run
-
-    def place_wgrad(self, wstep, at):
-        """default: a layer's weight gradient (second stream) sits at `at`, BEFORE its data gradient; WGRAD_LATE: behind it"""
-        self.bwd.insert(len(self.bwd) if WGRAD_LATE else at, wstep)
 
     def conv_dgrad(self, tin, dy, cout, pk, r, k, dil):
         """data gradient of a convolution into dL/d tin, added where that tensor already holds a gradient (several consumers)"""
@@ -1298,15 +1128,11 @@ class _BackwardLowering:
         if pending[lay.name] == 0:
             del pending[lay.name]
         lo = max((self.layer_hi[k] for k in pending), default=0)
-        if not self.sums.layer_done(lo, bool(pending)):
-            return
         plan, rt, m = self.plan, self.rt, self.m
 
         def ckpt(st, lo=lo):
             sync = getattr(m, '_sync_grads', None)
             if sync is not None and hasattr(sync, 'ready_above'):
-                if plan._last_red_ev is not None:            # (gradients are final behind their slab sums on the third stream)
-                    plan.side.wait_event(plan._last_red_ev)
                 sync.ready_above(rt.gflat, lo, plan.side)
         self.bwd.append(ckpt)
 
@@ -1436,8 +1262,7 @@ class _BackwardLowering:
         """the steps and records of an accepted fused backward launch: whose workspace, BatchNorm reduce / finalize, the launch itself"""
         n, cx, lay = self.n, v.cx, v.node.layer
         r, cout = cx['r'], cx['cout']
-        if not self.sums.own_workspace(fz, 'f', nb, 4 * 9 * fz.cin * cout, not v.accum and lay.name not in self.shared_layers):
-            self.fused_ws_need = max(self.fused_ws_need, nb)
+        self.fused_ws_need = max(self.fused_ws_need, nb)
         self.fdescs.append(fz)
         self.keep.append(fz)
         self.bwd += [fin] if (v.pre is not None or red is None) else [red, fin]
@@ -1537,13 +1362,13 @@ class _BackwardLowering:
         self.dbg['dy:' + lay.name] = dy
         self.dbg_ctx(lay, v.da, v.dp, cx)
         pk = rt.packed[lay.name]
+        # a layer's weight gradient (second stream) is enqueued BEFORE its data gradient -- it starts beside its own layer's data gradient and
+        # the side stream finishes earlier
         # (the weight gradient of a layer fed by a model input is the last launch of the backward pass: nothing runs beside it)
-        wstep = self.wgrad_step(r, dy.data_ptr(), cout, lay, pk['cin'], cout, hh, ww, cx['k'], cx['dil'], accum=v.accum,
-                                last=tin.node.op == 'input' and len(self.m.inputs) == 1 and switches.read('wgrad_last_full'))
-        at = len(self.bwd)
+        self.bwd.append(self.wgrad_step(r, dy.data_ptr(), cout, lay, pk['cin'], cout, hh, ww, cx['k'], cx['dil'], accum=v.accum,
+                                        last=tin.node.op == 'input' and len(self.m.inputs) == 1 and switches.read('wgrad_last_full')))
         if tin.node.op != 'input':
             self.set_grad(tin, lay, self.conv_dgrad(tin, dy, cout, pk, r, cx['k'], cx['dil']), r.c)
-        self.place_wgrad(wstep, at)
 
     def dropout(self, node, cx):
         n, dt = self.n, self.dt
@@ -1680,9 +1505,7 @@ class _BackwardLowering:
             cstep.work = dict(kind='convt_bwd_fused', px=n * r.h * r.w, cin=cinp, cout=cout, esize=self.es)
             self.bwd.append(cstep)
         else:
-            wstep = self.wgrad_step(r, du.data_ptr(), cout, lay, pk['cin'], cout, r.h, r.w, 1, 1, f=f)
-            at = len(self.bwd)
+            self.bwd.append(self.wgrad_step(r, du.data_ptr(), cout, lay, pk['cin'], cout, r.h, r.w, 1, 1, f=f))      # (before its data gradient, as in _separate)
             self.bwd.append(self.dgrad_step(tin, x0=du.data_ptr(), c0=cout, w=pk['dgrad'].data_ptr(), y=gin.data_ptr(), ldy=cinp, n=n, h=r.h,
                                             w_=r.w, cout=cinp, cout_pad=rup(cinp, 32), kh=1, kw=1, dil=1, mode_in=1, f=f, dtype=dt))
-            self.place_wgrad(wstep, at)
         self.set_grad(tin, lay, gin, cinp)

@@ -1120,24 +1120,11 @@ class Model:
         plan.step_count += 1                     # fresh dropout masks every step
         plan.run_forward(st)
         self._loss_launch(plan, st)
-        # (single replica: the bulk of the optimizer step may run inside the backward pass, engine._SlabSums `early` -- an opt-in experiment
-        # that exists for plain Adam only: a clipped step needs every gradient first, and the other rules have no `_part` form)
-        plan.eo_done = False
-        early_ok = sync_grads is None and opt.kind == 'adam' and opt.clipvalue is None and opt.global_clipnorm is None
-        plan.early_opt = dict(beta_1=opt.beta_1, beta_2=opt.beta_2, epsilon=opt.epsilon) if early_ok else None
         plan.run_backward(st)
         if sync_grads is not None:
             sync_grads(rt.gflat)
-        if plan.eo_done:
-            lo = plan.eo_lo                  # [lo, n) was updated and repacked on the side stream (joined at the end of the backward pass)
-            check(lib.satcv_adam_step_part(rt.pflat.data_ptr(), rt.gflat.data_ptr(), rt.adam_m.data_ptr(), rt.adam_v.data_ptr(), lo,
-                                           opt.beta_1, opt.beta_2, opt.epsilon, rt.adam_state.data_ptr(),
-                                           rt.lr_mul.data_ptr() if rt.lr_mul is not None else None, 1, st))
-            rt.repack(0, lo)
-        else:
-            apply_optimizer(opt, rt, st)         # all-reduce (above), then clip if asked, then the optimizer's step
-            rt.repack()
-        plan.early_opt = None                    # (other callers run this plan's backward pass -- HybridModel.train_on_batch -- with their own full step)
+        apply_optimizer(opt, rt, st)             # all-reduce (above), then clip if asked, then the optimizer's step
+        rt.repack()
         self._weights_version = getattr(self, '_weights_version', 0) + 1
         return plan
 

@@ -26,12 +26,6 @@ def integer(var, default):
     return int(os.environ.get(var, default))
 
 
-def int_or_none(var, default):
-    """int(), None when the variable is unset"""
-    v = os.environ.get(var, default)
-    return None if v is None else int(v)
-
-
 def int_list(var, default):
     """comma list of ints; empty items are skipped"""
     return tuple(int(v) for v in os.environ.get(var, default).split(',') if v)
@@ -47,19 +41,14 @@ def level012(var, default):
 
 
 Row = namedtuple('Row', 'key env default reader when cls meaning')
-PROD, NULL, OPT_IN, COMPAT, TEST, PROF = 'production', 'null experiment', 'opt-in feature', 'compatibility aid', 'test aid', 'profiling aid'
+PROD, OPT_IN, COMPAT, TEST, PROF = 'production', 'opt-in feature', 'compatibility aid', 'test aid', 'profiling aid'
 
 _ROWS = tuple(Row(*r) for r in (
     ('bn_bias_noise', 'SATCV_BN_BIAS_NOISE', '0', only, 'import', COMPAT, "1: the summed (rounding-noise) bias gradient under BatchNorm, as TensorFlow forms it; otherwise the exact zero"),
-    ('wgrad_late', 'SATCV_WGRAD_LATE', '0', only, 'import', NULL, "1: a layer's weight gradient is enqueued behind its data gradient, the round-3 order (7.99-8.00 against 7.89-7.90 ms, profiles/r06_ab_env_switches.txt)"),
     ('ctbf', 'SATCV_CTBF', '1', on, 'import', PROD, "the decoder's up-sampling path backward as one launch, csrc/convt_bwd_fused.hip (profiles/r05_ab_convt_bwd_fused.txt)"),
     ('ctbf_couts', 'SATCV_CTBF_COUTS', '32,64', int_list, 'import', PROD, "the Conv2DTranspose filter counts that launch serves"),
     ('fuse_residual', 'SATCV_FUSE_RESIDUAL', '1', only, 'import', PROD, "inference: residual joins written in place by the block's last convolution; off: separate satcv_add_act launches (profiles/r04_deeplab_ab_residual_in_place.txt)"),
-    ('early_opt', 'SATCV_EARLY_OPT', '0', only, 'import', NULL, "Adam + repack of the early-final parameters on the weight-gradient stream; kept for tests (profiles/r06_ab_early_opt_and_reduce_stream.txt)"),
     ('fuse_dgrad_bn_bwd', 'SATCV_FUSE_DGRAD_BN_BWD', '1', level012, 'import', PROD, "data-gradient epilogues form the BatchNorm-backward sums of the layer below: 0 none (read again per model), 2 every eligible one (at import; measured slower, profiles/r06_ab_env_switches.txt)"),
-    ('side_priority', 'SATCV_SIDE_PRIORITY', None, int_or_none, 'plan', NULL, "HIP stream priority of the weight-gradient stream, positive = below the main stream (profiles/r05_ab_side_priority.txt)"),
-    ('defer_reduce', 'SATCV_DEFER_REDUCE', '0', integer, 'plan', NULL, "non-zero: one batched launch sums the weight-gradient slabs of several layers; measured slower, kept for tests (profiles/r05_ab_defer_reduce.txt)"),
-    ('reduce_stream', 'SATCV_REDUCE_STREAM', '0', only, 'plan', NULL, "slab sums on a third stream; kept for tests (profiles/r06_ab_early_opt_and_reduce_stream.txt)"),
     ('wgrad_last_full', 'SATCV_WGRAD_LAST_FULL', '1', on, 'plan', PROD, "the last weight gradient of the step on the whole chip; 0 on the shared workgroup count too"),
     ('deeplab_splitk', 'SATCV_DEEPLAB_SPLITK', '1', only, 'model', PROD, "DeepLab inference plans of one or two tiles set library option splitk to 2 around their launches (profiles/r04_deeplab_ab_splitk_1x1.txt)"),
     ('prefetch', 'SATCV_PREFETCH', '1', on, 'call', PROD, "fit / evaluate: host batches uploaded one batch ahead on a copy stream; 0 on the compute stream"),

@@ -1,11 +1,10 @@
-"""Small models that between them reach every arm and every fused form of the plan lowering (engine._ForwardLowering, _BackwardLowering,
-_SlabSums): shared by tools/plan_manifest.py -- step lists, recorded library calls and result hashes of a plan, compared between two
+"""Small models that between them reach every arm and every fused form of the plan lowering (engine._ForwardLowering, _BackwardLowering):
+shared by tools/plan_manifest.py -- step lists, recorded library calls and result hashes of a plan, compared between two
 checkouts -- and by tests/test_model_gpu.py::test_plan_lowering_reaches_its_forms.
 
-A case is Case(name, make, dtype, training, env, early_opt, labels):
+A case is Case(name, make, dtype, training, env, labels):
   make(mt, lt)  -> (model, x, y): built from a fixed seed; x a batch (a list of batches for two-input models), y its target (None: inference)
   env            SATCV_* variables set while the model and its plan are built (model and plan rows of switches.py)
-  early_opt      engine.EARLY_OPT for the case (the tests' way of switching it: tests/test_model_gpu.py)
   labels         label fragments the backward step list of the case must contain
 IMPORT_VARIANTS are import rows: they need a process of their own and apply to the five-level bf16 case.
 
@@ -20,7 +19,7 @@ from collections import Counter, namedtuple
 
 import numpy as np
 
-Case = namedtuple('Case', 'name make dtype training env early_opt labels', defaults=(True, {}, False, ()))
+Case = namedtuple('Case', 'name make dtype training env labels', defaults=(True, {}, ()))
 
 
 def _xy(rng, n, h, w, ch=4, ncls=2):
@@ -126,21 +125,16 @@ CASES = [
     Case('hybrid', _hybrid, 'float32'),
     Case('unet5_infer', _unet_infer, 'float32', training=False),
     Case('deeplab_infer', _deeplab, 'float32', training=False),
-    # the plan / model rows of the switch table and engine.EARLY_OPT, on the five-level bf16 case
-    Case(FIVE + '[defer_reduce]', _unet(), 'bfloat16', env={'SATCV_DEFER_REDUCE': '1'}, labels=('wgrad_reduce_batched',)),
-    Case(FIVE + '[reduce_stream]', _unet(), 'bfloat16', env={'SATCV_REDUCE_STREAM': '1'}),
-    Case(FIVE + '[early_opt]', _unet(), 'bfloat16', early_opt=True, labels=('early optimizer step',)),
+    # the plan / model rows of the switch table, on the five-level bf16 case
     Case(FIVE + '[wgrad_stream=0]', _unet(), 'bfloat16', env={'SATCV_WGRAD_STREAM': '0'}),
     Case(FIVE + '[wgrad_last_full=0]', _unet(), 'bfloat16', env={'SATCV_WGRAD_LAST_FULL': '0'}),
 ]
-IMPORT_VARIANTS = {'wgrad_late': {'SATCV_WGRAD_LATE': '1'}, 'ctbf=0': {'SATCV_CTBF': '0'}, 'bn_bias_noise': {'SATCV_BN_BIAS_NOISE': '1'},
-                   'fuse_dgrad_bn_bwd=2': {'SATCV_FUSE_DGRAD_BN_BWD': '2'}}
+IMPORT_VARIANTS = {'ctbf=0': {'SATCV_CTBF': '0'}, 'bn_bias_noise': {'SATCV_BN_BIAS_NOISE': '1'}, 'fuse_dgrad_bn_bwd=2': {'SATCV_FUSE_DGRAD_BN_BWD': '2'}}
 # every suffix the backward lowering can put on a label: the union over CASES and IMPORT_VARIANTS must hold them all
 # the cases whose label fragments no other test of the suite asserts (tests/test_model_gpu.py holds bwd_fused / pooled / +poolsums /
-# +skipsums, wgrad_reduce_batched and the early optimizer step; tests/test_bn_numerics_gpu.py the fused +bnred)
+# +skipsums; tests/test_bn_numerics_gpu.py the fused +bnred)
 IN_SUITE = (FIVE, 'unet3_wide')
-SUFFIXES = ('+bnred', '+poolsums', '+skipsums', '(skip half)', '(part)', 'pooled', 'pooled nodx', '+headgrad', 'convt_bwd_fused',
-            'wgrad_reduce_batched', 'early optimizer step', 'convT f2')
+SUFFIXES = ('+bnred', '+poolsums', '+skipsums', '(skip half)', '(part)', 'pooled', 'pooled nodx', '+headgrad', 'convt_bwd_fused', 'convT f2')
 
 
 # ------------------------------------------------------------------ folded inference (fp8_infer.Fp8Plan)

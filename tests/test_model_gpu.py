@@ -937,93 +937,6 @@ def test_full_size_training_step_permutation_property(mt):
     assert torch.isfinite(g1).all() and g1.abs().max() > 0
 
 
-def test_deferred_batched_slab_sums_agree_with_the_per_layer_sums(mt, monkeypatch):
-    """round 5: the slab sums of the weight-gradient launches run deferred, several layers per launch (satcv_reduce_slabs_batched, engine.Plan);
-    SATCV_DEFER_REDUCE=0 keeps one sum launch per layer.  Same slabs, another (fixed) summation order: every gradient of a four-level bf16
-    step agrees to fp32 rounding, and the deferred form is bit-reproducible."""
-    def grads(defer):
-        monkeypatch.setenv('SATCV_DEFER_REDUCE', defer)
-        mt.reset_uids(); mt.set_seed(9)
-        m = mt.get_unet_model(2, 4, [32, 64, 128, 256], [2, 2, 2, 2])
-        m.compute_dtype = 'bfloat16'
-        m.compile(optimizer=mt.Adam(0.0), loss=lambda t, p: mt.weighted_categorical_crossentropy(t, p, [1.0, 5.0]))
-        rng = np.random.default_rng(4)
-        x = rng.random((4, 64, 96, 4)).astype(np.float32)
-        y = np.eye(2, dtype=np.float32)[(rng.random((4, 64, 96)) < 0.3).astype(np.int64)]
-        m.train_on_batch(x, y)
-        g = m.runtime.gflat.clone()
-        m.train_on_batch(x, y)
-        assert torch.equal(g, m.runtime.gflat)
-        labels = [getattr(s, 'label', '') for s in m.runtime.plan(4, 64, 96, True).bwd]
-        return g, sum('wgrad_reduce_batched' in l for l in labels)
-    g1, n1 = grads('1')
-    g0, n0 = grads('0')
-    assert n1 >= 1 and n0 == 0
-    assert ((g1 - g0).norm() / g0.norm()).item() < 1e-5
-    assert (g1 - g0).abs().max().item() <= 1e-4 * g0.abs().max().item()
-
-
-def test_round6_scheduling_switches_leave_the_numbers_alone(mt, monkeypatch):
-    """round 6, both measured as nulls and off by default: (1) SATCV_EARLY_OPT -- Adam + operand repack of the parameters whose
-    gradients are final once the deep encoder blocks are done run on the weight-gradient stream inside the backward pass (satcv_adam_step_part, the
-    step counter bumped by the last part): elementwise, so three steps must give BIT-identical parameters and packed images; (2) SATCV_REDUCE_STREAM --
-    every side-stream weight gradient's slab sum on a third stream behind events, a workspace per layer (the batched sum kernel: another fixed order)."""
-    from satellite_computervision_amd import engine as E
-    rng = np.random.default_rng(12)
-    xs = [rng.random((2, 64, 64, 4)).astype(np.float32) for _ in range(3)]
-    ys = [np.eye(2, dtype=np.float32)[(rng.random((2, 64, 64)) < 0.3).astype(np.int64)] for _ in range(3)]
-
-    def run(early, red3):
-        monkeypatch.setattr(E, 'EARLY_OPT', early)
-        monkeypatch.setenv('SATCV_REDUCE_STREAM', '1' if red3 else '0')
-        mt.reset_uids(); mt.set_seed(21)
-        m = mt.get_unet_model(2, 4)
-        m.compute_dtype = 'bfloat16'
-        m.compile(optimizer=mt.Adam(1e-3), loss=lambda t, p: mt.weighted_categorical_crossentropy(t, p, [1.0, 5.0]))
-        losses, gfirst = [], None
-        for x, y in zip(xs, ys):
-            losses.append(m.train_on_batch(x, y))
-            if gfirst is None:
-                gfirst = m.runtime.gflat.clone()          # (the first step's gradient: before any parameter has moved)
-        torch.cuda.synchronize()
-        plan = m.runtime.plan(2, 64, 64, True)
-        labels = [getattr(s_, 'label', '') or '' for s_ in plan.bwd]
-        packed = torch.cat([pk['fwd'].float().flatten() for pk in m.runtime.packed.values()])
-        return m.runtime.pflat.clone(), m.runtime.gflat.clone(), packed, losses, labels, plan, gfirst
-    p0, g0, k0, l0, lab0, _, f0 = run(False, False)
-    p1, g1, k1, l1, lab1, plan1, _ = run(True, False)
-    assert any('early optimizer step' in l for l in lab1) and not any('early optimizer step' in l for l in lab0)
-    assert plan1.eo_done and 0 < plan1.eo_lo < 0.05 * p1.numel()
-    assert torch.equal(p0, p1) and torch.equal(g0, g1) and torch.equal(k0, k1)
-    np.testing.assert_allclose(l1, l0, rtol=1e-6)                  # (the loss scalar is a float atomic sum: last bit)
-    p2, g2, k2, l2, _, plan2, f2 = run(False, True)
-    assert plan2.rstream is not None
-    # the first step's gradients: the same slabs summed in another fixed order (fp32 rounding).  Later steps are not compared element by
-    # element -- Adam's first updates are +-lr whatever the gradient's size, so last-bit differences move weights by 2 lr and the bf16
-    # BatchNorm chain amplifies that (DESIGN.md section 4) -- only the loss curve
-    assert ((f2 - f0).norm() / f0.norm()).item() < 1e-5
-    assert (f2 - f0).abs().max().item() <= 1e-4 * f0.abs().max().item()
-    np.testing.assert_allclose(l2, l0, rtol=2e-2)
-
-
-def test_early_optimizer_step_is_cleared_after_the_training_step(mt, monkeypatch):
-    """Model.train_step_device arms plan.early_opt for its own backward pass only: once the step is done the plan carries none, so another caller
-    of plan.run_backward (HybridModel.train_on_batch, which runs its own full step afterwards) cannot run the early partial Adam as well."""
-    from satellite_computervision_amd import engine as E
-    monkeypatch.setattr(E, 'EARLY_OPT', True)
-    rng = np.random.default_rng(12)
-    x = rng.random((2, 64, 64, 4)).astype(np.float32)
-    y = np.eye(2, dtype=np.float32)[(rng.random((2, 64, 64)) < 0.3).astype(np.int64)]
-    mt.reset_uids(); mt.set_seed(21)
-    m = mt.get_unet_model(2, 4)
-    m.compute_dtype = 'bfloat16'
-    m.compile(optimizer=mt.Adam(1e-3), loss=lambda t, p: mt.weighted_categorical_crossentropy(t, p, [1.0, 5.0]))
-    plan = m.train_step_device(x, y)
-    torch.cuda.synchronize()
-    assert plan.eo_done                          # (the early step did run inside this step's backward pass)
-    assert plan.early_opt is None
-
-
 @pytest.mark.parametrize('channels', [4, 13])
 def test_timed_configuration_bf16_batch64_training_step_properties(mt, channels):
     """The configuration bench.py times (BASELINE configs[1]; configs[3] with 13 bands): ONE bf16 training step of get_unet_model(2, C) at

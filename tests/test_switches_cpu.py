@@ -26,16 +26,11 @@ TEXT = {'0': '0', '1': '1', '2': '2', 'x': 'x', '': ''}                         
 # key: (variable, default as the appendix prints it, read time, value when unset, {text: value})
 PINNED = {
     'bn_bias_noise': ('SATCV_BN_BIAS_NOISE', '0', 'import', False, ONLY),
-    'wgrad_late': ('SATCV_WGRAD_LATE', '0', 'import', False, ONLY),
     'ctbf': ('SATCV_CTBF', '1', 'import', True, ON),
     'ctbf_couts': ('SATCV_CTBF_COUTS', '`32,64`', 'import', (32, 64),
                    {'0': (0,), '1': (1,), '2': (2,), '32,,64,': (32, 64), '': (), ',': (), '16': (16,), 'x': ERR, '32,x': ERR}),
     'fuse_residual': ('SATCV_FUSE_RESIDUAL', '1', 'import', True, ONLY),
-    'early_opt': ('SATCV_EARLY_OPT', '0', 'import', False, ONLY),
     'fuse_dgrad_bn_bwd': ('SATCV_FUSE_DGRAD_BN_BWD', '1', 'import', 1, {'0': 0, '1': 1, '2': 2, 'x': 1, '': 1, '02': 1, '3': 1}),
-    'side_priority': ('SATCV_SIDE_PRIORITY', 'unset', 'plan', None, dict(INT, **{'-1': -1})),
-    'defer_reduce': ('SATCV_DEFER_REDUCE', '0', 'plan', 0, INT),
-    'reduce_stream': ('SATCV_REDUCE_STREAM', '0', 'plan', False, ONLY),
     'wgrad_last_full': ('SATCV_WGRAD_LAST_FULL', '1', 'plan', True, ON),
     'deeplab_splitk': ('SATCV_DEEPLAB_SPLITK', '1', 'model', True, ONLY),
     'prefetch': ('SATCV_PREFETCH', '1', 'call', True, ON),
@@ -62,28 +57,27 @@ PINNED = {
     'lstm_graph': ('SATCV_LSTM_GRAPH', '1', 'call', True, ON),
     'lib': ('SATCV_LIB', 'unset', 'import', None, dict(TEXT, **{'/a/b.so': '/a/b.so'})),
 }
-KEYS = (       # the 35, in the order of the appendix
-    'bn_bias_noise', 'wgrad_late', 'ctbf', 'ctbf_couts', 'fuse_residual', 'early_opt', 'fuse_dgrad_bn_bwd', 'side_priority', 'defer_reduce',
-    'reduce_stream', 'wgrad_last_full', 'deeplab_splitk', 'prefetch', 'fuse_head_bn_bwd', 'wgrad_stream', 'fuse_pool_bn_sums', 'fuse_head_grad',
-    'fuse_pool_bwd', 'fuse_thin_bwd', 'sync_bn', 'folded_infer', 'infer_graph', 'infer_graph_min', 'fp8_scaled', 'fuse_pool', 'fp8_hybrid',
-    'fp8_thin', 'siamese_pair', 'force_collectives', 'cabi_comm', 'grad_payload', 'overlap_allreduce', 'lstm_recurrent_activation', 'lstm_graph',
-    'lib')
-CLASSES = {'production', 'null experiment', 'opt-in feature', 'compatibility aid', 'test aid', 'profiling aid'}
+KEYS = (       # the 30, in the order of the appendix
+    'bn_bias_noise', 'ctbf', 'ctbf_couts', 'fuse_residual', 'fuse_dgrad_bn_bwd', 'wgrad_last_full', 'deeplab_splitk', 'prefetch', 'fuse_head_bn_bwd',
+    'wgrad_stream', 'fuse_pool_bn_sums', 'fuse_head_grad', 'fuse_pool_bwd', 'fuse_thin_bwd', 'sync_bn', 'folded_infer', 'infer_graph',
+    'infer_graph_min', 'fp8_scaled', 'fuse_pool', 'fp8_hybrid', 'fp8_thin', 'siamese_pair', 'force_collectives', 'cabi_comm', 'grad_payload',
+    'overlap_allreduce', 'lstm_recurrent_activation', 'lstm_graph', 'lib')
+CLASSES = {'production', 'opt-in feature', 'compatibility aid', 'test aid', 'profiling aid'}
 
 # the import-time module constants at their defaults, and in a process that has every `import` row at another value (IMPORT_ENV)
 _LIB_DEFAULT = os.path.join(PKG, 'libsatcv.so')
 CONSTANTS = {
-    'engine': dict(BIAS_NOISE=False, WGRAD_LATE=False, CTBF=True, CTBF_COUTS=[32, 64], FUSE_RESIDUAL=True, EARLY_OPT=False, FUSE_DGRAD_ALL=False),
+    'engine': dict(BIAS_NOISE=False, CTBF=True, CTBF_COUTS=[32, 64], FUSE_RESIDUAL=True, FUSE_DGRAD_ALL=False),
     'fp8_infer': dict(USE_SCALED_MFMA=True, FUSE_POOL=True, HYBRID=True, THIN_FP8=True, SIAMESE_PAIR=True),
     'parallel': dict(FORCE=False, CABI_COMM=False),
     'lstm_tools': dict(RECURRENT_ACTIVATION='hard_sigmoid'),
     '_lib': dict(LIB_PATH=_LIB_DEFAULT)}
 IMPORT_ENV = {
-    'SATCV_BN_BIAS_NOISE': '1', 'SATCV_WGRAD_LATE': '1', 'SATCV_CTBF': '0', 'SATCV_CTBF_COUTS': '16,', 'SATCV_FUSE_RESIDUAL': '2', 'SATCV_EARLY_OPT': '1',
+    'SATCV_BN_BIAS_NOISE': '1', 'SATCV_CTBF': '0', 'SATCV_CTBF_COUTS': '16,', 'SATCV_FUSE_RESIDUAL': '2',
     'SATCV_FUSE_DGRAD_BN_BWD': '2', 'SATCV_FP8_SCALED': '0', 'SATCV_FUSE_POOL': '0', 'SATCV_FP8_HYBRID': '0', 'SATCV_FP8_THIN': '0',
     'SATCV_SIAMESE_PAIR': '0', 'SATCV_FORCE_COLLECTIVES': '1', 'SATCV_CABI_COMM': '1', 'SATCV_LSTM_RECURRENT_ACTIVATION': 'sigmoid'}      # + SATCV_LIB
 CONSTANTS_CHANGED = {
-    'engine': dict(BIAS_NOISE=True, WGRAD_LATE=True, CTBF=False, CTBF_COUTS=[16], FUSE_RESIDUAL=False, EARLY_OPT=True, FUSE_DGRAD_ALL=True),
+    'engine': dict(BIAS_NOISE=True, CTBF=False, CTBF_COUTS=[16], FUSE_RESIDUAL=False, FUSE_DGRAD_ALL=True),
     'fp8_infer': dict(USE_SCALED_MFMA=False, FUSE_POOL=False, HYBRID=False, THIN_FP8=False, SIAMESE_PAIR=False),
     'parallel': dict(FORCE=True, CABI_COMM=True),
     'lstm_tools': dict(RECURRENT_ACTIVATION='sigmoid')}         # + _lib.LIB_PATH
@@ -108,11 +102,11 @@ def _constants_in_child(env):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
-def test_the_table_holds_the_35_keys():
+def test_the_table_holds_its_keys():
     from satellite_computervision_amd import switches
     rows = switches.rows()
-    assert tuple(r.key for r in rows) == KEYS and len(KEYS) == 35 and set(KEYS) == set(PINNED)
-    assert len({r.env for r in rows}) == 35
+    assert tuple(r.key for r in rows) == KEYS and len(KEYS) == 30 and set(KEYS) == set(PINNED)
+    assert len({r.env for r in rows}) == 30
     for r in rows:
         env, _, when, _, _ = PINNED[r.key]
         assert (r.env, r.when) == (env, when), r.key
@@ -162,12 +156,7 @@ def test_the_quirks_the_consumers_depend_on(monkeypatch):
         monkeypatch.setenv(var, text)
         return switches.read(key)
     assert at('SATCV_FUSE_RESIDUAL', '2', 'fuse_residual') is False and at('SATCV_CTBF', '2', 'ctbf') is True
-    assert (at('SATCV_DEFER_REDUCE', '2', 'defer_reduce') != 0) is True                 # engine: DEFER = read(...) != 0
-    assert (at('SATCV_DEFER_REDUCE', '0', 'defer_reduce') != 0) is False
-    with pytest.raises(ValueError):
-        at('SATCV_DEFER_REDUCE', 'x', 'defer_reduce')
     assert at('SATCV_CTBF_COUTS', '32,,64,', 'ctbf_couts') == (32, 64) and at('SATCV_CTBF_COUTS', '', 'ctbf_couts') == ()
-    assert switches.read('side_priority') is None and at('SATCV_SIDE_PRIORITY', '-1', 'side_priority') == -1
     for text, want in (('0', (False, False)), ('1', (True, False)), ('2', (True, True))):
         v = at('SATCV_FUSE_DGRAD_BN_BWD', text, 'fuse_dgrad_bn_bwd')
         assert (v != 0, v == 2) == want            # (Model.fuse_dgrad_bn_bwd, engine.FUSE_DGRAD_ALL)
@@ -204,10 +193,10 @@ def test_later_rows_are_read_when_they_are_used(monkeypatch):
     monkeypatch.setenv('SATCV_GRAD_PAYLOAD', 'bf16')
     assert parallel.GradSync(10).payload == 'bf16' and parallel.GradSync(10, payload='fp32').payload == 'fp32'
     # every plan / model / call row at another value than its default
-    late = {'side_priority': ('3', 3), 'defer_reduce': ('1', 1), 'reduce_stream': ('1', True), 'wgrad_last_full': ('0', False), 'deeplab_splitk': ('0', False),
-            'prefetch': ('0', False), 'fuse_head_bn_bwd': ('0', False), 'wgrad_stream': ('0', False), 'fuse_pool_bn_sums': ('0', False),
-            'fuse_head_grad': ('0', False), 'fuse_pool_bwd': ('0', False), 'fuse_thin_bwd': ('0', False), 'sync_bn': ('1', True), 'folded_infer': ('0', False),
-            'infer_graph': ('2', 2), 'infer_graph_min': ('8', 8), 'grad_payload': ('bf16', 'bf16'), 'overlap_allreduce': ('0', False), 'lstm_graph': ('0', False)}
+    late = {'wgrad_last_full': ('0', False), 'deeplab_splitk': ('0', False), 'prefetch': ('0', False), 'fuse_head_bn_bwd': ('0', False),
+            'wgrad_stream': ('0', False), 'fuse_pool_bn_sums': ('0', False), 'fuse_head_grad': ('0', False), 'fuse_pool_bwd': ('0', False),
+            'fuse_thin_bwd': ('0', False), 'sync_bn': ('1', True), 'folded_infer': ('0', False), 'infer_graph': ('2', 2), 'infer_graph_min': ('8', 8),
+            'grad_payload': ('bf16', 'bf16'), 'overlap_allreduce': ('0', False), 'lstm_graph': ('0', False)}
     assert set(late) == {k for k, p in PINNED.items() if p[2] != 'import'}
     for k, (text, want) in late.items():
         assert want != PINNED[k][3]
@@ -236,7 +225,7 @@ def test_import_rows_are_read_at_import(tmp_path):
 
 # ------------------------------------------------------------------ one reader
 ALLOWED = {'switches.py': None, 'parallel.py': {'WORLD_SIZE', 'LOCAL_RANK'}, 'build.py': {'HIPCC'}}         # None: any variable
-SITES = {'engine.py': 11, 'model_tools.py': 13, 'fp8_infer.py': 5, 'parallel.py': 4, 'lstm_tools.py': 2, '_lib.py': 1}
+SITES = {'engine.py': 6, 'model_tools.py': 13, 'fp8_infer.py': 5, 'parallel.py': 4, 'lstm_tools.py': 2, '_lib.py': 1}
 
 
 def _package_sources():
@@ -277,7 +266,7 @@ def test_one_reader_of_the_environment_in_the_package():
 
 
 def test_every_row_has_its_consumers():
-    """every read goes through switches.read('<literal key>'): 36 sites, each key once and SATCV_FUSE_DGRAD_BN_BWD in engine.py and model_tools.py"""
+    """every read goes through switches.read('<literal key>'): 31 sites, each key once and SATCV_FUSE_DGRAD_BN_BWD in engine.py and model_tools.py"""
     sites = []
     for rel, tree in _package_sources():
         for n in ast.walk(tree):
@@ -298,7 +287,7 @@ def test_table_and_appendix_agree():
     doc = doc[doc.index('### Python side'):]
     doc = doc[:doc.index('Outside both tables')]
     found = re.findall(r'^\| `(SATCV_\w+)` \| `(\w+)` \| (\S+) \| (\w+) \| ([^|]+) \| (.*) \|$', doc, re.M)
-    assert len(found) == len([l for l in doc.splitlines() if l.startswith('| `')]) == 35
+    assert len(found) == len([l for l in doc.splitlines() if l.startswith('| `')]) == 30
     by_key = {f[1]: f for f in found}
     assert set(by_key) == set(KEYS) == {r.key for r in switches.rows()}
     for r in switches.rows():

@@ -8,7 +8,7 @@ With --folded the same for plan_cases.FOLDED_CASES, the folded inference plans o
 
 For every case of tests/plan_cases.py (always the list beside THIS file; the package is the first one on the path):
   steps   (phase, label or null, work or null) of every step of plan.fwd and plan.bwd
-  calls   one step under a recording wrapper around every lib.satcv_* entry point: (name, stream: main | side | third, the non-pointer
+  calls   one step under a recording wrapper around every lib.satcv_* entry point: (name, stream: main | side, the non-pointer
           fields of every ctypes structure argument, the non-pointer scalar arguments)
   hashes  training: three steps from a fixed seed, sha256 of pflat / gflat / sflat, of the first step's gflat and of the packed images,
           and the three losses; inference: sha256 of every output
@@ -54,7 +54,7 @@ def _fields(s):
 
 
 class Recorder:
-    """wraps every satcv_* entry point the library object has bound; `streams`: {handle: name} of the plan's side and third streams"""
+    """wraps every satcv_* entry point the library object has bound; `streams`: {handle: name} of the plan's side stream"""
 
     def __init__(self, lib):
         self.lib, self.calls, self.streams, self.orig = lib, [], {}, {}
@@ -79,11 +79,10 @@ class Recorder:
 
 def run_case(case):
     import torch
-    from satellite_computervision_amd import engine as E, lstm_tools as lt, model_tools as mt, ops
+    from satellite_computervision_amd import lstm_tools as lt, model_tools as mt, ops
     from satellite_computervision_amd._lib import lib
     saved = {k: os.environ.get(k) for k in case.env}
     os.environ.update(case.env)
-    eo, E.EARLY_OPT = E.EARLY_OPT, case.early_opt or E.EARLY_OPT
     mt.set_compute_dtype(case.dtype)
     try:
         m, x, y = case.make(mt, lt)
@@ -94,7 +93,7 @@ def run_case(case):
                 losses = [m.train_on_batch(x, y)]
                 torch.cuda.synchronize()
                 plan = next(p for p in rt.plans.values() if p.training)
-                rec.streams = {s.cuda_stream: k for k, s in (('side', plan.side), ('third', getattr(plan, 'rstream', None))) if s is not None}
+                rec.streams = {plan.side.cuda_stream: 'side'} if plan.side is not None else {}
                 rec.calls.clear()
                 g_first = _sha(rt.gflat)
                 losses.append(m.train_on_batch(x, y))            # (the recorded step: plan and streams exist)
@@ -117,7 +116,6 @@ def run_case(case):
         steps = [[ph, getattr(s, 'label', None), getattr(s, 'work', None)] for ph, lst in (('fwd', plan.fwd), ('bwd', getattr(plan, 'bwd', []))) for s in lst]
         return dict(steps=steps, calls=calls, hashes=hashes, losses=[float(v) for v in losses])
     finally:
-        E.EARLY_OPT = eo
         mt.set_compute_dtype('bfloat16')
         for k, v in saved.items():
             if v is None:
@@ -164,6 +162,8 @@ def child(variant, out, only):
         cases = [c._replace(name=f'{pc.FIVE}[{variant}]') for c in pc.CASES if c.name == pc.FIVE]
     else:
         cases = pc.CASES
+    import satellite_computervision_amd
+    print('package:', os.path.dirname(satellite_computervision_amd.__file__), flush=True)
     res = {}
     for c in [c for c in cases if not only or c.name in only]:
         res[c.name] = run_case(c)
