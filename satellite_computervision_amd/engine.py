@@ -10,6 +10,7 @@ Fusion contract (what the HIP kernels expect):
     whichever kernel consumes it (conv loader, pool kernel, head);
   * concat([skip, up]) is never materialised: the consumer conv reads two sources;
   * train-mode BN statistics come from the producing kernel's epilogue.
+Parameters, gradients, optimizer state and packed weight images are the params.FlatParams that `Runtime` is.
 There is no CPU path: everything here requires the HIP library and a ROCm device.
 """
 import ctypes as C
@@ -22,6 +23,7 @@ import torch
 
 from . import ops, parallel, switches
 from ._lib import lib, check, F32, BF16, STAT_ROWS
+from .params import FlatParams
 
 _M16_DEFAULT = ops.options()['igemm_m16']      # the library's value of option igemm_m16 at import (csrc/options.hpp)
 
@@ -113,42 +115,33 @@ def _fp(t, off=0):
     return None if t is None else t.data_ptr() + t.element_size() * off
 
 
-class Runtime:
-    """Device state of one model: flat fp32 parameters / gradients / Adam slots, packed MFMA
-    weight images, BN moving statistics."""
+class Runtime(FlatParams):
+    """Device state of one graph model: the FlatParams store of its trainables (params.py), the BN moving statistics beside it (sflat),
+    every layer's packed MFMA weight images -- allocated here, repacked at once whenever the parameters change -- and the plans."""
 
     def __init__(self, model, dtype):
         if not torch.cuda.is_available():
             raise RuntimeError('satellite_computervision_amd needs a ROCm GPU (no CPU fallback)')
+        super().__init__()
         self.model, self.dtype = model, dtype
+        self.pack_dtype = dtype
         self.tdtype = ops.TORCH_DTYPE[dtype]
         self.esize = 2 if dtype == BF16 else 4
         self.dev = torch.device('cuda', torch.cuda.current_device())
-        # flat layout: trainables (Adam sees one buffer), then non-trainable BN moving statistics
-        self.offsets = {}
-        off = 0
-        for p in model.param_specs:
-            if p.kind in ('moving_mean', 'moving_var'):
-                continue
-            self.offsets[p.name] = off
-            off += rup(p.size, 4)
-        self.n_train = off
-        soff = 0
-        self.soffsets = {}
+        # flat layout: trainables (the optimizer sees one buffer), then non-trainable BN moving statistics in a buffer of their own
+        self.offsets, self.soffsets = {}, {}
+        off = soff = 0
         for p in model.param_specs:
             if p.kind in ('moving_mean', 'moving_var'):
                 self.soffsets[p.name] = soff
                 soff += rup(p.size, 4)
-        self.pflat = torch.zeros(max(off, 4), dtype=torch.float32, device=self.dev)
-        self.gflat = torch.zeros_like(self.pflat)
-        self.sflat = torch.zeros(max(soff, 4), dtype=torch.float32, device=self.dev)
-        self.adam_m = self.adam_v = None
-        self.slot_kind, self.slots, self._clip_ws = None, {}, None      # SGD / RMSprop slots by name, allocated on their first step
-        self.adam_state = torch.tensor([1e-3, 0.0, 1.0, 0.0], dtype=torch.float32, device=self.dev)
-        self.lr_mul = None
+            else:
+                self.offsets[p.name] = off
+                off += rup(p.size, 4)
+        self.n_train = off
         self.dropout_seed = 0x5A7C0FFEE
-        host = np.zeros(self.pflat.numel(), np.float32)
-        hs = np.zeros(self.sflat.numel(), np.float32)
+        host = np.zeros(max(off, 4), np.float32)
+        hs = np.zeros(max(soff, 4), np.float32)
         self.zero_gamma = set()
         for p in model.param_specs:
             v = np.asarray(p.init(), np.float32).reshape(-1)
@@ -157,11 +150,10 @@ class Runtime:
                 host[self.offsets[p.name]:self.offsets[p.name] + p.size] = v
             else:
                 hs[self.soffsets[p.name]:self.soffsets[p.name] + p.size] = v
-        self.pflat.copy_(torch.from_numpy(host))
-        self.sflat.copy_(torch.from_numpy(hs))
+        self.allocate(host, self.dev)
+        self.sflat = torch.from_numpy(hs).to(self.dev)
         self.specs = {p.name: p for p in model.param_specs}
         # packed weights per conv-like layer
-        self.packed = {}
         for node in model.nodes:
             if node.op in ('cba', 'convT'):
                 lay = node.layer
@@ -172,13 +164,15 @@ class Runtime:
                 cin, cout = (ks[3], ks[2]) if tr else (ks[2], ks[3])
                 cin_pad = rup(cin, 16)
                 ef, ed, _, _ = ops.packed_sizes(ks[0], ks[1], cin, cout, cin_pad, tr)
-                self.packed[lay.name] = dict(
-                    fwd=torch.zeros(ef, dtype=self.tdtype, device=self.dev),
-                    dgrad=torch.zeros(ed, dtype=self.tdtype, device=self.dev),
-                    k=(ks[0], ks[1]), cin=cin, cout=cout, cin_pad=cin_pad, transposed=tr)
-        self._ptab = None
+                self.register_image(lay.name, self.pptr(lay.name + '/kernel'), torch.zeros(ef, dtype=self.tdtype, device=self.dev),
+                                    torch.zeros(ed, dtype=self.tdtype, device=self.dev), (ks[0], ks[1]), cin, cout, cin_pad, tr)
         self.repack()
         self.plans = {}
+
+    def weights_changed(self):
+        """after every optimizer step and every set_weights_dict: the images follow at once (one batched launch), `version` moves on"""
+        self.repack()
+        self.bump()
 
     # ---- parameter access
     def pptr(self, name):
@@ -216,64 +210,6 @@ class Runtime:
                 self.zero_gamma.add(bn)
             else:
                 self.zero_gamma.discard(bn)
-
-    def _pack_table(self):
-        """device table of the pack jobs (forward + data-gradient image) of every layer, for satcv_pack_weights_batched"""
-        from ._lib import PackJob
-        jobs = []
-        for lname, pk in self.packed.items():
-            taps, cin, cout, cp = pk['k'][0] * pk['k'][1], pk['cin'], pk['cout'], pk['cin_pad']
-            src = self.pptr(lname + '/kernel')
-            if not pk['transposed']:
-                jobs.append(PackJob(src, pk['fwd'].data_ptr(), 0, taps, cin, cout, cp, rup(cout, 32)))
-                jobs.append(PackJob(src, pk['dgrad'].data_ptr(), 1, taps, cin, cout, rup(cout, 16), rup(cin, 32)))
-            else:
-                jobs.append(PackJob(src, pk['fwd'].data_ptr(), 2, taps, cin, cout, cp, rup(taps * cout, 32)))
-                jobs.append(PackJob(src, pk['dgrad'].data_ptr(), 3, taps, cin, cout, rup(taps * cout, 16), rup(cin, 32)))
-        return ops.job_table(jobs, lib.satcv_pack_job_items, self.dev)
-
-    def repack(self):
-        """fp32 Keras-layout kernels -> MFMA operand images (after every weight update), one launch for all layers"""
-        if not self.packed:
-            return
-        if self._ptab is None:
-            self._ptab = self._pack_table()
-        t = self._ptab
-        check(lib.satcv_pack_weights_batched(t['jobs'].data_ptr(), t['prefix'].data_ptr(), t['n'], t['total'], self.dtype, ops.stream_ptr()))
-
-    def ensure_adam(self):
-        if self.adam_m is None:
-            self.adam_m = torch.zeros_like(self.pflat)
-            self.adam_v = torch.zeros_like(self.pflat)
-
-    # ---- what training.apply_optimizer asks of the owner of the flat buffers
-    def opt_buffers(self):
-        return self.pflat, self.gflat, self.adam_state, self.lr_mul
-
-    def opt_slots(self, opt):
-        """the slots of `opt` by name, zero-filled on first use; slots of another kind (or of another flag set) are dropped"""
-        if opt.kind == 'adam':
-            self.ensure_adam()
-            return {'m': self.adam_m, 'v': self.adam_v}
-        if self.slot_kind != opt.kind or set(self.slots) != set(opt.slot_names):
-            self.slot_kind, self.slots = opt.kind, {k: torch.zeros_like(self.pflat) for k in opt.slot_names}
-        return self.slots
-
-    def clip_workspace(self):
-        if self._clip_ws is None:
-            self._clip_ws = ops.grad_clip_workspace(self.gflat.numel(), self.dev)
-        return self._clip_ws
-
-    def reset_opt_slots(self):
-        self.adam_m = self.adam_v = None
-        self.slot_kind, self.slots = None, {}
-        self.adam_state[1:2].zero_()
-
-    def restore_opt_slots(self, kind, arrays, state):
-        """slots read back from a file written by Model.save"""
-        self.slot_kind = kind
-        self.slots = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(self.dev) for k, v in arrays.items()}
-        self.adam_state.copy_(torch.from_numpy(np.asarray(state, np.float32)))
 
     def plan(self, n, h, w, training):
         # tf.keras runs a BatchNormalization whose `trainable` is False in INFERENCE mode even inside fit() (moving statistics, no

@@ -4,6 +4,7 @@ get_lstm_autoencoder / get_hybrid_model / get_hierarchical_model (utils/model_to
 Unlike the U-Net plans (engine.Plan: one static launch list per input shape) these models are small, recurrent and multi-input, so
 they run as an eager TAPE of C-ABI launches: every layer object has forward / backward methods that call the library (ops.py wrappers
 around include/satcv.h) on device tensors; torch is the allocator.  No CPU path, no torch arithmetic on the data path.
+The parameters live in `_Params`, a params.FlatParams.
 
 Layout: a sequence (B, T, H, W, C) is ingested TIME-MAJOR, (T, B, H, W, Cpad) (satcv_ingest_seq), so that
   * the input convolution of ALL time steps of a ConvLSTM2D is ONE implicit-GEMM launch over T * B images (it does not depend on h),
@@ -25,6 +26,7 @@ from . import ops, switches
 from . import model_tools as mt
 from .training import MeanIoU, resolve_optimizer, resolve_loss, reset_slots_on_recompile, apply_optimizer, metric_from_confusion, fit_loop
 from ._lib import lib, check, F32, BF16, LstmGatesDesc, DenseDesc
+from .params import FlatParams
 
 RECURRENT_ACTIVATION = switches.read('lstm_recurrent_activation')
 BN_EPS, BN_MOMENTUM = 1e-3, 0.99
@@ -39,68 +41,43 @@ def graph_enabled():
     return bool(switches.read('lstm_graph'))
 
 
-class _Params:
-    """flat float32 parameters / gradients / Adam slots of one model (what engine.Runtime is to the U-Net graphs)"""
+class _Params(FlatParams):
+    """The FlatParams store (params.py) of one tape model: variables added by name, the BatchNorm moving statistics inside the flat
+    buffer under lr_mul = 0, and packed images that are made -- and repacked -- when a layer next asks for them."""
 
     def __init__(self):
-        self.specs, self.n = {}, 0
-        self.flat = self.grad = self.m = self.v = None
-        self.state = None
-        self.init = {}
-        # MFMA operand images of the convolution kernels (kernel name -> forward / data-gradient image), valid for parameter version `ver`
-        self.version = 0
-        self._pk, self._pk_tab, self._pk_dtype = {}, None, None
-
-    def bump(self):
-        """the parameters changed (optimizer step, set_weights): every packed image is stale"""
-        self.version += 1
+        super().__init__()
+        self.specs, self.n, self.init = {}, 0, {}
 
     def get_packed(self, name, cin_pad, dtype):
         """forward and data-gradient operand images of Conv2D kernel `name` (ops.pack_weights layouts).  The images live in persistent buffers;
         when the parameters have changed since they were packed, ALL registered kernels are repacked by ONE launch (satcv_pack_weights_batched) --
         a training step packed every layer's kernels with a launch each (40 launches of ~5 us in a get_lstm_model step: profiles/r05_lstm_kernel_stats.csv),
         and inference repacked unchanged weights on every call."""
-        if self._pk_dtype != dtype:
-            self._pk, self._pk_tab, self._pk_dtype = {}, None, dtype
-        e = self._pk.get(name)
+        if self.pack_dtype != dtype:
+            self.packed, self._ptab, self.pack_dtype = {}, None, dtype
+        e = self.packed.get(name)
         if e is None:
             k = self.p(name)
             fwd, dg = ops.pack_weights(k, cin_pad, dtype)
-            self._pk[name] = e = dict(fwd=fwd, dg=dg, cin_pad=cin_pad, shape=tuple(k.shape), ver=self.version)
-            self._pk_tab = None
+            self.register_image(name, k.data_ptr(), fwd, dg, k.shape[:2], k.shape[2], k.shape[3], cin_pad, ver=self.version)
             return fwd, dg
         if e['cin_pad'] != cin_pad:
             raise ValueError(f'{name}: packed with cin_pad {e["cin_pad"]}, asked for {cin_pad}')
         if e['ver'] != self.version:
-            self._repack_all(dtype)
-        return e['fwd'], e['dg']
+            self.repack()
+            for o in self.packed.values():
+                o['ver'] = self.version
+        return e['fwd'], e['dgrad']
 
     def prepare_capture(self):
         """called right before a training step is captured into a graph: the captured step must CONTAIN the repack launch -- replays update
         the parameters on the device and only bump `version` on the host, so a graph captured while the images happened to be fresh (an eager
         predict / evaluate after the last optimizer step) would multiply with the images of capture time for ever.  The job table is built
         here, outside the capture (a host-to-device copy)."""
-        if self._pk:
-            self._job_table()
+        if self.packed:
+            self.pack_table()
         self.bump()
-
-    def _job_table(self):
-        from ._lib import PackJob
-        if self._pk_tab is None:
-            jobs = []
-            for name, e in self._pk.items():
-                kh, kw, cin, cout = e['shape']
-                src = self.p(name).data_ptr()
-                jobs.append(PackJob(src, e['fwd'].data_ptr(), 0, kh * kw, cin, cout, e['cin_pad'], ops.rup(cout, 32)))
-                jobs.append(PackJob(src, e['dg'].data_ptr(), 1, kh * kw, cin, cout, ops.rup(cout, 16), ops.rup(cin, 32)))
-            self._pk_tab = ops.job_table(jobs, lib.satcv_pack_job_items, _dev())
-        return self._pk_tab
-
-    def _repack_all(self, dtype):
-        t = self._job_table()
-        check(lib.satcv_pack_weights_batched(t['jobs'].data_ptr(), t['prefix'].data_ptr(), t['n'], t['total'], dtype, ops.stream_ptr()))
-        for e in self._pk.values():
-            e['ver'] = self.version
 
     def add(self, name, shape, init, trainable=True):
         size = int(np.prod(shape))
@@ -111,53 +88,21 @@ class _Params:
 
     def build(self):
         host = np.zeros(max(self.n, 4), np.float32)
-        for name, (off, shape, _) in self.specs.items():
-            host[off:off + int(np.prod(shape))] = np.asarray(self.init[name](), np.float32).reshape(-1)
-        self.flat = torch.from_numpy(host).to(_dev())
-        self.grad = torch.zeros_like(self.flat)
-        self.m = self.v = None                                      # optimizer slots: allocated on the first step that needs them
-        self.slot_kind, self.slots, self._clip_ws = None, {}, None
-        self.state = torch.tensor([1e-3, 0.0, 1.0, 0.0], dtype=torch.float32, device=_dev())
         mul = np.ones(max(self.n, 4), np.float32)
         for name, (off, shape, tr) in self.specs.items():
+            host[off:off + int(np.prod(shape))] = np.asarray(self.init[name](), np.float32).reshape(-1)
             if not tr:
                 mul[off:off + int(np.prod(shape))] = 0
+        self.allocate(host, _dev())
         self.lr_mul = torch.from_numpy(mul).to(_dev())
-
-    # ---- what training.apply_optimizer asks of the owner of the flat buffers (as engine.Runtime)
-    @property
-    def adam_state(self):
-        return self.state
-
-    def opt_buffers(self):
-        return self.flat, self.grad, self.state, self.lr_mul
-
-    def opt_slots(self, opt):
-        if opt.kind == 'adam':
-            if self.m is None:
-                self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
-            return {'m': self.m, 'v': self.v}
-        if self.slot_kind != opt.kind or set(self.slots) != set(opt.slot_names):
-            self.slot_kind, self.slots = opt.kind, {k: torch.zeros_like(self.flat) for k in opt.slot_names}
-        return self.slots
-
-    def clip_workspace(self):
-        if self._clip_ws is None:
-            self._clip_ws = ops.grad_clip_workspace(self.grad.numel(), self.grad.device)
-        return self._clip_ws
-
-    def reset_opt_slots(self):
-        self.m = self.v = None
-        self.slot_kind, self.slots = None, {}
-        self.state[1:2].zero_()
 
     def p(self, name):
         off, shape, _ = self.specs[name]
-        return self.flat[off:off + int(np.prod(shape))].view(shape)
+        return self.pflat[off:off + int(np.prod(shape))].view(shape)
 
     def g(self, name):
         off, shape, _ = self.specs[name]
-        return self.grad[off:off + int(np.prod(shape))].view(shape)
+        return self.gflat[off:off + int(np.prod(shape))].view(shape)
 
 
 def _glorot(rng, shape, fan_in, fan_out):
@@ -628,7 +573,7 @@ class _SeqModelBase:
         self.optimizer = new_opt
         reset_slots_on_recompile(self.P, prev, new_opt)
         self.optimizer._rt = self.P              # (`optimizer.learning_rate = ...` lands in the device state buffer at once)
-        self.P.state[0:1].fill_(self.optimizer._lr)
+        self.P.adam_state[0:1].fill_(self.optimizer._lr)
 
     def _loss_grad(self, out, y_true, activation):
         """fused device loss on the model output: returns (loss tensor, dL/dlogits for softmax / sigmoid heads, dL/dout for linear ones)"""
@@ -654,12 +599,12 @@ class _SeqModelBase:
     def _graphed_step(self, step_fn, tensors):
         """step_fn(*device tensors) -> loss tensor (no host synchronisation inside); returns the loss tensor of this step"""
         if not graph_enabled() or getattr(self, '_no_graph', False):
-            self.P.state[0:1].fill_(self.optimizer._lr)
+            self.P.adam_state[0:1].fill_(self.optimizer._lr)
             return step_fn(*tensors)
         graphs = self.__dict__.setdefault('_graphs', {})
         key = (self.compute_dtype,) + tuple((tuple(t.shape), t.dtype) for t in tensors)
         st = graphs.setdefault(key, {'n': 0})
-        self.P.state[0:1].fill_(self.optimizer._lr)
+        self.P.adam_state[0:1].fill_(self.optimizer._lr)
         if 'g' not in st:
             st['n'] += 1
             if st['n'] <= 2 or st.get('off'):
@@ -687,7 +632,7 @@ class _SeqModelBase:
     def _adam(self, set_lr=True):
         P, opt = self.P, self.optimizer
         if set_lr:
-            P.state[0:1].fill_(opt._lr)
+            P.adam_state[0:1].fill_(opt._lr)
         apply_optimizer(opt, P)                  # (clip if asked, then the step of whichever optimizer was compiled)
         P.bump()
 
@@ -696,7 +641,7 @@ class _SeqModelBase:
 
     def set_weights_dict(self, d):
         for k, v in d.items():
-            self.P.p(k).copy_(torch.as_tensor(np.asarray(v, np.float32)).to(self.P.flat.device).view(self.P.specs[k][1]))
+            self.P.p(k).copy_(torch.as_tensor(np.asarray(v, np.float32)).to(self.P.pflat.device).view(self.P.specs[k][1]))
         self.P.bump()
 
     # Model.save_weights / load_weights / evaluate call sites of the reference (utils/model_tools.py:1162-1196 and the notebooks):
@@ -901,7 +846,7 @@ class LSTMModel(_SeqModelBase):
         return float(self._graphed_step(self._train_device, (xd, yd)).item())
 
     def _train_device(self, xd, yd):
-        self.P.grad.zero_()
+        self.P.gflat.zero_()
         out = self._forward(xd, True)
         loss, dout = self._loss_grad(out, yd, 'linear')
         (da,) = self.dense.backward(dout, need_dx=(True,))
@@ -1043,7 +988,7 @@ class HybridModel(_SeqModelBase):
             raise RuntimeError('compile() the model before fit/train')
         rt = self.unet.runtime
         rt.opt_slots(self.optimizer)
-        self.P.grad.zero_(); rt.gflat.zero_()
+        self.P.gflat.zero_(); rt.gflat.zero_()
         probs, _ = self._forward(x, True)
         loss, dlog = self._loss_grad(probs, y, 'softmax')
         dzl, dau = self.fusion.backward(dlog, need_dx=(True, True))
@@ -1059,8 +1004,7 @@ class HybridModel(_SeqModelBase):
         opt = self.optimizer
         rt.adam_state[0:1].fill_(opt._lr)
         apply_optimizer(opt, rt)
-        rt.repack()
-        self.unet._weights_version = getattr(self.unet, '_weights_version', 0) + 1
+        rt.weights_changed()
         self._adam()
         return float(loss.item())
 
@@ -1145,7 +1089,7 @@ class LSTMAutoencoder(_SeqModelBase):
         return float(self._graphed_step(self._train_device, tensors).item())
 
     def _train_device(self, xs, sincos, ty, sy):
-        self.P.grad.zero_()
+        self.P.gflat.zero_()
         tout, sout = self._forward([xs, sincos], True)
         B, T, H, W = self._shape
         ty = ty.permute(1, 0, 2, 3, 4).contiguous().view(T * B, H, W, -1)
@@ -1359,7 +1303,7 @@ class HierarchicalModel(_SeqModelBase):
         return float(self._graphed_step(self._train_device, tensors).item())
 
     def _train_device(self, xa, xl, y0, y1, y2):
-        self.P.grad.zero_()
+        self.P.gflat.zero_()
         outs = self._forward([xa, xl], True)
         total, dl = None, []
         for o, yy in zip(outs, (y0, y1, y2)):

@@ -712,10 +712,9 @@ class Model:
                     continue
                 raise ValueError(f'{k}: shape {np.shape(v)} != {rt.specs[k].shape}')
             rt.set_param(k, v)
-        rt.repack()
+        rt.weights_changed()                                 # (folded inference plans re-derive their arrays: _infer_plan reads rt.version)
         if getattr(self, '_fp8_plans', None):
             self._fp8_plans = {}                             # fp8 weight images are re-quantised when the plans are rebuilt
-        self._weights_version = getattr(self, '_weights_version', 0) + 1      # folded inference plans re-derive their arrays
 
     # ---- persistence.  Paths ending in .h5 / .hdf5 are Keras HDF5 files (hdf5_io.py: written and read without h5py / TensorFlow, in the
     # layer grouping tf.keras uses for this network so that the reference's own model can load them in layer order); anything else
@@ -802,28 +801,20 @@ class Model:
         self.set_weights_dict({k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()})
 
     def save(self, path):
-        rt = self.runtime
+        kind, slots, state = self.runtime.optimizer_arrays()
         if self._is_h5_path(path):
             from . import hdf5_io
             layers = self._keras_layers()
             cfg = {'class_name': 'Functional', 'config': {'name': self.name, 'layers': [{'name': n} for n, _ in layers]}}
             attrs = {'model_config': json.dumps(cfg), 'satcv_builder': json.dumps(self._builder or {}), 'keras_version': b'2.6.0', 'backend': b'tensorflow'}
-            extra = None
-            if rt.adam_m is not None:
-                extra = {'optimizer_weights': [('satcv_adam/m:0', rt.adam_m.cpu().numpy()), ('satcv_adam/v:0', rt.adam_v.cpu().numpy()),
-                                               ('satcv_adam/state:0', rt.adam_state.cpu().numpy())]}
-            elif rt.slots:       # SGD / RMSprop slots travel like the Adam moments: satcv_<kind>/<slot>
-                extra = {'optimizer_weights': [(f'satcv_{rt.slot_kind}/{k}:0', v.cpu().numpy()) for k, v in rt.slots.items()] +
-                                              [(f'satcv_{rt.slot_kind}/state:0', rt.adam_state.cpu().numpy())]}
+            # the optimizer's slots (none: nothing to store) travel as satcv_<kind>/<slot> beside the state vector
+            extra = {'optimizer_weights': [(f'satcv_{kind}/{k}:0', v) for k, v in slots.items()] + [(f'satcv_{kind}/state:0', state)]} if slots else None
             return hdf5_io.write_keras_weights(path, layers, root_attrs=attrs, model_weights_group=True, extra_groups=extra)
         d = self.get_weights_dict()
         d['__builder__'] = np.asarray(json.dumps(self._builder or {}))
-        if rt.adam_m is not None:
-            d['__adam_m__'], d['__adam_v__'] = rt.adam_m.cpu().numpy(), rt.adam_v.cpu().numpy()
-            d['__adam_state__'] = rt.adam_state.cpu().numpy()
-        elif rt.slots:
-            d.update({f'__{rt.slot_kind}_{k}__': v.cpu().numpy() for k, v in rt.slots.items()})
-            d['__opt_kind__'], d['__opt_state__'] = np.asarray(rt.slot_kind), rt.adam_state.cpu().numpy()
+        if slots:
+            d.update({f'__{kind}_{k}__': v for k, v in slots.items()})
+            d.update({'__adam_state__': state} if kind == 'adam' else {'__opt_kind__': np.asarray(kind), '__opt_state__': state})      # (Adam files carry no kind)
         np.savez(path if path.endswith('.npz') else path + '.npz', **d)
 
     # ---- compile
@@ -882,7 +873,7 @@ class Model:
         unless enable_folded_inference / enable_fp8_inference asked for the folded one; DeepLab graphs)."""
         from . import fp8_infer
         key = (n, h, w)
-        ver = getattr(self, '_weights_version', 0)
+        ver = self.runtime.version
         if getattr(self, '_fp8_q', None) is not None:
             plan = self._fp8_plans.get(key)
             if plan is None or getattr(plan, 'weights_version', ver) != ver:      # folded weights follow training / set_weights_dict
@@ -1124,8 +1115,7 @@ class Model:
         if sync_grads is not None:
             sync_grads(rt.gflat)
         apply_optimizer(opt, rt, st)             # all-reduce (above), then clip if asked, then the optimizer's step
-        rt.repack()
-        self._weights_version = getattr(self, '_weights_version', 0) + 1
+        rt.weights_changed()
         return plan
 
     def train_on_batch(self, x, y):
@@ -1243,12 +1233,11 @@ def load_model(path, custom_objects=None, compile=False):
         layers = hdf5_io.read_keras_weights(p)
         with hdf5_io.File(p) as f:
             cfg = json.loads(f.attrs['satcv_builder']) if 'satcv_builder' in f.attrs else {}
-            opt = {k: f['optimizer_weights/satcv_adam/' + k + ':0'].read() for k in ('m', 'v', 'state')} if 'optimizer_weights/satcv_adam/m:0' in f else None
-            other = None
-            for kind, names in (('sgd', ('v',)), ('rmsprop', ('ms', 'mg', 'mom'))):
+            opt = None
+            for kind, names in (('adam', ('m', 'v')), ('sgd', ('v',)), ('rmsprop', ('ms', 'mg', 'mom'))):
                 have = [k for k in names if f'optimizer_weights/satcv_{kind}/{k}:0' in f]
                 if have:
-                    other = (kind, {k: f[f'optimizer_weights/satcv_{kind}/{k}:0'].read() for k in have}, f[f'optimizer_weights/satcv_{kind}/state:0'].read())
+                    opt = (kind, {k: f[f'optimizer_weights/satcv_{kind}/{k}:0'].read() for k in have}, f[f'optimizer_weights/satcv_{kind}/state:0'].read())
         builders = {fn.__name__: fn for fn in (get_unet_model, get_deeplabv3_model, get_acnn_model, get_acnn_model2)}
         reset_uids()
         if cfg.get('fn') in builders:            # written by Model.save of this build: any of its network families
@@ -1257,11 +1246,7 @@ def load_model(path, custom_objects=None, compile=False):
             m = get_unet_model(**unet_config_from_keras_weights(layers))
         m._load_keras_hdf5(layers, False, False)
         if opt is not None:
-            rt = m.runtime
-            rt.ensure_adam()
-            rt.adam_m.copy_(torch.from_numpy(opt['m'])); rt.adam_v.copy_(torch.from_numpy(opt['v'])); rt.adam_state.copy_(torch.from_numpy(opt['state']))
-        elif other is not None:
-            m.runtime.restore_opt_slots(*other)
+            m.runtime.restore_optimizer(*opt)
         return m
     with np.load(p, allow_pickle=False) as z:
         cfg = json.loads(str(z['__builder__']))
@@ -1272,16 +1257,11 @@ def load_model(path, custom_objects=None, compile=False):
         reset_uids()
         m = fn(**cfg)
         m.set_weights_dict({k: z[k] for k in z.files if not k.startswith('__')})
-        if '__adam_m__' in z.files:
-            rt = m.runtime
-            rt.ensure_adam()
-            rt.adam_m.copy_(torch.from_numpy(z['__adam_m__']))
-            rt.adam_v.copy_(torch.from_numpy(z['__adam_v__']))
-            rt.adam_state.copy_(torch.from_numpy(z['__adam_state__']))
-        elif '__opt_kind__' in z.files:
-            kind = str(z['__opt_kind__'])
+        kind = str(z['__opt_kind__']) if '__opt_kind__' in z.files else 'adam' if '__adam_m__' in z.files else None      # (Adam files carry no kind)
+        if kind is not None:
             pre = f'__{kind}_'
-            m.runtime.restore_opt_slots(kind, {k[len(pre):-2]: z[k] for k in z.files if k.startswith(pre)}, z['__opt_state__'])
+            slots = {k[len(pre):-2]: z[k] for k in z.files if k.startswith(pre) and k != '__adam_state__'}
+            m.runtime.restore_optimizer(kind, slots, z['__adam_state__' if kind == 'adam' else '__opt_state__'])
     return m
 
 

@@ -1,7 +1,7 @@
 """The Keras-facing training surface shared by the two model families: losses as LossSpec, the optimizers and their one step
 dispatch, metrics, History, the callbacks and the epoch loop of fit().  model_tools.Model (static engine plans) and
 lstm_tools._SeqModelBase (eager tape) differ in how an epoch is trained and validated; everything around that is here, once.
-This module knows neither executor: it imports no model_tools, lstm_tools or engine."""
+This module knows neither executor: it imports no model_tools, lstm_tools or engine; the optimizer step works on a params.FlatParams."""
 import json
 import os
 import time
@@ -189,9 +189,9 @@ def reset_slots_on_recompile(owner, prev, new):
 
 def apply_optimizer(opt, owner, st=None):
     """The one step dispatch of every training path (U-Net engine, ConvLSTM tape, hybrid, data parallel -- whose all-reduce has run by
-    now): clip the flat gradient if the optimizer asks for it, then launch its update.  `owner` holds the flat buffers and the slots
+    now): clip the flat gradient if the optimizer asks for it, then launch its update.  `owner` is the model's FlatParams
     (engine.Runtime or lstm_tools._Params).  A missing kernel is an error: there is no eager fallback."""
-    p, g, state, lr_mul = owner.opt_buffers()
+    p, g, state, lr_mul = owner.pflat, owner.gflat, owner.adam_state, owner.lr_mul
     st = ops.stream_ptr() if st is None else st
     if opt.clipvalue is not None:
         check(lib.satcv_grad_clip(g.data_ptr(), g.numel(), ops.CLIP_VALUE, float(opt.clipvalue), state.data_ptr(), None, st))

@@ -95,6 +95,31 @@ def _hybrid(mt, lt):
     return m, [xu, rng.random((2, 3, 8, 8, 6)).astype(np.float32)], y
 
 
+# the tape models (no engine plan: the manifest holds their calls, losses and weights), at the hybrid case's scale
+def _lstm(mt, lt):
+    mt.reset_uids(); mt.set_seed(4)
+    m = lt.get_lstm_model(6, 3, 3, optim=mt.Adam(1e-3), loss=mt.mse_4d)
+    rng = np.random.default_rng(2)
+    return m, rng.random((2, 3, 8, 8, 6)).astype(np.float32), rng.random((2, 8, 8, 3)).astype(np.float32)
+
+
+def _lstm_autoencoder(mt, lt):
+    mt.reset_uids(); mt.set_seed(4)
+    m = lt.get_lstm_autoencoder(6, 3, 6, compile=True, optim=mt.Adam(1e-3), loss=mt.mse_4d)
+    rng = np.random.default_rng(2)
+    x = rng.random((2, 3, 8, 8, 6)).astype(np.float32)
+    return m, [x, rng.random((2, 8, 8, 2)).astype(np.float32)], [np.flip(x, axis=1).copy(), rng.random((2, 8, 8, 6)).astype(np.float32)]
+
+
+def _hierarchical(mt, lt):
+    mt.reset_uids(); mt.set_seed(4)
+    m = lt.get_hierarchical_model(3, 4, 5, (24, 24, 4), (3, 8, 8, 6), 16, 3)
+    m.compile(optimizer=mt.Adam(1e-3), loss=lambda t, p: mt.weighted_categorical_crossentropy(t, p, [1.0] * 5))
+    rng = np.random.default_rng(2)
+    ys = [np.eye(k, dtype=np.float32)[rng.integers(0, k, (2, 24, 24))] for k in (5, 4, 3)]
+    return m, [rng.random((2, 24, 24, 4)).astype(np.float32), rng.random((2, 3, 8, 8, 6)).astype(np.float32)], ys
+
+
 def _deeplab(mt, lt):
     mt.reset_uids(); mt.set_seed(7)
     return mt.get_deeplabv3_model(3, 4), np.random.default_rng(8).random((1, 64, 64, 4)).astype(np.float32), None
@@ -123,6 +148,9 @@ CASES = [
     Case('zero_gamma', _zero_gamma, 'bfloat16'),
     Case('unet16', _unet([16, 32], [2, 2], 2, 32), 'bfloat16'),
     Case('hybrid', _hybrid, 'float32'),
+    Case('lstm', _lstm, 'float32'),
+    Case('lstm_autoencoder', _lstm_autoencoder, 'float32'),
+    Case('hierarchical', _hierarchical, 'float32'),
     Case('unet5_infer', _unet_infer, 'float32', training=False),
     Case('deeplab_infer', _deeplab, 'float32', training=False),
     # the plan / model rows of the switch table, on the five-level bf16 case

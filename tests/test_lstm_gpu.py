@@ -179,7 +179,7 @@ def test_hybrid_model_forward_and_training_step(lt):
             assert np.abs(w1[k] - w0[k]).max() > 0, k
         assert float((m.unet.runtime.pflat - u0).abs().max()) > 0
         # gradient check of the fusion head's two data gradients against the oracle (finite structure: softmax cross-entropy)
-        m.P.grad.zero_()
+        m.P.gflat.zero_()
         pr, _ = m._forward([xu, xl], True)
         loss, dlog = m._loss_grad(pr, y, 'softmax')
         dzl, dau = m.fusion.backward(dlog, need_dx=(True, True))

@@ -493,6 +493,8 @@ def test_fit_reduces_loss_and_evaluate(mt, tmp_path):
     assert os.path.exists(tmp_path / 'best.npz') and ck.best > 0.5
     # save / load round trip reproduces predictions exactly
     m.save(str(tmp_path / 'model.npz'))
+    with np.load(str(tmp_path / 'model.npz')) as z:                    # the Adam keys of the container (no kind entry: Adam is the default)
+        assert {'__adam_m__', '__adam_v__', '__adam_state__'} <= set(z.files) and not {'__opt_kind__', '__opt_state__'} & set(z.files)
     m2 = mt.load_model(str(tmp_path / 'model.npz'))
     a, b = m.predict(x[:4]), m2.predict(x[:4])
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
@@ -1429,7 +1431,9 @@ def test_models_save_and_load_as_keras_hdf5(mt, tmp_path):
     m2 = mt.load_model(path)
     a, b = m.predict(x), m2.predict(x)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-    assert np.array_equal(m2.runtime.adam_m.cpu().numpy(), m.runtime.adam_m.cpu().numpy())
+    assert m2.runtime.slot_kind == 'adam' and np.array_equal(m2.runtime.slots['m'].cpu().numpy(), m.runtime.slots['m'].cpu().numpy())
+    with H.File(path) as f:
+        assert all(f'optimizer_weights/satcv_adam/{k}:0' in f for k in ('m', 'v', 'state'))
     m.save_weights(str(tmp_path / 'w.h5'))
     mt.reset_uids(); mt.set_seed(99)
     m3 = mt.get_unet_model(2, 4, filters=[32, 64], factors=[2, 2])
@@ -1474,7 +1478,7 @@ def test_training_is_bit_reproducible(mt):
             m.train_on_batch(xs[step % 3], ys[step % 3])
         rt = m.runtime
         torch.cuda.synchronize()
-        runs.append((m.get_weights_dict(), rt.adam_m.cpu().numpy().copy(), rt.adam_v.cpu().numpy().copy()))
+        runs.append((m.get_weights_dict(), rt.slots['m'].cpu().numpy().copy(), rt.slots['v'].cpu().numpy().copy()))
     (w0, m0, v0), (w1, m1, v1) = runs
     diff = [k for k in w0 if not np.array_equal(w0[k], w1[k])]
     assert not diff, diff

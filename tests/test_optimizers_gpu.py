@@ -389,11 +389,11 @@ def test_recompiling_with_another_optimizer_resets_the_slots(mt):
     m.compile(optimizer=mt.Adam(1e-3), loss=unet_loss(mt))
     m.train_on_batch(x, t)
     rt = m.runtime
-    assert rt.adam_m is not None and rt.adam_state[1].item() == 1.0 and not rt.slots
+    assert rt.slot_kind == 'adam' and set(rt.slots) == {'m', 'v'} and rt.adam_state[1].item() == 1.0
     m.compile(optimizer=mt.SGD(0.01, momentum=0.9), loss=unet_loss(mt))
-    assert rt.adam_m is None and rt.adam_state[1].item() == 0.0
+    assert rt.slot_kind != 'adam' and 'm' not in rt.slots and rt.adam_state[1].item() == 0.0
     m.train_on_batch(x, t)
-    assert set(rt.slots) == {'v'} and rt.slots['v'].any() and rt.adam_m is None
+    assert set(rt.slots) == {'v'} and rt.slots['v'].any() and rt.slot_kind != 'adam' and 'm' not in rt.slots
     v1 = rt.slots['v'].clone()
     m.compile(optimizer=mt.SGD(0.01, momentum=0.9), loss=unet_loss(mt))         # a NEW optimizer object: fresh slots, as in Keras
     assert not rt.slots
@@ -420,7 +420,15 @@ def test_saved_model_carries_the_new_slots(mt, tmp_path, ext):
         m2 = mt.load_model(path)
     finally:
         mt.set_compute_dtype('bfloat16')
-    assert m2.runtime.slot_kind == 'rmsprop' and set(m2.runtime.slots) == {'ms', 'mg', 'mom'}
+    keys = {'ms', 'mg', 'mom'}
+    if ext == 'npz':
+        with np.load(path) as z:
+            assert {f'__rmsprop_{k}__' for k in keys} | {'__opt_kind__', '__opt_state__'} <= set(z.files) and str(z['__opt_kind__']) == 'rmsprop'
+    else:
+        from satellite_computervision_amd import hdf5_io
+        with hdf5_io.File(path) as f:
+            assert all(f'optimizer_weights/satcv_rmsprop/{k}:0' in f for k in keys | {'state'})
+    assert m2.runtime.slot_kind == 'rmsprop' and set(m2.runtime.slots) == keys
     for k, v in m.runtime.slots.items():
         assert torch.equal(v.cpu(), m2.runtime.slots[k].cpu()), k
     m2.compile(optimizer=mt.RMSprop(1e-3, momentum=0.5, centered=True), loss=unet_loss(mt))
@@ -429,6 +437,18 @@ def test_saved_model_carries_the_new_slots(mt, tmp_path, ext):
     w, w2 = m.get_weights_dict(), m2.get_weights_dict()
     for k in w:
         assert np.array_equal(w[k].view(np.uint32), w2[k].view(np.uint32)), k
+    if ext == 'h5':                          # the SGD momentum slot under its own group of the same file layout
+        m.compile(optimizer=mt.SGD(0.01, momentum=0.9), loss=unet_loss(mt))
+        m.train_on_batch(x, t)
+        m.save(path)
+        with hdf5_io.File(path) as f:
+            assert 'optimizer_weights/satcv_sgd/v:0' in f and 'optimizer_weights/satcv_sgd/state:0' in f and 'optimizer_weights/satcv_rmsprop/ms:0' not in f
+        mt.set_compute_dtype('float32')
+        try:
+            m3 = mt.load_model(path)
+        finally:
+            mt.set_compute_dtype('bfloat16')
+        assert m3.runtime.slot_kind == 'sgd' and set(m3.runtime.slots) == {'v'} and torch.equal(m3.runtime.slots['v'].cpu(), m.runtime.slots['v'].cpu())
 
 
 # ------------------------------------------------------------------ the C-ABI calls of a step
@@ -542,7 +562,7 @@ def test_lstm_model_trains_with_the_new_optimizers_and_replay_equals_the_tape(lt
         me, le = lstm_run(lt, mt, '0', mk(), xs, ys)
         mg, lg = lstm_run(lt, mt, '1', mk(), xs, ys)
         assert any('g' in st for st in mg._graphs.values()), 'no step was captured'
-        assert set(mg.P.slots) == set(mg.optimizer.slot_names) and mg.P.m is None, 'the Adam moments are not allocated for another optimizer'
+        assert set(mg.P.slots) == set(mg.optimizer.slot_names) and mg.P.slot_kind != 'adam' and 'm' not in mg.P.slots, 'the Adam moments are not allocated for another optimizer'
         print(f'[fig] lstm {which}: eager {le} replay {lg}')
         np.testing.assert_allclose(lg, le, rtol=5e-3)
         assert le[-1] < le[0] and lg[-1] < lg[0]
@@ -573,7 +593,7 @@ def test_lstm_rate_change_through_reduce_lr_on_plateau_reaches_the_replayed_grap
         assert any('g' in st for st in m._graphs.values()), 'no step was captured'
         want, final = O.reduce_lr_on_plateau(h.history['loss'], 0.1, factor=0.1, patience=1, min_delta=100.0, mode='min')
         assert h.history['lr'] == pytest.approx(want, rel=1e-12) and want == pytest.approx([0.1, 0.1, 0.01, 0.001])
-        assert m.P.state[0].item() == np.float32(final)
+        assert m.P.adam_state[0].item() == np.float32(final)
         xs, ys = [x[i:i + 4] for i in range(0, 16, 4)] * 4, [y[i:i + 4] for i in range(0, 16, 4)] * 4
         per_step = [r for r in want for _ in range(4)]
         me, _ = lstm_run(lt, mt, '0', mt.SGD(0.1), xs, ys, lrs=per_step)
@@ -622,4 +642,4 @@ def test_hybrid_model_refuses_global_clipnorm_and_trains_with_clipvalue(lt, mt):
     y = np.eye(3, dtype=np.float32)[rng.integers(0, 3, (2, 48, 48))]
     losses = [m.train_on_batch([xu, xl], y) for _ in range(6)]
     assert np.all(np.isfinite(losses)) and losses[-1] < losses[0], losses
-    assert set(m.P.slots) == {'v'} and set(m.unet.runtime.slots) == {'v'} and m.unet.runtime.adam_m is None
+    assert set(m.P.slots) == {'v'} and set(m.unet.runtime.slots) == {'v'} and m.unet.runtime.slot_kind != 'adam' and 'm' not in m.unet.runtime.slots

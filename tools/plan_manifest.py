@@ -11,7 +11,7 @@ For every case of tests/plan_cases.py (always the list beside THIS file; the pac
   calls   one step under a recording wrapper around every lib.satcv_* entry point: (name, stream: main | side, the non-pointer
           fields of every ctypes structure argument, the non-pointer scalar arguments)
   hashes  training: three steps from a fixed seed, sha256 of pflat / gflat / sflat, of the first step's gflat and of the packed images,
-          and the three losses; inference: sha256 of every output
+          and the three losses; inference: sha256 of every output; a tape model (no `runtime`): no steps, sha256 of every variable
 The import rows of the switch table (plan_cases.IMPORT_VARIANTS) run in a process each.  --compare holds steps, calls and hashes to
 equality and the losses to rtol 1e-6 (a float atomic sum); with --baseline (further runs of checkout A) a case whose A runs differ among
 themselves is held to equal steps and calls and to the largest loss difference between two A runs, and says so."""
@@ -86,9 +86,19 @@ def run_case(case):
     mt.set_compute_dtype(case.dtype)
     try:
         m, x, y = case.make(mt, lt)
-        rt = (m.unet if hasattr(m, 'unet') else m).runtime
+        rt = getattr(m.unet if hasattr(m, 'unet') else m, 'runtime', None)
         rec = Recorder(lib)
         try:
+            if rt is None:                     # a tape model (lstm_tools): no plan, no steps -- the calls of the second step, the weights
+                losses = [m.train_on_batch(x, y)]
+                rec.calls.clear()
+                losses.append(m.train_on_batch(x, y))
+                calls = list(rec.calls)
+                rec.restore()
+                losses.append(m.train_on_batch(x, y))
+                torch.cuda.synchronize()
+                hashes = {k: hashlib.sha256(v.tobytes()).hexdigest() for k, v in m.get_weights_dict().items()}
+                return dict(steps=[], calls=calls, hashes=hashes, losses=[float(v) for v in losses])
             if case.training:
                 losses = [m.train_on_batch(x, y)]
                 torch.cuda.synchronize()

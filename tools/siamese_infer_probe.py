@@ -29,7 +29,7 @@ def build(variant, n, s, q):
     if variant == 'regular':
         return None
     plan = fi.Fp8Plan(m, n, s, s, q, store=fi.FP8 if variant == 'fp8' else fi.BF16, pair=variant != 'folded-unpaired')
-    plan.weights_version = getattr(m, '_weights_version', 0)
+    plan.weights_version = m.runtime.version
     return {(n, s, s): plan}
 
 
