@@ -371,6 +371,7 @@ int satcv_bn_affine_infer_batched(const satcv_bn_affine_job* jobs_device, int32_
 
 /* act = relu(scale*yraw+shift) (written if act != NULL), pooled = maxpool_f(act) ('valid'),
  * optional sum/sumsq rows of `act` (feeds the decoder's concat BatchNormalization).
+ * act_ld (<= 0: c) and, with stats, stats_ld must be >= c.
  * Replaces Activation('relu') + MaxPooling2D (utils/model_tools.py:180,281). */
 int satcv_bn_relu_pool(const void* yraw, const float* scale, const float* shift, void* act, int32_t act_ld,
                        void* pooled, satcv_stat_t* stats, int32_t stats_ld, int32_t n, int32_t h,

@@ -412,6 +412,7 @@ extern "C" int satcv_bn_relu_pool(const void* yraw, const float* scale, const fl
                                   int32_t stats_ld, int32_t n, int32_t h, int32_t w_, int32_t c, int32_t f, int32_t dtype, void* stream) {
   if (act_ld <= 0) act_ld = c;
   SATCV_CHECK(yraw && scale && shift && n > 0 && h > 0 && w_ > 0 && c > 0 && c % 8 == 0 && c <= 2048 && f >= 1, "bn_relu_pool: bad args");
+  SATCV_CHECK(act_ld >= c && (!stats || stats_ld >= c), "bn_relu_pool: act_ld / stats_ld narrower than c");
   const long long items = (long long)n * cdiv(h, f) * cdiv(w_, f) * (c / 8);
   if (f == 2 && h % 2 == 0 && w_ % 2 == 0) {
     DISPATCH_T(dtype, hipLaunchKernelGGL((bn_relu_pool_kernel<T, false, 2>), dim3(ew_grid(items)), dim3(EW_BLOCK), stats ? (EW_BLOCK + 8) * 16 * sizeof(float) : 0,
@@ -428,6 +429,7 @@ extern "C" int satcv_bn_relu_pool_amax(const void* yraw, const float* scale, con
   if (act_ld <= 0) act_ld = c;
   SATCV_CHECK(yraw && scale && shift && pooled && amax && n > 0 && h > 0 && w_ > 0 && c > 0 && c % 8 == 0 && c <= 2048 && f >= 1 && f * f <= 255,
               "bn_relu_pool_amax: bad args");
+  SATCV_CHECK(act_ld >= c && (!stats || stats_ld >= c), "bn_relu_pool_amax: act_ld / stats_ld narrower than c");
   const long long items = (long long)n * cdiv(h, f) * cdiv(w_, f) * (c / 8);
   if (f == 2 && h % 2 == 0 && w_ % 2 == 0) {
     DISPATCH_T(dtype, hipLaunchKernelGGL((bn_relu_pool_kernel<T, true, 2>), dim3(ew_grid(items)), dim3(EW_BLOCK), stats ? (EW_BLOCK + 8) * 16 * sizeof(float) : 0,
