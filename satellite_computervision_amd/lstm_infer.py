@@ -16,7 +16,6 @@ one channel order.  c and h stay in natural order.
 Numerics: with fused=False the plan issues the tape's launches and is bit-equal to predict_on_device.  The fused step in bf16 is NOT: the
 pair of launches rounds hg to bf16 before the gates, the fused step keeps z = xg + conv(h) in fp32.
 """
-import ctypes as C
 import warnings
 
 import numpy as np
@@ -24,7 +23,7 @@ import torch
 
 from . import ops
 from . import lstm_tools as lt
-from ._lib import lib, check, LstmGatesDesc, LstmStepDesc
+from ._lib import lib
 
 STEP_FILTERS = (16, 32, 64)          # filter counts satcv_convlstm_step_fwd is built for
 
@@ -61,13 +60,13 @@ def _capture_stream():
 class _PlannedLayer:
     """one ConvLSTM2D of the plan: buffers, packed weights, and its launches"""
 
-    def __init__(self, layer, T, B, H, W, dtype, fused, repeat=False):
-        self.layer, self.T, self.B, self.H, self.W, self.dtype, self.repeat = layer, T, B, H, W, dtype, repeat
+    def __init__(self, layer, T, B, H, W, dtype, fused):
+        self.layer, self.T, self.B, self.dtype = layer, T, B, dtype
         F = self.F = layer.F
         td, dev = ops.TORCH_DTYPE[dtype], lt._dev()
         self.fused = bool(fused) and step_supported(F, dtype)                   # decided here, never by catching an error per step
         self.Fp = ops.rup(F, 16)
-        self.xg = torch.empty((B if repeat else T * B), H, W, ops.rup(4 * F, 16), dtype=td, device=dev)
+        self.xg = torch.empty(T * B, H, W, ops.rup(4 * F, 16), dtype=td, device=dev)
         self.hseq = torch.zeros(T * B, H, W, self.Fp, dtype=td, device=dev)      # (pad channels stay zero: the kernels write F of them)
         self.c = [torch.empty(B * H * W, F, dtype=torch.float32, device=dev) for _ in range(2)]
         self.hg = None if self.fused else torch.empty(B, H, W, ops.rup(4 * F, 16), dtype=td, device=dev)
@@ -77,7 +76,6 @@ class _PlannedLayer:
         self.wr = torch.empty(er, dtype=td, device=dev)
         self.bias = torch.empty(4 * F, dtype=torch.float32, device=dev)
         self.perm = torch.from_numpy(gate_order(F)).to(dev) if self.fused else None
-        self.rk = 0 if lt.RECURRENT_ACTIVATION == 'hard_sigmoid' else 1
 
     def refresh(self):
         """(re)pack the kernels and the bias from the model's parameters -- permuted to the gate-interleaved order for the fused step"""
@@ -90,35 +88,11 @@ class _PlannedLayer:
         self.bias.copy_(b)
 
     def launch(self, x):
-        """x: lstm_tools.Act, time-major (T * B, H, W, Cpad) (or (B, ...) with repeat).  -> Act of the raw h sequence"""
-        L, F, T, B, H, W = self.layer, self.F, self.T, self.B, self.H, self.W
-        ops.conv2d(x.t, self.wk, 4 * F, dil=L.dil, bias=self.bias, in_scale=x.scale, in_shift=x.shift, in_relu=x.relu, out=self.xg)
-        st = ops.stream_ptr()
-        code = ops.DTYPE_CODE[self.xg.dtype]
-        for t in range(T):
-            xg = self.xg if self.repeat else self.xg[t * B:(t + 1) * B]
-            h_prev = self.hseq[(t - 1) * B:t * B] if t > 0 else None
-            c_prev, c_out, h_out = (self.c[(t - 1) & 1] if t > 0 else None), self.c[t & 1], self.hseq[t * B:(t + 1) * B]
-            if self.fused:
-                d = LstmStepDesc()
-                d.h_prev, d.ldh_prev = (h_prev.data_ptr(), self.Fp) if t > 0 else (None, 0)
-                d.w, d.xg, d.ldx = self.wr.data_ptr(), xg.data_ptr(), self.xg.shape[-1]
-                d.c_prev = c_prev.data_ptr() if t > 0 else None
-                d.c_out, d.h_out, d.ldh = c_out.data_ptr(), h_out.data_ptr(), self.Fp
-                d.n, d.h, d.w_, d.filters, d.rec_act, d.act, d.dtype = B, H, W, F, self.rk, L.act, code
-                check(lib.satcv_convlstm_step_fwd(C.byref(d), st))
-            else:
-                if t > 0:
-                    ops.conv2d(h_prev, self.wr, 4 * F, out=self.hg)
-                d = LstmGatesDesc()
-                d.xg, d.ldx = xg.data_ptr(), self.xg.shape[-1]
-                d.hg, d.ldh_g = (self.hg.data_ptr(), self.hg.shape[-1]) if t > 0 else (None, 0)
-                d.c_prev = c_prev.data_ptr() if t > 0 else None
-                d.c_out, d.h_out, d.ldh = c_out.data_ptr(), h_out.data_ptr(), self.Fp
-                d.npix, d.filters, d.rec_act, d.act, d.dtype = B * H * W, F, self.rk, L.act, code
-                check(lib.satcv_convlstm_gates_fwd(C.byref(d), st))
-        self.h_last = self.hseq[(T - 1) * B:]
-        return lt.Act(self.hseq if L.rs else self.h_last, F)
+        """x: lstm_tools.Act, time-major (T * B, H, W, Cpad).  -> Act of the raw output: lstm_tools.convlstm_forward, the tape's routine,
+        on the plan's buffers and images, the c of step t in slot t & 1"""
+        out, self.h_last = lt.convlstm_forward(self.layer, x, self.T, self.B, self.wk, self.wr, self.bias, self.xg, self.hseq,
+                                               lambda t: self.c[t & 1], hg=self.hg, fused=self.fused)
+        return out
 
 
 class _PlannedBN:
@@ -130,16 +104,7 @@ class _PlannedBN:
         self.shift = torch.empty(cp, dtype=torch.float32, device=lt._dev())
 
     def refresh(self):
-        P, n, c, cp = self.bn.P, self.bn.name, self.bn.c, self.cp
-
-        def padded(v, fill):
-            if cp == c:
-                return v
-            out = torch.full((cp,), fill, dtype=torch.float32, device=v.device)
-            out[:c] = v
-            return out
-        sc, sh = ops.bn_affine_infer(padded(P.p(f'{n}/gamma'), 1.0), padded(P.p(f'{n}/beta'), 0.0), padded(P.p(f'{n}/moving_mean'), 0.0),
-                                     padded(P.p(f'{n}/moving_var'), 1.0), lt.BN_EPS)
+        sc, sh = lt.bn_affine_infer(self.bn, self.cp)
         self.scale.copy_(sc); self.shift.copy_(sh)
 
     def apply(self, a, relu=True):
@@ -265,23 +230,15 @@ class SeriesInferPlan(_ConvLstmPlan):
 
     # ------------------------------------------------------------------ the launch list (the structure of _forward_ingested, inference)
     def _launch(self):
-        B, T, H, W = self.shape
         h2 = self._launch_lstm()
         if not self.is_ae:
-            feats = self.bn2.apply(h2)
-            srcs = [(feats, False)]
+            srcs = [(self.bn2.apply(h2), False)]
         else:
             # build_lstm_layers2: ReLU(state_h + BatchNorm(h2)), state_h the first layer's last hidden state; the decoder branch
             # (`temporal`) is left out, as in LSTMAutoencoder.predict_on_device
-            z2 = self.bn2.apply(h2, relu=False)
-            state_h, out = self.l1.h_last, self.enc_out
-            check(lib.satcv_add_act(z2.t.data_ptr(), z2.scale.data_ptr(), z2.shift.data_ptr(), state_h.data_ptr(), None, None, 1, out.data_ptr(),
-                                    B * H * W, out.shape[-1], ops.DTYPE_CODE[out.dtype], ops.stream_ptr()))
-            srcs = [(lt.Act(out, self.l1.F), False), (lt.Act(self.sc_in, 2), False)]
-        d = self.head._desc(srcs, (H, W))
-        d.out, d.npix = self.out.data_ptr(), B * H * W
-        d.classes = self.classes.data_ptr() if self.classes is not None else None
-        check(lib.satcv_dense_small_fwd(C.byref(d), ops.stream_ptr()))
+            lt.lstm_layers2_tail(self.bn2.apply(h2, relu=False), self.l1.h_last, self.enc_out)
+            srcs = [(lt.Act(self.enc_out, self.l1.F), False), (lt.Act(self.sc_in, 2), False)]
+        self.head.forward(srcs, out=self.out, classes=self.classes)
 
     # ------------------------------------------------------------------ run
     def _stage(self, dst, src, lead, what):
@@ -336,11 +293,7 @@ class HybridInferPlan(_ConvLstmPlan):
 
     def _launch(self):
         """the captured chain: conv_lstm -> batch_norm -> dilated_conv_lstm -> batch_norm2 -> lstm_dense (ReLU), into self.zl"""
-        m, (B, S, SL) = self.model, self.shape
-        feats = self.bn2.apply(self._launch_lstm())
-        d = m.lstm_dense._desc([(feats, False)], (SL, SL))
-        d.out, d.npix = self.zl.data_ptr(), B * SL * SL
-        check(lib.satcv_dense_small_fwd(C.byref(d), ops.stream_ptr()))
+        self.model.lstm_dense.forward([(self.bn2.apply(self._launch_lstm()), False)], out=self.zl)
 
     def run(self, xu, xt, scene_head=None, want_classes=False):
         """xu: (n, side, side, C) float32 CUDA tensor, xt: the ingested time-major tensor (T * n, side_lo, side_lo, cpad), n <= batch (a
@@ -350,7 +303,7 @@ class HybridInferPlan(_ConvLstmPlan):
         Everything returned, and everything the descriptor points to, belongs to the plan and is overwritten by its next run."""
         m, (B, S, SL) = self.model, self.shape
         self._check_dtype()
-        if not (isinstance(xu, torch.Tensor) and xu.is_cuda and xu.dtype == torch.float32 and xu.dim() == 4 and tuple(xu.shape[1:]) == (S, S, m.hi_channels)):
+        if not (m._is_fine_batch(xu) and tuple(xu.shape[1:3]) == (S, S)):
             raise ValueError(f'xu: expected an (n, {S}, {S}, {m.hi_channels}) float32 CUDA tensor, got {getattr(xu, "dtype", None)} {tuple(getattr(xu, "shape", ()))}')
         n = _stage_prefix(self.x_in, xt, self.T, B, 'xt')
         if xu.shape[0] != n:
@@ -358,14 +311,10 @@ class HybridInferPlan(_ConvLstmPlan):
         self._refresh()
         _, zu = m._unet_branch(xu, False)
         self._run_captured()
-        srcs = m._fusion_sources(self.zl[:n], zu)
-        d = m.fusion._desc(srcs, (S, S))
-        d.npix = n * S * S
-        if scene_head is not None:
-            return scene_head(d)
-        if self.out is None:
+        if scene_head is None and self.out is None:
             self.out = torch.empty(B, S, S, m.n_classes, dtype=torch.float32, device=self.zl.device)
             self.classes = torch.empty(B, S, S, dtype=torch.int32, device=self.zl.device)
-        d.out, d.classes = self.out.data_ptr(), self.classes.data_ptr()
-        check(lib.satcv_dense_small_fwd(C.byref(d), ops.stream_ptr()))
+        res = m._fuse(self.zl[:n], zu, scene_head, out=self.out, classes=self.classes)
+        if scene_head is not None:
+            return res
         return (self.out[:n], self.classes[:n]) if want_classes else self.out[:n]

@@ -25,7 +25,7 @@ import torch
 from . import ops, switches
 from . import model_tools as mt
 from .training import MeanIoU, resolve_optimizer, resolve_loss, reset_slots_on_recompile, apply_optimizer, metric_from_confusion, fit_loop
-from ._lib import lib, check, F32, BF16, LstmGatesDesc, DenseDesc
+from ._lib import lib, check, F32, BF16, LstmGatesDesc, LstmStepDesc, DenseDesc
 from .params import FlatParams
 
 RECURRENT_ACTIVATION = switches.read('lstm_recurrent_activation')
@@ -138,6 +138,47 @@ class Act:
 
 
 # ------------------------------------------------------------------------------------------------ layers
+def _rec_act_code():
+    return 0 if RECURRENT_ACTIVATION == 'hard_sigmoid' else 1
+
+
+def convlstm_forward(layer, x, T, B, wk, wr, bias, xg, hseq, c_at, hg=None, gates=None, stats=None, repeat=False, fused=False):
+    """THE launch list of one ConvLSTM2D forward, for the tape (ConvLSTM2D.forward: fresh tensors, a T-deep c sequence, gates and statistics
+    for the backward) and for the inference plans (lstm_infer._PlannedLayer.launch: preallocated buffers, a two-slot c ring, the plan's own
+    operand images) -- the only place that fills LstmGatesDesc for the forward, and the only one that fills LstmStepDesc.
+    x: Act, time-major (T * B, H, W, Cpad), or ONE image set (B, ...) with `repeat`; wk / wr / bias: packed input and recurrent images and
+    the bias; written: xg ((T * B | B), H, W, 4 F), hseq (T * B, H, W, Fp; the pad channels are the caller's zeros), c_at(t) (npix, F)
+    float32 of step t, gates[t] (npix, 4 F) and the statistics rows where given.  hg: the buffer every recurrent convolution writes (None:
+    a fresh one per step).  Per step: the recurrent ops.conv2d (t > 0) + satcv_convlstm_gates_fwd, or with `fused` (inference: no gates,
+    no statistics; operands in lstm_infer.gate_order) ONE satcv_convlstm_step_fwd.  -> (raw output Act, the last hidden state)"""
+    F, (_, H, W, Fp) = layer.F, hseq.shape
+    assert not fused or (gates is None and stats is None)
+    ops.conv2d(x.t, wk, 4 * F, dil=layer.dil, bias=bias, in_scale=x.scale, in_shift=x.shift, in_relu=x.relu, out=xg)
+    st, rk, code, ldx = ops.stream_ptr(), _rec_act_code(), ops.DTYPE_CODE[xg.dtype], xg.shape[-1]
+    for t in range(T):
+        xg_t = xg if repeat else xg[t * B:(t + 1) * B]
+        h_prev, c_prev = (hseq[(t - 1) * B:t * B], c_at(t - 1)) if t > 0 else (None, None)
+        if fused:
+            d = LstmStepDesc()
+            d.h_prev, d.ldh_prev = (h_prev.data_ptr(), Fp) if t > 0 else (None, 0)
+            d.w, d.n, d.h, d.w_ = wr.data_ptr(), B, H, W
+        else:
+            hg_t = ops.conv2d(h_prev, wr, 4 * F, out=hg) if t > 0 else None
+            d = LstmGatesDesc()
+            d.hg, d.ldh_g = (hg_t.data_ptr(), hg_t.shape[-1]) if t > 0 else (None, 0)
+            d.gates_out = gates[t].data_ptr() if gates is not None else None
+            if stats is not None and (layer.rs or t == T - 1):
+                d.stats, d.stats_ld = stats.data_ptr(), Fp
+            d.npix = B * H * W
+        d.xg, d.ldx = xg_t.data_ptr(), ldx
+        d.c_prev = c_prev.data_ptr() if t > 0 else None
+        d.c_out, d.h_out, d.ldh = c_at(t).data_ptr(), hseq[t * B:(t + 1) * B].data_ptr(), Fp
+        d.filters, d.rec_act, d.act, d.dtype = F, rk, layer.act, code
+        check((lib.satcv_convlstm_step_fwd if fused else lib.satcv_convlstm_gates_fwd)(C.byref(d), st))
+    h_last = hseq[(T - 1) * B:]
+    return Act(hseq if layer.rs else h_last, F), h_last
+
+
 class ConvLSTM2D:
     """layers.ConvLSTM2D(filters, [3, 3], padding='same', activation=None, dilation_rate=d, return_sequences=..., return_state=...)
     (utils/model_tools.py:690-700, 710-720)"""
@@ -175,29 +216,15 @@ class ConvLSTM2D:
         td = x.t.dtype
         dev = x.t.device
         Fp = ops.rup(F, 16)
-        xg = ops.conv2d(x.t, self.wk, 4 * F, dil=self.dil, bias=P.p(f'{self.name}/bias'), in_scale=x.scale, in_shift=x.shift, in_relu=x.relu)
+        xg = torch.empty(n, H, W, ops.rup(4 * F, 16), dtype=td, device=dev)
         hseq = torch.zeros(T * B, H, W, Fp, dtype=td, device=dev)
         cseq = torch.empty(T, B * H * W, F, dtype=torch.float32, device=dev)
         gates = torch.empty(T, B * H * W, 4 * F, dtype=td, device=dev) if training else None
         stats = ops.new_stats(Fp, dev) if want_stats else None
-        rk = 0 if RECURRENT_ACTIVATION == 'hard_sigmoid' else 1
-        npix = B * H * W
-        for t in range(T):
-            hg = ops.conv2d(hseq[(t - 1) * B:t * B], self.wr, 4 * F) if t > 0 else None
-            d = LstmGatesDesc()
-            d.xg, d.ldx = (xg if repeat else xg[t * B:(t + 1) * B]).data_ptr(), xg.shape[-1]
-            d.hg, d.ldh_g = (hg.data_ptr(), hg.shape[-1]) if hg is not None else (None, 0)
-            d.c_prev = cseq[t - 1].data_ptr() if t > 0 else None
-            d.c_out, d.h_out, d.ldh = cseq[t].data_ptr(), hseq[t * B:(t + 1) * B].data_ptr(), Fp
-            d.gates_out = gates[t].data_ptr() if gates is not None else None
-            if stats is not None and (self.rs or t == T - 1):
-                d.stats, d.stats_ld = stats.data_ptr(), Fp
-            d.npix, d.filters, d.rec_act, d.act, d.dtype = npix, F, rk, self.act, ops.DTYPE_CODE[td]
-            check(lib.satcv_convlstm_gates_fwd(C.byref(d), ops.stream_ptr()))
-        self.ctx = dict(x=x, T=T, B=B, H=H, W=W, hseq=hseq, cseq=cseq, gates=gates, rk=rk, td=td, repeat=repeat)
-        out = hseq if self.rs else hseq[(T - 1) * B:]
-        self.h_last = hseq[(T - 1) * B:]
-        return Act(out, F), stats, (T * B * H * W if self.rs else B * H * W)
+        out, self.h_last = convlstm_forward(self, x, T, B, self.wk, self.wr, P.p(f'{self.name}/bias'), xg, hseq, cseq.__getitem__,
+                                            gates=gates, stats=stats, repeat=repeat)
+        self.ctx = dict(x=x, T=T, B=B, H=H, W=W, hseq=hseq, cseq=cseq, gates=gates, rk=_rec_act_code(), td=td, repeat=repeat)
+        return out, stats, (T * B * H * W if self.rs else B * H * W)
 
     def backward(self, dout, dstate_h=None, need_dx=True):
         """dout: gradient of the returned tensor (storage type, F padded channels), dstate_h: gradient of the final hidden state taken
@@ -257,6 +284,23 @@ class ConvLSTM2D:
         return ops.conv2d_dgrad(dz_in, self.wk_d, self.cin, dil=self.dil)
 
 
+def bn_vectors(bn, cp):
+    """gamma, beta, moving mean, moving variance of the BatchNorm `bn` over the STORED channel count cp: the parameters themselves where
+    cp is the real count, else copies whose pad channels are the identity (the pad channels of the data hold zeros: scale 1, shift 0)"""
+    vs = [bn.P.p(f'{bn.name}/{k}') for k in ('gamma', 'beta', 'moving_mean', 'moving_var')]
+    if cp == bn.c:
+        return vs
+    out = [torch.full((cp,), fill, dtype=torch.float32, device=v.device) for v, fill in zip(vs, (1.0, 0.0, 0.0, 1.0))]
+    for o, v in zip(out, vs):
+        o[:bn.c] = v
+    return out
+
+
+def bn_affine_infer(bn, cp):
+    """the inference (scale, shift) of `bn` over cp stored channels, from its moving statistics"""
+    return ops.bn_affine_infer(*bn_vectors(bn, cp), BN_EPS)
+
+
 class BatchNorm:
     """layers.BatchNormalization() on a ConvLSTM2D output (statistics over batch, time and space), followed -- or not -- by ReLU"""
 
@@ -270,23 +314,13 @@ class BatchNorm:
     def forward(self, a, stats, count, training, relu=True, bessel=True):
         P, n = self.P, self.name
         cp = a.t.shape[-1]
-
-        def padded(v, fill):                         # per-channel vectors over the PADDED channel count (pad channels hold zeros: scale 1, shift 0)
-            if cp == self.c:
-                return v
-            out = torch.full((cp,), fill, dtype=torch.float32, device=v.device)
-            out[:self.c] = v
-            return out
         if training:
-            g, b = padded(P.p(f'{n}/gamma'), 1.0), padded(P.p(f'{n}/beta'), 0.0)
-            mm, mv = padded(P.p(f'{n}/moving_mean'), 0.0), padded(P.p(f'{n}/moving_var'), 1.0)
+            g, b, mm, mv = bn_vectors(self, cp)
             scale, shift, mean, rstd = ops.bn_finalize_train(stats, count, g, b, mm, mv, BN_EPS, BN_MOMENTUM, 1, bessel)
             if cp != self.c:
                 P.p(f'{n}/moving_mean').copy_(mm[:self.c]); P.p(f'{n}/moving_var').copy_(mv[:self.c])
         else:
-            scale, shift = ops.bn_affine_infer(padded(P.p(f'{n}/gamma'), 1.0), padded(P.p(f'{n}/beta'), 0.0),
-                                               padded(P.p(f'{n}/moving_mean'), 0.0), padded(P.p(f'{n}/moving_var'), 1.0), BN_EPS)
-            mean = rstd = None
+            (scale, shift), mean, rstd = bn_affine_infer(self, cp), None, None
         self.ctx = dict(a=a, relu=relu)
         out = Act(a.t, a.c, (scale, shift, mean, rstd), relu)
         self.out = out
@@ -385,14 +419,17 @@ class Dense1x1:
             self._id = (torch.ones(c, dtype=torch.float32, device=dev), torch.zeros(c, dtype=torch.float32, device=dev))
         return self._id
 
-    def forward(self, srcs, out_hw=None, want_classes=False):
-        """srcs: list of (Act, resize flag).  Returns float32 (N, H, W, cout) (and int32 classes for softmax heads)."""
+    def forward(self, srcs, out_hw=None, want_classes=False, out=None, classes=None):
+        """srcs: list of (Act, resize flag).  Returns float32 (N, H, W, cout) (and int32 classes for softmax heads).  out= / classes=: the
+        tensors to write (an inference plan's own, at least N images deep) instead of fresh ones."""
         a0 = srcs[0][0]
         nimg = a0.t.shape[0]
         H, W = out_hw if out_hw is not None else (a0.t.shape[1], a0.t.shape[2])
         d = self._desc(srcs, (H, W))
-        out = torch.empty(nimg, H, W, self.cout, dtype=torch.float32, device=a0.t.device)
-        classes = torch.empty(nimg, H, W, dtype=torch.int32, device=a0.t.device) if (want_classes and self.activation == 0) else None
+        if out is None:
+            out = torch.empty(nimg, H, W, self.cout, dtype=torch.float32, device=a0.t.device)
+        if classes is None and want_classes and self.activation == 0:
+            classes = torch.empty(nimg, H, W, dtype=torch.int32, device=a0.t.device)
         d.out, d.classes, d.npix = out.data_ptr(), classes.data_ptr() if classes is not None else None, nimg * H * W
         check(lib.satcv_dense_small_fwd(C.byref(d), ops.stream_ptr()))
         self.ctx = dict(srcs=srcs, hw=(H, W), out=out)
@@ -434,66 +471,62 @@ class LSTMLayers:
         self.bn2 = BatchNorm(params, prefix + 'batch_norm2', filters)
         self.F = filters
 
-    def forward(self, x, T, B, training, dtype):
-        s1, st1, n1 = self.l1.forward(x, T, B, training, dtype)
+    def forward(self, x, T, B, training, dtype, relu=True):
+        # (statistics only where BatchNorm reads them: in eval mode the gate launches are then field for field an unfused plan's)
+        s1, st1, n1 = self.l1.forward(x, T, B, training, dtype, want_stats=training)
         a1 = self.bn1.forward(s1, st1, n1, training)
         if self.drop is not None:
             a1 = self.drop.forward(a1, training)
-        h2, st2, n2 = self.l2.forward(a1, T, B, training, dtype)
-        return self.bn2.forward(h2, st2, n2, training)
+        h2, st2, n2 = self.l2.forward(a1, T, B, training, dtype, want_stats=training)
+        return self.bn2.forward(h2, st2, n2, training, relu=relu)
 
-    def backward(self, da2, need_dx=False):
+    def backward(self, da2, need_dx=False, dstate_h=None):
         dh2 = self.bn2.backward(da2)
         da1 = self.l2.backward(dh2)
         if self.drop is not None:
             da1 = self.drop.backward(da1)
         ds1 = self.bn1.backward(da1)
-        return self.l1.backward(ds1, need_dx=need_dx)
+        return self.l1.backward(ds1, dstate_h=dstate_h, need_dx=need_dx)
 
 
-class LSTMLayers2:
+def lstm_layers2_tail(z2, state_h, out):
+    """the tail of build_lstm_layers2, on the tape (LSTMLayers2.forward) and in SeriesInferPlan._launch: out = ReLU(state_h + BatchNorm(h2)),
+    z2 the second layer's raw output Act with its pending BatchNorm, state_h the first layer's last hidden state; -> out"""
+    nb, H, W, cp = state_h.shape
+    check(lib.satcv_add_act(z2.t.data_ptr(), z2.scale.data_ptr(), z2.shift.data_ptr(), state_h.data_ptr(), None, None, 1, out.data_ptr(),
+                            nb * H * W, cp, ops.DTYPE_CODE[out.dtype], ops.stream_ptr()))
+    return out
+
+
+class LSTMLayers2(LSTMLayers):
     """build_lstm_layers2 (utils/model_tools.py:719-771): ConvLSTM2D(16, return_sequences, return_state) 'conv_lstm' -> BatchNormalization
     'batch_norm' -> ReLU -> ConvLSTM2D(16, dilation (3, 3), last state) 'dilated_conv_lstm' -> BatchNormalization 'batch_norm2';
-    output = ReLU(state_h + normalized2) with state_h the FIRST layer's final hidden state."""
+    output = ReLU(state_h + normalized2) with state_h the FIRST layer's final hidden state.  The same stack as build_lstm_layers (its
+    Dropout is :752-753 here) with the last ReLU moved behind the residual."""
 
     def __init__(self, params, rng, n_channels, filters=16, prefix='', dropout=None):
-        self.l1 = ConvLSTM2D(params, rng, prefix + 'conv_lstm', n_channels, filters, 1, True)
-        self.bn1 = BatchNorm(params, prefix + 'batch_norm', filters)
-        self.drop = Dropout(dropout, False, rng.integers(1 << 62)) if dropout else None       # layers.Dropout(dropout)(activated), :752-753
-        self.l2 = ConvLSTM2D(params, rng, prefix + 'dilated_conv_lstm', filters, filters, 3, False)
-        self.bn2 = BatchNorm(params, prefix + 'batch_norm2', filters)
-        self.F = filters
+        super().__init__(params, rng, n_channels, filters, False, prefix, dropout)
 
     def forward(self, x, T, B, training, dtype):
-        s1, st1, n1 = self.l1.forward(x, T, B, training, dtype)
-        a1 = self.bn1.forward(s1, st1, n1, training)
-        if self.drop is not None:
-            a1 = self.drop.forward(a1, training)
-        h2, st2, n2 = self.l2.forward(a1, T, B, training, dtype)
-        z2 = self.bn2.forward(h2, st2, n2, training, relu=False)
-        state_h = self.l1.h_last
-        out = torch.empty_like(state_h)
-        nb, H, W, cp = state_h.shape
-        check(lib.satcv_add_act(z2.t.data_ptr(), z2.scale.data_ptr(), z2.shift.data_ptr(), state_h.data_ptr(), None, None, 1, out.data_ptr(),
-                                nb * H * W, cp, ops.DTYPE_CODE[out.dtype], ops.stream_ptr()))
-        self.out = out
-        return Act(out, self.F)
+        z2 = super().forward(x, T, B, training, dtype, relu=False)
+        self.out = lstm_layers2_tail(z2, self.l1.h_last, torch.empty_like(self.l1.h_last))
+        return Act(self.out, self.F)
 
     def backward(self, dout, need_dx=False):
         g = dout.clone()
         check(lib.satcv_relu_bwd(self.out.data_ptr(), g.data_ptr(), g.numel(), ops.DTYPE_CODE[g.dtype], ops.stream_ptr()))
-        dh2 = self.bn2.backward(g)                    # the masked gradient serves both addends
-        da1 = self.l2.backward(dh2)
-        if self.drop is not None:
-            da1 = self.drop.backward(da1)
-        ds1 = self.bn1.backward(da1)
-        return self.l1.backward(ds1, dstate_h=g, need_dx=need_dx)
+        return super().backward(g, need_dx, dstate_h=g)           # the masked gradient serves both addends
+
+
+def _dev_f32(a):
+    """host array or tensor -> contiguous float32 tensor on the current device (a tensor that already is one is returned as it is)"""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    return t.to(_dev(), torch.float32).contiguous()
 
 
 def _ingest_seq(x, cpad, dtype):
     """(B, T, H, W, C) float32 host / device array -> time-major storage tensor (T * B, H, W, cpad)"""
-    xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-    xt = xt.to(_dev(), torch.float32).contiguous()
+    xt = _dev_f32(x)
     B, T, H, W, Cc = xt.shape
     out = torch.empty(T * B, H, W, cpad, dtype=ops.TORCH_DTYPE[dtype], device=xt.device)
     check(lib.satcv_ingest_seq(xt.data_ptr(), out.data_ptr(), B, T, H, W, Cc, cpad, dtype, ops.stream_ptr()))
@@ -504,11 +537,6 @@ def _check_ingested(xt, shape, cpad, dtype):
     B, T, H, W = shape
     if tuple(xt.shape) != (T * B, H, W, cpad) or xt.dtype != ops.TORCH_DTYPE[dtype] or not xt.is_contiguous():
         raise ValueError(f'expected a contiguous time-major {ops.TORCH_DTYPE[dtype]} tensor {(T * B, H, W, cpad)}, got {xt.dtype} {tuple(xt.shape)}')
-
-
-def _dev_f32(a):
-    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
-    return t.to(_dev(), torch.float32).contiguous()
 
 
 class _SeqModelBase:
@@ -583,10 +611,7 @@ class _SeqModelBase:
             w = self.__dict__.get('_loss_w_dev')
             if w is None or w.device != out.device:
                 w = self._loss_w_dev = torch.as_tensor(np.asarray(self._loss.weights, dtype=np.float32)).to(out.device)
-        y = y_true if isinstance(y_true, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y_true, dtype=np.float32))
-        y = y.to(out.device, torch.float32).contiguous()
-        loss, dlog = ops.loss_fwd_bwd(self._loss.kind, out, y, w, activation=activation, eps=self._loss.eps)
-        return loss, dlog
+        return ops.loss_fwd_bwd(self._loss.kind, out, _dev_f32(y_true), w, activation=activation, eps=self._loss.eps)
 
     # ---- hipGraph replay of a training step (SATCV_LSTM_GRAPH=0: always eager).  A ConvLSTM2D step is ~300 launches of a few
     # microseconds on the tape (per time step: recurrent convolution, gate kernel, their backward twins): the host, not the GPU, sets
@@ -635,6 +660,19 @@ class _SeqModelBase:
             P.adam_state[0:1].fill_(opt._lr)
         apply_optimizer(opt, P)                  # (clip if asked, then the step of whichever optimizer was compiled)
         P.bump()
+
+    def train_on_batch(self, x, y, sample_weight=None):
+        """one step on a batch: x and y single arrays or lists of them (host or device) in the order `_train_device` takes them -> the loss"""
+        if sample_weight is not None:
+            raise NotImplementedError('sample_weight: the fused device losses have no per-sample weights')
+        if self._loss is None:
+            raise RuntimeError('compile() the model before fit/train')
+        tensors = tuple(_dev_f32(a) for v in (x, y) for a in (v if isinstance(v, (list, tuple)) else [v]))
+        return float(self._graphed_step(self._train_device, tensors).item())
+
+    def _train_device(self, *tensors):
+        """forward, loss, backward and optimizer step on float32 device tensors -> the loss tensor (no host synchronisation inside)"""
+        raise NotImplementedError
 
     def get_weights_dict(self):
         return {k: self.P.p(k).detach().cpu().numpy().copy() for k in self.P.specs}
@@ -836,15 +874,6 @@ class LSTMModel(_SeqModelBase):
     def _eval_outputs(self, xb):
         return [(self._forward(xb, False), 'linear', lambda t: t)]
 
-    def train_on_batch(self, x, y, sample_weight=None):
-        if sample_weight is not None:
-            raise NotImplementedError('sample_weight: the fused device losses have no per-sample weights')
-        if self._loss is None:
-            raise RuntimeError('compile() the model before fit/train')
-        xd = (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))).to(_dev(), torch.float32).contiguous()
-        yd = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y, dtype=np.float32))).to(_dev(), torch.float32).contiguous()
-        return float(self._graphed_step(self._train_device, (xd, yd)).item())
-
     def _train_device(self, xd, yd):
         self.P.gflat.zero_()
         out = self._forward(xd, True)
@@ -863,7 +892,29 @@ def get_lstm_model(n_channels, n_classes, n_time, optim=None, metrics=None, loss
     return m
 
 
-class HybridModel(_SeqModelBase):
+class _TwoResolutionModel(_SeqModelBase):
+    """what HybridModel and HierarchicalModel share: the check of their device input pair [fine batch (n, h, w, hi_channels), coarse
+    sequence of n_time steps of n_channels bands]"""
+
+    def _is_fine_batch(self, xu):
+        return isinstance(xu, torch.Tensor) and xu.is_cuda and xu.dtype == torch.float32 and xu.dim() == 4 and xu.shape[-1] == self.hi_channels
+
+    def _device_inputs(self, xs, shape):
+        """[xu, xt] as the gathers leave them -> (xu, xt, (B, T, hh, ww)), checked"""
+        if not isinstance(xs, (list, tuple)) or len(xs) != 2:
+            raise ValueError('predict_on_device takes the pair [fine batch, coarse sequence]')
+        xu, xl = xs
+        if not self._is_fine_batch(xu):
+            raise ValueError(f'predict_on_device takes the fine batch as an (n, h, w, {self.hi_channels}) float32 CUDA tensor')
+        xt, shape = self._ingested_input(xl, shape)
+        if shape[1] != self.n_time:
+            raise ValueError(f'model was built for {self.n_time} time steps, got {shape[1]}')
+        if shape[0] != xu.shape[0]:
+            raise ValueError(f'the two inputs hold different numbers of chips: {xu.shape[0]} and {shape[0]}')
+        return xu, xt, shape
+
+
+class HybridModel(_TwoResolutionModel):
     """get_hybrid_model (utils/model_tools.py:874-920): a U-Net branch (build_unet_layers, factors [3, 2, 2, 2]) and an LSTM branch
     (build_lstm_layers), each through Conv2D(n_classes, [1, 1], relu); the LSTM map is brought to the U-Net grid with
     tf.image.resize(..., 'nearest'), concatenated [lstm, unet] and classified by Conv2D(n_classes, [1, 1], softmax) 'probabilities'.
@@ -921,33 +972,25 @@ class HybridModel(_SeqModelBase):
         if self.lstm_drop is not None:
             feats = self.lstm_drop.forward(feats, training)
         zl = self.lstm_dense.forward([(feats, False)])                # float32 (B, hh, ww, k), already through its ReLU
+        self._plan, self._zu = plan, zu
+        return self._fuse(zl, zu, scene_head)
+
+    def _fuse(self, zl, zu, scene_head=None, out=None, classes=None):
+        """the fusion step, for the tape and for HybridInferPlan.run: the `lstm_dense` output zl and the `unet_dense` pre-activation zu of
+        the same n = zu.shape[0] chips -> scene_head(the descriptor of the `probabilities` layer, npix set, out NULL), or without one the
+        launched head's (probabilities, classes), written to out / classes where given (a plan's own tensors, at least n chips deep)"""
         n, h, w, _ = zu.shape
         srcs = self._fusion_sources(zl, zu)
-        self._plan, self._zu = plan, zu
         if scene_head is not None:
             d = self.fusion._desc(srcs, (h, w))
             d.npix = n * h * w
             return scene_head(d)
-        return self.fusion.forward(srcs, out_hw=(h, w), want_classes=True)
+        return self.fusion.forward(srcs, out_hw=(h, w), want_classes=True, out=out, classes=classes)
 
     def _forward(self, xs, training):
         xu, xl = xs
         xt, shape = _ingest_seq(xl, ops.rup(self.lstm_dim[-1], 16), self.dtype_code)
         return self._forward_ingested(xu, xt, shape, training)
-
-    def _device_inputs(self, xs, shape):
-        """[xu, xt] as the gathers leave them -> (xu, xt, (B, T, hh, ww)), checked"""
-        if not isinstance(xs, (list, tuple)) or len(xs) != 2:
-            raise ValueError('predict_on_device takes the pair [fine batch, coarse sequence]')
-        xu, xl = xs
-        if not (isinstance(xu, torch.Tensor) and xu.is_cuda and xu.dtype == torch.float32 and xu.dim() == 4 and xu.shape[-1] == self.hi_channels):
-            raise ValueError(f'predict_on_device takes the fine batch as an (n, h, w, {self.hi_channels}) float32 CUDA tensor')
-        xt, shape = self._ingested_input(xl, shape)
-        if shape[1] != self.n_time:
-            raise ValueError(f'model was built for {self.n_time} time steps, got {shape[1]}')
-        if shape[0] != xu.shape[0]:
-            raise ValueError(f'the two inputs hold different numbers of chips: {xu.shape[0]} and {shape[0]}')
-        return xu, xt, shape
 
     def predict_on_device(self, xs, shape=None, want_classes=False, scene_head=None):
         """Inference that stays on the device.  xs = [xu, xt]: the fine batch, an (n, side, side, C) float32 CUDA tensor, and the coarse
@@ -981,15 +1024,13 @@ class HybridModel(_SeqModelBase):
     def _eval_outputs(self, xb):
         return [(self._forward(xb, False)[0], 'softmax', lambda t: t)]
 
-    def train_on_batch(self, x, y, sample_weight=None):
-        if sample_weight is not None:
-            raise NotImplementedError('sample_weight: the fused device losses have no per-sample weights')
-        if self._loss is None:
-            raise RuntimeError('compile() the model before fit/train')
+    _no_graph = True             # the step stays eager: its U-Net branch runs an engine plan (own streams, own optimizer launch)
+
+    def _train_device(self, xu, xl, y):
         rt = self.unet.runtime
         rt.opt_slots(self.optimizer)
         self.P.gflat.zero_(); rt.gflat.zero_()
-        probs, _ = self._forward(x, True)
+        probs, _ = self._forward([xu, xl], True)
         loss, dlog = self._loss_grad(probs, y, 'softmax')
         dzl, dau = self.fusion.backward(dlog, need_dx=(True, True))
         (dfeat,) = self.lstm_dense.backward(dzl, need_dx=(True,))
@@ -1005,8 +1046,8 @@ class HybridModel(_SeqModelBase):
         rt.adam_state[0:1].fill_(opt._lr)
         apply_optimizer(opt, rt)
         rt.weights_changed()
-        self._adam()
-        return float(loss.item())
+        self._adam(set_lr=False)             # (the tape's state buffer got the learning rate in _graphed_step, before the step began)
+        return loss
 
 
 def get_hybrid_model(unet_dim, lstm_dim, n_classes, filters=[32, 64, 128, 256], factors=[3, 2, 2, 2], dropout=None, compile_model=False,
@@ -1051,9 +1092,7 @@ class LSTMAutoencoder(_SeqModelBase):
         if temporal:
             dseq, _, _ = self.dec.forward(enc, T, B, training, self.dtype_code, want_stats=False, repeat=True)
             tout = self.temporal.forward([(dseq, False)])                     # (T * B, H, W, k), time-major
-        sc = sincos if isinstance(sincos, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(sincos, dtype=np.float32))
-        sc = sc.to(_dev(), torch.float32).contiguous()
-        sout = self.single.forward([(enc, False), (Act(sc, 2), False)])
+        sout = self.single.forward([(enc, False), (Act(_dev_f32(sincos), 2), False)])
         return tout, sout
 
     def predict_on_device(self, xs, shape=None):
@@ -1081,12 +1120,10 @@ class LSTMAutoencoder(_SeqModelBase):
         return [(tout, 'linear', lambda t: t.permute(1, 0, 2, 3, 4).contiguous().view(T * B, H, W, -1)), (sout, 'linear', lambda t: t)]
 
     def train_on_batch(self, x, y, sample_weight=None):
+        """(a generator built without weights yields a list of Nones: accepted)"""
         if sample_weight is not None and any(w is not None for w in (sample_weight if isinstance(sample_weight, (list, tuple)) else [sample_weight])):
             raise NotImplementedError('sample_weight: the fused device losses have no per-sample weights (LSTMAutoencoderGenerator(sample_weights=False))')
-        if self._loss is None:
-            raise RuntimeError('compile() the model before fit/train')
-        tensors = tuple(_dev_f32(a) for a in x) + tuple(_dev_f32(a) for a in y)
-        return float(self._graphed_step(self._train_device, tensors).item())
+        return super().train_on_batch(x, y)
 
     def _train_device(self, xs, sincos, ty, sy):
         self.P.gflat.zero_()
@@ -1221,7 +1258,7 @@ class ACNN2Trunk:
                 dfa_next = g
 
 
-class HierarchicalModel(_SeqModelBase):
+class HierarchicalModel(_TwoResolutionModel):
     """get_hierarchical_model (utils/model_tools.py:1016-1060): get_acnn_model2's trunk with three softmax heads -- 'sub_probs' on the
     middle block's ReLU{(depth-1)//2}_2, 'acnn_probs' on the last block's, 'lstm_probs' on concat([nearest-resized build_lstm_layers output,
     last block's activation]).  Inputs [acnn_input (B, H, W, C), lstm_input (B, T, h, w, c)], outputs [sub_probs, acnn_probs, lstm_probs]."""
@@ -1239,15 +1276,33 @@ class HierarchicalModel(_SeqModelBase):
         self._finish()
 
     def _forward(self, xs, training):
-        xa, xl = xs
-        xa = xa if isinstance(xa, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(xa, dtype=np.float32))
-        x = ops.ingest_nhwc(xa.to(_dev(), torch.float32), ops.rup(self.acnn_dim[-1], 16), self.dtype_code)
+        return self._forward_ingested(_dev_f32(xs[0]), xs[1], None, training, self.output_names)
+
+    def _forward_ingested(self, xa, xt, shape, training, outputs, scene_head=None):
+        """xa: the fine batch (n, H, W, C), float32 on the device; xt: the time-major storage tensor (T * n, hh, ww, cpad) with shape =
+        (n, T, hh, ww) -- or, with shape=None, the sequence (n, T, hh, ww, c) itself, ingested where the ConvLSTM branch begins (behind
+        the trunk: the launch order of the training step).  -> the heads named in `outputs` (of output_names), in that order; the ConvLSTM
+        branch runs only if 'lstm_probs' is among them.  With `scene_head` a head is not launched: the callable receives its descriptor
+        (sources, weights, grid, npix) and its result takes the head's place."""
+        x = ops.ingest_nhwc(xa, ops.rup(self.acnn_dim[-1], 16), self.dtype_code)
         feats = self.trunk.forward(Act(x, self.acnn_dim[-1]), training, self.dtype_code)
-        xt, (B, T, hh, ww) = _ingest_seq(xl, ops.rup(self.lstm_dim[-1], 16), self.dtype_code)
-        lf = self.lstm.forward(Act(xt, self.lstm_dim[-1]), T, B, training, self.dtype_code)
-        H, W = x.shape[1], x.shape[2]
-        return [self.sub.forward([(feats[self.mid], False)]), self.acnn.forward([(feats[-1], False)]),
-                self.fuse.forward([(lf, True), (feats[-1], False)], out_hw=(H, W))]
+        n, H, W, _ = x.shape
+        heads = {'sub_probs': (self.sub, [(feats[self.mid], False)]), 'acnn_probs': (self.acnn, [(feats[-1], False)])}
+        if 'lstm_probs' in outputs:
+            if shape is None:
+                xt, shape = _ingest_seq(xt, ops.rup(self.lstm_dim[-1], 16), self.dtype_code)
+            lf = self.lstm.forward(Act(xt, self.lstm_dim[-1]), shape[1], shape[0], training, self.dtype_code)
+            heads['lstm_probs'] = (self.fuse, [(lf, True), (feats[-1], False)])
+        res = []
+        for name in outputs:
+            head, srcs = heads[name]
+            if scene_head is not None:
+                d = head._desc(srcs, (H, W))
+                d.npix = n * H * W
+                res.append(scene_head(d))
+            else:
+                res.append(head.forward(srcs, out_hw=(H, W)))
+        return res
 
     def predict(self, x, batch_size=None, verbose=0, **kw):
         return [o.cpu().numpy() for o in self._forward(x, False)]
@@ -1262,45 +1317,13 @@ class HierarchicalModel(_SeqModelBase):
         sources, weights, grid and npix set, out NULL) and its result is returned."""
         if output not in self.output_names:
             raise ValueError(f'output must be one of {self.output_names}, got {output!r}')
-        if not isinstance(xs, (list, tuple)) or len(xs) != 2:
-            raise ValueError('predict_on_device takes the pair [fine batch, coarse sequence]')
-        xa, xl = xs
-        if not (isinstance(xa, torch.Tensor) and xa.is_cuda and xa.dtype == torch.float32 and xa.dim() == 4 and xa.shape[-1] == self.hi_channels):
-            raise ValueError(f'predict_on_device takes the fine batch as an (n, h, w, {self.hi_channels}) float32 CUDA tensor')
-        xt, shape = self._ingested_input(xl, shape)
-        B, T, hh, ww = shape
-        if T != self.n_time:
-            raise ValueError(f'model was built for {self.n_time} time steps, got {T}')
-        if B != xa.shape[0]:
-            raise ValueError(f'the two inputs hold different numbers of chips: {xa.shape[0]} and {B}')
-        x = ops.ingest_nhwc(xa.contiguous(), ops.rup(self.acnn_dim[-1], 16), self.dtype_code)
-        feats = self.trunk.forward(Act(x, self.acnn_dim[-1]), False, self.dtype_code)
-        n, H, W = x.shape[0], x.shape[1], x.shape[2]
-        if output == 'sub_probs':
-            head, srcs = self.sub, [(feats[self.mid], False)]
-        elif output == 'acnn_probs':
-            head, srcs = self.acnn, [(feats[-1], False)]
-        else:
-            lf = self.lstm.forward(Act(xt, self.lstm_dim[-1]), T, B, False, self.dtype_code)
-            head, srcs = self.fuse, [(lf, True), (feats[-1], False)]
-        if scene_head is not None:
-            d = head._desc(srcs, (H, W))
-            d.npix = n * H * W
-            return scene_head(d)
-        return head.forward(srcs, out_hw=(H, W))
+        xa, xt, shape = self._device_inputs(xs, shape)
+        return self._forward_ingested(xa, xt, shape, False, (output,), scene_head=scene_head)[0]
 
     output_names = ('sub_probs', 'acnn_probs', 'lstm_probs')
 
     def _eval_outputs(self, xb):
         return [(o, 'softmax', lambda t: t) for o in self._forward(xb, False)]
-
-    def train_on_batch(self, x, y, sample_weight=None):
-        if sample_weight is not None:
-            raise NotImplementedError('sample_weight: the fused device losses have no per-sample weights')
-        if self._loss is None:
-            raise RuntimeError('compile() the model before fit/train')
-        tensors = tuple(_dev_f32(a) for a in x) + tuple(_dev_f32(a) for a in y)
-        return float(self._graphed_step(self._train_device, tensors).item())
 
     def _train_device(self, xa, xl, y0, y1, y2):
         self.P.gflat.zero_()

@@ -14,7 +14,10 @@ tests/test_fp8_gpu.py::test_folded_lowering_reaches_its_forms.  A case is Folded
                  initialised model would hide an error in the folding); x a batch, a pair of batches for the Siamese graph
   store          'bf16' | 'fp8' (fp8: the scales come from fp8_infer.calibrate on x)
   plan_kw        hybrid / first_bf16 / pair of fp8_infer.Fp8Plan
-  arms           what the case is there to reach (documentation; folded_forms() says what a recorded run did reach)"""
+  arms           what the case is there to reach (documentation; folded_forms() says what a recorded run did reach)
+
+SERIES_CASES are the inference passes of the ConvLSTM2D family (lstm_tools' tape, lstm_infer's plans), for the same tool (--series):
+predict_on_device, an unfused plan eager and replayed, a fused plan -- see the list."""
 from collections import Counter, namedtuple
 
 import numpy as np
@@ -252,6 +255,86 @@ FOLDED_CASES = [
     FoldedCase('two-date extras bf16', _f_two_date_extras, 'bf16', dict(pair=True), 'two-date dropout, two-date separate max-pool (2n images), centre-tap cut'),
 ]
 FOLDED_IN_SUITE = ('siamese bf16 paired', 'siamese bf16 unpaired', 'unet3 fp8 hybrid', 'hybrid-branch bf16')
+
+
+# ------------------------------------------------------------------ inference of the ConvLSTM2D family (lstm_tools, lstm_infer)
+SeriesCase = namedtuple('SeriesCase', 'name make dtype')
+
+
+def randomise(m, seed):
+    """non-trivial BatchNorm statistics and biases of a tape model; the kernels keep their initialisers"""
+    rng = np.random.default_rng(seed)
+    w = {}
+    for k, v in m.get_weights_dict().items():
+        if k.endswith('/moving_var'):
+            w[k] = (0.5 + rng.random(v.shape)).astype(np.float32)
+        elif k.endswith('/gamma'):
+            w[k] = (1 + 0.2 * rng.standard_normal(v.shape)).astype(np.float32)
+        elif k.endswith(('/beta', '/moving_mean')):
+            w[k] = (0.2 * rng.standard_normal(v.shape)).astype(np.float32)
+        elif k.endswith('/bias'):
+            w[k] = (v + 0.1 * rng.standard_normal(v.shape)).astype(np.float32)
+    m.set_weights_dict(w)
+    return m
+
+
+def _ingested(lt, m, x):
+    import torch
+    return lt._ingest_seq(torch.from_numpy(x).cuda(), (m.n_channels + 15) // 16 * 16, m.dtype_code)
+
+
+def _plan_passes(run):
+    """the first run of a plan (eager) and its third (the second captures, the third replays), recorded; the second not"""
+    return [('plan, run 1 (eager)', run), (None, run), ('plan, run 3 (replayed)', run)]
+
+
+def _s_series(autoencoder):
+    """get_lstm_model(6, 3, 3) / get_lstm_autoencoder(2, 2, 1) at B = 3, 16 x 16, the shapes of tests/test_series_plan_gpu.py: T = 3 is the
+    smallest length at which the plan's two-slot c ring is reused (step 2 writes slot 0 again) and a step has both neighbours"""
+    def make(mt, lt):
+        import torch
+        mt.set_seed(9 if autoencoder else 7)
+        m = randomise(lt.get_lstm_autoencoder(2, 2, 1) if autoencoder else lt.get_lstm_model(6, 3, 3), 9 if autoencoder else 7)
+        rng = np.random.default_rng(1)
+        x, shape = _ingested(lt, m, rng.random((3, m.n_time, 16, 16, m.n_channels)).astype(np.float32))
+        if autoencoder:
+            x = [x, torch.from_numpy(rng.standard_normal((3, 16, 16, 2)).astype(np.float32)).cuda()]
+        plan = m.inference_plan(shape, fused=False)
+        return m, ([('predict_on_device', lambda: m.predict_on_device(x, shape=shape))] + _plan_passes(lambda: plan.run(x)) +
+                   [('fused plan, run 1', lambda: m.inference_plan(shape, fused=True).run(x))])
+    return make
+
+
+def _s_hybrid(mt, lt):
+    """the hybrid case above: predict_on_device, scene_plan(2, 48, 8) unfused, and that plan on ONE chip (the prefix staging)"""
+    import torch
+    m, (xu, xl), _ = _hybrid(mt, lt)
+    randomise(m, 4)
+    xu = torch.from_numpy(xu).cuda()
+    (xt, shape), (xt1, _) = _ingested(lt, m, xl), _ingested(lt, m, xl[:1])
+    plan = m.scene_plan(2, 48, 8)
+    return m, ([('predict_on_device', lambda: m.predict_on_device([xu, xt], shape=shape, want_classes=True))] +
+               _plan_passes(lambda: plan.run(xu, xt, want_classes=True)) + [('plan, 1 chip (prefix)', lambda: plan.run(xu[:1], xt1, want_classes=True))])
+
+
+def _s_hierarchical(mt, lt):
+    import torch
+    m, (xa, xl), _ = _hierarchical(mt, lt)
+    randomise(m, 4)
+    xa = torch.from_numpy(xa).cuda()
+    xt, shape = _ingested(lt, m, xl)
+    return m, [(f'predict_on_device {o}', lambda o=o: m.predict_on_device([xa, xt], shape=shape, output=o)) for o in m.output_names]
+
+
+# make(mt, lt) -> (model, [(label, pass)]) under the case's compute dtype: every pass returns a tensor or a tuple of tensors; the passes
+# with a label are recorded (tools/plan_manifest.py --series: their library calls and output hashes), one with None only runs
+SERIES_CASES = [
+    SeriesCase('lstm_model fp32', _s_series(False), 'float32'),
+    SeriesCase('lstm_model bf16', _s_series(False), 'bfloat16'),
+    SeriesCase('lstm_autoencoder bf16', _s_series(True), 'bfloat16'),
+    SeriesCase('hybrid', _s_hybrid, 'bfloat16'),
+    SeriesCase('hierarchical', _s_hierarchical, 'float32'),
+]
 
 
 def folded_forms(calls):

@@ -4,6 +4,8 @@
   * a captured plan replays what it ran eagerly: two different inputs through one captured plan, each torch.equal to an eager plan;
   * the fused plan against predict_on_device in float32 within 1e-4 of the output scale, and in bf16 BOTH paths against
     oracle/convlstm.py within 2e-2 -- the two model-level forward bounds of tests/test_lstm_gpu.py (its inference comparison);
+  * the contract structurally: under the call recorder of tools/plan_manifest.py the convolution / gate / add / head launches of
+    predict_on_device and of an unfused plan's first run are the same list, field for field;
   * a filter count the step kernel refuses (LSTMLayers(..., filters=8)) takes the fallback, torch.equal to the tape;
   * predict_series_scene(plan=...) on an int16 (3, 6, 80, 112) stack, kernel 16, buff 16, batch_size 4 (short last batch), both covers.
 """
@@ -14,8 +16,12 @@ import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+HERE = os.path.dirname(os.path.abspath(__file__))
+for _p in (os.path.dirname(HERE), HERE):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
 from oracle import convlstm as CL  # noqa: E402
+from plan_cases import randomise as _randomise  # noqa: E402  (non-trivial BatchNorm statistics and biases; the kernels keep their initialisers)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,23 +38,6 @@ def env():
 
 def rel(got, ref):
     return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-30)
-
-
-def _randomise(m, seed):
-    """non-trivial BatchNorm statistics and biases; the kernels keep their initialisers"""
-    rng = np.random.default_rng(seed)
-    w = {}
-    for k, v in m.get_weights_dict().items():
-        if k.endswith('/moving_var'):
-            w[k] = (0.5 + rng.random(v.shape)).astype(np.float32)
-        elif k.endswith('/gamma'):
-            w[k] = (1 + 0.2 * rng.standard_normal(v.shape)).astype(np.float32)
-        elif k.endswith(('/beta', '/moving_mean')):
-            w[k] = (0.2 * rng.standard_normal(v.shape)).astype(np.float32)
-        elif k.endswith('/bias'):
-            w[k] = (v + 0.1 * rng.standard_normal(v.shape)).astype(np.float32)
-    m.set_weights_dict(w)
-    return m
 
 
 def _lstm(env, dtype, activation='relu', seed=7):
@@ -108,6 +97,41 @@ def test_unfused_plan_of_the_autoencoder_equals_predict_on_device(env, dtype):
     for _ in range(3):
         assert torch.equal(plan.run([xt, sincos]), want)
     assert want.abs().max() > 0
+
+def _launch_list(calls):
+    """the launches the tape and an unfused plan must share, with every non-pointer field; the prologue (weight packing, the BatchNorm
+    affine) legitimately differs: the tape packs through the model's parameter store, the plan into its own images"""
+    names = ('satcv_conv2d_igemm', 'satcv_convlstm_gates_fwd', 'satcv_add_act', 'satcv_dense_small_fwd')
+    return [(name, structs, scalars) for name, _, structs, scalars in calls if name in names]
+
+
+@pytest.mark.parametrize('kind', ['lstm_model', 'autoencoder'])
+def test_unfused_plan_issues_the_launch_list_of_the_tape(env, kind):
+    """`fused=False` issues exactly the tape's launches: both go through lstm_tools.convlstm_forward, the BatchNorm helpers, the
+    build_lstm_layers2 tail and Dense1x1.forward.  bf16, B = 3, 16 x 16: per ConvLSTM2D one input convolution, T gate launches and T - 1
+    recurrent convolutions; one satcv_add_act for the autoencoder's residual; one head."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('plan_manifest', os.path.join(HERE, '..', 'tools', 'plan_manifest.py'))
+    pm = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(pm)
+    from satellite_computervision_amd._lib import lib
+    m = _lstm(env, 'bfloat16') if kind == 'lstm_model' else _autoencoder(env, 'bfloat16')
+    _, x, shape = _ingested(env, m, 21)
+    if kind == 'autoencoder':
+        x = [x, torch.from_numpy(np.random.default_rng(22).standard_normal((B, H, W, 2)).astype(np.float32)).cuda()]
+    plan = m.inference_plan(shape, fused=False)
+    want, tape = pm.record_pass(lib, lambda: m.predict_on_device(x, shape=shape))
+    got, planned = pm.record_pass(lib, lambda: plan.run(x))
+    assert not plan.replaying and plan._runs == 1                        # the recorded run was the eager one
+    tape, planned = _launch_list(tape), _launch_list(planned)
+    steps = m.n_time
+    count = {n: sum(c[0] == n for c in tape) for n in ('satcv_conv2d_igemm', 'satcv_convlstm_gates_fwd', 'satcv_add_act', 'satcv_dense_small_fwd')}
+    assert count == {'satcv_conv2d_igemm': 2 * steps, 'satcv_convlstm_gates_fwd': 2 * steps, 'satcv_add_act': int(kind == 'autoencoder'),
+                     'satcv_dense_small_fwd': 1}
+    assert [c[0] for c in planned] == [c[0] for c in tape]
+    for i, (a, b) in enumerate(zip(planned, tape)):
+        assert a == b, (i, a[0])
+    assert torch.equal(got, want) and want.abs().max() > 0
 
 
 def test_hybrid_and_hierarchical_models_are_refused(env):

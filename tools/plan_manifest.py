@@ -4,7 +4,9 @@ that must not change a launch) on the same library:
     SATCV_LIB=<libsatcv.so> PYTHONPATH=<checkout A> python tools/plan_manifest.py --out a.json
     SATCV_LIB=<libsatcv.so> PYTHONPATH=<checkout B> python tools/plan_manifest.py --out b.json
     python tools/plan_manifest.py --compare a.json b.json [--baseline a2.json]
-With --folded the same for plan_cases.FOLDED_CASES, the folded inference plans of fp8_infer.Fp8Plan (a change of its lowering).
+With --folded the same for plan_cases.FOLDED_CASES, the folded inference plans of fp8_infer.Fp8Plan (a change of its lowering); with
+--series for plan_cases.SERIES_CASES, the inference passes of the ConvLSTM2D family (predict_on_device, lstm_infer's plans eager, replayed
+and fused: a change of lstm_tools.convlstm_forward or of a plan's launch list).
 
 For every case of tests/plan_cases.py (always the list beside THIS file; the package is the first one on the path):
   steps   (phase, label or null, work or null) of every step of plan.fwd and plan.bwd
@@ -154,14 +156,47 @@ def run_folded(case, made=None):
     return dict(steps=[], calls=rec.calls, hashes={f'output{i}': _sha(plan.outputs[t.id]) for i, t in enumerate(m.outputs)}, losses=[])
 
 
-def child_folded(out, only):
+def record_pass(lib, fn):
+    """-> (what fn() returned, the library calls it made)"""
+    import torch
+    rec = Recorder(lib)
+    try:
+        res = fn()
+        torch.cuda.synchronize()
+    finally:
+        rec.restore()
+    return res, rec.calls
+
+
+def run_series(case):
+    """the inference passes of a SeriesCase: the calls of every labelled pass behind a ['# label'] row, and the hashes of what it returned"""
+    from satellite_computervision_amd import lstm_tools as lt, model_tools as mt
+    from satellite_computervision_amd._lib import lib
+    mt.set_compute_dtype(case.dtype)
+    try:
+        _, passes = case.make(mt, lt)
+        calls, hashes = [], {}
+        for label, fn in passes:
+            if label is None:
+                fn()
+                continue
+            res, made = record_pass(lib, fn)
+            calls += [['# ' + label, 'main', [], []]] + made
+            hashes.update({f'{label} / output{i}': _sha(t) for i, t in enumerate(res if isinstance(res, (list, tuple)) else [res])})
+        return dict(steps=[], calls=calls, hashes=hashes, losses=[])
+    finally:
+        mt.set_compute_dtype('bfloat16')
+
+
+def child_folded(out, only, series=False):
     import satellite_computervision_amd
     print('package:', os.path.dirname(satellite_computervision_amd.__file__), flush=True)
     pc = _cases()
     res = {}
-    for c in [c for c in pc.FOLDED_CASES if not only or c.name in only]:
-        res[c.name] = run_folded(c)
-        print(f"{c.name}: {len(res[c.name]['calls'])} calls, reaches {dict(pc.folded_forms(res[c.name]['calls']))}", flush=True)
+    for c in [c for c in (pc.SERIES_CASES if series else pc.FOLDED_CASES) if not only or c.name in only]:
+        res[c.name] = run_series(c) if series else run_folded(c)
+        reach = [r[0] for r in res[c.name]['calls'] if r[0][0] == '#'] if series else dict(pc.folded_forms(res[c.name]['calls']))
+        print(f"{c.name}: {len(res[c.name]['calls'])} calls, reaches {reach}", flush=True)
     json.dump(res, open(out, 'w'), indent=0, sort_keys=True)
 
 
@@ -242,11 +277,12 @@ if __name__ == '__main__':
     ap.add_argument('--baseline', nargs='+', help='further runs of checkout A')
     ap.add_argument('--cases', type=lambda v: v.split(','), help='only these cases (comma-separated names)')
     ap.add_argument('--folded', action='store_true', help='the folded inference cases (plan_cases.FOLDED_CASES), in this process')
+    ap.add_argument('--series', action='store_true', help='the ConvLSTM2D inference cases (plan_cases.SERIES_CASES), in this process')
     a = ap.parse_args()
     if a.compare:
         sys.exit(compare(a.compare[0], a.compare[1], a.baseline))
-    if a.folded:
-        sys.exit(child_folded(a.out, a.cases))
+    if a.folded or a.series:
+        sys.exit(child_folded(a.out, a.cases, series=a.series))
     if a.child is not None:
         child(a.child, a.out, a.cases)
     else:
