@@ -56,7 +56,9 @@ int satcv_ingest_nhwc(const float* src, void* dst, int64_t npix, int32_t c, int3
 /* same with a multiplier (the fp8 path feeds x/q_in so that the reflectances use the upper e4m3 range) */
 int satcv_ingest_nhwc_scaled(const float* src, void* dst, int64_t npix, int32_t c, int32_t cpad, float mul, int32_t dtype, void* stream);
 /* planar CHW (c,h,w) per tile, any of u8/u16/f32 (src_kind 0/1/2), scaled by `scale`
- * -> dtype NHWC (n,h,w,cpad).  Mirrors the CHW->HWC + rescale of utils/processing.py:544-613. */
+ * -> dtype NHWC (n,h,w,cpad): (float)value * scale in float32, then the storage rounding; channels [c,cpad) zero.  dtype SATCV_F32 or
+ * SATCV_BF16.  Mirrors the CHW->HWC + rescale of utils/processing.py:544-613.  Refused: null pointers, n, c, h or w <= 0, cpad < c,
+ * cpad % 8 != 0, another src_kind or dtype. */
 int satcv_ingest_chw(const void* src, int32_t src_kind, float scale, void* dst, int32_t n,
                      int32_t c, int32_t h, int32_t w, int32_t cpad, int32_t dtype, void* stream);
 
@@ -66,7 +68,10 @@ int satcv_ingest_chw(const void* src, int32_t src_kind, float scale, void* dst, 
  * transposed=1: source is a Conv2DTranspose kernel (kh,kw,cout,cin) (utils/model_tools.py:306);
  *   fwd   : [1][cin_pad/8][kh*kw*cout][8]  (N index = (i*kw+j)*cout + o)
  *   dgrad : [1][kh*kw*cout/8][cin_pad32][8] (K index = (i*kw+j)*cout + o)
- * Either destination may be NULL. */
+ * Either destination may be NULL.  Every element outside the kernel's (k, n) range is written as +0; dtype SATCV_F32, SATCV_BF16,
+ * SATCV_FP8 (saturating round-to-nearest-even) or SATCV_FP8X (forward image only, 16-element granules [tap][K/16][Npad][16]).
+ * Refused: a null src; kh, kw, cin or cout <= 0; cin_pad < cin or cin_pad % 16 != 0; SATCV_FP8X with a dgrad destination or without a
+ * forward one; another dtype. */
 int satcv_pack_weights(const float* src, void* dst_fwd, void* dst_dgrad, int32_t kh, int32_t kw,
                        int32_t cin, int32_t cout, int32_t cin_pad, int32_t transposed,
                        int32_t dtype, void* stream);
@@ -74,7 +79,8 @@ int satcv_pack_weights(const float* src, void* dst_fwd, void* dst_dgrad, int32_t
  * kpad / npad = K and N paddings of the image exactly as satcv_pack_weights derives them) and the exclusive prefix sum of
  * satcv_pack_job_items() over the jobs.  satcv_pack_job_items() is the job's number of 16-byte output items ROUNDED UP TO 256: a block of
  * 256 consecutive items then belongs to one job and the kernel looks its job up once per block; total_items must be the sum of those values
- * (SATCV_ERR_INVALID otherwise). */
+ * (SATCV_ERR_INVALID otherwise).  satcv_pack_job_items() returns -1 for a null job, a mode outside 0..3, kpad <= 0 or kpad % 8 != 0,
+ * npad <= 0, or taps, cin or cout <= 0. */
 typedef struct { const float* src; void* dst; int32_t mode, taps, cin, cout, kpad, npad; } satcv_pack_job;
 int64_t satcv_pack_job_items(const satcv_pack_job* job);
 int satcv_pack_weights_batched(const satcv_pack_job* jobs_dev, const int64_t* prefix_dev, int32_t njobs, int64_t total_items, int32_t dtype,
@@ -518,7 +524,19 @@ uint32_t satcv_crc32c(const void* data, uint64_t nbytes, uint32_t crc_in);
  *   ch_mean != NULL: (x - mean)*contra_mul + mean*bright_mul, mean = nanmean over (h, w_) per image and channel from
  *   satcv_tile_channel_mean                                             -- utils/array_tools.py:159-186
  *   flip_v, flip_h, rot (np.rot90 k) of the stacked batch               -- utils/array_tools.py:188-213, processing.py:748
- * dst: fp32 NHWC (n, ho, wo, ldc) written at channel offset coff (ho, wo = w_, h when rot is odd). */
+ * dst: fp32 NHWC (n, ho, wo, ldc) written at channel offset coff (ho, wo = w_, h when rot is odd).
+ * Arithmetic: float32 planes stay float32 (x / (float)rescale, (float)mean, (float) multipliers, every operation rounded on its own, as
+ * NumPy does with Python scalars); every other kind is converted to double first.  The colour step is t1 = (v - mean) * contra_mul,
+ * t2 = mean * bright_mul, t1 + t2, without contraction; the result is rounded to float32 once.  The centre trim starts at
+ * (hin - h) / 2 and (win - w_) / 2, rounded down.
+ * Draws: a counter generator keyed on the element's index idx in the SOURCE planes ((image * c + channel) * hin + y) * win + x, so a value
+ * does not depend on the morph: r = splitmix64(seed ^ idx * 0xD1342543DE82EF95) (64-bit wrap-around);  U[0,1) = (r >> 11) * 2^-53;
+ * N(0,1) = sqrt(-2 log u1) cos(6.283185307179586 u2) in double with u1 = ((r >> 32) + 1) / (2^32 + 1), u2 = (r & 0xffffffff) / 2^32.
+ * satcv_tile_channel_mean sums in double and returns NaN for a channel without a valid value; in mode 2 it averages the very draws
+ * that satcv_tile_ingest writes.
+ * Refused (error code, satcv_last_error naming the entry point, nothing written): a null descriptor, src, dst or mean_out; n, c, h or
+ * w_ <= 0; hin < h, win < w_; src_kind outside 0..6; rot outside 0..3; nan_mask outside 0..2; nan_mask 1 together with ch_mean;
+ * coff < 0; ldc < coff + c (+ 1 with a mask channel). */
 typedef struct {
   const void* src; int32_t src_kind;
   int32_t n, c, hin, win, h, w_;
@@ -534,7 +552,12 @@ int satcv_tile_channel_mean(const satcv_tile_desc* d, double* mean_out /* (n, c)
 int satcv_tile_ingest(const satcv_tile_desc* d, void* stream);
 /* labels (n, 1, hin, win) -> merge_classes (utils/array_tools.py:26-44) as 256-entry look-up tables (-1 = keep): lut on the
  * land-cover value, then lu_lut on the optional land-use array -> trim -> morph -> tf.one_hot(depth nclasses) fp32
- * (utils/processing.py:656-704). */
+ * (utils/processing.py:656-704).  The label value is truncated toward zero (.astype(int)); lut applies to values in [0, 256), lu_lut to
+ * land-use values that are integral and in [0, 256).  A label that is NaN, infinite or outside the int64 range gives an all-zero row
+ * (the reference's conversion yields an out-of-range integer, which tf.one_hot encodes as zeros); such a land-use value matches no
+ * entry.  Any class outside [0, nclasses) gives an all-zero row.
+ * Refused (error code, satcv_last_error naming label_onehot, nothing written): a null lc or dst; n, h, w_ or nclasses <= 0; hin < h,
+ * win < w_; a kind outside 0..6; lu without lu_lut; rot outside 0..3; coff < 0; ldc < coff + nclasses. */
 int satcv_label_onehot(const void* lc, int32_t lc_kind, const int32_t* lut, const void* lu, int32_t lu_kind, const int32_t* lu_lut,
                        int32_t n, int32_t hin, int32_t win, int32_t h, int32_t w_, int32_t nclasses, int32_t flip_v, int32_t flip_h,
                        int32_t rot, float* dst, int32_t ldc, int32_t coff, void* stream);

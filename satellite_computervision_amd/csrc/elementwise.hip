@@ -84,7 +84,8 @@ __global__ void ingest_chw_kernel(const S* __restrict__ src, float scale, T* __r
   }
 }
 extern "C" int satcv_ingest_chw(const void* src, int32_t src_kind, float scale, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t cpad, int32_t dtype, void* stream) {
-  SATCV_CHECK(src && dst && n > 0 && c > 0 && cpad >= c && cpad % 8 == 0, "ingest_chw: bad args");
+  SATCV_CHECK(src && dst && n > 0 && c > 0 && h > 0 && w > 0 && cpad >= c && cpad % 8 == 0, "ingest_chw: bad args");
+  SATCV_CHECK(dtype == SATCV_F32 || dtype == SATCV_BF16, "ingest_chw: bad dtype %d", (int)dtype);
   const int hw = h * w; const int grid = ew_grid((long long)n * hw * (cpad / 8));
   DISPATCH_T(dtype, {
     if (src_kind == 0) hipLaunchKernelGGL((ingest_chw_kernel<T, uint8_t>), dim3(grid), dim3(EW_BLOCK), 0, (hipStream_t)stream, (const uint8_t*)src, scale, (T*)dst, n, c, hw, cpad);
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(EW_BLOCK) void pack_batched_kernel(const satcv_pack
   }
 }
 extern "C" int64_t satcv_pack_job_items(const satcv_pack_job* j) {
-  if (!j || j->kpad <= 0 || j->kpad % 8 || j->npad <= 0 || j->mode < 0 || j->mode > 3) return -1;
+  if (!j || j->kpad <= 0 || j->kpad % 8 || j->npad <= 0 || j->mode < 0 || j->mode > 3 || j->taps <= 0 || j->cin <= 0 || j->cout <= 0) return -1;
   // (rounded up to the block size of the batched kernel: a block of items never straddles two jobs)
   const int64_t real = (int64_t)(j->mode >= 2 ? 1 : j->taps) * (j->kpad / 8) * j->npad;
   return (real + EW_BLOCK - 1) / EW_BLOCK * EW_BLOCK;
@@ -188,6 +189,7 @@ extern "C" int satcv_pack_weights_batched(const satcv_pack_job* jobs_dev, const 
                                           void* stream) {
   SATCV_CHECK(jobs_dev && prefix_dev && njobs > 0 && total_items > 0, "pack_weights_batched: bad args");
   SATCV_CHECK(total_items % EW_BLOCK == 0, "pack_weights_batched: the prefix table must be built from satcv_pack_job_items (multiples of 256)");
+  SATCV_CHECK(dtype == SATCV_F32 || dtype == SATCV_BF16 || dtype == SATCV_FP8, "pack_weights_batched: bad dtype %d", (int)dtype);
   DISPATCH_T8(dtype, hipLaunchKernelGGL(pack_batched_kernel<T>, dim3(ew_grid(total_items)), dim3(EW_BLOCK), 0, (hipStream_t)stream, jobs_dev,
                                         (const long long*)prefix_dev, njobs, (long long)total_items));
   LAUNCH_OK("pack_weights_batched");
@@ -195,7 +197,8 @@ extern "C" int satcv_pack_weights_batched(const satcv_pack_job* jobs_dev, const 
 }
 
 extern "C" int satcv_pack_weights(const float* src, void* dst_fwd, void* dst_dgrad, int32_t kh, int32_t kw, int32_t cin, int32_t cout, int32_t cin_pad, int32_t transposed, int32_t dtype, void* stream) {
-  SATCV_CHECK(src && cin > 0 && cout > 0 && cin_pad >= cin && cin_pad % 16 == 0, "pack_weights: bad args");
+  SATCV_CHECK(src && kh > 0 && kw > 0 && cin > 0 && cout > 0 && cin_pad >= cin && cin_pad % 16 == 0, "pack_weights: bad args");
+  SATCV_CHECK(dtype == SATCV_F32 || dtype == SATCV_BF16 || dtype == SATCV_FP8 || dtype == SATCV_FP8X, "pack_weights: bad dtype %d", (int)dtype);
   const int taps = kh * kw;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == SATCV_FP8X) {          // scaled fp8: 16-channel granules, forward images only (inference)

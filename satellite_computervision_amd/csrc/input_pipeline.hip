@@ -144,13 +144,19 @@ __global__ void label_onehot_kernel(const LabelArgs a) {
     int y, x;
     morph_src(yo, xo, a.h, a.w, a.fv, a.fh, a.rot, y, x);
     const size_t idx = (size_t)b * a.hin * a.win + (size_t)(y + ty) * a.win + x + tx;
-    const long long v = (long long)load_src(a.lc, a.lc_kind, idx);          // .astype(int): truncation
+    // .astype(int): truncation.  A NaN, infinite or out-of-int64-range label converts to no class (-1: an all-zero row, what tf.one_hot
+    // makes of the reference's out-of-range integer) -- the conversion itself would be undefined
+    const double lv = load_src(a.lc, a.lc_kind, idx);
+    const bool lok = lv >= -9223372036854775808.0 && lv < 9223372036854775808.0;       // false for NaN
+    const long long v = lok ? (long long)lv : -1;
     long long cls = v;
     if (a.lut && v >= 0 && v < 256 && a.lut[v] >= 0) cls = a.lut[v];
     if (a.lu) {
       const double u = load_src(a.lu, a.lu_kind, idx);
-      const long long ui = (long long)u;
-      if ((double)ui == u && ui >= 0 && ui < 256 && a.lu_lut[ui] >= 0) cls = a.lu_lut[ui];
+      if (u >= 0.0 && u < 256.0) {                                                  // false for NaN; only these can match a table entry
+        const long long ui = (long long)u;
+        if ((double)ui == u && a.lu_lut[ui] >= 0) cls = a.lu_lut[ui];
+      }
     }
     float* o = a.dst + (size_t)it * a.ldc + a.coff;
     for (int k = 0; k < a.ncls; ++k) o[k] = (cls == k) ? 1.f : 0.f;          // tf.one_hot: out-of-range -> all zeros
@@ -184,7 +190,7 @@ extern "C" int satcv_tile_channel_mean(const satcv_tile_desc* d, double* mean_ou
 extern "C" int satcv_tile_ingest(const satcv_tile_desc* d, void* stream) {
   int rc = check_desc(d, "tile_ingest");
   if (rc) return rc;
-  SATCV_CHECK(d->dst && d->ldc >= d->coff + d->c + (d->nan_mask ? 1 : 0), "tile_ingest: destination channel range");
+  SATCV_CHECK(d->dst && d->coff >= 0 && d->ldc >= d->coff + d->c + (d->nan_mask ? 1 : 0), "tile_ingest: destination channel range");
   SATCV_CHECK(!(d->nan_mask == 1 && d->ch_mean), "tile_ingest: UNETDataGenerator applies the colour augmentation only to unmasked sources");
   SATCV_CHECK(d->nan_mask >= 0 && d->nan_mask <= 2, "tile_ingest: nan_mask must be 0, 1 (UNETDataGenerator) or 2 (SiameseDataGenerator)");
   hipLaunchKernelGGL(tile_ingest_kernel, dim3(grid_for((long long)d->n * d->h * d->w_)), dim3(256), 0, (hipStream_t)stream, *d);
@@ -196,7 +202,7 @@ extern "C" int satcv_tile_ingest(const satcv_tile_desc* d, void* stream) {
 extern "C" int satcv_label_onehot(const void* lc, int32_t lc_kind, const int32_t* lut, const void* lu, int32_t lu_kind, const int32_t* lu_lut,
                                   int32_t n, int32_t hin, int32_t win, int32_t h, int32_t w_, int32_t nclasses, int32_t flip_v, int32_t flip_h,
                                   int32_t rot, float* dst, int32_t ldc, int32_t coff, void* stream) {
-  SATCV_CHECK(lc && dst && n > 0 && h > 0 && w_ > 0 && hin >= h && win >= w_ && nclasses > 0 && ldc >= coff + nclasses, "label_onehot: bad args");
+  SATCV_CHECK(lc && dst && n > 0 && h > 0 && w_ > 0 && hin >= h && win >= w_ && nclasses > 0 && coff >= 0 && ldc >= coff + nclasses, "label_onehot: bad args");
   SATCV_CHECK(lc_kind >= 0 && lc_kind <= 6 && (!lu || (lu_kind >= 0 && lu_kind <= 6 && lu_lut)) && rot >= 0 && rot <= 3, "label_onehot: bad kinds");
   LabelArgs a{lc, lc_kind, lut, lu, lu_kind, lu_lut, n, hin, win, h, w_, nclasses, flip_v, flip_h, rot, dst, ldc, coff};
   hipLaunchKernelGGL(label_onehot_kernel, dim3(grid_for((long long)n * h * w_)), dim3(256), 0, (hipStream_t)stream, a);

@@ -55,11 +55,13 @@ def split_files(files, labels=['label', 'lu', 'naip', 'lidar', 's2'], delim='_',
 
 
 def merge_lut(trans, device):
-    """merge_classes (utils/array_tools.py:26-44) as a 256-entry table: rules test the ORIGINAL value, the last one wins."""
+    """merge_classes (utils/array_tools.py:26-44) as a 256-entry table: rules test the ORIGINAL value, the last one wins.  A rule whose
+    source value the table cannot hold (not integral, or outside 0 ... 255) would be applied by the reference: it raises ValueError."""
     lut = np.full(256, -1, np.int32)
     for x, y in trans or []:
-        if 0 <= int(x) < 256:
-            lut[int(x)] = int(y)
+        if not (np.isfinite(x) and float(x) == int(x) and 0 <= int(x) < 256):
+            raise ValueError(f'merge_lut: the rule {(x, y)!r} tests a value that is not an integer in 0 ... 255; the device look-up table cannot apply it')
+        lut[int(x)] = int(y)
     return torch.from_numpy(lut).to(device)
 
 
