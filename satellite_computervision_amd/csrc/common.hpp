@@ -45,6 +45,26 @@ void satcv_set_error(const char* fmt, ...);
 // opt a kernel into > 48 KB of dynamic LDS, once per (kernel, device); thread-safe (api.hip)
 int satcv_ensure_dynamic_lds(const void* kern, size_t bytes);
 
+// the tail of a launch function: dynamic-LDS opt-in, launch, and the report of a refused launch as "<name> launch: <HIP's text>".
+// (The opt-in returns at once for up to 48 KB, so a kernel with little or no dynamic LDS pays one compare for it.)
+template <typename... P, typename... A>
+static inline int satcv_launch(void (*kern)(P...), dim3 grid, dim3 threads, size_t lds, hipStream_t st, const char* name, A... args) {
+  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
+  hipLaunchKernelGGL(kern, grid, threads, lds, st, args...);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { satcv_set_error("%s launch: %s", name, hipGetErrorString(e)); return SATCV_ERR_HIP; }
+  return SATCV_OK;
+}
+
+// per-kind launch timing of the profiling runs (api.hip)
+void satcv_prof_begin(int kind, double flops, hipStream_t st);
+void satcv_prof_end(int kind, hipStream_t st);
+// slab sum of [nslab][taps][kpad][npad] partial weight gradients into dW (conv_wgrad.hip), for every producer of such slabs: plain HWIO
+// layout, or with `transposed` the transposed-convolution layout (f, f, cout, cin) from slabs [nslab][kpad = cin][npad = f f cout], taps = 1
+int wgrad_reduce_launch(const float* ws, float* dw, int nslab, int taps, int kpad, int npad, int cin, int nvalid, int transposed, int accumulate, hipStream_t st);
+// ... and the same sum described as a job of satcv_reduce_slabs_batched
+void reduce_job_fill(satcv_reduce_job* job, const float* ws, float* dw, int nslab, int taps, int kpad, int npad, int cin, int nvalid, int transposed, int accumulate);
+
 __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // n * h * w * f * f pixels (f = depth-to-space / space-to-depth factor or 1) stay below 2^31 -- evaluated without overflowing anything itself
 static inline bool satcv_pixels_ok(long long n, long long h, long long w, long long f) {

@@ -26,11 +26,6 @@
 #endif
 #define FABL(bit) ((BWDF_ABL & (bit)) != 0)
 
-int wgrad_reduce_slabs(const float* ws, float* dw, int nslab, int taps, int kpad, int npad, int cin, int nvalid, int accumulate, hipStream_t st);   // conv_wgrad.hip
-void reduce_job_fill(satcv_reduce_job* job, const float* ws, float* dw, int nslab, int taps, int kpad, int npad, int cin, int nvalid, int transposed, int accumulate);
-void satcv_prof_begin(int kind, double flops, hipStream_t st);
-void satcv_prof_end(int kind, hipStream_t st);
-
 struct BwdfArgs {
   IgemmArgs e;                                   // the data gradient's output side, as the shared epilogue reads it (y = dx, ldy, n, h, w_, cout = CIN)
   const void* g; const void* yraw; int ldg;      // gradient w.r.t. the activated output, raw conv output (same channel stride)
@@ -649,7 +644,7 @@ static int bwdf_launch(const satcv_bwdf_desc* d, hipStream_t st, bool query, int
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { satcv_set_error("bwd_fused launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
   if (d->defer_reduce) return SATCV_OK;              // the caller sums the slabs later (satcv_reduce_slabs_batched)
-  return wgrad_reduce_slabs(d->workspace, d->dw, grid, 9, CIN, COUT, d->cin, COUT, d->accumulate, st);
+  return wgrad_reduce_launch(d->workspace, d->dw, grid, 9, CIN, COUT, d->cin, COUT, 0, d->accumulate, st);
 }
 
 static int bwdf_dispatch(const satcv_bwdf_desc* d, hipStream_t st, bool query, int64_t* ws_bytes, satcv_reduce_job* job = nullptr, int ncu = 0,

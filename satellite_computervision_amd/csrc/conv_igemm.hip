@@ -294,9 +294,6 @@ static int launch_t(IgemmArgs& a, hipStream_t st, bool dry) {
   }
 }
 
-void satcv_prof_begin(int kind, double flops, hipStream_t st);
-void satcv_prof_end(int kind, hipStream_t st);
-
 static int igemm_fill_args(const satcv_conv_desc* d, IgemmArgs& a) {
   SATCV_CHECK(d && d->x0 && d->w && d->y, "igemm: null pointer");
   SATCV_CHECK(d->c0 > 0 && d->c0 % 16 == 0 && d->c1 % 16 == 0, "igemm: channels must be multiples of 16 (c0=%d c1=%d)", d->c0, d->c1);

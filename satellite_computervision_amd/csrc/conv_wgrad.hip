@@ -1165,9 +1165,22 @@ __global__ __launch_bounds__(256) void wgrad_reduce16_kernel(const float* __rest
 // ------------------------------------------------------------------ host side
 struct WgradPlan { int tw, nci, nco, nw, nks, ntaps, nsplit, kpad, npad, n_ci_blk, n_co_blk, pix, db, dma; size_t ws_bytes; };
 // the template instantiation a launch function serves.  The plan query (satcv_conv2d_wgrad_plan_info) walks the SAME wgrad_any ->
-// wgrad_cfg -> wgrad_db_cfg -> *_launch chain as a launch, with a non-null `pick`: the launch function runs its fit tests, records
+// wgrad_cfg -> wgrad_form -> *_launch chain as a launch, with a non-null `pick`: the launch function runs its fit tests, records
 // itself here and returns before it touches the device.  There is no second copy of the decision.
 struct WgradPick { int kernel, tw, nci, nco, nks, ntaps, pix, nw, m16; size_t lds; };
+
+// Pixel tiles of tw x th pixels over n maps of h x w: a map of at least th rows is cut into tiles_y bands of rpi = th rows; shorter maps
+// are stacked, imgs whole images of rpi = h rows per tile, in ngroups groups.  The one copy of this arithmetic: the planner's slab count,
+// the DMA kernel's fit test and the kernels' arguments all read it here.
+struct WgradTileGrid { int tiles_x, tiles_y, rpi, imgs, ngroups; long long ptiles; };
+static WgradTileGrid wgrad_tile_grid(int n, int h, int w, int tw, int th) {
+  WgradTileGrid g;
+  g.tiles_x = cdiv(w, tw);
+  if (h >= th) { g.rpi = th; g.imgs = 1; g.tiles_y = cdiv(h, th); g.ngroups = n; }
+  else { g.rpi = h; g.imgs = th / h; g.tiles_y = 1; g.ngroups = cdiv(n, g.imgs); }
+  g.ptiles = (long long)g.ngroups * g.tiles_y * g.tiles_x;
+  return g;
+}
 
 static int pick_tw_w(int w) {
   int best = 8, bestpad = cdiv(w, 8) * 8;
@@ -1182,9 +1195,9 @@ static int pick_tw_w(int w) {
 // wgrad_dma_launch.
 static bool wgrad_dma_fits(const satcv_wgrad_desc* d, int tw) {
   const int th = 128 / tw;
-  const int imgs = d->h >= th ? 1 : th / d->h, rpi = d->h >= th ? th : d->h;
-  if (imgs * (rpi + 2) > wgrad_halo_rows(th)) return false;                               // (the kernel's XMAXPIX = wgrad_halo_rows(TH) * (TW + 2) pixels)
-  if ((long long)imgs * d->h * d->w_ * d->lddy * 2 >= (1ll << 31)) return false;
+  const WgradTileGrid g = wgrad_tile_grid(d->n, d->h, d->w_, tw, th);
+  if (g.imgs * (g.rpi + 2) > wgrad_halo_rows(th)) return false;                           // (the kernel's XMAXPIX = wgrad_halo_rows(TH) * (TW + 2) pixels)
+  if ((long long)g.imgs * d->h * d->w_ * d->lddy * 2 >= (1ll << 31)) return false;
   return true;
 }
 
@@ -1232,11 +1245,7 @@ static int wgrad_plan(const satcv_wgrad_desc* d, WgradPlan& p) {
            d->dil == 1 && g_opt.wgrad_pix256) ? 256 : 128;
   if (p.nw > 1) p.pix = 64;
   if (p.dma) p.pix = 128;
-  const int th = p.pix / p.tw;
-  const int tiles_x = cdiv(d->w_, p.tw);
-  long long ptiles;
-  if (d->h >= th) ptiles = (long long)d->n * cdiv(d->h, th) * tiles_x;
-  else ptiles = (long long)cdiv(d->n, th / d->h) * tiles_x;
+  const long long ptiles = wgrad_tile_grid(d->n, d->h, d->w_, p.tw, p.pix / p.tw).ptiles;
   // two workgroups are resident per CU (144 accumulator registers): 512 fill the chip exactly once -- a third one per CU only
   // started a second, half-empty round (thin layers: 257 -> 217 us, 450 -> 366 us).  Layers with many (ci, co) blocks keep 768:
   // their per-block pixel share would get too coarse to balance.
@@ -1276,58 +1285,45 @@ extern "C" int64_t satcv_conv2d_wgrad_workspace(const satcv_wgrad_desc* d) {
   return (int64_t)need;
 }
 
-template <typename T, int TW, int NCI, int NCO, int NKS, int NTAPS, int PIX = 128>
-static int wgrad_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0, WgradPick* pick = nullptr) {
-  using G = WgradGeom<TW, NCI, NCO, NTAPS, T>;
-  constexpr int TH = PIX / TW;
+// the kernels' arguments, the same for every kernel form (all zero where nothing is said, padding included): a launch function tests its
+// own limits on the halo tile (rl rows of cl pixels) it finds here.  ntaps == 1 with a 3x3 descriptor is one tap of the per-tap path.
+static WgradArgs wgrad_args(const satcv_wgrad_desc* d, const WgradPlan& p, int tw, int th, int ntaps, int sy, int sx) {
   WgradArgs a;
+  memset(&a, 0, sizeof(a));
   a.x0 = d->x0; a.x1 = d->x1; a.c0 = d->c0; a.c1 = d->c1;
   a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.in_relu = d->in_relu;
   a.dy = d->dy; a.lddy = d->lddy; a.ws = d->workspace;
-  a.n = d->n; a.h = d->h; a.w_ = d->w_; a.kh = NTAPS == 1 ? 1 : d->kh; a.kw = NTAPS == 1 ? 1 : d->kw; a.dil = d->dil;
+  a.n = d->n; a.h = d->h; a.w_ = d->w_; a.kh = ntaps == 1 ? 1 : d->kh; a.kw = ntaps == 1 ? 1 : d->kw; a.dil = d->dil;
   a.sy = sy; a.sx = sx;
   a.mode_dy = d->mode_dy; a.f = d->f; a.cout_t = d->cout;
   a.kpad = p.kpad; a.npad = p.npad;
   a.cin_lim = d->c0 + d->c1; a.n_lim = d->mode_dy ? d->f * d->f * d->cout : d->cout;
   a.halh = a.dil * (a.kh - 1) / 2; a.halw = a.dil * (a.kw - 1) / 2;
-  a.tiles_x = cdiv(d->w_, TW);
-  if (d->h >= TH) { a.rpi = TH; a.imgs = 1; a.tiles_y = cdiv(d->h, TH); a.ngroups = d->n; }
-  else { a.rpi = d->h; a.imgs = TH / d->h; a.tiles_y = 1; a.ngroups = cdiv(d->n, a.imgs); }
-  a.seg = a.rpi + 2 * a.halh; a.rl = a.imgs * a.seg; a.cl = TW + 2 * a.halw;
+  const WgradTileGrid g = wgrad_tile_grid(d->n, d->h, d->w_, tw, th);
+  a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.rpi = g.rpi; a.imgs = g.imgs; a.ngroups = g.ngroups;
+  a.seg = a.rpi + 2 * a.halh; a.rl = a.imgs * a.seg; a.cl = tw + 2 * a.halw;
   a.n_ci_blk = p.n_ci_blk; a.n_co_blk = p.n_co_blk; a.nsplit = p.nsplit;
-  a.total_ptiles = a.ngroups * a.tiles_y * a.tiles_x;
+  a.total_ptiles = (int)g.ptiles;
+  return a;
+}
+static dim3 wgrad_grid(const WgradPlan& p) { return dim3(p.n_ci_blk * p.n_co_blk * p.nsplit); }      // one workgroup per (ci block, co block, slab)
+
+template <typename T, int TW, int NCI, int NCO, int NKS, int NTAPS, int PIX = 128>
+static int wgrad_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0, WgradPick* pick = nullptr) {
+  using G = WgradGeom<TW, NCI, NCO, NTAPS, T>;
+  const WgradArgs a = wgrad_args(d, p, TW, PIX / TW, NTAPS, sy, sx);
   size_t lds = ((size_t)a.rl * a.cl * G::XP + PIX * G::DP) * sizeof(T) + (PIX + (size_t)a.rl * a.cl) * sizeof(int);
   if (lds < 3 * 4096) lds = 3 * 4096;          // k-slice reduction scratch
   if (lds > 160 * 1024) return SATCV_ERR_UNSUPPORTED;
   if (pick) { *pick = WgradPick{SATCV_WGRAD_KERNEL_SINGLE, TW, NCI, NCO, NKS, NTAPS, PIX, 1, 0, lds}; return SATCV_OK; }
-  auto kern = wgrad_kernel<T, TW, NCI, NCO, NKS, NTAPS, PIX>;
-  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-  hipLaunchKernelGGL(kern, dim3(p.n_ci_blk * p.n_co_blk * p.nsplit), dim3(NCI * NCO * NKS * 64), lds, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { satcv_set_error("wgrad launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
-  return SATCV_OK;
+  return satcv_launch(wgrad_kernel<T, TW, NCI, NCO, NKS, NTAPS, PIX>, wgrad_grid(p), dim3(NCI * NCO * NKS * 64), lds, st, "wgrad", a);
 }
 
 template <typename T, int TW, int NCI, int NCO, int NKS, int NTAPS, int PIX = 128, int NW = 1>
 static int wgrad_db_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0, WgradPick* pick = nullptr) {
   using G = WgradGeom<TW, NCI, NCO * NW, NTAPS, T>;
   constexpr int TH = PIX / TW, NTHREADS = NCI * NCO * NKS * 64, GX = G::CI_T / 8;
-  WgradArgs a;
-  a.x0 = d->x0; a.x1 = d->x1; a.c0 = d->c0; a.c1 = d->c1;
-  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.in_relu = d->in_relu;
-  a.dy = d->dy; a.lddy = d->lddy; a.ws = d->workspace;
-  a.n = d->n; a.h = d->h; a.w_ = d->w_; a.kh = NTAPS == 1 ? 1 : d->kh; a.kw = NTAPS == 1 ? 1 : d->kw; a.dil = d->dil;
-  a.sy = sy; a.sx = sx;
-  a.mode_dy = d->mode_dy; a.f = d->f; a.cout_t = d->cout;
-  a.kpad = p.kpad; a.npad = p.npad;
-  a.cin_lim = d->c0 + d->c1; a.n_lim = d->mode_dy ? d->f * d->f * d->cout : d->cout;
-  a.halh = a.dil * (a.kh - 1) / 2; a.halw = a.dil * (a.kw - 1) / 2;
-  a.tiles_x = cdiv(d->w_, TW);
-  if (d->h >= TH) { a.rpi = TH; a.imgs = 1; a.tiles_y = cdiv(d->h, TH); a.ngroups = d->n; }
-  else { a.rpi = d->h; a.imgs = TH / d->h; a.tiles_y = 1; a.ngroups = cdiv(d->n, a.imgs); }
-  a.seg = a.rpi + 2 * a.halh; a.rl = a.imgs * a.seg; a.cl = TW + 2 * a.halw;
-  a.n_ci_blk = p.n_ci_blk; a.n_co_blk = p.n_co_blk; a.nsplit = p.nsplit;
-  a.total_ptiles = a.ngroups * a.tiles_y * a.tiles_x;
+  const WgradArgs a = wgrad_args(d, p, TW, TH, NTAPS, sy, sx);
   // register-staged items per thread (same bound as in the kernel)
   constexpr int XMAXPIX = NTAPS == 1 ? PIX : (PIX == 256 ? (TH + 2) * (TW + 2) : wgrad_halo_rows(TH) * (TW + 2));
   constexpr int XI = (XMAXPIX * GX + NTHREADS - 1) / NTHREADS;
@@ -1340,33 +1336,18 @@ static int wgrad_db_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStr
   if (lds < red) lds = red;
   if (lds > 160 * 1024) return SATCV_ERR_UNSUPPORTED;
   if (pick) { *pick = WgradPick{SATCV_WGRAD_KERNEL_DB, TW, NCI, NCO, NKS, NTAPS, PIX, NW, 0, lds}; return SATCV_OK; }
-  auto kern = wgrad_db_kernel<T, TW, NCI, NCO, NKS, NTAPS, PIX, NW>;
-  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-  hipLaunchKernelGGL(kern, dim3(p.n_ci_blk * p.n_co_blk * p.nsplit), dim3(NTHREADS), lds, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { satcv_set_error("wgrad_db launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
-  return SATCV_OK;
+  return satcv_launch(wgrad_db_kernel<T, TW, NCI, NCO, NKS, NTAPS, PIX, NW>, wgrad_grid(p), dim3(NTHREADS), lds, st, "wgrad_db", a);
 }
 
 template <int TW, bool M16 = false>
 static int wgrad_dma_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, WgradPick* pick = nullptr) {
   constexpr int PIX = 128, TH = PIX / TW, NTHREADS = 512, XP = M16 ? 80 : 96, GX = 8;
-  WgradArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x0 = d->x0; a.x1 = d->x1; a.c0 = d->c0; a.c1 = d->c1;
-  a.in_scale = d->in_scale; a.in_shift = d->in_shift; a.in_relu = d->in_relu;
-  a.dy = d->dy; a.lddy = d->lddy; a.ws = d->workspace;
-  a.n = d->n; a.h = d->h; a.w_ = d->w_; a.kh = 3; a.kw = 3; a.dil = 1;
-  a.f = 1; a.cout_t = d->cout;
-  a.kpad = p.kpad; a.npad = p.npad;
-  a.cin_lim = d->c0 + d->c1; a.n_lim = d->cout;
-  a.halh = 1; a.halw = 1;
-  a.tiles_x = d->w_ / TW;
-  if (d->h >= TH) { a.rpi = TH; a.imgs = 1; a.tiles_y = d->h / TH; a.ngroups = d->n; }
-  else { a.rpi = d->h; a.imgs = TH / d->h; a.tiles_y = 1; a.ngroups = d->n / a.imgs; }
-  a.seg = a.rpi + 2; a.rl = a.imgs * a.seg; a.cl = TW + 2;
-  a.n_ci_blk = p.n_ci_blk; a.n_co_blk = p.n_co_blk; a.nsplit = p.nsplit;
-  a.total_ptiles = a.ngroups * a.tiles_y * a.tiles_x;
+  // The kernel walks whole tiles only, and wgrad_plan sends it nothing else (`whole` there; this function does not test it again): for
+  // whole tiles the grid's rounded-up tile and group counts are the exact quotients.  The planner also sends only 3x3 taps at dilation 1 of a plain convolution, so the common fill already
+  // holds what the kernel is written for; its fixed values are pinned all the same (a plain convolution's f may be 0 or 1).
+  WgradArgs a = wgrad_args(d, p, TW, TH, 9, 0, 0);
+  a.kh = a.kw = 3; a.dil = 1;
+  a.mode_dy = 0; a.f = 1; a.n_lim = d->cout;
   // the halo tile fits the kernel's register staging (rl <= wgrad_halo_rows(TH), cl == TW + 2): the planner's test, and the only one
   if (!wgrad_dma_fits(d, TW)) return SATCV_ERR_UNSUPPORTED;
   if (a.rl >= 1024 || a.cl >= 1024 || a.imgs >= 1024) return SATCV_ERR_UNSUPPORTED;
@@ -1374,56 +1355,48 @@ static int wgrad_dma_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipSt
   const size_t lds = 2 * stage * sizeof(bf16) + (size_t)PIX * sizeof(int) + (size_t)GX * 16 * sizeof(float);
   if (lds > 160 * 1024) return SATCV_ERR_UNSUPPORTED;
   if (pick) { *pick = WgradPick{SATCV_WGRAD_KERNEL_DMA, TW, 2, 4, 1, 9, PIX, 1, M16 ? 1 : 0, lds}; return SATCV_OK; }
-  auto kern = wgrad_dma_kernel<TW, M16>;
-  { const int rc = satcv_ensure_dynamic_lds(reinterpret_cast<const void*>(kern), lds); if (rc) return rc; }
-  hipLaunchKernelGGL(kern, dim3(p.n_ci_blk * p.n_co_blk * p.nsplit), dim3(NTHREADS), lds, st, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { satcv_set_error("wgrad_dma launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
-  return SATCV_OK;
+  return satcv_launch(wgrad_dma_kernel<TW, M16>, wgrad_grid(p), dim3(NTHREADS), lds, st, "wgrad_dma", a);
 }
 
-// the double-buffered kernel (bf16): 8 waves = (ci, co) tiles x k-slices
-template <typename T, int TW>
-static int wgrad_db_cfg(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy, int sx, WgradPick* pick) {
-  if constexpr (std::is_same<T, bf16>::value) {
-    if (p.dma) {
-      // option wgrad_m16 (SATCV_WGRAD_M16, default 0): the 16x16x32 form -- correct, and measured 33 % SLOWER per launch (profiles/r06_ab_wgrad_m16.txt)
-      return g_opt.wgrad_m16 ? wgrad_dma_launch<TW, true>(d, p, st, pick) : wgrad_dma_launch<TW, false>(d, p, st, pick);
-    }      // (the plan's slab geometry is this kernel's: no other kernel can serve it)
+// one block form of the double-buffered kernel (DB, bf16: 8 waves) or of the single-buffered one (4 waves): waves = (ci, co) tiles x k-slices
+template <bool DB, typename T, int TW, int NCI, int NCO, int NTAPS, int PIX = 128, int NW = 1>
+static int wgrad_form_launch(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy, int sx, WgradPick* pick) {
+  constexpr int NKS = (DB ? 8 : 4) / (NCI * NCO);
+  if constexpr (DB) return wgrad_db_launch<T, TW, NCI, NCO, NKS, NTAPS, PIX, NW>(d, p, st, sy, sx, pick);
+  else return wgrad_launch<T, TW, NCI, NCO, NKS, NTAPS, PIX>(d, p, st, sy, sx, pick);
+}
+// the block forms, one chain for both kernels.  Only the double-buffered kernel has the two wide 1x1 blocks; a plan with one of them
+// never comes here with DB off (wgrad_cfg).  The 256-pixel form exists at tw = 32 in bf16 only.
+template <bool DB, typename T, int TW>
+static int wgrad_form(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy, int sx, WgradPick* pick) {
+  if constexpr (DB) {
+    if (p.ntaps == 1 && p.nw == 4) return wgrad_form_launch<DB, T, TW, 4, 2, 1, 64, 4>(d, p, st, sy, sx, pick);
+    if (p.ntaps == 1 && p.nci == 2) return wgrad_form_launch<DB, T, TW, 2, 4, 1>(d, p, st, sy, sx, pick);
   }
-  if (p.ntaps == 1 && p.nw == 4) return wgrad_db_launch<T, TW, 4, 2, 1, 1, 64, 4>(d, p, st, sy, sx, pick);
-  if (p.ntaps == 1 && p.nci == 2) return wgrad_db_launch<T, TW, 2, 4, 1, 1>(d, p, st, sy, sx, pick);
-  if (p.ntaps == 1) return wgrad_db_launch<T, TW, 1, 4, 2, 1>(d, p, st, sy, sx, pick);
-  if (p.nci == 1 && p.nco == 4) return wgrad_db_launch<T, TW, 1, 4, 2, 9>(d, p, st, 0, 0, pick);
-  if (p.nci == 2 && p.nco == 2) return wgrad_db_launch<T, TW, 2, 2, 2, 9>(d, p, st, 0, 0, pick);
-  if constexpr (TW == 32) {
-    if (p.pix == 256 && p.nci == 1 && p.nco == 1) return wgrad_db_launch<T, TW, 1, 1, 8, 9, 256>(d, p, st, 0, 0, pick);
+  if (p.ntaps == 1) return wgrad_form_launch<DB, T, TW, 1, 4, 1>(d, p, st, sy, sx, pick);
+  if (p.nci == 1 && p.nco == 4) return wgrad_form_launch<DB, T, TW, 1, 4, 9>(d, p, st, 0, 0, pick);
+  if (p.nci == 2 && p.nco == 2) return wgrad_form_launch<DB, T, TW, 2, 2, 9>(d, p, st, 0, 0, pick);
+  if constexpr (TW == 32 && std::is_same<T, bf16>::value) {
+    if (p.pix == 256 && p.nci == 1 && p.nco == 1) return wgrad_form_launch<DB, T, TW, 1, 1, 9, 256>(d, p, st, 0, 0, pick);
   }
-  if (p.nci == 1 && p.nco == 2) return wgrad_db_launch<T, TW, 1, 2, 4, 9>(d, p, st, 0, 0, pick);
-  if (p.nci == 2 && p.nco == 1) return wgrad_db_launch<T, TW, 2, 1, 4, 9>(d, p, st, 0, 0, pick);
-  return wgrad_db_launch<T, TW, 1, 1, 8, 9>(d, p, st, 0, 0, pick);
+  if (p.nci == 1 && p.nco == 2) return wgrad_form_launch<DB, T, TW, 1, 2, 9>(d, p, st, 0, 0, pick);
+  if (p.nci == 2 && p.nco == 1) return wgrad_form_launch<DB, T, TW, 2, 1, 9>(d, p, st, 0, 0, pick);
+  return wgrad_form_launch<DB, T, TW, 1, 1, 9>(d, p, st, 0, 0, pick);
 }
 
 template <typename T, int TW>
 static int wgrad_cfg(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0, WgradPick* pick = nullptr) {
   if constexpr (std::is_same<T, bf16>::value) {
     if (p.db) {
-      const int rc = wgrad_db_cfg<T, TW>(d, p, st, sy, sx, pick);
+      int rc;
+      // option wgrad_m16 (SATCV_WGRAD_M16, default 0): the 16x16x32 form -- correct, and measured 33 % SLOWER per launch (profiles/r06_ab_wgrad_m16.txt)
+      if (p.dma) rc = g_opt.wgrad_m16 ? wgrad_dma_launch<TW, true>(d, p, st, pick) : wgrad_dma_launch<TW, false>(d, p, st, pick);
+      else rc = wgrad_form<true, T, TW>(d, p, st, sy, sx, pick);
       if (rc != SATCV_ERR_UNSUPPORTED) return rc;
       if (p.dma || (p.ntaps == 1 && (p.nci != 1 || p.nw != 1))) { satcv_set_error("wgrad: block plan without a kernel"); return rc; }   // (the plan's slab geometry is the db / dma kernel's)
     }
   }
-  if (p.ntaps == 1) return wgrad_launch<T, TW, 1, 4, 1, 1>(d, p, st, sy, sx, pick);
-  if (p.nci == 1 && p.nco == 4) return wgrad_launch<T, TW, 1, 4, 1, 9>(d, p, st, 0, 0, pick);
-  if (p.nci == 2 && p.nco == 2) return wgrad_launch<T, TW, 2, 2, 1, 9>(d, p, st, 0, 0, pick);
-  if constexpr (TW == 32) {
-    if constexpr (std::is_same<T, bf16>::value) {
-      if (p.pix == 256 && p.nci == 1 && p.nco == 1) return wgrad_launch<T, TW, 1, 1, 4, 9, 256>(d, p, st, 0, 0, pick);
-    }
-  }
-  if (p.nci == 1 && p.nco == 2) return wgrad_launch<T, TW, 1, 2, 2, 9>(d, p, st, 0, 0, pick);
-  if (p.nci == 2 && p.nco == 1) return wgrad_launch<T, TW, 2, 1, 2, 9>(d, p, st, 0, 0, pick);
-  return wgrad_launch<T, TW, 1, 1, 4, 9>(d, p, st, 0, 0, pick);
+  return wgrad_form<false, T, TW>(d, p, st, sy, sx, pick);
 }
 template <typename T>
 static int wgrad_t(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t st, int sy = 0, int sx = 0, WgradPick* pick = nullptr) {
@@ -1440,61 +1413,27 @@ static int wgrad_any(const satcv_wgrad_desc* d, const WgradPlan& p, hipStream_t 
   return SATCV_ERR_INVALID;
 }
 // which slab-sum kernel serves a launch (SATCV_WGRAD_REDUCE_*): asked by wgrad_reduce_launch and by the plan query
-static int wgrad_reduce_kind(const satcv_wgrad_desc* d, const WgradPlan& p, const float* dw, int nvalid) {
-  if (!d->transposed && nvalid % 4 == 0 && p.npad % 4 == 0 && ((uintptr_t)dw % 16) == 0 && ((uintptr_t)d->workspace % 16) == 0)
-    return p.nsplit >= 32 ? SATCV_WGRAD_REDUCE_16 : SATCV_WGRAD_REDUCE_4;
+static int wgrad_reduce_kind(const float* ws, const float* dw, int nslab, int npad, int nvalid, int transposed) {
+  if (!transposed && nvalid % 4 == 0 && npad % 4 == 0 && ((uintptr_t)dw % 16) == 0 && ((uintptr_t)ws % 16) == 0)
+    return nslab >= 32 ? SATCV_WGRAD_REDUCE_16 : SATCV_WGRAD_REDUCE_4;
   return SATCV_WGRAD_REDUCE_GENERIC;
 }
-static int wgrad_reduce_launch(const satcv_wgrad_desc* d, const WgradPlan& p, float* dw, int nvalid, hipStream_t st) {
-  const long long total = (long long)p.ntaps * d->cin * nvalid;
-  const int kind = wgrad_reduce_kind(d, p, dw, nvalid);
-  if (kind != SATCV_WGRAD_REDUCE_GENERIC) {
-    if (kind == SATCV_WGRAD_REDUCE_16) {
+// the slab sum of this file's launches and of the fused backward kernels (conv_bwd_fused.hip, convt_bwd_fused.hip): see common.hpp
+int wgrad_reduce_launch(const float* ws, float* dw, int nslab, int taps, int kpad, int npad, int cin, int nvalid, int transposed, int accumulate, hipStream_t st) {
+  const long long total = (long long)taps * cin * nvalid;
+  const char* const name = "wgrad reduce";
+  switch (wgrad_reduce_kind(ws, dw, nslab, npad, nvalid, transposed)) {
+    case SATCV_WGRAD_REDUCE_16: {
       int grid16 = (int)((total / 4 + 15) / 16); if (grid16 > 16384) grid16 = 16384;
-      hipLaunchKernelGGL(wgrad_reduce16_kernel, dim3(grid16), dim3(256), 0, st, (const float*)d->workspace, dw, p.nsplit, p.ntaps, p.kpad, p.npad, d->cin, nvalid,
-                         d->accumulate);
-      hipError_t e16 = hipGetLastError();
-      if (e16 != hipSuccess) { satcv_set_error("wgrad reduce launch: %s", hipGetErrorString(e16)); return SATCV_ERR_HIP; }
-      return SATCV_OK;
+      return satcv_launch(wgrad_reduce16_kernel, dim3(grid16), dim3(256), 0, st, name, ws, dw, nslab, taps, kpad, npad, cin, nvalid, accumulate);
     }
-    int grid4 = (int)((total / 4 + 63) / 64); if (grid4 > 8192) grid4 = 8192;
-    hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3(grid4), dim3(256), 0, st, (const float*)d->workspace, dw, p.nsplit, p.ntaps, p.kpad, p.npad, d->cin, nvalid,
-                       d->accumulate);
-    hipError_t e4 = hipGetLastError();
-    if (e4 != hipSuccess) { satcv_set_error("wgrad reduce launch: %s", hipGetErrorString(e4)); return SATCV_ERR_HIP; }
-    return SATCV_OK;
+    case SATCV_WGRAD_REDUCE_4: {
+      int grid4 = (int)((total / 4 + 63) / 64); if (grid4 > 8192) grid4 = 8192;
+      return satcv_launch(wgrad_reduce4_kernel, dim3(grid4), dim3(256), 0, st, name, ws, dw, nslab, taps, kpad, npad, cin, nvalid, accumulate);
+    }
   }
   int grid = (int)((total + 63) / 64); if (grid > 8192) grid = 8192;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(grid), dim3(256), 0, st, d->workspace, dw, p.nsplit, p.ntaps, p.kpad, p.npad, d->cin, nvalid,
-                     d->transposed, d->accumulate);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { satcv_set_error("wgrad reduce launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
-  return SATCV_OK;
-}
-
-void satcv_prof_begin(int kind, double flops, hipStream_t st);
-void satcv_prof_end(int kind, hipStream_t st);
-
-// slab sum for other producers of [nslab][taps][kpad][npad] partial weight gradients (conv_bwd_fused.hip): plain HWIO layout
-int wgrad_reduce_slabs(const float* ws, float* dw, int nslab, int taps, int kpad, int npad, int cin, int nvalid, int accumulate, hipStream_t st) {
-  satcv_wgrad_desc d;
-  memset(&d, 0, sizeof(d));
-  d.workspace = const_cast<float*>(ws); d.cin = cin; d.accumulate = accumulate; d.transposed = 0;
-  WgradPlan p;
-  memset(&p, 0, sizeof(p));
-  p.nsplit = nslab; p.ntaps = taps; p.kpad = kpad; p.npad = npad;
-  return wgrad_reduce_launch(&d, p, dw, nvalid, st);
-}
-
-// ... and for the transposed-convolution layout (f, f, cout, cin) of convt_bwd_fused.hip: slabs [nslab][kpad = cin][npad = f f cout]
-int wgrad_reduce_slabs_t(const float* ws, float* dw, int nslab, int kpad, int npad, int cin, int nvalid, int accumulate, hipStream_t st) {
-  satcv_wgrad_desc d;
-  memset(&d, 0, sizeof(d));
-  d.workspace = const_cast<float*>(ws); d.cin = cin; d.accumulate = accumulate; d.transposed = 1;
-  WgradPlan p;
-  memset(&p, 0, sizeof(p));
-  p.nsplit = nslab; p.ntaps = 1; p.kpad = kpad; p.npad = npad;
-  return wgrad_reduce_launch(&d, p, dw, nvalid, st);
+  return satcv_launch(wgrad_reduce_kernel, dim3(grid), dim3(256), 0, st, name, ws, dw, nslab, taps, kpad, npad, cin, nvalid, transposed, accumulate);
 }
 
 // the descriptor checks that need no pointer: shared by the launch and the plan query
@@ -1510,7 +1449,7 @@ static void wgrad_fill_info(satcv_wgrad_plan_info* o, const satcv_wgrad_desc* d,
   o->kernel = k.kernel; o->tw = k.tw; o->nci = k.nci; o->nco = k.nco; o->nw = k.nw; o->nks = k.nks; o->ntaps = k.ntaps; o->pix = k.pix;
   o->db = k.kernel != SATCV_WGRAD_KERNEL_SINGLE; o->dma = k.kernel == SATCV_WGRAD_KERNEL_DMA; o->m16 = k.m16;
   o->nsplit = p.nsplit; o->kpad = p.kpad; o->npad = p.npad; o->n_ci_blk = p.n_ci_blk; o->n_co_blk = p.n_co_blk;
-  o->reduce = wgrad_reduce_kind(d, p, d->dw, nvalid); o->per_tap = per_tap;
+  o->reduce = wgrad_reduce_kind(d->workspace, d->dw, p.nsplit, p.npad, nvalid, d->transposed); o->per_tap = per_tap;
   o->ws_bytes = (int64_t)p.ws_bytes; o->lds_bytes = (int64_t)k.lds;
 }
 
@@ -1547,7 +1486,8 @@ static int wgrad_drive(const satcv_wgrad_desc* d, hipStream_t st, satcv_wgrad_pl
     if (rc == SATCV_OK && (size_t)d->workspace_bytes < p1.ws_bytes) { satcv_set_error("wgrad: workspace too small for the per-tap path"); rc = SATCV_ERR_INVALID; }
     for (int tap = 0; tap < 9 && rc == SATCV_OK; ++tap) {
       rc = wgrad_any(&d1, p1, st, (tap / 3 - 1) * d->dil, (tap % 3 - 1) * d->dil);
-      if (rc == SATCV_OK) rc = wgrad_reduce_launch(&d1, p1, d->dw + (size_t)tap * d->cin * nvalid, nvalid, st);
+      if (rc == SATCV_OK)
+        rc = wgrad_reduce_launch(d->workspace, d->dw + (size_t)tap * d->cin * nvalid, p1.nsplit, p1.ntaps, p1.kpad, p1.npad, d->cin, nvalid, d->transposed, d->accumulate, st);
     }
     satcv_prof_end(2, st);
     return rc;
@@ -1559,7 +1499,7 @@ static int wgrad_drive(const satcv_wgrad_desc* d, hipStream_t st, satcv_wgrad_pl
   satcv_prof_end(2, st);
   if (rc) return rc;
   if (d->defer_reduce) return SATCV_OK;            // the caller sums the slabs later (satcv_reduce_slabs_batched)
-  return wgrad_reduce_launch(d, p, d->dw, nvalid, st);
+  return wgrad_reduce_launch(d->workspace, d->dw, p.nsplit, p.ntaps, p.kpad, p.npad, d->cin, nvalid, d->transposed, d->accumulate, st);
 }
 
 extern "C" int satcv_conv2d_wgrad(const satcv_wgrad_desc* d, void* stream) {
@@ -1639,11 +1579,8 @@ extern "C" int satcv_reduce_slabs_batched(const satcv_reduce_job* jobs_dev, cons
   SATCV_CHECK(jobs_dev && prefix_dev && njobs > 0 && njobs <= 4096 && total_items > 0, "reduce_slabs_batched: bad arguments");
   SATCV_CHECK(total_items % 16 == 0, "reduce_slabs_batched: the prefix table must be built from satcv_reduce_job_items (multiples of 16)");
   long long grid = (total_items + 255) / 256; if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(reduce_slabs_batched_kernel, dim3((unsigned)grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), jobs_dev,
-                     reinterpret_cast<const long long*>(prefix_dev), njobs, (long long)total_items);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { satcv_set_error("reduce_slabs_batched launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
-  return SATCV_OK;
+  return satcv_launch(reduce_slabs_batched_kernel, dim3((unsigned)grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), "reduce_slabs_batched", jobs_dev,
+                      reinterpret_cast<const long long*>(prefix_dev), njobs, (long long)total_items);
 }
 void reduce_job_fill(satcv_reduce_job* job, const float* ws, float* dw, int nslab, int taps, int kpad, int npad, int cin, int nvalid, int transposed, int accumulate) {
   job->ws = ws; job->dw = dw; job->nslab = nslab; job->taps = taps; job->kpad = kpad; job->npad = npad; job->cin = cin; job->nvalid = nvalid;

@@ -22,11 +22,6 @@
 #include <cstdlib>
 #include <cstring>
 
-void reduce_job_fill(satcv_reduce_job* job, const float* ws, float* dw, int nslab, int taps, int kpad, int npad, int cin, int nvalid, int transposed, int accumulate);
-int wgrad_reduce_slabs_t(const float* ws, float* dw, int nslab, int kpad, int npad, int cin, int nvalid, int accumulate, hipStream_t st);      // conv_wgrad.hip
-void satcv_prof_begin(int kind, double flops, hipStream_t st);
-void satcv_prof_end(int kind, hipStream_t st);
-
 struct CtbfArgs {
   const void* g; int ldg;              // gradient of the activated concatenation, offset to the first `up` channel; (n, 2h, 2w, ldg)
   const void* yup; int ldy;            // raw output of the transposed convolution (n, 2h, 2w, ldy)
@@ -411,7 +406,7 @@ static int ctbf_launch(const satcv_ctbf_desc* d, hipStream_t st, bool query, int
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { satcv_set_error("convt_bwd_fused launch: %s", hipGetErrorString(e)); return SATCV_ERR_HIP; }
   if (d->defer_reduce) return SATCV_OK;
-  return wgrad_reduce_slabs_t(d->workspace, d->dw, (int)slabs, d->cin, COUT4, d->cin, COUT4, d->accumulate, st);
+  return wgrad_reduce_launch(d->workspace, d->dw, (int)slabs, 1, d->cin, COUT4, d->cin, COUT4, 1, d->accumulate, st);
 }
 
 static int ctbf_dispatch(const satcv_ctbf_desc* d, hipStream_t st, bool query, int64_t* ws_bytes, satcv_reduce_job* job = nullptr, int ncu = 0,

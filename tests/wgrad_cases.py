@@ -8,7 +8,7 @@ An instantiation KEY names one template instantiation of csrc/conv_wgrad.hip:
            'db'     wgrad_db_kernel<bf16, tw, nci, nco, nks, ntaps, pix, nw>
            'dma'    wgrad_dma_kernel<tw, m16>       (always the 2 x 4 block, 9 taps, 128 pixels)
 
-ALL_KEYS is written out by hand from the `if` chains of wgrad_cfg, wgrad_db_cfg and wgrad_dma_launch; CASES is the table, every entry
+ALL_KEYS is written out by hand from the `if` chain of wgrad_form (once per kernel), wgrad_cfg and wgrad_dma_launch; CASES is the table, every entry
 with the key it is meant to reach.  The CPU test asks the library's plan query (satcv_conv2d_wgrad_plan_info: the launch path's own
 decision chain, nothing launched) that every case lands on its key and that the union of the reached keys is ALL_KEYS minus UNREACHABLE;
 the GPU test runs every case against a float64 oracle and, on integer data, bit-exactly.
@@ -28,9 +28,9 @@ KEY_FIELDS = ('dtype', 'kernel', 'tw', 'nci', 'nco', 'nks', 'ntaps', 'pix', 'nw'
 TWS = (8, 16, 32)
 
 # ------------------------------------------------------------------------------------------------ every instantiation, by hand
-# wgrad_cfg (single-buffered wgrad_kernel), both storage types, every tile width: (nci, nco, nks, ntaps)
+# wgrad_form<false> (single-buffered wgrad_kernel), both storage types, every tile width: (nci, nco, nks, ntaps)
 _SINGLE = [(1, 4, 1, 1), (1, 4, 1, 9), (2, 2, 1, 9), (1, 2, 2, 9), (2, 1, 2, 9), (1, 1, 4, 9)]
-# wgrad_db_cfg (wgrad_db_kernel, bf16 only), every tile width: (nci, nco, nks, ntaps, pix, nw)
+# wgrad_form<true> (wgrad_db_kernel, bf16 only), every tile width: (nci, nco, nks, ntaps, pix, nw)
 _DB = [(4, 2, 1, 1, 64, 4), (2, 4, 1, 1, 128, 1), (1, 4, 2, 1, 128, 1), (1, 4, 2, 9, 128, 1), (2, 2, 2, 9, 128, 1), (1, 2, 4, 9, 128, 1),
        (2, 1, 4, 9, 128, 1), (1, 1, 8, 9, 128, 1)]
 ALL_KEYS = set()
