@@ -972,6 +972,59 @@ int satcv_crs_transform(const satcv_crs* from, const satcv_crs* to, const double
 int satcv_grid_coords(const satcv_reproject_map* m, int32_t dh, int32_t dw, int32_t row0, int32_t col0, double* u, double* v, void* stream);
 int satcv_raster_reproject(const satcv_warp_desc* d, const satcv_reproject_map* m, void* stream);
 
+/* ------------------------------------------------------------------ Radiometric calibration: histogram matching between scenes
+ * utils/calibration.py on arrays: clamp_and_scale (:12-45), get_overlap (:64-76), hist_to_FC / make_FC (:78-134), equalize (:136-182)
+ * and the chain of equalize_collection (:184-233).  The reference takes a 4096-bucket Earth Engine histogram and fits two 100-tree
+ * random-forest regressors (DN -> cumulative probability -> DN), an approximation of CDF matching; this library computes the thing
+ * it approximates, exactly and in integers, one bin per stored value.  Every decision is exact on the stored sample values.
+ *
+ * Kinds: 0 u8 (256 bins), 1 u16 (65536 bins), 3 i16 (65536 bins, bin = v + 32768).  f32 (2) and i32 (5) are refused: f32 needs a
+ * binning rule whose rounding can be pinned.  Rasters are (c, h, w_) planar and contiguous, 1 <= c <= 16, h * w_ < 2^31.
+ * Validity: a sample equal to nodata (with has_nodata) is invalid; a nodata that is no value of the kind matches no sample.
+ *
+ * satcv_calib_overlap (get_overlap :64-76 with the footprint geometry replaced by validity): region[y, x] = 1 where EVERY band of a
+ *   and (b may be NULL: one raster alone) of b is valid and mask (uint8 (h, w_), may be NULL) is non-zero there, else 0.  A streaming
+ *   kernel: a lane takes 16 bytes of every plane per step.
+ * satcv_calib_histogram (make_FC :106-134, every stored value its own bucket): hist[band][k] = number of pixels with region != 0
+ *   whose band has bin k; uint32 (c, bins), zeroed by the call.  One workgroup takes a strip of 2^18 samples of one plane, counts the
+ *   values 0 ... split - 1 in an LDS-private histogram (LDS atomics) and the others straight in global memory, and adds its non-zero
+ *   private bins to global memory at the end.  split: 0 the library's choice (16384); n > 0 that many private bins (at most 32768; u8
+ *   privatises all 256 whatever n); negative none (global atomics only).  Integer counts: the result does not depend on the arrival order.
+ * satcv_calib_match_lut (equalize :136-182): with cum1, cum2 the inclusive cumulative counts of hist1, hist2 and n1, n2 their totals,
+ *   lut[band][v] = the value (in the kind) of the smallest bin u with cum1[u] * n2 >= cum2[v] * n1, compared in unsigned 64 bits (the
+ *   products stay below 2^62); n1 == 0 or n2 == 0: the identity (the `ee.Algorithms.If(overlap.area(5).gt(0), ...)` of :225, decided
+ *   on the device).  Below image 2's smallest occupied bin cum2[v] is 0 and the inequality would hold at bin 0, occupied or not: there
+ *   cum2[v] counts as 1, so those bins map where image 2's smallest occupied bin maps at the least.  Every table value is therefore
+ *   an occupied bin of image 1 -- never nodata: the validity of an equalized scene is that of the original.  lut is (c, bins) of the
+ *   kind; counts (may be NULL) receives n1, n2 per band, int64 (c, 2).
+ * satcv_calib_scale_lut (clamp_and_scale :12-45): upper[band] = the value of the smallest bin v with cum[v] * 100 >= p * n (nearest
+ *   rank, p = 1 ... 100; the reference ignores its p and always asks for 99), -1 for an empty band; table[band][k] = (float)((double)
+ *   min(value(k), upper) / (double)upper), NaN for every k when n == 0 or upper == 0.  table is float32 (c, bins), upper int32 (c).
+ * satcv_calib_apply: dst = table[band][bin(src)] for every valid sample of the (c, h, w_) raster src.  table is (c, bins) of the source
+ *   kind (dst_kind = src_kind; dst may be src itself: in place) or float32 (dst_kind = 2).  dst is addressed like the warp's
+ *   destination: layout 0 (h, w_, ld), layout 1 (ld, h, w_), bands at channels coff ... coff + c - 1, no other channel is written.
+ *   An invalid sample leaves dst untouched with keep (an equalized scene painted straight into a mosaic); otherwise it becomes nodata
+ *   (source kind; 0 without has_nodata, where no sample is invalid) or NaN (float32).  The table is read through the L2.
+ * Refused on the host before any launch: null pointers, unsupported kinds, c < 1 or c > 16, non-positive sizes, h * w_ >= 2^31, p
+ * outside 1 ... 100, split above 32768, a dst_kind that is neither src_kind nor 2, an unknown layout, channels outside ld, dst
+ * overlapping src other than exactly in place. */
+typedef struct satcv_calib_apply_desc {
+  const void* src; int32_t src_kind;
+  int32_t c, h, w_;
+  int32_t has_nodata; double nodata;
+  const void* table;
+  void* dst; int32_t dst_kind, dst_layout;
+  int32_t dst_ld, dst_coff;
+  int32_t keep;
+} satcv_calib_apply_desc;
+int satcv_calib_overlap(const void* a, const void* b, int32_t kind, int32_t c, int32_t h, int32_t w_, int32_t has_nodata, double nodata,
+                        const uint8_t* mask, uint8_t* region, void* stream);
+int satcv_calib_histogram(const void* src, int32_t kind, int32_t c, int32_t h, int32_t w_, const uint8_t* region, uint32_t* hist,
+                          int32_t split, void* stream);
+int satcv_calib_match_lut(const uint32_t* hist1, const uint32_t* hist2, int32_t kind, int32_t c, void* lut, int64_t* counts, void* stream);
+int satcv_calib_scale_lut(const uint32_t* hist, int32_t kind, int32_t c, int32_t p, float* table, int32_t* upper, void* stream);
+int satcv_calib_apply(const satcv_calib_apply_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ losses
  * Each writes loss_out[0] += mean loss contribution (caller zeroes) and
  * dlogits = dL/dlogits (through the head activation).

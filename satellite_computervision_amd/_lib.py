@@ -122,6 +122,12 @@ class ReprojectMap(C.Structure):
                 ('has_src_transform', c_i32), ('src_a', C.c_double), ('src_c', C.c_double), ('src_e', C.c_double), ('src_f', C.c_double)]
 
 
+class CalibApplyDesc(C.Structure):
+    """satcv_calib_apply_desc: a (c, h, w_) raster through a per-band table into a planar or pixel-interleaved destination"""
+    _fields_ = [('src', c_vp), ('src_kind', c_i32), ('c', c_i32), ('h', c_i32), ('w_', c_i32), ('has_nodata', c_i32), ('nodata', C.c_double),
+                ('table', c_vp), ('dst', c_vp), ('dst_kind', c_i32), ('dst_layout', c_i32), ('dst_ld', c_i32), ('dst_coff', c_i32), ('keep', c_i32)]
+
+
 RECORD_MAX_PLANES = 32     # SATCV_RECORD_MAX_PLANES of include/satcv.h
 RECORD_STAT_SPLITS = 16    # SATCV_RECORD_STAT_SPLITS
 _i32p, _f32p = c_i32 * RECORD_MAX_PLANES, c_f32 * RECORD_MAX_PLANES
@@ -344,6 +350,11 @@ _SIGS = {
     'satcv_crs_transform': (C.c_int, [C.POINTER(Crs), C.POINTER(Crs), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp]),
     'satcv_grid_coords': (C.c_int, [C.POINTER(ReprojectMap), c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'satcv_raster_reproject': (C.c_int, [C.POINTER(WarpDesc), C.POINTER(ReprojectMap), c_vp]),
+    'satcv_calib_overlap': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, C.c_double, c_vp, c_vp, c_vp]),
+    'satcv_calib_histogram': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp]),
+    'satcv_calib_match_lut': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'satcv_calib_scale_lut': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    'satcv_calib_apply': (C.c_int, [C.POINTER(CalibApplyDesc), c_vp]),
     'satcv_record_stats': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_record_to_tuple': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_label_onehot': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),

@@ -985,13 +985,59 @@ def _same_kind(files, bands):
     return first.dtype, n, first.nodata
 
 
+def _footprint_x(f, grid):
+    """the x of the centre of a file's footprint in the grid's CRS"""
+    g = _as_grid(f.levels[0], str(f.path))
+    left, bottom, right, top = g.bounds
+    x, y = 0.5 * (left + right), 0.5 * (bottom + top)
+    if g.epsg is not None and grid.epsg is not None and g.epsg != grid.epsg:
+        xs, _ = transform_points([x], [y], g.crs, grid.crs)
+        x = float(xs[0])
+    return x
+
+
+def _read_mosaic_equalized(files, grid, bands, resampling, level, layout, first, nodata, dtype, out, channel_offset, decode, reproject, name, c):
+    """`read_mosaic(equalize=True)`: one slot per file, the chain of `calibration.equalize_collection` west to east, then every slot
+    painted into the filled destination by satcv_calib_apply with keep.  Every refusal comes before the slots are allocated."""
+    from . import calibration
+    if name not in calibration.KINDS:
+        raise ValueError(f'equalize=True bins uint8, uint16 and int16 files, got {name} (float32 needs a binning rule whose rounding can be pinned)')
+    if nodata is None:
+        raise ValueError('equalize=True needs a nodata value (the files\' or nodata=): it is what tells where a file has data on the grid')
+    dst = _dest_view(grid.shape, c, name, dtype, layout=layout, out=out, channel_offset=channel_offset) if out is not None else None
+    if (dst.kind if dst is not None else (dtype or name)) != name:
+        raise ValueError(f'equalize=True writes the files\' kind {name}: a float32 destination is not served')
+    xs = [_footprint_x(f, grid) for f in files]
+    order = sorted(range(len(files)), key=lambda i: xs[i])       # (stable: ties keep the order of the paths)
+    slots = _device_empty((len(files), c) + grid.shape, _torch_dtype(name), 'the slots of the equalized mosaic')
+    for s, f in enumerate(files):
+        r = read_warped(f, grid, bands, resampling, level=level, layout='chw', out=slots[s], nodata=nodata, decode=decode, reproject=reproject)
+    calibration._chain(slots, name, nodata, order)
+    _mark('equalize')
+    out, dname = _filled(grid.shape, c, name, nodata, layout=layout, out=out, channel_offset=channel_offset, what='the mosaic')
+    lay = _chw_or_hwc(layout)
+    ld = c if dst is None else dst.ld
+    # the identity table, by bytes: bin k holds the value k - bias (a uint16 value as the int16 with its bytes)
+    k = torch.arange(calibration.BINS[name], device='cuda', dtype=torch.int32) - calibration.BIAS[name]
+    identity = k.to(torch.uint8) if name == 'uint8' else ((k + 32768) % 65536 - 32768).to(torch.int16)
+    identity = identity.repeat(c, 1).contiguous()
+    for s in (reversed(range(len(files))) if first else range(len(files))):
+        calibration._apply(slots[s], name, identity, out, nodata, layout=lay, ld=ld, coff=channel_offset, keep=True)
+    _mark('paint')
+    return Raster(out, grid.transform, r.crs, nodata=nodata, dtype=dname)
+
+
 def read_mosaic(paths, grid=None, bands=None, resampling='nearest', level=0, layout='hwc', first=False, nodata=None, dtype=None, out=None,
-                channel_offset=0, decode=None, reproject=False):
+                channel_offset=0, decode=None, reproject=False, equalize=False):
     """Files of one CRS mosaicked onto one grid: -> `Raster`.  grid: None is `union_grid(paths)`.  The destination is filled with
     nodata, then every file is read onto it with keep=True, in order: a later file lies on top wherever it has valid data
     (gdal.BuildVRT's order); first=True goes through the files in reverse, so the first file wins (rioxarray's merge_arrays).
     nodata: None is the first file's, without one NaN (float32) or 0.  The other arguments as for `read_warped`; with reproject=True the
     files may be in several EPSG codes (the two-UTM-zone case), grid=None is then `union_grid(paths, reproject=True)`.
+    equalize=True removes the radiometric seam between the files (utils/calibration.py's equalize_collection): every file is warped into a
+    slot of its own (S x C x H x W samples are resident), the slots are histogram-matched west to east -- by the x of each file's
+    footprint centre in the grid's CRS, ties in path order; `calibration.equalize_collection` -- and painted in the order `first`
+    prescribes.  For uint8, uint16 and int16 files with a nodata value; float32 and int32 files are refused.
     Inside the package the paths may be `_File`s, files that are already parsed (`read_aligned_stack`)."""
     files = _files(paths)
     if not files:
@@ -1003,6 +1049,8 @@ def read_mosaic(paths, grid=None, bands=None, resampling='nearest', level=0, lay
     name, c, file_nodata = _same_kind(files, bands)
     if nodata is None:
         nodata = file_nodata
+    if equalize:
+        return _read_mosaic_equalized(files, grid, bands, resampling, level, layout, first, nodata, dtype, out, channel_offset, decode, reproject, name, c)
     out, dname = _filled(grid.shape, c, name if dtype is None else dtype, nodata, layout=layout, out=out, channel_offset=channel_offset, what='the mosaic')
     for f in (reversed(files) if first else files):
         r = read_warped(f, grid, bands, resampling, level=level, layout=layout, out=out, keep=True, nodata=nodata, dtype=dtype,
@@ -1010,13 +1058,14 @@ def read_mosaic(paths, grid=None, bands=None, resampling='nearest', level=0, lay
     return Raster(out, grid.transform, r.crs, nodata=nodata, dtype=dname)
 
 
-def read_aligned_stack(items, grid=None, resolution=None, bands=None, resampling='nearest', level=0, reproject=False):
+def read_aligned_stack(items, grid=None, resolution=None, bands=None, resampling='nearest', level=0, reproject=False, equalize=False):
     """The acquisitions of a time series on ONE grid as a resident stack: -> (stack, transform, crs, nodata), the contract of
     `read_stack` -- stack a (T, C, H, W) CUDA tensor in the files' kind -- for files that need not share a grid: other footprints,
     other resolutions (the 20 m bands beside the 10 m ones), one CRS.  items: per acquisition a path, or a list of paths mosaicked
     into the slot (`read_mosaic`).  grid: None is `union_grid` of every file at `resolution` (None: the finest).  Every file is
     resampled straight into its slot.  With files that already share the grid, nearest gives `read_stack`'s result bit for bit.
-    reproject=True: the files may be in several EPSG codes (`read_warped`); the grid built here is `union_grid(..., reproject=True)`."""
+    reproject=True: the files may be in several EPSG codes (`read_warped`); the grid built here is `union_grid(..., reproject=True)`.
+    equalize=True: the items that are lists of paths are mosaicked with `read_mosaic(equalize=True)`."""
     items = [[it] if isinstance(it, (str, os.PathLike)) else list(it) for it in items]
     flat = _files([p for it in items for p in it])
     if not flat or any(not it for it in items):
@@ -1036,7 +1085,7 @@ def read_aligned_stack(items, grid=None, resolution=None, bands=None, resampling
         if len(files) == 1:
             r = read_warped(files[0], grid, bands, resampling, **slot)
         else:
-            r = read_mosaic(files, grid, bands, resampling, **slot)
+            r = read_mosaic(files, grid, bands, resampling, equalize=equalize, **slot)
     return stack, grid.transform, r.crs, nodata
 
 
