@@ -1025,6 +1025,74 @@ int satcv_calib_match_lut(const uint32_t* hist1, const uint32_t* hist2, int32_t 
 int satcv_calib_scale_lut(const uint32_t* hist, int32_t kind, int32_t c, int32_t p, float* table, int32_t* upper, void* stream);
 int satcv_calib_apply(const satcv_calib_apply_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ Polygon rasterization: clipping rasters to an area of interest
+ * What the reference leaves to rioxarray: `rio.clip([aoi], crs)` on its composites (utils/pc_tools.py:595-606; the same call stands
+ * commented out at :384, :439 and :493).  Polygons become a uint8 mask or a burned label raster on the device, and one mask is applied
+ * to every plane of a raster or a stack.  The rule below is THIS library's, the pixel-centre scanline rule (all_touched = False); it
+ * is modelled on GDAL's filled-polygon scanline but nothing pins it to GDAL.  tests/rasterize_oracle.py says it again in float64
+ * NumPy; csrc/rasterize_core.hpp is the one source of the crossing column for the host loop and the kernels; csrc/rasterize.hip is
+ * compiled with floating-point contraction off.
+ *
+ * Vertices are grid pixel coordinates in float64 (px = (X - c) / a, py = (Y - f) / e, each operation rounded on its own); a ring is
+ * closed implicitly.  Every ring edge is ordered so that y0 < y1; edges with y0 == y1 are dropped.  The edge crosses row i iff
+ * y0 <= i + 0.5 < y1, at x = x0 + ((i + 0.5) - y0) * (x1 - x0) / (y1 - y0), evaluated in that order and not fused; its crossing column
+ * is col = floor(x + 0.5), clamped to [0, w_] before the integer conversion.  Pixel (i, j) belongs to a geometry iff the number of
+ * that geometry's crossings of row i with col <= j is odd: even-odd over all rings of the geometry, so holes and the parts of a
+ * MultiPolygon need no special case.  A mask is the union of the geometries; a burn takes the value of the LAST geometry in list
+ * order that covers the pixel.
+ *
+ * The edge table is built on the host (polygons.edge_table): float64 rows {x0, y0, x1, y1, r0, r1, g}, [r0, r1) the rows the edge
+ * crosses clipped to [0, h) -- found with the comparison above, not with a ceil -- g the geometry index; an edge of more than 64 rows
+ * is split into work items of at most 64.  row_start (int32, h + 1) is the running sum of the per-row crossing counts, which follow
+ * from the row ranges alone (a difference array): the workspace is sized without asking the device.  edges, row_start and values are
+ * HOST pointers; the call copies them into the workspace on the stream.  They need to stay valid only until the call returns: they are
+ * ordinary pageable memory, which the runtime reads (into its own staging buffers) before hipMemcpyAsync returns.  For the same reason
+ * the call is refused while the stream is being captured into a graph: a replay would read host memory that is gone.
+ * satcv_rasterize_workspace: the bytes satcv_rasterize needs for n_items table rows, h grid rows, n_keys = row_start[h] crossings and
+ *   n_geoms values.
+ * satcv_rasterize: on_device = 1 -- dst and workspace are device pointers.  Crossings kernel: one lane per (work item, row) appends
+ *   key = g << 32 | col at row_start[i] + atomicAdd(cursor[i], 1).  Fill kernel: one workgroup per (row, strip of 8192 columns) sorts
+ *   the row's keys in LDS (bitonic, padded to a power of two), walks the consecutive pairs of one g as spans and raises an LDS strip of
+ *   int32 winners with atomicMax(g + 1) -- order-independent, so two runs give the same bytes -- then stores the strip.  mode 0 (mask):
+ *   dst is u8, 1 inside and 0 outside, swapped by invert.  mode 1 (burn): values[g] (n_geoms samples of dst_kind) inside, fill (in the
+ *   kind, as the writer's nodata) outside.  dst is addressed like the warp's destination: layout 0 (h, w_, ld) or 1 (ld, h, w_), the
+ *   one channel coff; with keep a pixel no geometry covers is left untouched.  At most 4096 crossings per row (32 KiB of keys beside
+ *   the 32 KiB strip: two workgroups per CU).  on_device = 0: dst is a host pointer and the same rule runs on the CPU; no workspace.
+ * satcv_raster_mask_apply: where mask (u8 (h, w_)) is 0 -- with invert: is not 0 -- the samples of the channels coff ... coff + c - 1
+ *   become nodata in the kind (without has_nodata NaN for f32, 0 for integers); every other sample is copied, or left alone when dst
+ *   is src (in place).  layout 0 (h, w_, ld), 1 (ld, h, w_): a (T, C, H, W) stack is ld = T * C planes, a slot of it coff = t * C.  A
+ *   streaming kernel: planar rasters (and layout 0 with ld = 1, which is the same memory) take 16 bytes of samples per lane and step; in place
+ *   a vector wholly inside the mask is neither read nor written.  Pixel-interleaved rasters with ld > 1 take one pixel and its c channels per lane.
+ * Refused on the host before any launch: null pointers, unknown kinds, layouts or modes, a mask that is not u8, non-positive sizes,
+ * h * w_ >= 2^31, channels outside ld, non-finite vertices, an unordered edge, r0 / r1 outside [0, h] or not the rows the edge crosses,
+ * a work item of more than 64 rows, g outside the values table, a row with more than 4096 crossings (the message names the row and the
+ * count), row_start not matching the edge table, a workspace too small or misaligned, a stream that is being captured, dst overlapping the
+ * workspace, the mask or (other than exactly in place) src. */
+typedef struct satcv_rasterize_desc {
+  const double* edges; int64_t n_items;
+  const int32_t* row_start;
+  int32_t h, w_;
+  int32_t n_geoms;
+  int32_t mode, invert;
+  const void* values; double fill;
+  void* dst; int32_t dst_kind, dst_layout;
+  int32_t dst_ld, dst_coff;
+  int32_t keep;
+  int32_t on_device;
+  void* workspace; int64_t workspace_bytes;
+} satcv_rasterize_desc;
+typedef struct satcv_mask_apply_desc {
+  const uint8_t* mask; int32_t h, w_;
+  int32_t invert;
+  const void* src; void* dst;
+  int32_t kind, layout;
+  int32_t c, ld, coff;
+  int32_t has_nodata; double nodata;
+} satcv_mask_apply_desc;
+int satcv_rasterize_workspace(int64_t n_items, int32_t h, int64_t n_keys, int32_t n_geoms, int64_t* bytes);
+int satcv_rasterize(const satcv_rasterize_desc* d, void* stream);
+int satcv_raster_mask_apply(const satcv_mask_apply_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ losses
  * Each writes loss_out[0] += mean loss contribution (caller zeroes) and
  * dlogits = dL/dlogits (through the head activation).

@@ -128,6 +128,19 @@ class CalibApplyDesc(C.Structure):
                 ('table', c_vp), ('dst', c_vp), ('dst_kind', c_i32), ('dst_layout', c_i32), ('dst_ld', c_i32), ('dst_coff', c_i32), ('keep', c_i32)]
 
 
+class RasterizeDesc(C.Structure):
+    """satcv_rasterize_desc: an edge table (host pointers) burned into a mask or a label raster (satcv_rasterize)"""
+    _fields_ = [('edges', c_vp), ('n_items', c_i64), ('row_start', c_vp), ('h', c_i32), ('w_', c_i32), ('n_geoms', c_i32), ('mode', c_i32), ('invert', c_i32),
+                ('values', c_vp), ('fill', C.c_double), ('dst', c_vp), ('dst_kind', c_i32), ('dst_layout', c_i32), ('dst_ld', c_i32), ('dst_coff', c_i32),
+                ('keep', c_i32), ('on_device', c_i32), ('workspace', c_vp), ('workspace_bytes', c_i64)]
+
+
+class MaskApplyDesc(C.Structure):
+    """satcv_mask_apply_desc: one uint8 (h, w_) mask applied to the channels coff ... coff + c - 1 of a raster or a stack"""
+    _fields_ = [('mask', c_vp), ('h', c_i32), ('w_', c_i32), ('invert', c_i32), ('src', c_vp), ('dst', c_vp), ('kind', c_i32), ('layout', c_i32),
+                ('c', c_i32), ('ld', c_i32), ('coff', c_i32), ('has_nodata', c_i32), ('nodata', C.c_double)]
+
+
 RECORD_MAX_PLANES = 32     # SATCV_RECORD_MAX_PLANES of include/satcv.h
 RECORD_STAT_SPLITS = 16    # SATCV_RECORD_STAT_SPLITS
 _i32p, _f32p = c_i32 * RECORD_MAX_PLANES, c_f32 * RECORD_MAX_PLANES
@@ -355,6 +368,9 @@ _SIGS = {
     'satcv_calib_match_lut': (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'satcv_calib_scale_lut': (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp]),
     'satcv_calib_apply': (C.c_int, [C.POINTER(CalibApplyDesc), c_vp]),
+    'satcv_rasterize_workspace': (C.c_int, [c_i64, c_i32, c_i64, c_i32, C.POINTER(c_i64)]),
+    'satcv_rasterize': (C.c_int, [C.POINTER(RasterizeDesc), c_vp]),
+    'satcv_raster_mask_apply': (C.c_int, [C.POINTER(MaskApplyDesc), c_vp]),
     'satcv_record_stats': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_record_to_tuple': (C.c_int, [C.POINTER(RecordDesc), c_vp]),
     'satcv_label_onehot': (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),

@@ -523,3 +523,18 @@ def convt_bwd_fused(g_cat, c_skip, yup, scale, shift, mean, rstd, coef, x, w_dgr
     d.workspace, d.workspace_bytes = ws.data_ptr(), nb
     check(lib.satcv_convt_bwd_fused(C.byref(d), stream_ptr()))
     return dx, dw
+
+
+def rasterize(desc):
+    """one satcv_rasterize call of a filled `_lib.RasterizeDesc` (raster_tools._burn fills it): the crossings and fill kernels on the current
+    stream, or with on_device = 0 the same rule on the CPU from host pointers -- then no stream is asked for and the device is not touched"""
+    check(lib.satcv_rasterize(C.byref(desc), stream_ptr() if desc.on_device else None))
+
+
+def raster_mask_apply(mask, src, dst, kind, layout, h, w_, c, coff, ld, nodata=None, invert=False):
+    """satcv_raster_mask_apply: where the uint8 (h, w_) mask is 0 (invert: is not 0) the channels coff ... coff + c - 1 of dst become nodata
+    (None: NaN for f32, 0 for integers), every other sample is src's; dst may be src (in place).  rio.clip of utils/pc_tools.py:595-606."""
+    d = _lib.MaskApplyDesc(mask=_p(mask), h=h, w_=w_, invert=int(bool(invert)), src=_p(src), dst=_p(dst), kind=kind, layout=layout, c=c, ld=ld, coff=coff,
+                           has_nodata=int(nodata is not None), nodata=float(nodata if nodata is not None else 0.0))
+    check(lib.satcv_raster_mask_apply(C.byref(d), stream_ptr()))
+    return dst

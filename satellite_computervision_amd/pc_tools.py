@@ -5,9 +5,10 @@
       -> normalize_dataArray over bands (:90-107) -> [before bands, after bands] (:650) -> chips -> model -> stitched map
 
 The first four arrows are ONE kernel (satcv_median_composite, csrc/composite.hip) on a stack that is uploaded once; its output is the
-(H, W, C) float32 scene the device-resident prediction loop of prediction_tools reads in place.  Acquisition (STAC search, rioxarray),
-reprojection between coordinate systems and clipping stay with the caller; files of one CRS on differing grids are aligned by
-`predict_change_files` (raster_tools.read_aligned_stack, what stackstac.stack(resolution=) does for the reference).
+(H, W, C) float32 scene the device-resident prediction loop of prediction_tools reads in place.  Acquisition (STAC search, rioxarray)
+stays with the caller; files on differing grids are aligned by `predict_change_files` (raster_tools.read_aligned_stack, what
+stackstac.stack(resolution=) does for the reference; reproject=True for several coordinate systems), and its aoi= / `predict_change`'s
+region= clip to a polygon, the reference's rio.clip([aoi], crs) (:595-606; raster_tools.geometry_mask, mask_apply).
 
 The composites the reference's models were trained on were masked per acquisition first (utils/ee_tools.py: basicQA :159, maskTOA
 :288, maskSR :270, mask :257).  `median_composite(clear=...)` / `predict_change(quality=...)` take those masks from `ee_tools` as bit-planes
@@ -170,7 +171,7 @@ def median_composite(stack, times=None, offsets=None, fill=None, out=None, chann
 
 def predict_change(before, after, m, before_times=None, after_times=None, buff=128, kernel=256, batch_size=16, channel=0,
                    cover='reference', fill=None, quality=None, band_names=None, bands=None, out_file=None, transform=None, crs=None,
-                   cog_options=None):
+                   cog_options=None, region=None):
     """`run_local` (utils/pc_tools.py:620-668) from the two time stacks on: `(output, bef_median, aft_median)` -- the change map
     (H, W) float32 and the two median composites (H, W, C) float32 as host arrays (the reference's return without the geotransform).
 
@@ -187,6 +188,10 @@ def predict_change(before, after, m, before_times=None, after_times=None, buff=1
     otherwise) straight from the device map, where the reference hands its array to numpy_to_raster; needs transform (a, b, c, d, e, f)
     and crs ('EPSG:n' or an int).  cog_options: a dict of further `write_cog` arguments (dtype, scale, nodata, compress, ...).  The
     return value is unchanged.
+    region: a uint8 or bool (H, W) mask, 1 inside (`raster_tools.geometry_mask` of an area of interest; a host array goes up once):
+    the `rio.clip([aoi], crs)` of :595-606.  Both stacks are clipped before their composites -- a sample outside becomes 0 (NaN for
+    float32), nodata by the rule above, so it drops out of the median -- and the change map is NaN outside the region before it is
+    returned and written.  The caller's stacks are not modified.  None: the launches and results are exactly those without it.
     The composites stay on the device from the composite kernel to the stitch; the three returned arrays are the only copies back."""
     import torch
     from . import prediction_tools as pt
@@ -219,12 +224,18 @@ def predict_change(before, after, m, before_times=None, after_times=None, buff=1
                 raise ValueError(f'{cs} planes need {cs} band_names, got {len(band_names)}')
             table = ee.band_table(band_names)
             ee._require(table, rules, band_names)
+    if region is not None:
+        from . import raster_tools as rt
+        from .calibration import _mask
+        region = _mask(region, (H, W))
     two_inputs = len(getattr(m, 'inputs', ())) > 1
     scene = None if two_inputs else _device_empty((H, W, 2 * nb), torch.float32, 'the two-date scene')
     medians, norms = [], []
     for k, (stack, times, clear) in enumerate(((before, before_times, masks[0]), (after, after_times, masks[1]))):
         off_dev = _offsets_to_device(int(stack.shape[0]), times, None)
         src, kind = _stack_to_device(stack)                  # uploaded once: the mask kernel and the composite read the same copy
+        if region is not None:                               # (in place on the copy made here; a resident stack of the caller's is left as it is)
+            src = rt.mask_apply(src, region, layout='chw', inplace=src is not stack)
         if rules is not None:
             clear = ee._quality(src, kind, table, rules, off_dev, clear=True)[0]
         median, norm = _composite(src, kind, off_dev, fill, scene, 0 if two_inputs else k * nb, clear, idx)
@@ -234,17 +245,20 @@ def predict_change(before, after, m, before_times=None, after_times=None, buff=1
     bef_median, aft_median = medians
     if two_inputs:
         scene = (norms[1], norms[0])
-    if out_file is None:
+    if out_file is None and region is None:
         output = pt.predict_scene(scene, m, kernel=kernel, buff=buff, batch_size=batch_size, channel=channel, cover=cover)
     else:
         dev_map = pt.predict_scene(scene, m, kernel=kernel, buff=buff, batch_size=batch_size, channel=channel, cover=cover, device=True)
-        rt.write_cog(dev_map, out_file, transform, crs, **dict(cog_options or {}))
+        if region is not None:
+            rt.mask_apply(dev_map, region, inplace=True)
+        if out_file is not None:
+            rt.write_cog(dev_map, out_file, transform, crs, **dict(cog_options or {}))
         output = dev_map.cpu().numpy()
     return output, bef_median.cpu().numpy(), aft_median.cpu().numpy()
 
 
 def predict_change_files(before_items, after_items, m, grid=None, resolution=None, out_file=None, file_bands=None, resampling='nearest',
-                         reproject=False, **predict_change_kwargs):
+                         reproject=False, aoi=None, aoi_crs='EPSG:4326', **predict_change_kwargs):
     """`predict_change` from files that need not share a pixel grid: both periods are read as aligned stacks on ONE grid
     (`raster_tools.read_aligned_stack` -- what the reference gets from stackstac.stack(epsg=, resolution=)) and handed to
     `predict_change` with that grid's georeference; returns what `predict_change` returns.
@@ -255,17 +269,27 @@ def predict_change_files(before_items, after_items, m, grid=None, resolution=Non
     GeoTIFF with the grid's transform and CRS.  predict_change_kwargs: every other argument of `predict_change` (times, kernel, buff,
     quality, bands, fill, cog_options, ...); transform and crs come from the grid.
     reproject=True: the files may be in several EPSG codes (a series that straddles a UTM zone boundary): they are reprojected onto the
-    grid (`raster_tools.read_warped(reproject=True)`); the grid built here is in the code of the first file."""
+    grid (`raster_tools.read_warped(reproject=True)`); the grid built here is in the code of the first file.
+    aoi: an area of interest, a GeoJSON-like polygon in aoi_crs (`raster_tools.geometry_rings` says which forms): the `aoi` of `run_local`
+    and its `rio.clip([aoi], crs)` (:595-606).  With no `grid` the grid is `raster_tools.aoi_grid` of the polygon in the files' CRS, at
+    `resolution` or the files' finest; the polygon's mask on the grid is `predict_change`'s region: both stacks are clipped before the
+    composites and the change map is NaN outside.  None: everything is as without it."""
     import os
     from . import raster_tools as rt
-    for k in ('transform', 'crs'):
+    for k in ('transform', 'crs', 'region'):
         if k in predict_change_kwargs:
             raise ValueError(f'{k} comes from the common grid: it is not an argument of predict_change_files')
     if grid is None:
         flat = [p for it in list(before_items) + list(after_items) for p in ([it] if isinstance(it, (str, os.PathLike)) else it)]
         grid = rt.union_grid(flat, resolution=resolution, reproject=reproject)
+        if aoi is not None:
+            if grid.crs is None:
+                raise ValueError('the files carry no EPSG code: an aoi cannot be placed on them')
+            grid = rt.aoi_grid(aoi, grid.resolution, grid.crs, geom_crs=aoi_crs)
     elif resolution is not None:
         raise ValueError('resolution describes the grid that is built when none is given')
+    if aoi is not None:
+        predict_change_kwargs['region'] = rt.geometry_mask(aoi, grid, geom_crs=aoi_crs)
     before = rt.read_aligned_stack(before_items, grid, bands=file_bands, resampling=resampling, reproject=reproject)
     after = rt.read_aligned_stack(after_items, grid, bands=file_bands, resampling=resampling, reproject=reproject)
     if out_file is not None:

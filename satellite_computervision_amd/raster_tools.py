@@ -28,8 +28,10 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import RasterDesc, ReprojectMap, UntileDesc, WarpDesc, check, lib
+from ._lib import RasterDesc, RasterizeDesc, ReprojectMap, UntileDesc, WarpDesc, check, lib
 from .crs import crs_params, crs_struct
+from .polygons import (convert, convert_poly_coords, edge_table, geometry_rings, get_centroid, make_jittered_window, make_window,      # noqa: F401
+                       rings_bounds, to_pixels, win_jitter)
 from .prediction_tools import _device_empty, _to_device
 from .tiff_container import (DTYPES, LevelInfo, _COMPRESSION, _expected_bytes, _levels, _plan_read, _window_transform,      # noqa: F401
                              build_container, overview_shapes, parse_crs, read_info, tile_grid, write_tiles)
@@ -1224,3 +1226,196 @@ def reproject_window(src_transform, src_shape, src_crs, grid, resampling='neares
     last bits -- and clipped to the raster.  When some boundary pixel lies outside a projection's domain the extremes are unknown: the
     window is the whole raster; when every one does: None."""
     return _Mapping(src_transform, src_crs, grid, foreign=True).window(src_shape, resampling)
+
+
+# ----------------------------------------------------------------------------------------------------------------- polygons on a grid
+# `rio.clip([aoi], crs)` of utils/pc_tools.py:595-606 (commented out at :384, :439, :493): polygons become a mask or a burned label
+# raster on the device (csrc/rasterize.hip), and one mask serves every plane of a raster or a stack.  The rule -- pixel centres,
+# all_touched=False, even-odd -- is this library's own (include/satcv.h, "Polygon rasterization"; tests/rasterize_oracle.py).  Host code
+# (GeoJSON, the edge table, the window helpers of utils/raster_tools.py:70-331) is in `polygons`.  Out of scope, each a ValueError:
+# all_touched=True, lines and points, rotated grids, densifying edges before a change of CRS (only vertices are transformed, as
+# rio.clip does).
+def _rings_on(rings, grid, geom_crs):
+    """`geometry_rings` output with the vertices in the CRS of `grid`: only vertices are transformed"""
+    src, dst = _epsg_of(geom_crs), grid.epsg
+    if src is None or dst is None or src == dst:
+        return rings
+    out = []
+    for g in rings:
+        out.append([])
+        for r in g:
+            xs, ys = transform_points(r[:, 0], r[:, 1], f'EPSG:{src}', f'EPSG:{dst}')
+            out[-1].append(np.stack([xs, ys], axis=1))
+    return out
+
+
+def geometry_bounds(geoms, geom_crs=None, crs=None):
+    """(left, bottom, right, top) of the geometries; when `geom_crs` and `crs` name different codes, `transform_bounds` of that box in `crs`"""
+    b = rings_bounds(geometry_rings(geoms))
+    src, dst = _epsg_of(geom_crs), _epsg_of(crs)
+    if src is None or dst is None or src == dst:
+        return b
+    return transform_bounds(f'EPSG:{src}', f'EPSG:{dst}', *b)
+
+
+def aoi_grid(geoms, resolution, crs, geom_crs='EPSG:4326'):
+    """The north-up grid of `crs` at `resolution` that holds the geometries (given in `geom_crs`): `union_grid` of their bounds, snapped
+    outward to multiples of the resolution."""
+    return union_grid([], resolution=resolution, bounds=geometry_bounds(geoms, geom_crs=geom_crs, crs=crs), crs=crs)
+
+
+def _burn(geoms_px, shape, mode, invert, values, fill, dst, keep, device):
+    """one satcv_rasterize call: geometries in pixel coordinates into the `_View` dst (device) or the host array view (ptr) it describes"""
+    table, row_start = edge_table(geoms_px, shape)
+    vals = None if mode == 0 else np.ascontiguousarray(values, DTYPES[dst.kind][0])
+    d = RasterizeDesc(edges=table.ctypes.data if len(table) else None, n_items=len(table), row_start=row_start.ctypes.data, h=shape[0], w_=shape[1], n_geoms=len(geoms_px),
+                      mode=mode, invert=int(bool(invert)), values=vals.ctypes.data if vals is not None and vals.size else None, fill=float(fill), dst=dst.ptr,
+                      dst_kind=DTYPES[dst.kind][1], dst_layout=dst.layout, dst_ld=dst.ld, dst_coff=dst.coff, keep=int(bool(keep)), on_device=int(bool(device)))
+    ws = None
+    if device:
+        need = C.c_int64()
+        check(lib.satcv_rasterize_workspace(len(table), shape[0], int(row_start[-1]), len(geoms_px), C.byref(need)))
+        ws = _device_empty((max(int(need.value), 16),), torch.uint8, 'the rasterization workspace')
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    ops.rasterize(d)
+    return ws
+
+
+def _shapes(shapes, values):
+    """-> ([geometry (list of rings)], [value per geometry]) of `rasterize`'s shapes / values"""
+    if isinstance(shapes, dict) or hasattr(shapes, '__geo_interface__'):
+        shapes = [shapes]
+    shapes = list(shapes)
+    if values is not None:
+        values = list(np.atleast_1d(values))
+        if len(values) != len(shapes):
+            raise ValueError(f'{len(values)} values for {len(shapes)} shapes')
+    geoms, vals = [], []
+    for k, s in enumerate(shapes):
+        v = 1 if values is None else values[k]
+        if isinstance(s, (tuple, list)) and len(s) == 2 and np.ndim(s[1]) == 0 and not isinstance(s[1], (dict, str)) and not hasattr(s[1], '__geo_interface__'):
+            if values is not None:
+                raise ValueError('values are given twice: as (geometry, value) pairs and as values=')
+            s, v = s
+        g = geometry_rings(s)
+        geoms += g
+        vals += [v] * len(g)
+    return geoms, vals
+
+
+def rasterize(shapes, grid, values=None, fill=0, dtype='uint8', geom_crs=None, out=None, channel_offset=0, layout='hwc', keep=False, device=True,
+              all_touched=False):
+    """Polygons burned into a raster on `grid`: a pixel whose centre lies inside a geometry (even-odd over its rings; the rule of
+    include/satcv.h, this library's own) takes that geometry's value -- of the LAST one in list order that covers it -- every other
+    pixel `fill`, or with keep=True what `out` held (without `out` there is nothing to keep: `fill`).  shapes: geometries (`geometry_rings` says which) or (geometry, value) pairs;
+    values: one per shape instead of pairs; neither: 1.  geom_crs: the CRS of the vertices when it is not the grid's -- only vertices are
+    transformed (`transform_points`), edges are not densified.  dtype: 'uint8', 'uint16', 'int16', 'int32' or 'float32'.
+    device=True: -> a CUDA tensor (H, W), or `out` ((H, W), (H, W, ld) for layout 'hwc', (ld, H, W) for 'chw'; channel channel_offset is
+    written, no other).  device=False: the same rule on the CPU -> a NumPy array (H, W); `out` then is a C-contiguous array of the same forms.
+    ValueError: all_touched=True, lines and points, a non-finite vertex, an unknown dtype or layout; a row with more than 4096 crossings is
+    refused by the library (SatcvError) before anything is launched."""
+    if all_touched:
+        raise ValueError('all_touched=True is not implemented: the rule is the pixel-centre rule')
+    grid = _a_grid(grid)
+    if dtype not in DTYPES:
+        raise ValueError(f'dtype {dtype!r}: one of {sorted(DTYPES)}')
+    geoms, vals = _shapes(shapes, values)
+    px = to_pixels(_rings_on(geoms, grid, geom_crs), grid.transform)
+    keep = bool(keep) and out is not None                     # (a new raster holds nothing to keep: every uncovered pixel is `fill`)
+    if device:
+        dst = _dest_view(grid.shape, 1, dtype, None, layout, out=out, channel_offset=channel_offset, flat=True)
+        if dst.kind != dtype:
+            raise ValueError(f'out is {dst.owner.dtype}, the result {dtype}')
+    else:
+        dst = _host_dest(grid.shape, dtype, layout, out, channel_offset)
+    _burn(px, grid.shape, 1, False, vals, fill, dst, keep, device)
+    return dst.owner
+
+
+def _host_dest(shape, dtype, layout, out, channel_offset):
+    nt = np.dtype(DTYPES[dtype][0])
+    lay = _chw_or_hwc(layout)
+    if out is None:
+        out = np.empty(shape, nt)
+    if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.dtype == nt and out.ndim in (2, 3)):
+        raise ValueError(f'out must be a C-contiguous NumPy array of {nt}, (H, W), (H, W, ld) or (ld, H, W)')
+    hw = out.shape if out.ndim == 2 else (out.shape[:2] if lay == 0 else out.shape[1:])
+    ld = 1 if out.ndim == 2 else int(out.shape[2] if lay == 0 else out.shape[0])
+    if tuple(hw) != tuple(shape):
+        raise ValueError(f'out is {hw[0]} x {hw[1]}, the grid {shape[0]} x {shape[1]}')
+    if not 0 <= int(channel_offset) < ld:
+        raise ValueError(f'channel {channel_offset} does not fit the {ld} of out')
+    return _View(owner=out, ptr=out.ctypes.data, kind=dtype, h=shape[0], w=shape[1], c=1, ld=ld, coff=int(channel_offset), layout=lay, flat=out.ndim == 2)
+
+
+def _mask_of(rings, grid, invert=False, device=True):
+    px = to_pixels(rings, grid.transform)
+    if device:
+        dst = _dest_view(grid.shape, 1, 'uint8', None, 'hwc', flat=True)
+    else:
+        dst = _host_dest(grid.shape, 'uint8', 'hwc', None, 0)
+    _burn(px, grid.shape, 0, invert, None, 0, dst, False, device)
+    return dst.owner
+
+
+def geometry_mask(geoms, grid, invert=False, geom_crs=None, device=True, all_touched=False):
+    """The geometries as a uint8 (H, W) mask on `grid`, on the device: 1 INSIDE a geometry and 0 outside (their union) -- the opposite of
+    rasterio's `geometry_mask`, whose default is True outside; invert=True gives 0 inside and 1 outside.  This is the form
+    `calibration.*(region=)` and `clip` take.  device=False: a NumPy array from the host loop.  Rule and refusals: `rasterize`."""
+    if all_touched:
+        raise ValueError('all_touched=True is not implemented: the rule is the pixel-centre rule')
+    grid = _a_grid(grid)
+    return _mask_of(_rings_on(geometry_rings(geoms), grid, geom_crs), grid, invert, device)
+
+
+def mask_apply(arr, mask, nodata=None, invert=False, layout='hwc', inplace=False, src_dtype=None):
+    """Samples of `arr` where `mask` is 0 (invert=True: is not 0) become nodata -- None: NaN for float32, 0 for integers; every other
+    sample is kept.  arr: a contiguous CUDA tensor, (H, W) or (H, W, C) for layout 'hwc', (C, H, W) or a (T, C, H, W) stack for 'chw';
+    mask: a uint8 or bool (H, W) CUDA tensor.  inplace=True writes into `arr` (only the samples outside are touched) and returns it;
+    otherwise a new tensor.  One streaming launch (satcv_raster_mask_apply)."""
+    if not (isinstance(arr, torch.Tensor) and arr.is_cuda and arr.is_contiguous() and arr.dtype in _TENSOR_KINDS and arr.dtype != torch.float64):
+        raise ValueError('mask_apply takes a contiguous CUDA tensor of uint8, uint16, int16, int32 or float32')
+    lay = _chw_or_hwc(layout)
+    if lay == 0:
+        if arr.dim() not in (2, 3):
+            raise ValueError(f"an 'hwc' raster is (H, W) or (H, W, C), got shape {tuple(arr.shape)}")
+        h, w, ld = int(arr.shape[0]), int(arr.shape[1]), int(arr.shape[2]) if arr.dim() == 3 else 1
+    else:
+        if arr.dim() not in (2, 3, 4):
+            raise ValueError(f"a 'chw' raster is (H, W), (C, H, W) or a (T, C, H, W) stack, got shape {tuple(arr.shape)}")
+        h, w = int(arr.shape[-2]), int(arr.shape[-1])
+        ld = int(np.prod(arr.shape[:-2], dtype=np.int64)) if arr.dim() > 2 else 1
+    if 0 in arr.shape:
+        raise ValueError(f'an empty raster: shape {tuple(arr.shape)}')
+    if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if not (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (h, w)):
+        raise ValueError(f'mask is a uint8 or bool (H, W) = {(h, w)} CUDA tensor')
+    kind = _TENSOR_KINDS[arr.dtype] if src_dtype is None else src_dtype
+    mask = mask.contiguous()
+    dst = arr if inplace else _device_empty(tuple(arr.shape), arr.dtype, 'the masked raster')
+    ops.raster_mask_apply(mask, arr, dst, DTYPES[kind][1], lay, h, w, ld, 0, ld, nodata, invert)
+    return dst
+
+
+def clip(arr, grid, geoms, geom_crs=None, nodata=None, crop=True, layout='hwc', inplace=False):
+    """`rio.clip([aoi], crs)` on the device: -> (raster, Grid).  Samples of `arr` (on `grid`; forms as `mask_apply`) whose pixel centre
+    lies outside every geometry become nodata (None: NaN for float32, 0 for integers): `geometry_mask`, then `mask_apply`.  crop=True
+    returns the view of the geometries' pixel bounding box (clipped to the grid) and that window's Grid; ValueError when the
+    geometries miss the grid.  inplace=True masks `arr` itself."""
+    grid = _a_grid(grid)
+    rings = _rings_on(geometry_rings(geoms), grid, geom_crs)
+    mask = _mask_of(rings, grid)
+    out = mask_apply(arr, mask, nodata=nodata, layout=layout, inplace=inplace)
+    if not crop:
+        return out, grid
+    H, W = grid.shape
+    px = np.concatenate([r for g in to_pixels(rings, grid.transform) for r in g])
+    if not np.isfinite(px).all():
+        raise ValueError('a vertex lies outside the domain of the grid\'s projection')
+    c0, c1 = int(max(np.floor(px[:, 0].min()), 0)), int(min(np.ceil(px[:, 0].max()), W))
+    r0, r1 = int(max(np.floor(px[:, 1].min()), 0)), int(min(np.ceil(px[:, 1].max()), H))
+    if c0 >= c1 or r0 >= r1:
+        raise ValueError('the geometries do not intersect the grid')
+    view = out[r0:r1, c0:c1] if _chw_or_hwc(layout) == 0 else out[..., r0:r1, c0:c1]
+    return view, Grid(_window_transform(grid.transform, grid.shape, grid.shape, r0, c0), (r1 - r0, c1 - c0), grid.crs)
